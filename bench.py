@@ -11,21 +11,24 @@ d_head 128, non-causal.  For N>1 every rank runs that same per-GPU workload on i
 own batch shard (global batch = 4*N, no data-path collective, no RCCL traffic in
 the timed region): "scaling": "weak".
 
-One JSON line on rank 0:
+One JSON line on rank 0.  A plain run sets up, preconditions the clocks, runs the W warm-up and the K timed steps and
+prints the line; what it carries is measured on those timed launches alone:
   value      whole-job TFLOP/s = N * steps * 4*B*H*S^2*d / max-over-ranks time
+  ms_per_step  milliseconds of one timed step (max over ranks)
   roofline   MFMA-bound: achieved TFLOP/s of the kernel from HIP events recorded on
              the launch stream around the K timed launches (and after every launch: the
              per-launch distribution); peak = 2500 TFLOP/s (MI355X dense bf16 MFMA,
-             /opt/skills/guides/MI355X_MICROARCH.md); traffic = HBM bytes per launch from
-             rocprofv3 PMC passes over this same command (FETCH_SIZE x 2 + WRITE_SIZE);
-             pipe_counters = matrix-pipe busy fraction, instructions per MFMA and the
-             GRBM_GUI_ACTIVE-derived effective clock from a third pass
+             MI355X_MICROARCH.md)
   clocks     shader / memory clock and socket power sampled from the GPU's hwmon files
              during the timed region (SURVEY.md 8d asks for them: the chip clocks to its
              power budget)
-  cpu_baseline  torch CPU scaled_dot_product_attention (oracle.fa_oracle.sdpa_cpu)
-             on the SAME workload, on this host's cores, rank 0, N=1 only.
 
+--full adds everything that takes runs of its own (N = 1 unless stated):
+  roofline.traffic  HBM bytes per launch from rocprofv3 PMC passes over this same command
+             (FETCH_SIZE x 2 + WRITE_SIZE); pipe_counters = matrix-pipe busy fraction, instructions
+             per MFMA and the GRBM_GUI_ACTIVE-derived effective clock from a third pass
+  cpu_baseline  torch CPU scaled_dot_product_attention (oracle.fa_oracle.sdpa_cpu)
+             on the SAME workload, on this host's cores, rank 0.
   roofline.mfma_only_*  the matrix pipe's practical roof on THIS box in THIS run: a register-only MFMA
              loop (tools/mfma_energy.hip `quick`: the kernel's issue order, no memory traffic, ~20 ms
              launches) on zero and on N(0,1) operands, bf16 and fp16 -- the chip clocks to its power
@@ -33,10 +36,15 @@ One JSON line on rank 0:
   protocols  the same kernel under the reference's own timing protocol as well (pt_bench.py:145-174:
              cache flush + idle spin before every launch, >= 50 reps): `value` is back-to-back launches
              (what the driver's wall clock sees), `protocols.hermetic` the other figure, same run
-  speculative  fa_fwd_stats of the timed launches: work items and how many the speculative softmax
+  variants, robustness  the other softmax forms beside the default, interleaved, on N(0, 1) and on
+             non-Gaussian data
+  speculative  fa_fwd_stats of one more launch of the step: work items and how many the speculative softmax
              computed twice (--data sink / heavy show the cliff on non-Gaussian logits)
+  sustained  a >= 250 ms region of the same steps when the K-step region is shorter than 100 ms (any N)
 
 --hermetic makes the hermetic protocol the headline `value` instead.
+--dump-outputs DIR writes what the last timed step computed (a fixed, seeded sample of the output rows, float32) as
+DIR/<name>.npy: the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import glob
@@ -159,6 +167,34 @@ def timed_steps(step, steps, warmup, sync, barrier):
     barrier()
     sync()
     return time.perf_counter() - t0
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: every array of one run together, under the 64 MB a dump may take
+
+
+def output_sample(o, n_arrays, seed):
+    """--dump-outputs: the rows of `o` viewed as (rows, d_head), as float32 -- all of them when this run's `n_arrays` arrays
+    fit DUMP_BUDGET_BYTES whole, otherwise a fixed sample drawn with `seed`, in row order.  -> {"": rows, "_rows": their
+    indices into o.reshape(-1, d_head), as float64}."""
+    import numpy as np
+
+    flat = o.reshape(-1, o.shape[-1])
+    n, d = flat.shape
+    keep = DUMP_BUDGET_BYTES // (n_arrays * (d * 4 + 8))
+    if n <= keep:
+        idx = torch.arange(n)
+    else:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+    return {"": flat[idx.to(flat.device)].float().cpu().numpy(), "_rows": idx.numpy().astype(np.float64)}
+
+
+def write_outputs(out_dir, name, sample):
+    """out_dir/<name>.npy and out_dir/<name>_rows.npy of output_sample()."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for suffix, arr in sample.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), arr)
 
 
 HBM_PEAK_GBPS = 8000.0      # MI355X_MICROARCH.md: HBM3E peak (6.3 TB/s achievable)
@@ -578,6 +614,8 @@ def run_c2_sweep(args, device):
         t_end = time.perf_counter()
         sec = (t_end - t0) / args.steps
         sampler.stop()
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, f"o_s{seq}", output_sample(o, len(sweep), seq))
         clk = sampler.summary(t0, t_end)
         flop = mfma_flop(batch, 16, seq, 128)
         alg_bytes = 4 * batch * seq * 16 * 128 * 2
@@ -598,7 +636,7 @@ def run_c2_sweep(args, device):
                                    "peak": (HBM_PEAK_GBPS if bound == "hbm" else PEAK_TFLOPS["bf16"]),
                                    "unit": "GB/s" if bound == "hbm" else "TFLOP/s",
                                    "frac": tf / roof, "roof_tflops_equivalent": roof}}
-        if not args.no_traffic:  # HBM bytes per launch of this shape, measured (two rocprofv3 PMC passes)
+        if args.full and not args.no_traffic:  # HBM bytes per launch of this shape, measured (two rocprofv3 PMC passes)
             traffic, _how = measure_traffic(["--workload", "c2", "--c2-shape", str(seq)]
                                             + (["--kernel", args.kernel] if args.kernel else []))
             per_s[seq]["traffic"] = traffic
@@ -646,7 +684,8 @@ def dry_run(args, rank, world):
     seconds = timed_steps(lambda: time.sleep(0.002), args.steps, args.warmup, lambda: None, barrier)
     mine = mfma_flop(hi - lo, heads, seq, d) * args.steps / seconds / 1e12
     seconds = max_over_ranks(seconds, world, torch.device("cpu"))
-    sustained = sustained_region(lambda: time.sleep(0.002), lambda: None, barrier, seconds, args.steps, world, torch.device("cpu"))
+    sustained = (sustained_region(lambda: time.sleep(0.002), lambda: None, barrier, seconds, args.steps, world, torch.device("cpu"))
+                 if args.full else None)
     per_rank = [mine]
     affinities = [affinity]
     if world > 1:
@@ -854,13 +893,19 @@ def main():
     ap.add_argument("--data", default="randn", choices=["randn", "sink", "heavy"],
                     help="synthetic inputs: N(0,1) (the reference's; default) | an attention sink (+12 nats at the first 4 keys) "
                          "| heavy-tailed K (Student-t, 3 dof): what the speculative softmax's second pass costs (line: speculative)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement that takes launches or runs of its own (see the module docstring); "
+                         "the --no-* options and --hermetic-reps below leave parts of it out")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's output (float32; a fixed, seeded sample of its rows) as DIR/<name>.npy")
     ap.add_argument("--hermetic-reps", type=int, default=50,
-                    help="launches of the side measurement under the reference's flush + idle-spin protocol (protocols.hermetic); 0 = skip")
-    ap.add_argument("--no-mfma-roof", action="store_true", help="skip the register-only MFMA loop (roofline.mfma_only_*)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the side-by-side variants and the robustness block")
+                    help="--full: launches of the side measurement under the reference's flush + idle-spin protocol "
+                         "(protocols.hermetic); 0 = skip")
+    ap.add_argument("--no-mfma-roof", action="store_true", help="--full: skip the register-only MFMA loop (roofline.mfma_only_*)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the side-by-side variants and the robustness block")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="skip the three rocprofv3 PMC passes (HBM bytes per launch; matrix-pipe occupancy, "
+                    help="--full: skip the three rocprofv3 PMC passes (HBM bytes per launch; matrix-pipe occupancy, "
                          "instruction mix and effective clock) (~1 min)")
     ap.add_argument("--precondition-ms", type=float, default=400.0,
                     help="untimed launches of the same step for this long BEFORE the W warm-up steps: the chip's "
@@ -876,7 +921,7 @@ def main():
     ap.add_argument("--no-pin", action="store_true", help="N > 1: do not pin the ranks to the NUMA nodes of their GPUs")
     ap.add_argument("--rocprof-rank", type=int, default=-1,
                     help="N > 1: rank R runs under `rocprofv3 --kernel-trace --stats` and leaves --rocprof-dir/scale_rank<R>*.csv "
-                         "(one rank only: the profiled rank clocks a few % lower, see MI355X_MICROARCH.md DVFS)")
+                         "(one rank only: the profiled rank clocks a few %% lower, see MI355X_MICROARCH.md DVFS)")
     ap.add_argument("--rocprof-dir", default=os.path.join("profiles", "r06"))
     ap.add_argument("--batch-per-rank", type=int, default=0,
                     help="override the workload's per-GPU batch (weak scaling keeps it fixed per rank).  `--gpus 8 --workload c4 "
@@ -980,7 +1025,8 @@ def main():
         sync()
         return
 
-    flush_buf = torch.empty(512 * 1024 * 1024, dtype=torch.int8, device=device) if (args.hermetic or args.hermetic_reps) else None
+    flush_buf = (torch.empty(512 * 1024 * 1024, dtype=torch.int8, device=device)
+                 if (args.hermetic or (args.full and args.hermetic_reps)) else None)
 
     def hermetic_launch():
         """pt_bench.py:145-174: flush (> L2 + Infinity Cache), idle spin, events around ONE launch -> ms"""
@@ -1055,8 +1101,11 @@ def main():
     else:
         per_launch = [events[i].elapsed_time(events[i + 1]) for i in range(args.steps)]
         kernel_ms = events[0].elapsed_time(events[-1]) / args.steps  # avg launch duration, this rank
+    if args.dump_outputs:   # (before anything below launches into `o` again)
+        write_outputs(args.dump_outputs, "o" if world == 1 else f"o_rank{rank}", output_sample(o, world, rank))
     seconds = max_over_ranks(seconds, world, reduce_device)
-    sustained = None if args.hermetic else sustained_region(step, sync, barrier, seconds, args.steps, world, reduce_device)
+    sustained = (sustained_region(step, sync, barrier, seconds, args.steps, world, reduce_device)
+                 if (args.full and not args.hermetic) else None)
 
     flop_per_step_rank = mfma_flop(hi - lo, heads, seq, d)
     total_flop = flop_per_step_rank * world * args.steps  # equal shards
@@ -1064,19 +1113,22 @@ def main():
     achieved = flop_per_step_rank / (kernel_ms * 1e-3) / 1e12
     peak = PEAK_TFLOPS[dtype_name]
 
-    # one more launch, untimed, with the device-side statistics on: how many items the speculative softmax ran twice
-    stats = torch.zeros(2, dtype=torch.int32, device=device)
-    import flash_attention_kernels
+    speculative = None
+    if args.full:
+        # one more launch, untimed, with the device-side statistics on: how many items the speculative softmax ran twice
+        stats = torch.zeros(2, dtype=torch.int32, device=device)
+        import flash_attention_kernels
 
-    flash_attention_kernels.forward(cfg, q, k, v, o, stats=stats)
-    sync()
-    items, redone = (int(x) for x in stats.tolist())
-    adaptive_record = None
-    if getattr(cfg, "adaptive_softmax", False):  # what the adaptive mode did over this process's launches on the device
+        flash_attention_kernels.forward(cfg, q, k, v, o, stats=stats)
+        sync()
+        items, redone = (int(x) for x in stats.tolist())
+        speculative = {"items": items, "items_redone": redone, "second_pass_fraction": redone / items if items else None,
+                       "source": "fa_fwd_stats of one more (untimed) launch of the same step", "adaptive": None}
+    if speculative and getattr(cfg, "adaptive_softmax", False):  # what the adaptive mode did over this process's launches
         from flash_attention_from_scratch_amd import _capi
 
         st = _capi.adaptive_state(local_rank)
-        adaptive_record = {k_: st[k_] for k_ in ("launches", "demoted", "reports", "hold", "mode")}
+        speculative["adaptive"] = {k_: st[k_] for k_ in ("launches", "demoted", "reports", "hold", "mode")}
 
     per_rank = per_rank_clocks = None
     if world > 1:  # per-GPU rates, clocks and power next to the aggregate (rank order)
@@ -1162,10 +1214,9 @@ def main():
                 "frac_of_peak_at_measured_clock": achieved / (peak * sclk / MAX_SCLK_MHZ) if sclk else None,
             },
             "clocks": clocks,
-            "speculative": {"items": items, "items_redone": redone, "second_pass_fraction": redone / items if items else None,
-                            "source": "fa_fwd_stats of one more (untimed) launch of the same step",
-                            "adaptive": adaptive_record},
         }
+        if speculative:
+            line["speculative"] = speculative
         if sustained:
             sustained["tflops"] = flop_per_step_rank * world * sustained["steps"] / sustained["seconds"] / 1e12
             line["sustained"] = sustained
@@ -1176,7 +1227,7 @@ def main():
             line["per_gpu_tflops"] = per_rank
             line["per_gpu"] = per_rank_clocks
             line["aggregate_over_sum_of_gpus"] = value / sum(per_rank)
-        if world == 1 and args.hermetic_reps and not args.hermetic:
+        if world == 1 and args.full and args.hermetic_reps and not args.hermetic:
             # the same kernel under the reference's protocol, in the same run (pt_bench.py:145-174)
             for _ in range(3):
                 hermetic_launch()
@@ -1189,7 +1240,8 @@ def main():
                              "what": "512 MiB flush + idle spin + sync before every launch, events around the launch "
                                      "(tools/benchmark/pt_bench.py:145-174), 3 warm-ups"},
             }
-        if world == 1 and not args.kernel and not args.no_variants and hasattr(cfg, "prescaled_q") and not cfg.prescaled_q:
+        if (world == 1 and args.full and not args.kernel and not args.no_variants and hasattr(cfg, "prescaled_q")
+                and not cfg.prescaled_q):
             line["variants"] = side_by_side(cfg, q, k, v, o, args, flop_per_step_rank, sync)
             lz = line["variants"].get("lazy")
             if isinstance(lz, dict) and "tflops" in lz:
@@ -1199,7 +1251,7 @@ def main():
                 line["value_reference_arithmetic_what"] = ("TFLOP/s of the running-max (lazy rescale) kernel " + lz["kernel"]
                                                            + ": variants.lazy of this run; `value` is the speculative softmax")
             line["robustness"] = robustness(cfg, (hi - lo, seq, heads, d), dtype, device, args, flop_per_step_rank, sync)
-        if world == 1 and not args.no_mfma_roof:
+        if world == 1 and args.full and not args.no_mfma_roof:
             del flush_buf
             roof = mfma_only_roof(local_rank)
             line["roofline"]["mfma_only"] = roof
@@ -1211,7 +1263,7 @@ def main():
                 line["roofline"]["mfma_only_source"] = ("lib/mfma_energy quick (tools/mfma_energy.hip): register-only "
                                                         "v_mfma_f32_32x32x16 loop in the kernel's issue order, one wave per "
                                                         "SIMD, 256 workgroups, ~20 ms launches, this device, after the timed region")
-        if world == 1 and not args.no_traffic:
+        if world == 1 and args.full and not args.no_traffic:
             tail = ["--workload", args.workload, "--data", args.data] + (["--kernel", args.kernel] if args.kernel else []) \
                 + (["--dtype", args.dtype] if args.dtype else [])
             traffic, how = measure_traffic(tail)
@@ -1231,7 +1283,7 @@ def main():
                 if isinstance(pc, dict) and "wave_cycles_per_mfma" in pc:
                     line["wave_cycles_per_mfma"] = pc["wave_cycles_per_mfma"]
                     line["mfma_busy_frac_of_wave_time"] = pc["mfma_busy_frac_of_wave_time"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(dtype, batch, heads, seq, d)
         print(json.dumps(line), flush=True)
 

@@ -89,8 +89,8 @@ def test_wave_cycles_per_mfma_does_not_creep_up_between_rounds():
 
 
 def test_short_timed_regions_also_report_a_sustained_one():
-    """bench.py: a K-step region under 100 ms (the driver's --steps 20 at C1 is ~9 ms) also times >= 250 ms of the same
-    steps with the same brackets and reports it as `sustained`; a region of 100 ms or more does not."""
+    """bench.py --full: a K-step region under 100 ms (the driver's --steps 20 at C1 is ~9 ms) also times >= 250 ms of the
+    same steps with the same brackets and reports it as `sustained`; a region of 100 ms or more does not."""
     calls = []
 
     def step():
@@ -99,3 +99,30 @@ def test_short_timed_regions_also_report_a_sustained_one():
     got = bench.sustained_region(step, lambda: None, lambda: None, seconds=0.010, steps=20, world=1, device=None)
     assert got["steps"] == int(0.25 / (0.010 / 20)) + 1 == len(calls) and got["seconds"] > 0 and "ms_per_step" in got
     assert bench.sustained_region(step, lambda: None, lambda: None, seconds=0.2, steps=20, world=1, device=None) is None
+
+
+def test_dumped_outputs_are_a_fixed_sample_within_budget(tmp_path):
+    """bench.py --dump-outputs: the C1 output (B=4 S=4096 H=16 d=128) is larger than the budget, so a seeded sample of its
+    rows is written -- the same rows every run, float32 values equal to the rows they name, all arrays under 64 MB; an
+    output that fits is written whole."""
+    import numpy as np
+    import torch
+
+    _, batch, heads, seq, d = bench.WORKLOADS["c1"]
+    o = torch.randn((batch, seq, heads, d), generator=torch.Generator().manual_seed(5)).to(torch.bfloat16)
+    got, again = bench.output_sample(o, 1, 0), bench.output_sample(o, 1, 0)
+    rows = got["_rows"].astype(np.int64)
+    assert got[""].dtype == np.float32 and got["_rows"].dtype == np.float64
+    assert np.array_equal(got[""], again[""]) and np.array_equal(rows, again["_rows"].astype(np.int64))
+    assert 0 < len(rows) < batch * seq * heads and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got[""], o.reshape(-1, d)[torch.from_numpy(rows)].float().numpy())
+    assert got[""].nbytes + got["_rows"].nbytes <= bench.DUMP_BUDGET_BYTES < 64 << 20
+    for sweep_len in (6, 8):   # the c2 sweep's six shapes, eight ranks: the run's arrays share the budget
+        part = bench.output_sample(o, sweep_len, 1)
+        assert sweep_len * (part[""].nbytes + part["_rows"].nbytes) <= bench.DUMP_BUDGET_BYTES
+    small = torch.randn((2, 64, 3, d))
+    whole = bench.output_sample(small, 1, 0)
+    assert np.array_equal(whole[""], small.reshape(-1, d).numpy()) and np.array_equal(whole["_rows"], np.arange(2 * 64 * 3))
+    bench.write_outputs(str(tmp_path / "dump"), "o", got)
+    assert sorted(os.listdir(tmp_path / "dump")) == ["o.npy", "o_rows.npy"]
+    assert np.array_equal(np.load(tmp_path / "dump" / "o.npy"), got[""])

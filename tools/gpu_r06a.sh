@@ -12,9 +12,9 @@ echo "== data"
 : > $OUT/sink_data.txt
 for D in sink heavy; do for T in bf16 fp16; do for K in spec lazy; do
   KK="$SPEC"; [ $K = lazy ] && KK="$LAZY"; [ $T = fp16 ] && KK="${KK/BF16/FP16}"
-  timeout 600 python bench.py --steps 20 --warmup 5 --data $D --dtype $T --kernel "$KK" $QUICK > $OUT/b.json 2>/dev/null
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --data $D --dtype $T --kernel "$KK" $QUICK > $OUT/b.json 2>/dev/null
   python -c "import json;r=json.load(open('$OUT/b.json'));s=r['speculative'];print('%-6s %-5s %-9s %8.1f TFLOP/s   items %d redone %d' % ('$D','$T','$K',r['value'],s['items'],s['items_redone']))" | tee -a $OUT/sink_data.txt
 done; done; done
 echo "== pytest (all)"; timeout 2700 python -m pytest tests -m gpu -q --timeout 900 > $OUT/pytest_gpu.txt 2>&1; tail -30 $OUT/pytest_gpu.txt
-echo "== bench c1"; timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_c1.json 2> $OUT/bench.err; cut -c1-400 $OUT/bench_c1.json; tail -2 $OUT/bench.err
+echo "== bench c1"; timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_c1.json 2> $OUT/bench.err; cut -c1-400 $OUT/bench_c1.json; tail -2 $OUT/bench.err
 echo "== done"

@@ -8,5 +8,5 @@ echo "== pytest"; timeout 2400 python -m pytest tests -m gpu -q --timeout 900 > 
 echo "== soak 300 s"; timeout 600 python tools/soak.py 300 101 > $OUT/soak_300s.txt 2>&1; tail -1 $OUT/soak_300s.txt
 echo "== soak 300 s, jitter build"; FA_HIP_LIB=$PWD/$L/libfa_hip_jitter.so timeout 600 python tools/soak.py 300 103 > $OUT/soak_jitter_300s.txt 2>&1; tail -1 $OUT/soak_jitter_300s.txt
 echo "== soak 120 s, every variant"; timeout 400 python tools/soak.py 120 105 all > $OUT/soak_all_120s.txt 2>&1; tail -1 $OUT/soak_all_120s.txt
-echo "== bench (driver's command)"; timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_c1.json 2> $OUT/bench.err; cut -c1-260 $OUT/bench_c1.json
+echo "== bench (driver's command)"; timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_c1.json 2> $OUT/bench.err; cut -c1-260 $OUT/bench_c1.json
 echo "== done"

@@ -10,11 +10,11 @@ echo "== ring_c1"
 RB="(BF16, 128, 128, 64, 4): async+eager+swizzled+load_0_0_0_tiles"
 for rep in 1 2; do for kk in "$RB+buffer" "$RB+buffer+spec_softmax" "$RB" "${RB/BF16/FP16}+buffer" "${RB/BF16/FP16}+buffer+spec_softmax"; do
   dt=bf16; case "$kk" in "(FP16"*) dt=fp16;; esac
-  python bench.py --steps 20 --warmup 5 --dtype $dt --kernel "$kk" --no-variants --no-traffic --no-cpu-baseline --no-mfma-roof --hermetic-reps 20 2>/dev/null | python -c "
+  python bench.py --full --steps 20 --warmup 5 --dtype $dt --kernel "$kk" --no-variants --no-traffic --no-cpu-baseline --no-mfma-roof --hermetic-reps 20 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
         d = json.loads(l); print('$rep', d['config']['kernel'].ljust(88), '%.1f TFLOP/s  sustained %.1f  hermetic %.1f' % (d['value'], d.get('sustained', {}).get('tflops', 0), d.get('protocols', {}).get('hermetic', {}).get('tflops', 0)))"
 done; done > $OUT/ring_c1.txt; cat $OUT/ring_c1.txt
-echo "== bench c1 quick (default unchanged?)"; timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-traffic --hermetic-reps 0 --no-mfma-roof --no-variants > $OUT/bench_c1.json 2>/dev/null; cut -c1-200 $OUT/bench_c1.json
+echo "== bench c1 quick (default unchanged?)"; timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-traffic --hermetic-reps 0 --no-mfma-roof --no-variants > $OUT/bench_c1.json 2>/dev/null; cut -c1-200 $OUT/bench_c1.json
 echo "== done"

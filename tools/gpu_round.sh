@@ -33,31 +33,31 @@ echo "== pytest"; timeout 2400 python -m pytest tests -m gpu -q --timeout 900 > 
 fi
 if has bench; then
 echo "== bench c1 (the driver's command: value, hermetic protocol, MFMA-only roof, clocks, in-run PMC traffic + pipe counters, variants, robustness, cpu baseline)"
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_c1.json 2> $OUT/bench.err; cut -c1-300 $OUT/bench_c1.json; tail -2 $OUT/bench.err
-echo "== rocprof --kernel-trace --stats of the bench command (same lease as bench_c1.json)"; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o fa -- python bench.py --steps 20 --warmup 5 $QUICK --no-variants > $OUT/rocprof_bench.json 2> $OUT/rocprof.err; tail -2 $OUT/rocprof.err; for f in $(find $OUT/prof -name "*kernel_stats.csv"); do head -4 $f; cp $f $OUT/rocprof_kernel_stats.csv; done
-echo "== bench c1, 2000 steps (sustained)"; timeout 600 python bench.py --steps 2000 --warmup 10 $QUICK --no-variants > $OUT/bench_c1_sustained.json 2>/dev/null; cut -c1-200 $OUT/bench_c1_sustained.json
-echo "== bench c1, no preconditioning (cold clocks)"; timeout 600 python bench.py --steps 20 --warmup 5 --precondition-ms 0 $QUICK --no-variants > $OUT/bench_c1_cold.json 2>/dev/null; cut -c1-200 $OUT/bench_c1_cold.json
-echo "== bench c1, lazy-rescale build"; timeout 600 python bench.py --steps 20 --warmup 5 $QUICK --kernel "$LAZY" > $OUT/bench_c1_lazy.json 2>/dev/null; cut -c1-200 $OUT/bench_c1_lazy.json
-echo "== bench c1, pre-scaled Q (opt-in)"; timeout 600 python bench.py --steps 20 --warmup 5 $QUICK --kernel "$SPEC+prescaled_q" > $OUT/bench_c1_prescaled_q.json 2>/dev/null; cut -c1-200 $OUT/bench_c1_prescaled_q.json
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_c1.json 2> $OUT/bench.err; cut -c1-300 $OUT/bench_c1.json; tail -2 $OUT/bench.err
+echo "== rocprof --kernel-trace --stats of the bench command (same script run as bench_c1.json)"; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o fa -- python bench.py --full --steps 20 --warmup 5 $QUICK --no-variants > $OUT/rocprof_bench.json 2> $OUT/rocprof.err; tail -2 $OUT/rocprof.err; for f in $(find $OUT/prof -name "*kernel_stats.csv"); do head -4 $f; cp $f $OUT/rocprof_kernel_stats.csv; done
+echo "== bench c1, 2000 steps (sustained)"; timeout 600 python bench.py --full --steps 2000 --warmup 10 $QUICK --no-variants > $OUT/bench_c1_sustained.json 2>/dev/null; cut -c1-200 $OUT/bench_c1_sustained.json
+echo "== bench c1, no preconditioning (cold clocks)"; timeout 600 python bench.py --full --steps 20 --warmup 5 --precondition-ms 0 $QUICK --no-variants > $OUT/bench_c1_cold.json 2>/dev/null; cut -c1-200 $OUT/bench_c1_cold.json
+echo "== bench c1, lazy-rescale build"; timeout 600 python bench.py --full --steps 20 --warmup 5 $QUICK --kernel "$LAZY" > $OUT/bench_c1_lazy.json 2>/dev/null; cut -c1-200 $OUT/bench_c1_lazy.json
+echo "== bench c1, pre-scaled Q (opt-in)"; timeout 600 python bench.py --full --steps 20 --warmup 5 $QUICK --kernel "$SPEC+prescaled_q" > $OUT/bench_c1_prescaled_q.json 2>/dev/null; cut -c1-200 $OUT/bench_c1_prescaled_q.json
 echo "== bench c1 fp16 (default) with pipe counters, and fp16 lazy"
-timeout 600 python bench.py --steps 20 --warmup 5 --dtype fp16 --no-cpu-baseline --hermetic-reps 0 --no-variants > $OUT/bench_c1_fp16.json 2>/dev/null; cut -c1-200 $OUT/bench_c1_fp16.json
-timeout 600 python bench.py --steps 20 --warmup 5 --dtype fp16 $QUICK --kernel "${LAZY/BF16/FP16}" > $OUT/bench_c1_fp16_lazy.json 2>/dev/null; cut -c1-200 $OUT/bench_c1_fp16_lazy.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 --dtype fp16 --no-cpu-baseline --hermetic-reps 0 --no-variants > $OUT/bench_c1_fp16.json 2>/dev/null; cut -c1-200 $OUT/bench_c1_fp16.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 --dtype fp16 $QUICK --kernel "${LAZY/BF16/FP16}" > $OUT/bench_c1_fp16_lazy.json 2>/dev/null; cut -c1-200 $OUT/bench_c1_fp16_lazy.json
 fi
 if has data; then
 echo "== non-Gaussian data: what the speculative softmax's second pass costs (sink: +12 nats at the first 4 keys; heavy: Student-t K)"
 : > $OUT/sink_data.txt
 for D in randn sink heavy; do for T in bf16 fp16; do for K in spec adaptive lazy; do
   KK="$SPEC"; [ $K = lazy ] && KK="$LAZY"; [ $K = adaptive ] && KK="$ADAPT"; [ $T = fp16 ] && KK="${KK/BF16/FP16}"
-  timeout 600 python bench.py --steps 20 --warmup 5 --data $D --dtype $T --kernel "$KK" $QUICK > $OUT/b.json 2>/dev/null
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --data $D --dtype $T --kernel "$KK" $QUICK > $OUT/b.json 2>/dev/null
   python -c "import json;r=json.load(open('$OUT/b.json'));s=r['speculative'];print('%-6s %-5s %-9s %8.1f TFLOP/s   items %d redone %d (%.1f %%) in one more launch; adaptive: %s' % ('$D','$T','$K',r['value'],s['items'],s['items_redone'],100*s['second_pass_fraction'],s.get('adaptive')))" | tee -a $OUT/sink_data.txt
 done; done; done
 fi
 if has workloads; then
-for W in c3 c4; do echo "== bench $W"; timeout 900 python bench.py --workload $W --steps 10 --warmup 3 --no-cpu-baseline --hermetic-reps 0 --no-mfma-roof --no-variants > $OUT/bench_$W.json 2>/dev/null; cut -c1-200 $OUT/bench_$W.json; done
-echo "== bench c3 with the lazy rescale"; timeout 900 python bench.py --workload c3 --steps 10 --warmup 3 $QUICK --kernel "${LAZY/BF16/FP16}" > $OUT/bench_c3_lazy.json 2>/dev/null; cut -c1-200 $OUT/bench_c3_lazy.json
-echo "== bench c2 (seq sweep, harmonic mean; per-seq_len rooflines)"; timeout 900 python bench.py --workload c2 --steps 20 --warmup 5 > $OUT/bench_c2.json 2>/dev/null; cut -c1-200 $OUT/bench_c2.json
-echo "== bench --gpus 2, self-launched (gloo; both ranks on this box's one GPU: plumbing only -- NUMA pinning, affinities in the line)"; timeout 600 python bench.py --gpus 2 --warmup 2 > $OUT/bench_n2_selflaunch.json 2> $OUT/bench_n2.err; cut -c1-200 $OUT/bench_n2_selflaunch.json
-echo "== bench --gpus 8 --workload c4 --batch-per-rank 1, self-launched: eight launchers on ONE host against this box's one GPU (host us per launch, affinity, barrier latency per rank)"; timeout 900 python bench.py --gpus 8 --workload c4 --batch-per-rank 1 --steps 10 --warmup 3 --no-cpu-baseline --no-traffic --hermetic-reps 0 --no-mfma-roof --no-variants > $OUT/bench_n8_selflaunch.json 2> $OUT/bench_n8.err; cut -c1-300 $OUT/bench_n8_selflaunch.json; tail -2 $OUT/bench_n8.err
+for W in c3 c4; do echo "== bench $W"; timeout 900 python bench.py --full --workload $W --steps 10 --warmup 3 --no-cpu-baseline --hermetic-reps 0 --no-mfma-roof --no-variants > $OUT/bench_$W.json 2>/dev/null; cut -c1-200 $OUT/bench_$W.json; done
+echo "== bench c3 with the lazy rescale"; timeout 900 python bench.py --full --workload c3 --steps 10 --warmup 3 $QUICK --kernel "${LAZY/BF16/FP16}" > $OUT/bench_c3_lazy.json 2>/dev/null; cut -c1-200 $OUT/bench_c3_lazy.json
+echo "== bench c2 (seq sweep, harmonic mean; per-seq_len rooflines)"; timeout 900 python bench.py --full --workload c2 --steps 20 --warmup 5 > $OUT/bench_c2.json 2>/dev/null; cut -c1-200 $OUT/bench_c2.json
+echo "== bench --gpus 2, self-launched (gloo; both ranks on this box's one GPU: plumbing only -- NUMA pinning, affinities in the line)"; timeout 600 python bench.py --full --gpus 2 --warmup 2 > $OUT/bench_n2_selflaunch.json 2> $OUT/bench_n2.err; cut -c1-200 $OUT/bench_n2_selflaunch.json
+echo "== bench --gpus 8 --workload c4 --batch-per-rank 1, self-launched: eight launchers on ONE host against this box's one GPU (host us per launch, affinity, barrier latency per rank)"; timeout 900 python bench.py --full --gpus 8 --workload c4 --batch-per-rank 1 --steps 10 --warmup 3 --no-cpu-baseline --no-traffic --hermetic-reps 0 --no-mfma-roof --no-variants > $OUT/bench_n8_selflaunch.json 2> $OUT/bench_n8.err; cut -c1-300 $OUT/bench_n8_selflaunch.json; tail -2 $OUT/bench_n8.err
 echo "== where an S = 512 launch goes: kernel duration and gap to the next dispatch (rocprofv3 --kernel-trace), event-timed interval, workgroup walk"; timeout 900 python tools/s512_floor.py > $OUT/s512_launch_breakdown.txt 2>&1; cat $OUT/s512_launch_breakdown.txt | cut -c1-300; timeout 900 python tools/s512_floor.py --seq 1024 > $OUT/s1024_launch_breakdown.txt 2>&1; grep "dispatch records\|event-timed" $OUT/s1024_launch_breakdown.txt | cut -c1-300
 fi
 if has wideners; then
@@ -77,7 +77,7 @@ echo "== the reference's winning shape at C1 under the driver's protocol: ring f
 RB="(BF16, 128, 128, 64, 4): async+eager+swizzled+load_0_0_0_tiles"
 for rep in 1 2; do for kk in "$RB+buffer" "$RB+buffer+spec_softmax" "$RB" "${RB/BF16/FP16}+buffer" "${RB/BF16/FP16}+buffer+spec_softmax"; do
   dt=bf16; case "$kk" in "(FP16"*) dt=fp16;; esac
-  python bench.py --steps 20 --warmup 5 --dtype $dt --kernel "$kk" --no-variants --no-traffic --no-cpu-baseline --no-mfma-roof --hermetic-reps 20 2>/dev/null | python -c "
+  python bench.py --full --steps 20 --warmup 5 --dtype $dt --kernel "$kk" --no-variants --no-traffic --no-cpu-baseline --no-mfma-roof --hermetic-reps 20 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
