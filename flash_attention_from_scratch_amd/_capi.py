@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_masked_supported", "fa_fwd_launch_masked", "fa_device_state",
     "fa_fwd_ex_supported", "fa_fwd_launch_ex", "fa_fwd_query",
     "fa_adaptive_state", "fa_adaptive_state_for", "fa_adaptive_reset", "fa_adaptive_simulate", "fa_get_kernel_sized", "fa_fwd_query_sized", "fa_abi_version",
+    "fa_fwd_lse_supported", "fa_fwd_launch_lse", "fa_bwd_workspace_bytes", "fa_bwd_launch",
 )
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
 FA_ABI_VERSION = 6
@@ -77,6 +78,18 @@ class FaFwdOpts(ctypes.Structure):
         ("struct_size", ctypes.c_uint32), ("causal", ctypes.c_int32), ("allow_ragged", ctypes.c_int32),
         ("speculative", ctypes.c_int32), ("prescaled_q", ctypes.c_int32),
         ("ms", ctypes.POINTER(ctypes.c_float)), ("stats", ctypes.c_void_p),
+    ]
+
+
+class FaBwdArgs(ctypes.Structure):   # fa_bwd_args
+    _fields_ = [
+        ("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p),
+        ("o", ctypes.c_void_p), ("dout", ctypes.c_void_p), ("lse", ctypes.POINTER(ctypes.c_float)),
+        ("dq", ctypes.c_void_p), ("dk", ctypes.c_void_p), ("dv", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+        ("batch", ctypes.c_int64), ("seq_len", ctypes.c_int64), ("n_heads", ctypes.c_int64), ("d_head", ctypes.c_int64),
+        ("qkv_batch_stride", ctypes.c_int64), ("qkv_seq_stride", ctypes.c_int64), ("qkv_head_stride", ctypes.c_int64),
+        ("out_batch_stride", ctypes.c_int64), ("out_seq_stride", ctypes.c_int64), ("out_head_stride", ctypes.c_int64),
+        ("dtype", ctypes.c_int32), ("causal", ctypes.c_int32),
     ]
 
 
@@ -167,6 +180,14 @@ def load():
     lib.fa_fwd_query_sized.argtypes = [cfg_p, ctypes.POINTER(FaFwdOpts), ctypes.POINTER(FaKernelInfo), ctypes.c_uint32]
     lib.fa_abi_version.restype = ctypes.c_int
     lib.fa_abi_version.argtypes = []
+    lib.fa_fwd_lse_supported.restype = ctypes.c_int
+    lib.fa_fwd_lse_supported.argtypes = [cfg_p, ctypes.POINTER(FaFwdOpts)]
+    lib.fa_fwd_launch_lse.restype = ctypes.c_int
+    lib.fa_fwd_launch_lse.argtypes = [args_p, ctypes.POINTER(FaFwdOpts), ctypes.c_void_p, ctypes.c_void_p]
+    lib.fa_bwd_workspace_bytes.restype = ctypes.c_int64
+    lib.fa_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaBwdArgs)]
+    lib.fa_bwd_launch.restype = ctypes.c_int
+    lib.fa_bwd_launch.argtypes = [ctypes.POINTER(FaBwdArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p
     lib.fa_last_error.argtypes = []
     lib.fa_version.restype = ctypes.c_char_p

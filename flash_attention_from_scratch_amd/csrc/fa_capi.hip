@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/fa_hip.h"
+#include "fa_bwd_kernel.hpp"
 #include "fa_registry.hpp"
 
 extern "C" {
@@ -27,6 +28,13 @@ fa::KernelTable fa_inst_table_dt5_qt2();
 fa::KernelTable fa_inst16_table_dt15();
 fa::KernelTable fa_inst16_table_dt5();
 }
+namespace fa {
+// fa_inst_lse.hip: the persistent kernel's forms that also write the row log-sum-exp (fa_fwd_kernel64_lse)
+kernel_fn_lse lse_kernel_dt15(bool masked, bool spec);
+kernel_fn_lse lse_kernel_dt5(bool masked, bool spec);
+// fa_bwd.hip: delta, dK / dV and dQ of one backward, enqueued on `s`
+hipError_t bwd_enqueue(const BwdArgs &a, int dtype, bool causal, hipStream_t s);
+}  // namespace fa
 
 namespace {
 
@@ -234,6 +242,17 @@ void do_init_body(int dev, DeviceState *st) {
             }
         }
     }
+    // the forms that also write the row log-sum-exp (fa_fwd_launch_lse): the persistent kernel's LDS
+    for (int i = 0; i < 8; ++i) {
+        const fa::kernel_fn_lse fn = (i & 4) ? fa::lse_kernel_dt5((i & 1) != 0, (i & 2) != 0) : fa::lse_kernel_dt15((i & 1) != 0, (i & 2) != 0);
+        const hipError_t rc = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, fa::RingTraits<2>::kLdsBytes);
+        if (rc != hipSuccess) {
+            st->status = FA_ERR_LAUNCH;
+            snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, LSE form) on device %d: %s", fa::RingTraits<2>::kLdsBytes,
+                     dev, hipGetErrorString(rc));
+            return;
+        }
+    }
 }
 
 void do_init(int dev, DeviceState *st) {
@@ -323,8 +342,10 @@ int validate(const fa_fwd_args *a, const fa::KernelEntry **out, const Want &want
     return FA_OK;
 }
 
+// lse != nullptr (fa_fwd_launch_lse; e is a persistent 64-rows-per-wave entry, checked by the caller): the twin of e's
+// kernel that also writes the row log-sum-exp, always the plain walk (no alternating-direction twin is built)
 int launch(const fa_fwd_args *a, const fa::KernelEntry *e, const DeviceState *dev, hipStream_t stream, int causal = 0,
-           fa_fwd_stats *stats = nullptr, uint32_t *redo_flag = nullptr, uint32_t redo_seq = 0) {
+           fa_fwd_stats *stats = nullptr, uint32_t *redo_flag = nullptr, uint32_t redo_seq = 0, float *lse = nullptr) {
     fa::KernelArgs ka;
     ka.stats = (uint32_t *)stats;
     ka.redo_flag = redo_flag;
@@ -377,6 +398,12 @@ int launch(const fa_fwd_args *a, const fa::KernelEntry *e, const DeviceState *de
     const dim3 grid(n_wg);
     const dim3 block(threads);
     void *params[] = {&ka};
+    fa::KernelArgsLse kal{ka, lse};
+    if (lse) {
+        const bool masked = e->masked != 0, spec = e->softmax_mode == FA_SOFTMAX_SPECULATIVE;
+        fn = (fa::kernel_fn)(a->cfg.dtype == FA_BF16 ? fa::lse_kernel_dt15(masked, spec) : fa::lse_kernel_dt5(masked, spec));
+        params[0] = &kal;
+    }
     hipError_t rc = hipLaunchKernel((const void *)fn, grid, block, params, (size_t)lds_bytes, stream);
     if (rc != hipSuccess) return fail(FA_ERR_LAUNCH, "hipLaunchKernel: %s", hipGetErrorString(rc));
     return FA_OK;
@@ -437,9 +464,10 @@ struct ProbeHook {
 };
 static int launch_maybe_timed(const fa_fwd_args *args, const fa::KernelEntry *e, const DeviceState *dev,
                               hipStream_t s, int causal, float *ms, fa_fwd_stats *stats = nullptr,
-                              uint32_t *redo_flag = nullptr, uint32_t redo_seq = 0, ProbeHook probe = ProbeHook()) {
+                              uint32_t *redo_flag = nullptr, uint32_t redo_seq = 0, ProbeHook probe = ProbeHook(),
+                              float *lse = nullptr) {
     if (!ms) {
-        const int rc0 = launch(args, e, dev, s, causal, stats, redo_flag, redo_seq);
+        const int rc0 = launch(args, e, dev, s, causal, stats, redo_flag, redo_seq, lse);
         probe.after_launch(rc0, s);
         return rc0;
     }
@@ -449,7 +477,7 @@ static int launch_maybe_timed(const fa_fwd_args *args, const fa::KernelEntry *e,
     if (hrc == hipSuccess) hrc = hipEventRecord(start, s);
     int rc = FA_OK;
     if (hrc == hipSuccess) {
-        rc = launch(args, e, dev, s, causal, stats, redo_flag, redo_seq);
+        rc = launch(args, e, dev, s, causal, stats, redo_flag, redo_seq, lse);
         probe.after_launch(rc, s);
         hrc = hipEventRecord(stop, s);  // (recorded even if the launch failed: nothing is left pending)
         if (hrc == hipSuccess) hrc = hipEventSynchronize(stop);
@@ -543,7 +571,16 @@ int fa_fwd_ex_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) {
     return find_kernel(cfg, &why, w) != nullptr;
 }
 
-int fa_fwd_launch_ex(const fa_fwd_args *args, const fa_fwd_opts *opts, void *stream) {
+// Does the entry the options select have a form that writes the row log-sum-exp?  (the persistent 64-rows-per-wave kernel,
+// plain or causal, without the pre-scaled Q: fa_fwd_kernel64_lse; allow_ragged selects the masked entry, whose seq_len % 256
+// == 0 launches fa_fwd_launch_lse serves with its causal form -- a ragged seq_len is refused there)
+static bool lse_form(const fa_fwd_config *cfg, const fa_fwd_opts &o, const fa::KernelEntry *e) {
+    return e && e->persistent && e->rows_per_wave == 64 && e->d_head == 128 && !e->prescaled_q &&
+           !o.prescaled_q && cfg->d_head == 128 && (cfg->dtype == FA_BF16 || cfg->dtype == FA_FP16);
+}
+
+// fa_fwd_launch_ex, and fa_fwd_launch_lse (lse != nullptr; the caller has checked lse_form)
+static int launch_ex_impl(const fa_fwd_args *args, const fa_fwd_opts *opts, void *stream, float *lse) {
     fa_fwd_opts o;
     int rc = read_opts(opts, &o);
     if (rc != FA_OK) return rc;
@@ -601,7 +638,134 @@ int fa_fwd_launch_ex(const fa_fwd_args *args, const fa_fwd_opts *opts, void *str
             }  // (no such sibling: the speculative variant stays)
         }
     }
-    return launch_maybe_timed(args, e, dev, (hipStream_t)stream, o.causal != 0, o.ms, o.stats, redo_flag, redo_seq, hook);
+    return launch_maybe_timed(args, e, dev, (hipStream_t)stream, o.causal != 0, o.ms, o.stats, redo_flag, redo_seq, hook, lse);
+}
+
+int fa_fwd_launch_ex(const fa_fwd_args *args, const fa_fwd_opts *opts, void *stream) {
+    return launch_ex_impl(args, opts, stream, nullptr);
+}
+
+int fa_fwd_lse_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) {
+    if (!cfg) return 0;
+    fa_fwd_opts o;
+    if (read_opts(opts, &o) != FA_OK) return 0;
+    const char *why;
+    Want w;
+    w.masked = o.causal || o.allow_ragged;
+    w.ragged = o.allow_ragged != 0;
+    w.speculative = o.speculative != 0;
+    w.prescaled_q = o.prescaled_q != 0;
+    return lse_form(cfg, o, find_kernel(cfg, &why, w)) ? 1 : 0;
+}
+
+int fa_fwd_launch_lse(const fa_fwd_args *args, const fa_fwd_opts *opts, float *lse, void *stream) {
+    if (!args) return fail(FA_ERR_NULL, "null pointer argument");
+    if (!lse) return fail(FA_ERR_NULL, "lse is null: fa_fwd_launch_lse needs a (batch, n_heads, seq_len) fp32 buffer");
+    if ((uintptr_t)lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
+    fa_fwd_opts o;
+    int rc = read_opts(opts, &o);
+    if (rc != FA_OK) return rc;
+    if (!fa_fwd_lse_supported(&args->cfg, opts))
+        return fail(FA_ERR_NO_KERNEL, "the row log-sum-exp is written by the persistent (B_r 256, B_c 64, 4 warps) + buffer "
+                                      "configuration at d_head 128 only, plain or causal, without prescaled_q");
+    if (args->seq_len % 256 != 0)
+        return fail(FA_ERR_SHAPE, "fa_fwd_launch_lse needs seq_len %% 256 == 0 (got %lld)", (long long)args->seq_len);
+    // (the persistent kernel's Q request assumes it: a separate fix for every entry point)
+    if (args->seq_stride % 128 != 0)
+        return fail(FA_ERR_SHAPE, "fa_fwd_launch_lse needs seq_stride %% 128 == 0 (got %lld)", (long long)args->seq_stride);
+    return launch_ex_impl(args, opts, stream, lse);
+}
+
+namespace {
+// one stride set of the backward: positive multiples of 8, 32-bit per-lane row offsets inside a 256-row block
+int check_strides(const char *which, int64_t batch, int64_t n_heads, int64_t bs, int64_t ss, int64_t hs) {
+    if (ss <= 0 || bs < 0 || hs < 0 || (batch > 1 && bs == 0) || (n_heads > 1 && hs == 0))
+        return fail(FA_ERR_SHAPE, "%s strides must be positive (batch %lld, seq %lld, head %lld elements)", which, (long long)bs,
+                    (long long)ss, (long long)hs);
+    if ((bs | ss | hs) & 7) return fail(FA_ERR_ALIGN, "%s strides must be multiples of 8 elements (16 bytes)", which);
+    if (ss > (int64_t)0xffffffffLL / (2 * 256))
+        return fail(FA_ERR_SHAPE, "%s seq_stride %lld too large: 256 rows * seq_stride * 2 bytes must fit 32 bits", which, (long long)ss);
+    return FA_OK;
+}
+
+int bwd_validate(const fa_bwd_args *a) {
+    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
+    if (a->dtype != FA_FP16 && a->dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
+    if (a->d_head != 128) return fail(FA_ERR_SHAPE, "the backward supports d_head = 128 only (got %lld)", (long long)a->d_head);
+    if (a->batch <= 0 || a->seq_len <= 0 || a->n_heads <= 0) return fail(FA_ERR_SHAPE, "batch, seq_len and n_heads must be positive");
+    if (a->seq_len % 256 != 0)
+        return fail(FA_ERR_SHAPE, "the backward needs seq_len %% 256 == 0 (got %lld)", (long long)a->seq_len);
+    if (a->seq_len > INT32_MAX / 2 || a->batch * a->n_heads > INT32_MAX / 2 || a->batch * a->n_heads * (a->seq_len / 128) > INT32_MAX)
+        return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
+    int rc = check_strides("qkv", a->batch, a->n_heads, a->qkv_batch_stride, a->qkv_seq_stride, a->qkv_head_stride);
+    if (rc != FA_OK) return rc;
+    return check_strides("out", a->batch, a->n_heads, a->out_batch_stride, a->out_seq_stride, a->out_head_stride);
+}
+}  // namespace
+
+int64_t fa_bwd_workspace_bytes(const fa_bwd_args *args) {
+    const int rc = bwd_validate(args);
+    if (rc != FA_OK) return rc;
+    return (int64_t)sizeof(float) * args->batch * args->n_heads * args->seq_len;
+}
+
+int fa_bwd_launch(const fa_bwd_args *a, void *stream, float *ms) {
+    int rc = bwd_validate(a);
+    if (rc != FA_OK) return rc;
+    if (!a->q || !a->k || !a->v || !a->o || !a->dout || !a->dq || !a->dk || !a->dv)
+        return fail(FA_ERR_NULL, "null tensor pointer (q, k, v, o, dout, dq, dk and dv are all needed)");
+    if (!a->lse) return fail(FA_ERR_NULL, "lse is null: the backward needs the forward's (batch, n_heads, seq_len) fp32 lse");
+    if (!a->workspace) return fail(FA_ERR_NULL, "workspace is null: allocate fa_bwd_workspace_bytes(args) bytes of device memory");
+    if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o | (uintptr_t)a->dout | (uintptr_t)a->dq |
+         (uintptr_t)a->dk | (uintptr_t)a->dv) & 15)
+        return fail(FA_ERR_ALIGN, "q, k, v, o, dout, dq, dk, dv must be 16-byte aligned");
+    // (the kernels read lse and delta as single floats)
+    if (((uintptr_t)a->lse | (uintptr_t)a->workspace) & 3) return fail(FA_ERR_ALIGN, "lse and workspace must be 4-byte aligned");
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    fa::BwdArgs ba;
+    ba.q = (const uint16_t *)a->q;
+    ba.k = (const uint16_t *)a->k;
+    ba.v = (const uint16_t *)a->v;
+    ba.o = (const uint16_t *)a->o;
+    ba.dout = (const uint16_t *)a->dout;
+    ba.lse = a->lse;
+    ba.delta = (float *)a->workspace;
+    ba.dq = (uint16_t *)a->dq;
+    ba.dk = (uint16_t *)a->dk;
+    ba.dv = (uint16_t *)a->dv;
+    ba.qkv_bs = a->qkv_batch_stride;
+    ba.qkv_ss = a->qkv_seq_stride;
+    ba.qkv_hs = a->qkv_head_stride;
+    ba.out_bs = a->out_batch_stride;
+    ba.out_ss = a->out_seq_stride;
+    ba.out_hs = a->out_head_stride;
+    ba.seq_len = (int32_t)a->seq_len;
+    ba.n_heads = (int32_t)a->n_heads;
+    ba.n_bh = (int32_t)(a->batch * a->n_heads);
+    const hipStream_t s = (hipStream_t)stream;
+    if (!ms) {
+        const hipError_t hrc = fa::bwd_enqueue(ba, a->dtype, a->causal != 0, s);
+        return hrc == hipSuccess ? FA_OK : fail(FA_ERR_LAUNCH, "hipLaunchKernel (backward): %s", hipGetErrorString(hrc));
+    }
+    hipEvent_t start = nullptr, stop = nullptr;
+    hipError_t hrc = hipEventCreate(&start);
+    if (hrc == hipSuccess) hrc = hipEventCreate(&stop);
+    if (hrc == hipSuccess) hrc = hipEventRecord(start, s);
+    hipError_t lrc = hipSuccess;
+    if (hrc == hipSuccess) {
+        lrc = fa::bwd_enqueue(ba, a->dtype, a->causal != 0, s);
+        hrc = hipEventRecord(stop, s);
+        if (hrc == hipSuccess) hrc = hipEventSynchronize(stop);
+    }
+    float elapsed = 0.0f;
+    if (hrc == hipSuccess && lrc == hipSuccess) hrc = hipEventElapsedTime(&elapsed, start, stop);
+    if (start) (void)hipEventDestroy(start);
+    if (stop) (void)hipEventDestroy(stop);
+    if (lrc != hipSuccess) return fail(FA_ERR_LAUNCH, "hipLaunchKernel (backward): %s", hipGetErrorString(lrc));
+    if (hrc != hipSuccess) return fail(FA_ERR_LAUNCH, "event timing / kernel execution: %s", hipGetErrorString(hrc));
+    *ms = elapsed;
+    return FA_OK;
 }
 
 static void add_slot(const AdaptiveState &ad, int idx, fa_adaptive_info *out) {

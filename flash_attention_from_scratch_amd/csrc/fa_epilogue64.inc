@@ -55,9 +55,22 @@
                 // the first tile's LDS round trip and row stores, and goes through the staging area behind them
                 constexpr bool OVL = (TUNE & 512) != 0 && QT == 2;
                 u32x2 w_def[OVL ? DTILES : 1][4];
+                // LSE: this item's rows of lse (scalar: the item's batch*head from its ordinal)
+                float *lse_rows = nullptr;
+                if constexpr (LSE) {
+                    int bh_l, qb_l;
+                    coords_of(ord, bh_l, qb_l);
+                    lse_rows = lse + (bh_l * lse_len + qb_c * TR::kBr + wave * TR::kRowsPerWave);
+                }
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) {
                     const float l_row = pair_sum(rs[qt][0] + rs[qt][1]);
+                    if constexpr (LSE) {
+                        // ln sum_j exp(s_j / sqrt d) = (log2 l + m c) ln 2, from the reference the row ended with: -neg_msc = m c, the
+                        // running max (lazy form, second pass) or the first tile's max less the guard's binades (speculative first pass).
+                        // Row r31 of Q tile qt; both lane halves hold it.  A failed item's rows are rewritten by the second pass.
+                        if (hi == 0) lse_rows[qt * 32 + r31] = (__builtin_amdgcn_logf(l_row) - neg_msc[qt]) * 0.693147180559945309f;
+                    }
                     if constexpr (FAST) {
                         // every P of the row is <= l: below the limit nothing overflowed on the way (fp32 exp2, the
                         // 16-bit P, fp32 O); NaN fails the compare too.  A failed item is stored all the same (its

@@ -86,10 +86,33 @@ template <int QT, int NW = 4> struct RingTraits {
 // sinks sit (FWD below).  Which way an item walks is a function of its own Q block and the device's CU count, never of
 // the batch it sits in: (qb / (gridDim.x / 8)) & 1.  Same tiles, same arithmetic per tile; the fp32 sums add up in
 // the other order.  Everything else (the second pass, the other forms) keeps its order.
+// LSE (the training path, fa_fwd_launch_lse): the same body as fa_fwd_kernel64_lse, which also writes lse[bh, row] = ln sum_j
+// exp(s_j / sqrt d) (fa_epilogue64.inc).  Only fa_inst_lse.hip defines FA_KERNEL64_LSE, and gets that kernel INSTEAD of this
+// one: the product's kernels keep their names and, compiled from the same text, their code.
+struct KernelArgsLse {
+    KernelArgs base;
+    float *lse;   // (n_bh, seq_len) fp32
+};
+typedef void (*kernel_fn_lse)(const KernelArgsLse);
+#ifndef FA_KERNEL64_LSE
 template <int DT, bool MASK = false, int ABL = 0, bool RAG = false, bool SPEC = false, bool PSQ = false, int QTP = 2, bool ALT = false, int NW = 4>
 __global__ void
 __launch_bounds__(64 * NW, 1)
 fa_fwd_kernel64(const KernelArgs args) {
+    constexpr bool LSE = false;
+    float *const lse = nullptr;
+    const int lse_len = 0;
+#else
+template <int DT, bool MASK, bool SPEC, int ABL = 0, bool RAG = false, bool PSQ = false, int QTP = 2, bool ALT = false, int NW = 4>
+__global__ void __launch_bounds__(256, 1) fa_fwd_kernel64_lse(const KernelArgsLse args_lse) {
+    static_assert(QTP == 2 && NW == 4 && !RAG && !PSQ && !ALT, "the row log-sum-exp: the 64-row plain and causal forms");
+    constexpr bool LSE = true;
+    const KernelArgs &args = args_lse.base;
+    // (the epilogue's lse base and row count live in VGPRs: in SGPRs they cost the general visits spill reloads)
+    float *lse = args_lse.lse;
+    int lse_len = args.seq_len;
+    asm volatile("" : "+v"(lse), "+v"(lse_len));
+#endif
     static_assert(NW == 4 || (NW == 8 && QTP == 1 && !MASK && !PSQ && !ALT && ABL == 0), "eight waves: the one-Q-tile-per-wave plain forms");
     static_assert(!RAG || MASK, "the ragged form is a masked variant");
     static_assert(!PSQ || !MASK, "the pre-scaled Q is built for the plain form");

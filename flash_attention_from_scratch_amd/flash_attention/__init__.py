@@ -3,7 +3,12 @@
 
     forward(kernel_cfg, q, k, v, o=None) -> Tensor
     forward_timed(kernel_cfg, q, k, v, o=None) -> (Tensor, milliseconds)
+
+This build's additions: forward_ex (causal, ragged seq_len, the row log-sum-exp), backward (dQ, dK, dV) and
+attention (a torch.autograd.Function over the two).
 """
+
+import torch
 
 from .. import flash_attention_kernels
 
@@ -17,11 +22,55 @@ def forward_timed(kernel_cfg, q, k, v, o=None):
     return out, runtime_ms
 
 
-def forward_ex(kernel_cfg, q, k, v, o=None, causal=False, timed=False, stats=None):
+def forward_ex(kernel_cfg, q, k, v, o=None, causal=False, timed=False, stats=None, return_lse=False):
     """Scope wideners beyond the reference API: optional causal mask, and any
     seq_len (not only multiples of B_r / B_c).  `stats`: optional device tensor of two 32-bit counters
     (items computed, items the speculative softmax computed twice; fa_fwd_stats in include/fa_hip.h).
-    Returns Tensor, or (Tensor, ms) if timed."""
+    Returns Tensor, or (Tensor, ms) if timed.  return_lse: also the row log-sum-exp, an fp32 (batch, n_heads, seq_len)
+    tensor (ln sum_j exp(q_i . k_j / sqrt d)), with the same O bits -> (Tensor, lse) or (Tensor, lse, ms); RuntimeError
+    where the configuration has no such form (fa_fwd_launch_lse in include/fa_hip.h)."""
+    if return_lse:
+        out, lse, ms = flash_attention_kernels.forward_lse(kernel_cfg, q, k, v, o, benchmark=timed, causal=causal,
+                                                           allow_ragged=True, stats=stats)
+        return (out, lse, ms) if timed else (out, lse)
     out, ms = flash_attention_kernels.forward(kernel_cfg, q, k, v, o, benchmark=timed, causal=causal,
                                               allow_ragged=True, stats=stats)
     return (out, ms) if timed else out
+
+
+def backward(q, k, v, o, lse, dout, causal=False, timed=False):
+    """dQ, dK, dV from the forward's o and lse (forward_ex(..., return_lse=True)) and the gradient dout -> (dq, dk, dv), or
+    (dq, dk, dv, ms) if timed.  Deterministic: the same inputs give the same bits."""
+    return flash_attention_kernels.backward(q, k, v, o, lse, dout, causal=causal, timed=timed)
+
+
+def _needs_copy(t):
+    # the forward with LSE needs seq_stride % 128 == 0 and one stride set for q, k, v
+    return t.stride(3) != 1 or t.stride(1) % 128 != 0
+
+
+class _Attention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, causal):
+        from flash_helpers import kernel_configs as kc
+
+        if _needs_copy(q) or k.stride() != q.stride() or v.stride() != q.stride():
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        name = kc.DType.BF16 if q.dtype == torch.bfloat16 else kc.DType.FP16
+        cfg = kc.best_config(name, q.shape[1], masked=causal)
+        o, lse = forward_ex(cfg, q, k, v, causal=causal, return_lse=True)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.causal = causal
+        return o
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, o, lse = ctx.saved_tensors
+        dq, dk, dv = backward(q, k, v, o, lse, dout.contiguous(), causal=ctx.causal)
+        return dq, dk, dv, None
+
+
+def attention(q, k, v, causal=False):
+    """softmax(q k^T / sqrt d) v with gradients: (batch, seq_len, n_heads, 128) bf16 / fp16 tensors, seq_len % 256 == 0.
+    The forward is best_config(dtype, seq_len, masked=causal) with the row log-sum-exp; the backward is the HIP backward."""
+    return _Attention.apply(q, k, v, causal)

@@ -55,6 +55,22 @@ def forward(kernel_cfg, q, k, v, o=None, benchmark=False, causal=False, allow_ra
     int32 / uint32 device tensor of >= 2 elements whose [0] the kernel increases by the number of work
     items it computed and whose [1] by the number the speculative softmax had to compute twice
     (fa_fwd_stats)."""
+    return _forward(kernel_cfg, q, k, v, o, benchmark, causal, allow_ragged, stats, None)
+
+
+def forward_lse(kernel_cfg, q, k, v, o=None, benchmark=False, causal=False, allow_ragged=False, stats=None):
+    """forward(), and the row log-sum-exp: -> (o, lse, ms), lse an fp32 (batch, n_heads, seq_len) tensor,
+    lse[b, h, i] = ln sum_j exp(q_i . k_j / sqrt(d)) (fa_fwd_launch_lse).  The same O bits as forward() with the same
+    arguments.  RuntimeError where the configuration has no such form (only the persistent (256, 64, 4) + buffer
+    configuration at d_head 128 has one; seq_len % 256 == 0, seq_stride % 128 == 0)."""
+    if q.dim() != 4:
+        raise RuntimeError("q must have shape (batch, seq_len, n_heads, d_head)")
+    lse = torch.empty((q.shape[0], q.shape[2], q.shape[1]), dtype=torch.float32, device=q.device)
+    o, ms = _forward(kernel_cfg, q, k, v, o, benchmark, causal, allow_ragged, stats, lse)
+    return o, lse, ms
+
+
+def _forward(kernel_cfg, q, k, v, o, benchmark, causal, allow_ragged, stats, lse):
     masked = bool(causal or allow_ragged)
     _check_input(q, "q")
     _check_input(k, "k")
@@ -130,6 +146,15 @@ def forward(kernel_cfg, q, k, v, o=None, benchmark=False, causal=False, allow_ra
         stats_ptr = stats.data_ptr()
     with torch.cuda.device(q.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        if lse is not None:
+            ms = ctypes.c_float(0.0)
+            opts = _capi.make_opts(causal=causal, allow_ragged=allow_ragged, speculative=speculative,
+                                   prescaled_q=prescaled_q, ms=ms if benchmark else None, stats_ptr=stats_ptr)
+            if not lib.fa_fwd_lse_supported(ctypes.byref(cfg), ctypes.byref(opts)):
+                raise RuntimeError("Kernel configuration has no form that writes the row log-sum-exp (only the persistent "
+                                   "(B_r 256, B_c 64, 4 warps) + buffer configuration at d_head 128, without prescaled_q)")
+            _capi.check(lib.fa_fwd_launch_lse(ctypes.byref(args), ctypes.byref(opts), ctypes.c_void_p(lse.data_ptr()), stream))
+            return o, float(ms.value)
         if masked or speculative or prescaled_q or stats_ptr is not None:
             ms = ctypes.c_float(0.0)
             opts = _capi.make_opts(causal=causal, allow_ragged=allow_ragged, speculative=speculative,
@@ -142,3 +167,47 @@ def forward(kernel_cfg, q, k, v, o=None, benchmark=False, causal=False, allow_ra
             return o, float(ms.value)
         _capi.check(lib.fa_fwd_launch(ctypes.byref(args), stream))
     return o, 0.0
+
+
+def backward(q, k, v, o, lse, dout, causal=False, timed=False):
+    """dQ, dK, dV of attention softmax(q k^T / sqrt d) v (causal: key j contributes to query i iff j <= i) from the forward's
+    o and lse (forward_lse) and the gradient dout (fa_bwd_launch).  q, k, v share one stride set (a packed QKV view passes
+    as it is), o and dout another; the gradients come back contiguous.  d_head 128, bf16 / fp16, seq_len % 256 == 0.  The
+    workspace is allocated with torch on the tensors' stream.  -> (dq, dk, dv), or (dq, dk, dv, ms) if timed (blocks)."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (dout, "dout"), (lse, "lse")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError("Only fp16 and bf16 are supported")
+    if any(t.dtype != q.dtype for t in (k, v, o, dout)):
+        raise RuntimeError("q, k, v, o and dout must have the same data type")
+    if q.dim() != 4 or any(t.shape != q.shape for t in (k, v, o, dout)):
+        raise RuntimeError("q, k, v, o and dout must have one shape (batch, seq_len, n_heads, d_head)")
+    if k.stride() != q.stride() or v.stride() != q.stride():
+        raise RuntimeError("q, k and v must share their strides")
+    if q.stride(3) != 1:
+        raise RuntimeError("the last dimension of q, k and v must be contiguous")
+    o, dout = o.contiguous(), dout.contiguous()
+    batch, seq_len, n_heads, d_head = q.shape
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (batch, n_heads, seq_len) or not lse.is_contiguous():
+        raise RuntimeError("lse must be a contiguous fp32 (batch, n_heads, seq_len) tensor")
+    dq, dk, dv = torch.empty_like(o), torch.empty_like(o), torch.empty_like(o)
+    lib = _capi.load()
+    args = _capi.FaBwdArgs(
+        q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), o=o.data_ptr(), dout=dout.data_ptr(),
+        lse=ctypes.cast(ctypes.c_void_p(lse.data_ptr()), ctypes.POINTER(ctypes.c_float)),
+        dq=dq.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), workspace=None,
+        batch=batch, seq_len=seq_len, n_heads=n_heads, d_head=d_head,
+        qkv_batch_stride=q.stride(0), qkv_seq_stride=q.stride(1), qkv_head_stride=q.stride(2),
+        out_batch_stride=o.stride(0), out_seq_stride=o.stride(1), out_head_stride=o.stride(2),
+        dtype=15 if q.dtype == torch.bfloat16 else 5, causal=1 if causal else 0,
+    )
+    nbytes = lib.fa_bwd_workspace_bytes(ctypes.byref(args))
+    _capi.check(nbytes if nbytes < 0 else 0)
+    with torch.cuda.device(q.device):
+        workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)   # (on the current stream's allocator)
+        args.workspace = workspace.data_ptr()
+        stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        ms = ctypes.c_float(0.0)
+        _capi.check(lib.fa_bwd_launch(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
+    return (dq, dk, dv, float(ms.value)) if timed else (dq, dk, dv)

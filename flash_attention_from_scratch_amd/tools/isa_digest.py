@@ -36,11 +36,12 @@ def hipcc_version():
     return " | ".join(keep)
 
 
-def visits_of(text, kernel_regex, lo=56, hi=1 << 30):
+def visits_of(text, kernel_regex, lo=56, hi=1 << 30, prefix="_ZN2fa15fa_fwd_kernel64", suffix="EEvNS_10KernelArgsE"):
     """-> [{op class: count, "instructions": n}] for the visit blocks of the kernel matching `kernel_regex`: the basic blocks
     with lo <= MFMAs <= hi (the 64-row visits by default; lo, hi = 28, 32 gives the half-item visits of the round-6 second
-    pass, one 32-row Q tile per wave = 16 + 16 MFMAs)."""
-    m = re.search(r"^(_ZN2fa15fa_fwd_kernel64" + kernel_regex + r"EEvNS_10KernelArgsE):.*?\n(.*?)\n\s+s_endpgm", text, flags=re.S | re.M)
+    pass, one 32-row Q tile per wave = 16 + 16 MFMAs).  prefix / suffix: the mangled name around the template arguments
+    (the forms that write the row log-sum-exp: "_ZN2fa19fa_fwd_kernel64_lse", "EEvNS_13KernelArgsLseE")."""
+    m = re.search(r"^(" + prefix + kernel_regex + suffix + r"):.*?\n(.*?)\n\s+s_endpgm", text, flags=re.S | re.M)
     if not m:
         return None
     blocks, cur = [], ("entry", [])

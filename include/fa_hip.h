@@ -273,6 +273,63 @@ int fa_fwd_ex_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
 int fa_fwd_query(const fa_fwd_config *cfg, const fa_fwd_opts *opts, fa_kernel_info *out);
 int fa_fwd_launch_ex(const fa_fwd_args *args, const fa_fwd_opts *opts, void *stream);
 
+/*
+ * The training path: the forward that also writes the row log-sum-exp, and the backward (dQ, dK, dV).
+ *
+ * lse[b, h, i] = ln sum_j exp(q_i . k_j / sqrt(d_head)) over the keys query i sees (causal: j <= i), fp32, in a contiguous
+ * (batch, n_heads, seq_len) DEVICE buffer -- the convention of flash-attn's softmax_lse and of torch's flash SDPA logsumexp.
+ *
+ * fa_fwd_lse_supported: 1 if fa_fwd_launch_lse serves cfg with these options, else 0.  Served: the persistent 64-rows-per-
+ * wave configuration (B_r 256, B_c 64, 4 warps) + buffer, d_head 128, bf16 / fp16, plain or causal, speculative (1 or 2) or
+ * not, allow_ragged or not (a ragged seq_len is refused at the launch).  Not served: prescaled_q, every other configuration
+ * (the 32- and 16-rows-per-wave kernels, the ring form).
+ * fa_fwd_launch_lse: fa_fwd_launch_ex (opts: causal, speculative, ms, stats) with the same O bits as that call on the same
+ * device variant, plus lse.  seq_len must be a multiple of 256 and seq_stride a multiple of 128 (FA_ERR_SHAPE otherwise).
+ * Long sequences that fa_fwd_launch_ex sends through the alternating-direction form (fa_kernel_info.alt_form) take the
+ * plain walk here: O then differs from fa_fwd_launch_ex in the fp32 summation order only.
+ */
+int fa_fwd_lse_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_lse(const fa_fwd_args *args, const fa_fwd_opts *opts, float *lse, void *stream);
+
+/*
+ * One backward: given Q, K, V, the forward's O and lse and the gradient dO, writes dQ, dK and dV.  d_head 128, bf16 / fp16,
+ * seq_len a multiple of 256, causal (key j contributes to query i iff j <= i) or not.  All pointers are DEVICE pointers.
+ * q, k, v, o, dout, dq, dk, dv point to (batch, seq_len, n_heads, d_head) tensors of the 16-bit dtype with a contiguous
+ * last dimension, 16-byte aligned; lse and workspace (fp32) need 4-byte alignment.
+ * q, k, v share the qkv_* strides (a packed (B, S, 3, H, D) QKV passes without a copy), o, dout, dq, dk, dv the out_*
+ * strides; all strides are in elements, positive multiples of 8, and seq_stride * 256 * 2 bytes must fit 32 bits.
+ * dq, dk, dv are overwritten, and may alias none of the inputs.  workspace: fa_bwd_workspace_bytes(args) bytes of device
+ * memory (fp32 delta_i = sum_d dO_id O_id), private to the call until it completes.
+ * Deterministic: no float atomics, no ordering between workgroups -- the same inputs give the same bits.
+ * fa_bwd_launch enqueues on `stream`; ms != NULL brackets the launches with events, blocks and returns the elapsed ms.
+ */
+typedef struct fa_bwd_args {
+    const void *q;
+    const void *k;
+    const void *v;
+    const void *o;
+    const void *dout;
+    const float *lse;        /* (batch, n_heads, seq_len) fp32, contiguous */
+    void *dq;
+    void *dk;
+    void *dv;
+    void *workspace;
+    int64_t batch;
+    int64_t seq_len;
+    int64_t n_heads;
+    int64_t d_head;
+    int64_t qkv_batch_stride;
+    int64_t qkv_seq_stride;
+    int64_t qkv_head_stride;
+    int64_t out_batch_stride;
+    int64_t out_seq_stride;
+    int64_t out_head_stride;
+    int32_t dtype;           /* fa_dtype */
+    int32_t causal;
+} fa_bwd_args;
+int64_t fa_bwd_workspace_bytes(const fa_bwd_args *args);              /* bytes, or a negative fa_status */
+int fa_bwd_launch(const fa_bwd_args *args, void *stream, float *ms);
+
 /* The adaptive speculative mode's record on `device` (fa_speculative_mode), and a reset of its demotion state (tests,
  * or a caller that knows its data has changed character). */
 int fa_adaptive_state(int device, fa_adaptive_info *out);
