@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_ex_supported", "fa_fwd_launch_ex", "fa_fwd_query",
     "fa_adaptive_state", "fa_adaptive_state_for", "fa_adaptive_reset", "fa_adaptive_simulate", "fa_get_kernel_sized", "fa_fwd_query_sized", "fa_abi_version",
     "fa_fwd_lse_supported", "fa_fwd_launch_lse", "fa_bwd_workspace_bytes", "fa_bwd_launch",
+    "fa_fwd_gqa_supported", "fa_fwd_launch_gqa", "fa_bwd_gqa_workspace_bytes", "fa_bwd_launch_gqa",
 )
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
 FA_ABI_VERSION = 6
@@ -91,6 +92,26 @@ class FaBwdArgs(ctypes.Structure):   # fa_bwd_args
         ("out_batch_stride", ctypes.c_int64), ("out_seq_stride", ctypes.c_int64), ("out_head_stride", ctypes.c_int64),
         ("dtype", ctypes.c_int32), ("causal", ctypes.c_int32),
     ]
+
+
+class FaKvLayout(ctypes.Structure):   # fa_kv_layout (grouped-query attention: K's and V's heads and strides)
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("n_kv_heads", ctypes.c_int64),
+        ("kv_batch_stride", ctypes.c_int64), ("kv_seq_stride", ctypes.c_int64), ("kv_head_stride", ctypes.c_int64),
+    ]
+
+
+class FaBwdGqaArgs(ctypes.Structure):   # fa_bwd_gqa_args
+    _fields_ = [
+        ("base", FaBwdArgs), ("n_kv_heads", ctypes.c_int64),
+        ("kv_batch_stride", ctypes.c_int64), ("kv_seq_stride", ctypes.c_int64), ("kv_head_stride", ctypes.c_int64),
+        ("dkv_batch_stride", ctypes.c_int64), ("dkv_seq_stride", ctypes.c_int64), ("dkv_head_stride", ctypes.c_int64),
+    ]
+
+
+def make_kv_layout(n_kv_heads, batch_stride, seq_stride, head_stride):
+    return FaKvLayout(struct_size=ctypes.sizeof(FaKvLayout), n_kv_heads=n_kv_heads, kv_batch_stride=batch_stride,
+                      kv_seq_stride=seq_stride, kv_head_stride=head_stride)
 
 
 class FaAdaptiveInfo(ctypes.Structure):
@@ -188,6 +209,14 @@ def load():
     lib.fa_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaBwdArgs)]
     lib.fa_bwd_launch.restype = ctypes.c_int
     lib.fa_bwd_launch.argtypes = [ctypes.POINTER(FaBwdArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    lib.fa_fwd_gqa_supported.restype = ctypes.c_int
+    lib.fa_fwd_gqa_supported.argtypes = [cfg_p, ctypes.POINTER(FaFwdOpts)]
+    lib.fa_fwd_launch_gqa.restype = ctypes.c_int
+    lib.fa_fwd_launch_gqa.argtypes = [args_p, ctypes.POINTER(FaKvLayout), ctypes.POINTER(FaFwdOpts), ctypes.c_void_p, ctypes.c_void_p]
+    lib.fa_bwd_gqa_workspace_bytes.restype = ctypes.c_int64
+    lib.fa_bwd_gqa_workspace_bytes.argtypes = [ctypes.POINTER(FaBwdGqaArgs)]
+    lib.fa_bwd_launch_gqa.restype = ctypes.c_int
+    lib.fa_bwd_launch_gqa.argtypes = [ctypes.POINTER(FaBwdGqaArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p
     lib.fa_last_error.argtypes = []
     lib.fa_version.restype = ctypes.c_char_p

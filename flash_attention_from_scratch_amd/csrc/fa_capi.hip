@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "../../include/fa_hip.h"
-#include "fa_bwd_kernel.hpp"
+#include "fa_bwd_gqa.hpp"
 #include "fa_registry.hpp"
 
 extern "C" {
@@ -32,8 +32,12 @@ namespace fa {
 // fa_inst_lse.hip: the persistent kernel's forms that also write the row log-sum-exp (fa_fwd_kernel64_lse)
 kernel_fn_lse lse_kernel_dt15(bool masked, bool spec);
 kernel_fn_lse lse_kernel_dt5(bool masked, bool spec);
+// fa_inst_gqa.hip: their grouped-query attention forms (fa_fwd_kernel64_gqa)
+kernel_fn_gqa gqa_kernel_dt15(bool masked, bool spec);
+kernel_fn_gqa gqa_kernel_dt5(bool masked, bool spec);
 // fa_bwd.hip: delta, dK / dV and dQ of one backward, enqueued on `s`
 hipError_t bwd_enqueue(const BwdArgs &a, int dtype, bool causal, hipStream_t s);
+hipError_t bwd_gqa_enqueue(const BwdGqaArgs &g, int dtype, bool causal, hipStream_t s);
 }  // namespace fa
 
 namespace {
@@ -243,9 +247,11 @@ void do_init_body(int dev, DeviceState *st) {
         }
     }
     // the forms that also write the row log-sum-exp (fa_fwd_launch_lse): the persistent kernel's LDS
-    for (int i = 0; i < 8; ++i) {
-        const fa::kernel_fn_lse fn = (i & 4) ? fa::lse_kernel_dt5((i & 1) != 0, (i & 2) != 0) : fa::lse_kernel_dt15((i & 1) != 0, (i & 2) != 0);
-        const hipError_t rc = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, fa::RingTraits<2>::kLdsBytes);
+    for (int i = 0; i < 16; ++i) {   // (i & 8: their grouped-query attention forms)
+        const bool masked = (i & 1) != 0, spec = (i & 2) != 0;
+        const void *fn = (i & 8) ? ((i & 4) ? (const void *)fa::gqa_kernel_dt5(masked, spec) : (const void *)fa::gqa_kernel_dt15(masked, spec))
+                                 : ((i & 4) ? (const void *)fa::lse_kernel_dt5(masked, spec) : (const void *)fa::lse_kernel_dt15(masked, spec));
+        const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, fa::RingTraits<2>::kLdsBytes);
         if (rc != hipSuccess) {
             st->status = FA_ERR_LAUNCH;
             snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, LSE form) on device %d: %s", fa::RingTraits<2>::kLdsBytes,
@@ -343,9 +349,11 @@ int validate(const fa_fwd_args *a, const fa::KernelEntry **out, const Want &want
 }
 
 // lse != nullptr (fa_fwd_launch_lse; e is a persistent 64-rows-per-wave entry, checked by the caller): the twin of e's
-// kernel that also writes the row log-sum-exp, always the plain walk (no alternating-direction twin is built)
+// kernel that also writes the row log-sum-exp, always the plain walk (no alternating-direction twin is built); kv != nullptr as
+// well (fa_fwd_launch_gqa, validated by the caller): that kernel's grouped-query attention form
 int launch(const fa_fwd_args *a, const fa::KernelEntry *e, const DeviceState *dev, hipStream_t stream, int causal = 0,
-           fa_fwd_stats *stats = nullptr, uint32_t *redo_flag = nullptr, uint32_t redo_seq = 0, float *lse = nullptr) {
+           fa_fwd_stats *stats = nullptr, uint32_t *redo_flag = nullptr, uint32_t redo_seq = 0, float *lse = nullptr,
+           const fa_kv_layout *kv = nullptr) {
     fa::KernelArgs ka;
     ka.stats = (uint32_t *)stats;
     ka.redo_flag = redo_flag;
@@ -403,6 +411,16 @@ int launch(const fa_fwd_args *a, const fa::KernelEntry *e, const DeviceState *de
         const bool masked = e->masked != 0, spec = e->softmax_mode == FA_SOFTMAX_SPECULATIVE;
         fn = (fa::kernel_fn)(a->cfg.dtype == FA_BF16 ? fa::lse_kernel_dt15(masked, spec) : fa::lse_kernel_dt5(masked, spec));
         params[0] = &kal;
+    }
+    fa::KernelArgsGqa kag{kal, 0, 0, 0, 1};
+    if (lse && kv) {
+        const bool masked = e->masked != 0, spec = e->softmax_mode == FA_SOFTMAX_SPECULATIVE;
+        fn = (fa::kernel_fn)(a->cfg.dtype == FA_BF16 ? fa::gqa_kernel_dt15(masked, spec) : fa::gqa_kernel_dt5(masked, spec));
+        kag.kv_batch_stride = kv->kv_batch_stride;
+        kag.kv_seq_stride = kv->kv_seq_stride;
+        kag.kv_head_stride = kv->kv_head_stride;
+        kag.group = (int32_t)(a->n_heads / kv->n_kv_heads);
+        params[0] = &kag;
     }
     hipError_t rc = hipLaunchKernel((const void *)fn, grid, block, params, (size_t)lds_bytes, stream);
     if (rc != hipSuccess) return fail(FA_ERR_LAUNCH, "hipLaunchKernel: %s", hipGetErrorString(rc));
@@ -465,9 +483,9 @@ struct ProbeHook {
 static int launch_maybe_timed(const fa_fwd_args *args, const fa::KernelEntry *e, const DeviceState *dev,
                               hipStream_t s, int causal, float *ms, fa_fwd_stats *stats = nullptr,
                               uint32_t *redo_flag = nullptr, uint32_t redo_seq = 0, ProbeHook probe = ProbeHook(),
-                              float *lse = nullptr) {
+                              float *lse = nullptr, const fa_kv_layout *kv = nullptr) {
     if (!ms) {
-        const int rc0 = launch(args, e, dev, s, causal, stats, redo_flag, redo_seq, lse);
+        const int rc0 = launch(args, e, dev, s, causal, stats, redo_flag, redo_seq, lse, kv);
         probe.after_launch(rc0, s);
         return rc0;
     }
@@ -477,7 +495,7 @@ static int launch_maybe_timed(const fa_fwd_args *args, const fa::KernelEntry *e,
     if (hrc == hipSuccess) hrc = hipEventRecord(start, s);
     int rc = FA_OK;
     if (hrc == hipSuccess) {
-        rc = launch(args, e, dev, s, causal, stats, redo_flag, redo_seq, lse);
+        rc = launch(args, e, dev, s, causal, stats, redo_flag, redo_seq, lse, kv);
         probe.after_launch(rc, s);
         hrc = hipEventRecord(stop, s);  // (recorded even if the launch failed: nothing is left pending)
         if (hrc == hipSuccess) hrc = hipEventSynchronize(stop);
@@ -579,8 +597,8 @@ static bool lse_form(const fa_fwd_config *cfg, const fa_fwd_opts &o, const fa::K
            !o.prescaled_q && cfg->d_head == 128 && (cfg->dtype == FA_BF16 || cfg->dtype == FA_FP16);
 }
 
-// fa_fwd_launch_ex, and fa_fwd_launch_lse (lse != nullptr; the caller has checked lse_form)
-static int launch_ex_impl(const fa_fwd_args *args, const fa_fwd_opts *opts, void *stream, float *lse) {
+// fa_fwd_launch_ex, fa_fwd_launch_lse (lse != nullptr; the caller has checked lse_form) and fa_fwd_launch_gqa (kv != nullptr too)
+static int launch_ex_impl(const fa_fwd_args *args, const fa_fwd_opts *opts, void *stream, float *lse, const fa_kv_layout *kv = nullptr) {
     fa_fwd_opts o;
     int rc = read_opts(opts, &o);
     if (rc != FA_OK) return rc;
@@ -638,7 +656,7 @@ static int launch_ex_impl(const fa_fwd_args *args, const fa_fwd_opts *opts, void
             }  // (no such sibling: the speculative variant stays)
         }
     }
-    return launch_maybe_timed(args, e, dev, (hipStream_t)stream, o.causal != 0, o.ms, o.stats, redo_flag, redo_seq, hook, lse);
+    return launch_maybe_timed(args, e, dev, (hipStream_t)stream, o.causal != 0, o.ms, o.stats, redo_flag, redo_seq, hook, lse, kv);
 }
 
 int fa_fwd_launch_ex(const fa_fwd_args *args, const fa_fwd_opts *opts, void *stream) {
@@ -709,9 +727,9 @@ int64_t fa_bwd_workspace_bytes(const fa_bwd_args *args) {
     return (int64_t)sizeof(float) * args->batch * args->n_heads * args->seq_len;
 }
 
-int fa_bwd_launch(const fa_bwd_args *a, void *stream, float *ms) {
-    int rc = bwd_validate(a);
-    if (rc != FA_OK) return rc;
+namespace {
+// fa_bwd_launch / fa_bwd_launch_gqa: a validated a's pointer checks, then the kernels' argument block (strides as given)
+int bwd_prepare(const fa_bwd_args *a, fa::BwdArgs *out) {
     if (!a->q || !a->k || !a->v || !a->o || !a->dout || !a->dq || !a->dk || !a->dv)
         return fail(FA_ERR_NULL, "null tensor pointer (q, k, v, o, dout, dq, dk and dv are all needed)");
     if (!a->lse) return fail(FA_ERR_NULL, "lse is null: the backward needs the forward's (batch, n_heads, seq_len) fp32 lse");
@@ -721,9 +739,7 @@ int fa_bwd_launch(const fa_bwd_args *a, void *stream, float *ms) {
         return fail(FA_ERR_ALIGN, "q, k, v, o, dout, dq, dk, dv must be 16-byte aligned");
     // (the kernels read lse and delta as single floats)
     if (((uintptr_t)a->lse | (uintptr_t)a->workspace) & 3) return fail(FA_ERR_ALIGN, "lse and workspace must be 4-byte aligned");
-    DeviceState *dev = current_device(&rc);
-    if (!dev) return rc;
-    fa::BwdArgs ba;
+    fa::BwdArgs &ba = *out;
     ba.q = (const uint16_t *)a->q;
     ba.k = (const uint16_t *)a->k;
     ba.v = (const uint16_t *)a->v;
@@ -743,9 +759,14 @@ int fa_bwd_launch(const fa_bwd_args *a, void *stream, float *ms) {
     ba.seq_len = (int32_t)a->seq_len;
     ba.n_heads = (int32_t)a->n_heads;
     ba.n_bh = (int32_t)(a->batch * a->n_heads);
-    const hipStream_t s = (hipStream_t)stream;
+    return FA_OK;
+}
+
+// enqueue() on s; ms != nullptr: bracketed by events, blocking, the elapsed ms into *ms
+extern "C++" {   // (a template, inside the extern "C" block)
+template <class F> int bwd_run(F enqueue, hipStream_t s, float *ms) {
     if (!ms) {
-        const hipError_t hrc = fa::bwd_enqueue(ba, a->dtype, a->causal != 0, s);
+        const hipError_t hrc = enqueue();
         return hrc == hipSuccess ? FA_OK : fail(FA_ERR_LAUNCH, "hipLaunchKernel (backward): %s", hipGetErrorString(hrc));
     }
     hipEvent_t start = nullptr, stop = nullptr;
@@ -754,7 +775,7 @@ int fa_bwd_launch(const fa_bwd_args *a, void *stream, float *ms) {
     if (hrc == hipSuccess) hrc = hipEventRecord(start, s);
     hipError_t lrc = hipSuccess;
     if (hrc == hipSuccess) {
-        lrc = fa::bwd_enqueue(ba, a->dtype, a->causal != 0, s);
+        lrc = enqueue();
         hrc = hipEventRecord(stop, s);
         if (hrc == hipSuccess) hrc = hipEventSynchronize(stop);
     }
@@ -766,6 +787,114 @@ int fa_bwd_launch(const fa_bwd_args *a, void *stream, float *ms) {
     if (hrc != hipSuccess) return fail(FA_ERR_LAUNCH, "event timing / kernel execution: %s", hipGetErrorString(hrc));
     *ms = elapsed;
     return FA_OK;
+}
+}
+
+// Grouped-query attention: n_kv_heads divides n_heads, and K / V strides the kernels can address
+int kv_validate(const char *which, int64_t batch, int64_t n_heads, int64_t n_kv_heads, int64_t bs, int64_t ss, int64_t hs) {
+    if (n_kv_heads < 1 || n_kv_heads > n_heads || n_heads % n_kv_heads != 0)
+        return fail(FA_ERR_SHAPE, "grouped-query attention needs n_kv_heads (%lld) to divide n_heads (%lld)", (long long)n_kv_heads,
+                    (long long)n_heads);
+    return check_strides(which, batch, n_kv_heads, bs, ss, hs);
+}
+
+int bwd_gqa_validate(const fa_bwd_gqa_args *g) {
+    if (!g) return fail(FA_ERR_NULL, "null pointer argument");
+    int rc = bwd_validate(&g->base);
+    if (rc != FA_OK) return rc;
+    const fa_bwd_args &a = g->base;
+    rc = kv_validate("kv", a.batch, a.n_heads, g->n_kv_heads, g->kv_batch_stride, g->kv_seq_stride, g->kv_head_stride);
+    if (rc != FA_OK) return rc;
+    return check_strides("dkv", a.batch, g->n_kv_heads, g->dkv_batch_stride, g->dkv_seq_stride, g->dkv_head_stride);
+}
+
+// Workgroups per (K / V head, key block) of the dK / dV kernel: the smallest divisor of the group that gives the grid at least
+// 256 workgroups (one per CU of an MI355X), 1024 causal (a causal block's sweep is 1 .. seq_len / 128 tiles long: the
+// dispatcher evens that out only with several workgroups per CU).  A function of the shape alone.
+int64_t bwd_gqa_split(const fa_bwd_gqa_args *g) {
+    const fa_bwd_args &a = g->base;
+    const int64_t group = a.n_heads / g->n_kv_heads, wgs = a.batch * g->n_kv_heads * (a.seq_len / 128);
+    const int64_t want = a.causal ? 1024 : 256;
+    for (int64_t s = 1; s < group; ++s)
+        if (group % s == 0 && wgs * s >= want) return s;
+    return group;
+}
+
+int64_t bwd_gqa_part_bytes(const fa_bwd_gqa_args *g, int64_t split) {   // the split's fp32 partials
+    const fa_bwd_args &a = g->base;
+    return split > 1 ? (int64_t)sizeof(float) * a.batch * g->n_kv_heads * split * a.seq_len * 2 * 128 : 0;
+}
+}  // namespace
+
+int fa_bwd_launch(const fa_bwd_args *a, void *stream, float *ms) {
+    int rc = bwd_validate(a);
+    if (rc != FA_OK) return rc;
+    fa::BwdArgs ba;
+    rc = bwd_prepare(a, &ba);
+    if (rc != FA_OK) return rc;
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    return bwd_run([&] { return fa::bwd_enqueue(ba, a->dtype, a->causal != 0, s); }, s, ms);
+}
+
+int64_t fa_bwd_gqa_workspace_bytes(const fa_bwd_gqa_args *g) {
+    const int rc = bwd_gqa_validate(g);
+    if (rc != FA_OK) return rc;
+    return fa_bwd_workspace_bytes(&g->base) + bwd_gqa_part_bytes(g, bwd_gqa_split(g));
+}
+
+int fa_bwd_launch_gqa(const fa_bwd_gqa_args *g, void *stream, float *ms) {
+    int rc = bwd_gqa_validate(g);
+    if (rc != FA_OK) return rc;
+    const fa_bwd_args *a = &g->base;
+    fa::BwdGqaArgs ga;
+    rc = bwd_prepare(a, &ga.base);
+    if (rc != FA_OK) return rc;
+    const int64_t split = bwd_gqa_split(g);
+    if (split > 1 && ((uintptr_t)a->workspace & 15))
+        return fail(FA_ERR_ALIGN, "workspace must be 16-byte aligned (it holds the fp32 partials of dK / dV)");
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    ga.kv_bs = g->kv_batch_stride;
+    ga.kv_ss = g->kv_seq_stride;
+    ga.kv_hs = g->kv_head_stride;
+    ga.dkv_bs = g->dkv_batch_stride;
+    ga.dkv_ss = g->dkv_seq_stride;
+    ga.dkv_hs = g->dkv_head_stride;
+    // (behind delta: B * H * seq_len floats, a multiple of 1 KiB)
+    ga.part = split > 1 ? (float *)((char *)a->workspace + fa_bwd_workspace_bytes(a)) : nullptr;
+    ga.group = (int32_t)(a->n_heads / g->n_kv_heads);
+    ga.split = (int32_t)split;
+    const hipStream_t s = (hipStream_t)stream;
+    return bwd_run([&] { return fa::bwd_gqa_enqueue(ga, a->dtype, a->causal != 0, s); }, s, ms);
+}
+
+int fa_fwd_gqa_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) {
+    return fa_fwd_lse_supported(cfg, opts);
+}
+
+int fa_fwd_launch_gqa(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_fwd_opts *opts, float *lse, void *stream) {
+    if (!args || !kv) return fail(FA_ERR_NULL, "null pointer argument");
+    if (!lse) return fail(FA_ERR_NULL, "lse is null: fa_fwd_launch_gqa needs a (batch, n_heads, seq_len) fp32 buffer");
+    if (kv->struct_size < sizeof(fa_kv_layout))
+        return fail(FA_ERR_SHAPE, "fa_kv_layout.struct_size (%u) is smaller than this library's (%zu)", kv->struct_size, sizeof(fa_kv_layout));
+    fa_fwd_opts o;
+    int rc = read_opts(opts, &o);
+    if (rc != FA_OK) return rc;
+    if (!fa_fwd_gqa_supported(&args->cfg, opts))
+        return fail(FA_ERR_NO_KERNEL, "grouped-query attention is served by the persistent (B_r 256, B_c 64, 4 warps) + buffer "
+                                      "configuration at d_head 128 only, plain or causal, without prescaled_q");
+    if (args->n_heads <= 0) return fail(FA_ERR_SHAPE, "batch, seq_len and n_heads must be positive");
+    rc = kv_validate("kv", args->batch, args->n_heads, kv->n_kv_heads, kv->kv_batch_stride, kv->kv_seq_stride, kv->kv_head_stride);
+    if (rc != FA_OK) return rc;
+    // (fa_fwd_launch_lse checks seq_len, Q's seq_stride and lse's alignment, and validates the rest before any HIP call)
+    if (args->seq_len % 256 != 0)
+        return fail(FA_ERR_SHAPE, "fa_fwd_launch_gqa needs seq_len %% 256 == 0 (got %lld)", (long long)args->seq_len);
+    if (args->seq_stride % 128 != 0)
+        return fail(FA_ERR_SHAPE, "fa_fwd_launch_gqa needs seq_stride %% 128 == 0 (got %lld)", (long long)args->seq_stride);
+    if ((uintptr_t)lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
+    return launch_ex_impl(args, opts, stream, lse, kv);
 }
 
 static void add_slot(const AdaptiveState &ad, int idx, fa_adaptive_info *out) {

@@ -94,6 +94,7 @@ struct KernelArgsLse {
     float *lse;   // (n_bh, seq_len) fp32
 };
 typedef void (*kernel_fn_lse)(const KernelArgsLse);
+#include "fa_gqa64.inc"   // grouped-query attention (fa_fwd_kernel64_gqa): KernelArgsGqa and the K / V addressing (FA_KV_*)
 #ifndef FA_KERNEL64_LSE
 template <int DT, bool MASK = false, int ABL = 0, bool RAG = false, bool SPEC = false, bool PSQ = false, int QTP = 2, bool ALT = false, int NW = 4>
 __global__ void
@@ -102,6 +103,8 @@ fa_fwd_kernel64(const KernelArgs args) {
     constexpr bool LSE = false;
     float *const lse = nullptr;
     const int lse_len = 0;
+#elif defined(FA_KERNEL64_GQA)
+#include "fa_gqa64_kernel.inc"   // fa_fwd_kernel64_gqa's signature and K / V arguments
 #else
 template <int DT, bool MASK, bool SPEC, int ABL = 0, bool RAG = false, bool PSQ = false, int QTP = 2, bool ALT = false, int NW = 4>
 __global__ void __launch_bounds__(256, 1) fa_fwd_kernel64_lse(const KernelArgsLse args_lse) {
@@ -220,15 +223,15 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_kernel64_lse(const KernelArgsLs
         const int i = DMA_PER_WAVE * wave + j;  // piece index, wave-uniform; keys 4i .. 4i+3
         const int k_row = RPP * i + k_row_in_piece;
         const int k_swz = SWZ ? swz_of(k_row) : 0;
-        k_off[j] = (unsigned)(((int64_t)k_row * ss + (((lane & (CPR - 1)) ^ k_swz) << 3)) * 2) + DMA_BIAS - 1024u * j;
+        k_off[j] = (unsigned)(((int64_t)k_row * FA_KV_SS + (((lane & (CPR - 1)) ^ k_swz) << 3)) * 2) + DMA_BIAS - 1024u * j;
         const int sub = 2 * i + v_sub_in_piece;  // subtiles 2i, 2i+1
-        v_off[j] = (unsigned)(((8 * (sub / DSUB) + v_lane_row) * ss + (sub % DSUB) * 32 + v_lane_d) * 2) + DMA_BIAS - 1024u * j;
+        v_off[j] = (unsigned)(((8 * (sub / DSUB) + v_lane_row) * FA_KV_SS + (sub % DSUB) * 32 + v_lane_d) * 2) + DMA_BIAS - 1024u * j;
     }
-    const int64_t tile_stride = (int64_t)BC * ss;  // elements between consecutive KV blocks
+    const int64_t tile_stride = (int64_t)BC * FA_KV_SS;  // elements between consecutive KV blocks
     auto tile_at = [&](const uint16_t *head, int t) {  // first row of tile t of a head's K or V
         if constexpr (RAG) {
             const int r0 = 64 * t < args.seq_len - 64 ? 64 * t : args.seq_len - 64;  // (see the note at the top)
-            return head + (int64_t)r0 * ss;
+            return head + (int64_t)r0 * FA_KV_SS;
         } else {
             return head + (int64_t)t * tile_stride;
         }
@@ -293,8 +296,8 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_kernel64_lse(const KernelArgsLs
         const int b = bh / args.n_heads, h = bh % args.n_heads;
         const int64_t head_off = (int64_t)b * args.batch_stride + (int64_t)h * args.head_stride;
         const uint16_t *Qg = (const uint16_t *)args.q + head_off;
-        const uint16_t *Kg = (const uint16_t *)args.k + head_off - DMA_BIAS / 2;   // (see DMA_BIAS: only ever a DMA base)
-        const uint16_t *Vg = (const uint16_t *)args.v + head_off - DMA_BIAS / 2;
+        const uint16_t *Kg = (const uint16_t *)args.k + FA_KV_OFF(b, h, head_off) - DMA_BIAS / 2;   // (see DMA_BIAS: only ever a DMA base)
+        const uint16_t *Vg = (const uint16_t *)args.v + FA_KV_OFF(b, h, head_off) - DMA_BIAS / 2;
         uint16_t *Og = (uint16_t *)args.o + head_off;
         // KV blocks are visited last-to-first (forward_kernel.cuh:142,175-184): visit index `it` is
         // sequence block n_kv-1-it.  Causal: only the 4 (qb + 1) tiles up to the item's diagonal.
@@ -1091,8 +1094,8 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_kernel64_lse(const KernelArgsLs
                 const int b_n = bh_n / args.n_heads, h_n = bh_n % args.n_heads;
                 const int64_t off_n = (int64_t)b_n * args.batch_stride + (int64_t)h_n * args.head_stride;
                 Qn = (const uint16_t *)args.q + off_n;
-                Kn = (const uint16_t *)args.k + off_n - DMA_BIAS / 2;
-                Vn = (const uint16_t *)args.v + off_n - DMA_BIAS / 2;
+                Kn = (const uint16_t *)args.k + FA_KV_OFF(b_n, h_n, off_n) - DMA_BIAS / 2;
+                Vn = (const uint16_t *)args.v + FA_KV_OFF(b_n, h_n, off_n) - DMA_BIAS / 2;
                 On = (uint16_t *)args.o + off_n;
             };
             set_next();

@@ -28,7 +28,14 @@ def forward_ex(kernel_cfg, q, k, v, o=None, causal=False, timed=False, stats=Non
     (items computed, items the speculative softmax computed twice; fa_fwd_stats in include/fa_hip.h).
     Returns Tensor, or (Tensor, ms) if timed.  return_lse: also the row log-sum-exp, an fp32 (batch, n_heads, seq_len)
     tensor (ln sum_j exp(q_i . k_j / sqrt d)), with the same O bits -> (Tensor, lse) or (Tensor, lse, ms); RuntimeError
-    where the configuration has no such form (fa_fwd_launch_lse in include/fa_hip.h)."""
+    where the configuration has no such form (fa_fwd_launch_lse in include/fa_hip.h).
+    Grouped-query attention: k and v of shape (batch, seq_len, n_kv_heads, d_head), n_kv_heads dividing n_heads (query
+    head h reads K / V head h / (n_heads / n_kv_heads)); served by the configurations with the row log-sum-exp, which is
+    computed and dropped unless return_lse (fa_fwd_launch_gqa)."""
+    if flash_attention_kernels.is_gqa(q, k, v) and not return_lse:
+        out, _, ms = flash_attention_kernels.forward_lse(kernel_cfg, q, k, v, o, benchmark=timed, causal=causal,
+                                                         allow_ragged=True, stats=stats)
+        return (out, ms) if timed else out
     if return_lse:
         out, lse, ms = flash_attention_kernels.forward_lse(kernel_cfg, q, k, v, o, benchmark=timed, causal=causal,
                                                            allow_ragged=True, stats=stats)
@@ -40,7 +47,8 @@ def forward_ex(kernel_cfg, q, k, v, o=None, causal=False, timed=False, stats=Non
 
 def backward(q, k, v, o, lse, dout, causal=False, timed=False):
     """dQ, dK, dV from the forward's o and lse (forward_ex(..., return_lse=True)) and the gradient dout -> (dq, dk, dv), or
-    (dq, dk, dv, ms) if timed.  Deterministic: the same inputs give the same bits."""
+    (dq, dk, dv, ms) if timed.  Deterministic: the same inputs give the same bits.  Grouped-query attention (k, v with
+    n_kv_heads heads): dk and dv have n_kv_heads heads."""
     return flash_attention_kernels.backward(q, k, v, o, lse, dout, causal=causal, timed=timed)
 
 
@@ -54,7 +62,12 @@ class _Attention(torch.autograd.Function):
     def forward(ctx, q, k, v, causal):
         from flash_helpers import kernel_configs as kc
 
-        if _needs_copy(q) or k.stride() != q.stride() or v.stride() != q.stride():
+        if flash_attention_kernels.is_gqa(q, k, v):   # (K / V have strides of their own)
+            if _needs_copy(q):
+                q = q.contiguous()
+            if _needs_copy(k) or v.stride() != k.stride():
+                k, v = k.contiguous(), v.contiguous()
+        elif _needs_copy(q) or k.stride() != q.stride() or v.stride() != q.stride():
             q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         name = kc.DType.BF16 if q.dtype == torch.bfloat16 else kc.DType.FP16
         cfg = kc.best_config(name, q.shape[1], masked=causal)
@@ -72,5 +85,6 @@ class _Attention(torch.autograd.Function):
 
 def attention(q, k, v, causal=False):
     """softmax(q k^T / sqrt d) v with gradients: (batch, seq_len, n_heads, 128) bf16 / fp16 tensors, seq_len % 256 == 0.
-    The forward is best_config(dtype, seq_len, masked=causal) with the row log-sum-exp; the backward is the HIP backward."""
+    The forward is best_config(dtype, seq_len, masked=causal) with the row log-sum-exp; the backward is the HIP backward.
+    Grouped-query attention: k and v may have n_kv_heads heads (dividing n_heads); their gradients then have as many."""
     return _Attention.apply(q, k, v, causal)

@@ -58,11 +58,20 @@ def forward(kernel_cfg, q, k, v, o=None, benchmark=False, causal=False, allow_ra
     return _forward(kernel_cfg, q, k, v, o, benchmark, causal, allow_ragged, stats, None)
 
 
+def is_gqa(q, k, v):
+    """Grouped-query attention inputs: k and v of one shape (batch, seq_len, n_kv_heads, d_head) with fewer heads than q."""
+    return q.dim() == 4 and k.dim() == 4 and k.shape == v.shape and k.shape[2] != q.shape[2] and \
+        (k.shape[0], k.shape[1], k.shape[3]) == (q.shape[0], q.shape[1], q.shape[3])
+
+
 def forward_lse(kernel_cfg, q, k, v, o=None, benchmark=False, causal=False, allow_ragged=False, stats=None):
     """forward(), and the row log-sum-exp: -> (o, lse, ms), lse an fp32 (batch, n_heads, seq_len) tensor,
     lse[b, h, i] = ln sum_j exp(q_i . k_j / sqrt(d)) (fa_fwd_launch_lse).  The same O bits as forward() with the same
     arguments.  RuntimeError where the configuration has no such form (only the persistent (256, 64, 4) + buffer
-    configuration at d_head 128 has one; seq_len % 256 == 0, seq_stride % 128 == 0)."""
+    configuration at d_head 128 has one; seq_len % 256 == 0, seq_stride % 128 == 0).
+    Grouped-query attention (is_gqa: k, v with n_kv_heads heads, n_kv_heads dividing n_heads; query head h reads K / V
+    head h / (n_heads / n_kv_heads)) goes through fa_fwd_launch_gqa; k and v may be views with a contiguous last dimension
+    (one stride set for both), q is made contiguous."""
     if q.dim() != 4:
         raise RuntimeError("q must have shape (batch, seq_len, n_heads, d_head)")
     lse = torch.empty((q.shape[0], q.shape[2], q.shape[1]), dtype=torch.float32, device=q.device)
@@ -72,9 +81,20 @@ def forward_lse(kernel_cfg, q, k, v, o=None, benchmark=False, causal=False, allo
 
 def _forward(kernel_cfg, q, k, v, o, benchmark, causal, allow_ragged, stats, lse):
     masked = bool(causal or allow_ragged)
+    gqa = lse is not None and is_gqa(q, k, v)
+    if gqa:
+        q = q if not q.is_cuda or q.is_contiguous() else q.contiguous()
+        for t, name in ((k, "k"), (v, "v")):
+            if not t.is_cuda:
+                raise RuntimeError(f"{name} must be a CUDA tensor")
+            if t.stride(3) != 1 or t.stride() != k.stride():
+                raise RuntimeError("grouped-query attention: k and v need one stride set and a contiguous last dimension")
+        if q.shape[2] % k.shape[2] != 0:
+            raise RuntimeError(f"grouped-query attention: the K / V heads ({k.shape[2]}) must divide the query heads ({q.shape[2]})")
     _check_input(q, "q")
-    _check_input(k, "k")
-    _check_input(v, "v")
+    if not gqa:
+        _check_input(k, "k")
+        _check_input(v, "v")
 
     q_dtype = q.dtype
     if q_dtype not in (torch.float16, torch.bfloat16):
@@ -113,9 +133,9 @@ def _forward(kernel_cfg, q, k, v, o, benchmark, causal, allow_ragged, stats, lse
     if cfg_dtype != q_dtype:
         raise RuntimeError("Kernel configuration dtype does not match input dtype")
 
-    if q.shape != k.shape:
+    if q.shape != k.shape and not gqa:
         raise RuntimeError("Query and key tensors have same shape")
-    if q.shape != v.shape:
+    if q.shape != v.shape and not gqa:
         raise RuntimeError("Query and value tensors have same shape")
     batch, seq_len, n_heads, d_head = q.shape
     if not allow_ragged and seq_len % cfg.B_r != 0:
@@ -150,6 +170,14 @@ def _forward(kernel_cfg, q, k, v, o, benchmark, causal, allow_ragged, stats, lse
             ms = ctypes.c_float(0.0)
             opts = _capi.make_opts(causal=causal, allow_ragged=allow_ragged, speculative=speculative,
                                    prescaled_q=prescaled_q, ms=ms if benchmark else None, stats_ptr=stats_ptr)
+            if gqa:
+                if not lib.fa_fwd_gqa_supported(ctypes.byref(cfg), ctypes.byref(opts)):
+                    raise RuntimeError("Kernel configuration has no grouped-query attention form (only the persistent "
+                                       "(B_r 256, B_c 64, 4 warps) + buffer configuration at d_head 128, without prescaled_q)")
+                kv = _capi.make_kv_layout(k.shape[2], k.stride(0), k.stride(1), k.stride(2))
+                _capi.check(lib.fa_fwd_launch_gqa(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(opts),
+                                                  ctypes.c_void_p(lse.data_ptr()), stream))
+                return o, float(ms.value)
             if not lib.fa_fwd_lse_supported(ctypes.byref(cfg), ctypes.byref(opts)):
                 raise RuntimeError("Kernel configuration has no form that writes the row log-sum-exp (only the persistent "
                                    "(B_r 256, B_c 64, 4 warps) + buffer configuration at d_head 128, without prescaled_q)")
@@ -173,7 +201,11 @@ def backward(q, k, v, o, lse, dout, causal=False, timed=False):
     """dQ, dK, dV of attention softmax(q k^T / sqrt d) v (causal: key j contributes to query i iff j <= i) from the forward's
     o and lse (forward_lse) and the gradient dout (fa_bwd_launch).  q, k, v share one stride set (a packed QKV view passes
     as it is), o and dout another; the gradients come back contiguous.  d_head 128, bf16 / fp16, seq_len % 256 == 0.  The
-    workspace is allocated with torch on the tensors' stream.  -> (dq, dk, dv), or (dq, dk, dv, ms) if timed (blocks)."""
+    workspace is allocated with torch on the tensors' stream.  -> (dq, dk, dv), or (dq, dk, dv, ms) if timed (blocks).
+    Grouped-query attention (is_gqa(q, k, v)): fa_bwd_launch_gqa, k and v with one stride set of their own; dk and dv have
+    k's n_kv_heads heads."""
+    if is_gqa(q, k, v):
+        return _backward_gqa(q, k, v, o, lse, dout, causal, timed)
     for t, name in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (dout, "dout"), (lse, "lse")):
         if not t.is_cuda:
             raise RuntimeError(f"{name} must be a CUDA tensor")
@@ -210,4 +242,50 @@ def backward(q, k, v, o, lse, dout, causal=False, timed=False):
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
         ms = ctypes.c_float(0.0)
         _capi.check(lib.fa_bwd_launch(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
+    return (dq, dk, dv, float(ms.value)) if timed else (dq, dk, dv)
+
+
+def _backward_gqa(q, k, v, o, lse, dout, causal, timed):
+    for t, name in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (dout, "dout"), (lse, "lse")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError("Only fp16 and bf16 are supported")
+    if any(t.dtype != q.dtype for t in (k, v, o, dout)):
+        raise RuntimeError("q, k, v, o and dout must have the same data type")
+    if any(t.shape != q.shape for t in (o, dout)):
+        raise RuntimeError("q, o and dout must have one shape (batch, seq_len, n_heads, d_head)")
+    if v.stride() != k.stride() or k.stride(3) != 1 or q.stride(3) != 1:
+        raise RuntimeError("grouped-query attention: k and v need one stride set; q, k and v a contiguous last dimension")
+    o, dout = o.contiguous(), dout.contiguous()
+    batch, seq_len, n_heads, d_head = q.shape
+    n_kv = k.shape[2]
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (batch, n_heads, seq_len) or not lse.is_contiguous():
+        raise RuntimeError("lse must be a contiguous fp32 (batch, n_heads, seq_len) tensor")
+    dq = torch.empty_like(o)
+    dk = torch.empty((batch, seq_len, n_kv, d_head), dtype=q.dtype, device=q.device)
+    dv = torch.empty_like(dk)
+    lib = _capi.load()
+    base = _capi.FaBwdArgs(
+        q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), o=o.data_ptr(), dout=dout.data_ptr(),
+        lse=ctypes.cast(ctypes.c_void_p(lse.data_ptr()), ctypes.POINTER(ctypes.c_float)),
+        dq=dq.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), workspace=None,
+        batch=batch, seq_len=seq_len, n_heads=n_heads, d_head=d_head,
+        qkv_batch_stride=q.stride(0), qkv_seq_stride=q.stride(1), qkv_head_stride=q.stride(2),
+        out_batch_stride=o.stride(0), out_seq_stride=o.stride(1), out_head_stride=o.stride(2),
+        dtype=15 if q.dtype == torch.bfloat16 else 5, causal=1 if causal else 0,
+    )
+    args = _capi.FaBwdGqaArgs(
+        base=base, n_kv_heads=n_kv,
+        kv_batch_stride=k.stride(0), kv_seq_stride=k.stride(1), kv_head_stride=k.stride(2),
+        dkv_batch_stride=dk.stride(0), dkv_seq_stride=dk.stride(1), dkv_head_stride=dk.stride(2),
+    )
+    nbytes = lib.fa_bwd_gqa_workspace_bytes(ctypes.byref(args))
+    _capi.check(nbytes if nbytes < 0 else 0)
+    with torch.cuda.device(q.device):
+        workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)   # (on the current stream's allocator)
+        args.base.workspace = workspace.data_ptr()
+        stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        ms = ctypes.c_float(0.0)
+        _capi.check(lib.fa_bwd_launch_gqa(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
     return (dq, dk, dv, float(ms.value)) if timed else (dq, dk, dv)

@@ -330,6 +330,53 @@ typedef struct fa_bwd_args {
 int64_t fa_bwd_workspace_bytes(const fa_bwd_args *args);              /* bytes, or a negative fa_status */
 int fa_bwd_launch(const fa_bwd_args *args, void *stream, float *ms);
 
+/*
+ * Grouped-query attention (GQA; multi-query attention is n_kv_heads = 1): K and V have n_kv_heads heads, n_kv_heads divides
+ * n_heads, and query head h reads K / V head h / (n_heads / n_kv_heads) -- the convention of flash-attn and of torch SDPA's
+ * enable_gqa.  Q, O, dO, dQ and lse keep n_heads heads; K, V, dK and dV have n_kv_heads heads and strides of their own.
+ *
+ * fa_kv_layout: K's and V's head count and strides (elements; K and V share them).  struct_size = sizeof(fa_kv_layout).
+ * fa_fwd_gqa_supported: 1 if fa_fwd_launch_gqa serves cfg with these options (the configurations and options
+ * fa_fwd_lse_supported serves), else 0.
+ * fa_fwd_launch_gqa: fa_fwd_launch_lse with K / V described by kv (args: Q, O, n_heads and their strides; args->k, ->v
+ * the K / V pointers).  O and lse are bit-identical to fa_fwd_launch_lse on K / V expanded to n_heads heads.  lse is
+ * required (FA_ERR_NULL).  Refused before any HIP call: configurations without the form and prescaled_q
+ * (FA_ERR_NO_KERNEL); n_kv_heads < 1 or not dividing n_heads, seq_len % 256 != 0 (ragged lengths included), seq_stride %
+ * 128 != 0, K / V strides that are not positive or whose 256 rows * kv_seq_stride * 2 bytes exceed 32 bits (FA_ERR_SHAPE);
+ * K / V strides not multiples of 8 (FA_ERR_ALIGN).
+ */
+typedef struct fa_kv_layout {
+    uint32_t struct_size;
+    int64_t n_kv_heads;
+    int64_t kv_batch_stride;
+    int64_t kv_seq_stride;
+    int64_t kv_head_stride;
+} fa_kv_layout;
+int fa_fwd_gqa_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_gqa(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_fwd_opts *opts, float *lse, void *stream);
+
+/*
+ * The backward of grouped-query attention.  base: as for fa_bwd_launch, with qkv_* the strides of Q alone, out_* those of
+ * O, dO and dQ, and base.k, .v, .dk, .dv pointing to (batch, seq_len, n_kv_heads, d_head) tensors with the kv_* (K, V) and
+ * dkv_* (dK, dV) strides.  dQ is bit-identical to fa_bwd_launch on K / V expanded to n_heads heads; dK and dV sum the
+ * group's query heads in fp32 and are rounded once.  When batch * n_kv_heads * seq_len / 128 workgroups would be too few
+ * for the device (fewer than 256 plain, 1024 causal), a group's heads are split across workgroups whose fp32 partials
+ * are summed in a fixed order: the workspace (fa_bwd_gqa_workspace_bytes) then holds them too, and workspace must be
+ * 16-byte aligned.  Deterministic like fa_bwd_launch.
+ */
+typedef struct fa_bwd_gqa_args {
+    fa_bwd_args base;
+    int64_t n_kv_heads;
+    int64_t kv_batch_stride;
+    int64_t kv_seq_stride;
+    int64_t kv_head_stride;
+    int64_t dkv_batch_stride;
+    int64_t dkv_seq_stride;
+    int64_t dkv_head_stride;
+} fa_bwd_gqa_args;
+int64_t fa_bwd_gqa_workspace_bytes(const fa_bwd_gqa_args *args);      /* bytes, or a negative fa_status */
+int fa_bwd_launch_gqa(const fa_bwd_gqa_args *args, void *stream, float *ms);
+
 /* The adaptive speculative mode's record on `device` (fa_speculative_mode), and a reset of its demotion state (tests,
  * or a caller that knows its data has changed character). */
 int fa_adaptive_state(int device, fa_adaptive_info *out);
