@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "fa_adaptive_state", "fa_adaptive_state_for", "fa_adaptive_reset", "fa_adaptive_simulate", "fa_get_kernel_sized", "fa_fwd_query_sized", "fa_abi_version",
     "fa_fwd_lse_supported", "fa_fwd_launch_lse", "fa_bwd_workspace_bytes", "fa_bwd_launch",
     "fa_fwd_gqa_supported", "fa_fwd_launch_gqa", "fa_bwd_gqa_workspace_bytes", "fa_bwd_launch_gqa",
+    "fa_fwd_varlen_supported", "fa_fwd_launch_varlen", "fa_bwd_varlen_workspace_bytes", "fa_bwd_launch_varlen",
 )
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
 FA_ABI_VERSION = 6
@@ -107,6 +108,33 @@ class FaBwdGqaArgs(ctypes.Structure):   # fa_bwd_gqa_args
         ("kv_batch_stride", ctypes.c_int64), ("kv_seq_stride", ctypes.c_int64), ("kv_head_stride", ctypes.c_int64),
         ("dkv_batch_stride", ctypes.c_int64), ("dkv_seq_stride", ctypes.c_int64), ("dkv_head_stride", ctypes.c_int64),
     ]
+
+
+class FaVarlenLayout(ctypes.Structure):   # fa_varlen_layout (packed sequences: cu_seqlens on the device, and the host's bounds)
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("cu_seqlens", ctypes.c_void_p),
+        ("n_seqs", ctypes.c_int64), ("total_tokens", ctypes.c_int64), ("max_seqlen", ctypes.c_int64),
+    ]
+
+
+class FaBwdVarlenArgs(ctypes.Structure):   # fa_bwd_varlen_args
+    _fields_ = [
+        ("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p),
+        ("o", ctypes.c_void_p), ("dout", ctypes.c_void_p), ("lse", ctypes.POINTER(ctypes.c_float)),
+        ("dq", ctypes.c_void_p), ("dk", ctypes.c_void_p), ("dv", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+        ("n_heads", ctypes.c_int64), ("n_kv_heads", ctypes.c_int64), ("d_head", ctypes.c_int64),
+        ("q_seq_stride", ctypes.c_int64), ("q_head_stride", ctypes.c_int64),
+        ("out_seq_stride", ctypes.c_int64), ("out_head_stride", ctypes.c_int64),
+        ("kv_seq_stride", ctypes.c_int64), ("kv_head_stride", ctypes.c_int64),
+        ("dkv_seq_stride", ctypes.c_int64), ("dkv_head_stride", ctypes.c_int64),
+        ("dtype", ctypes.c_int32), ("causal", ctypes.c_int32),
+        ("varlen", FaVarlenLayout),
+    ]
+
+
+def make_varlen_layout(cu_seqlens_ptr, n_seqs, total_tokens, max_seqlen):
+    return FaVarlenLayout(struct_size=ctypes.sizeof(FaVarlenLayout), cu_seqlens=cu_seqlens_ptr, n_seqs=n_seqs,
+                          total_tokens=total_tokens, max_seqlen=max_seqlen)
 
 
 def make_kv_layout(n_kv_heads, batch_stride, seq_stride, head_stride):
@@ -217,6 +245,15 @@ def load():
     lib.fa_bwd_gqa_workspace_bytes.argtypes = [ctypes.POINTER(FaBwdGqaArgs)]
     lib.fa_bwd_launch_gqa.restype = ctypes.c_int
     lib.fa_bwd_launch_gqa.argtypes = [ctypes.POINTER(FaBwdGqaArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    lib.fa_fwd_varlen_supported.restype = ctypes.c_int
+    lib.fa_fwd_varlen_supported.argtypes = [cfg_p, ctypes.POINTER(FaFwdOpts)]
+    lib.fa_fwd_launch_varlen.restype = ctypes.c_int
+    lib.fa_fwd_launch_varlen.argtypes = [args_p, ctypes.POINTER(FaKvLayout), ctypes.POINTER(FaVarlenLayout), ctypes.POINTER(FaFwdOpts),
+                                         ctypes.c_void_p, ctypes.c_void_p]
+    lib.fa_bwd_varlen_workspace_bytes.restype = ctypes.c_int64
+    lib.fa_bwd_varlen_workspace_bytes.argtypes = [ctypes.POINTER(FaBwdVarlenArgs)]
+    lib.fa_bwd_launch_varlen.restype = ctypes.c_int
+    lib.fa_bwd_launch_varlen.argtypes = [ctypes.POINTER(FaBwdVarlenArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p
     lib.fa_last_error.argtypes = []
     lib.fa_version.restype = ctypes.c_char_p

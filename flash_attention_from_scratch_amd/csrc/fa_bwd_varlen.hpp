@@ -1,0 +1,376 @@
+// fa_bwd_varlen.hpp -- the backward over packed variable-length sequences (fa_bwd_launch_varlen): Q, dO, dQ, O are
+// (total_tokens, n_heads, 128), K, V, dK, dV (total_tokens, n_kv_heads, 128), and sequence i owns token rows
+// cu_seqlens[i] .. cu_seqlens[i + 1] - 1 (cu_seqlens on the DEVICE: the host never reads it, the launch stays asynchronous).
+//
+// The kernels of fa_bwd_gqa.hpp (MHA is their group = 1 case) with the workgroup -> (sequence, head, 128-row block) lookup in
+// front; the tile arithmetic (S, dP, dS, the five MFMA products, the operand orientation, the LDS images, the order of the
+// fp32 sums) is theirs, line for line, so that a sequence whose length is a multiple of 256 gets the dense kernels' bits.
+//   fa_bwd_delta_varlen_kernel        delta per (head, token): no sequence lookup at all
+//   fa_bwd_dkdv_varlen_kernel         one workgroup per (sequence, K / V head, split part, 128-key block of max_seqlen)
+//   fa_bwd_dkdv_reduce_varlen_kernel  split > 1 only: the sum of a row's split partials, in order, scaled and rounded once
+//   fa_bwd_dq_varlen_kernel           one workgroup per (sequence, head, 128-row Q block of max_seqlen)
+// A workgroup whose block starts at or beyond its sequence's length returns at once (before any barrier).  Rows of a tile,
+// and resident K / V or Q / dO rows, beyond the sequence's end are fetched from the sequence's LAST row (never from another
+// sequence or from beyond total_tokens) and their p is exactly 0: under the causal mask by the dense kernels' select
+// (key >= len or query >= len joins key > query); without the mask by starting the row's S at -inf, so that exp2 gives 0 --
+// a select behind exp2 would keep hipcc from fusing p * dP with its fp16 rounding as it does in the plain dense kernels, and
+// the bits would differ from theirs.  A lane whose own key (dK / dV) or query (dQ) lies beyond the end only feeds its own
+// accumulator column, which is never stored.  Nothing a neighbouring sequence holds reaches a result.
+// cu_seqlens is the caller's (non-decreasing, [0] = 0, [n_seqs] = total_tokens, lengths <= max_seqlen), but a violation
+// cannot fault: seq_range() clamps the first row to [0, total_tokens] and the length to [0, min(max_seqlen, what is left)].
+// No float atomics, no waiting between workgroups, no scratch: the same inputs give the same bits.
+#pragma once
+#include "fa_bwd_kernel.hpp"
+
+namespace fa {
+
+struct BwdVarlenArgs {
+    const uint16_t *q, *k, *v;        // q_* / kv_* strides
+    const uint16_t *o, *dout;         // out_* strides
+    const float *lse;                 // (n_heads, total_tokens), contiguous
+    float *delta;                     // workspace: (n_heads, total_tokens)
+    uint16_t *dq, *dk, *dv;           // dq: out_* strides; dk, dv: dkv_*
+    const int32_t *cu_seqlens;        // n_seqs + 1 entries
+    float *part;                      // split > 1: (n_kv_heads * split, total_tokens, 2, 128) fp32 dK^T | dV^T, unscaled
+    int64_t q_ss, q_hs;               // elements
+    int64_t out_ss, out_hs;
+    int64_t kv_ss, kv_hs;
+    int64_t dkv_ss, dkv_hs;
+    int32_t n_seqs, total_tokens, max_seqlen, n_heads;
+    int32_t group, split;             // query heads per K / V head; workgroups per (K / V head, key block), divides group
+    int32_t n_blocks;                 // ceil(max_seqlen / 128): blocks of the grid per (sequence, head)
+};
+
+namespace bwd {
+
+// sequence -> first row and length, clamped so that every row0 + i, 0 <= i < len, is a row of the tensors
+FA_DEV void seq_range(const BwdVarlenArgs &a, int seq, int &row0, int &len) {
+    const int64_t lo = a.cu_seqlens[seq], hi = a.cu_seqlens[seq + 1];
+    const int64_t total = a.total_tokens;
+    const int64_t r0 = lo < 0 ? 0 : (lo > total ? total : lo);
+    int64_t n = hi - r0;
+    const int64_t cap = total - r0 < a.max_seqlen ? total - r0 : a.max_seqlen;
+    n = n < 0 ? 0 : (n > cap ? cap : n);
+    row0 = (int)r0;
+    len = (int)n;
+}
+
+// tile_load with the tile's rows clamped to the sequence: row first + r comes from row min(first + r, last)
+FA_DEV void tile_load_clamped(TileRegs &t, const uint16_t *seq_rows, int64_t ss, int first, int last, int tid) {
+#pragma unroll
+    for (int u = 0; u < CHUNKS; ++u) {
+        const int c = tid + THREADS * u, ch = c & 15;
+        int row = first + (c >> 4);
+        row = row < last ? row : last;
+        t.v[u] = *(const u32x4 *)(seq_rows + (int64_t)row * ss + ch * 8);
+    }
+}
+
+}  // namespace bwd
+
+// delta_i = sum_d dO_id O_id per (head, token), 16 lanes per row: fa_bwd_delta_kernel's sum over the packed layout
+template <int DT>
+__global__ void __launch_bounds__(256) fa_bwd_delta_varlen_kernel(const BwdVarlenArgs a) {
+    using E = Elem<DT>;
+    const int64_t rows = (int64_t)a.n_heads * a.total_tokens;
+    const int64_t row = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int part = threadIdx.x & 15;
+    float acc = 0.0f;
+    if (row < rows) {
+        const int64_t hd = row / a.total_tokens, i = row % a.total_tokens;
+        const int64_t off = hd * a.out_hs + i * a.out_ss + part * 8;
+        const typename E::vec8 o = *(const typename E::vec8 *)(a.o + off);
+        const typename E::vec8 g = *(const typename E::vec8 *)(a.dout + off);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc += (float)o[j] * (float)g[j];
+    }
+#pragma unroll
+    for (int m = 8; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 16);
+    if (row < rows && part == 0) a.delta[row] = acc;
+}
+
+// dK, dV of one 128-key block of one K / V head of one sequence, summed over group / split query heads.
+// Grid: n_seqs * n_kv_heads * split * n_blocks workgroups of 256 threads.
+template <int DT, bool CAUSAL>
+__global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(const BwdVarlenArgs a) {
+    using namespace bwd;
+    using E = Elem<DT>;
+    using vec8 = typename E::vec8;
+    __shared__ __attribute__((aligned(16))) char img_q[TBYTES];
+    __shared__ __attribute__((aligned(16))) char img_do[TBYTES];
+    __shared__ __attribute__((aligned(16))) float lse_s[TROWS];   // -lse sqrt(d) of the tile's rows
+    __shared__ __attribute__((aligned(16))) float dl_s[TROWS];    // -delta
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    int wg, kb;   // wg = (sequence * n_kv_heads + K / V head) * split + part
+    block_coords(a.n_blocks, wg, kb);
+    const int n_kv = a.n_heads / a.group, skv = wg / a.split, seq = skv / n_kv, hk = skv % n_kv, sp = wg % a.split;
+    int row0, len;
+    seq_range(a, seq, row0, len);
+    if (kb * KB >= len) return;   // (workgroup-uniform, before any barrier)
+    const int last = len - 1;
+    const int n_hq = a.group / a.split;   // query heads of the sweep: hk * group + part * n_hq + 0 .. n_hq - 1
+    int hq = hk * a.group + sp * n_hq;
+    const uint16_t *q_seq = a.q + (int64_t)row0 * a.q_ss + (int64_t)hq * a.q_hs;
+    const uint16_t *do_seq = a.dout + (int64_t)row0 * a.out_ss + (int64_t)hq * a.out_hs;
+    const int key = kb * KB + 32 * wave + r;   // this lane's key (the accumulators' column)
+    const int key_c = key < last ? key : last;
+    // K, V of the wave's 32 keys: the B operands of S = Q K^T and dP = dO V^T, resident for the whole sweep
+    vec8 Kb[8], Vb[8];
+    {
+        const int64_t kv_row = (int64_t)(row0 + key_c) * a.kv_ss + (int64_t)hk * a.kv_hs + 8 * h;
+        const uint16_t *kr = a.k + kv_row;
+        const uint16_t *vr = a.v + kv_row;
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            Kb[ks] = *(const vec8 *)(kr + 16 * ks);
+            Vb[ks] = *(const vec8 *)(vr + 16 * ks);
+        }
+    }
+    const float c = (float)((double)(1.0f / __builtin_sqrtf((float)D)) * 1.4426950408889634074);
+    const float lse_scale = -log2e_over_c();
+    f32x16 dV[4], dK[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        dV[t] = f32x16{};
+        dK[t] = f32x16{};
+    }
+    const int n_it = (len + TROWS - 1) / TROWS;
+    const int it0 = CAUSAL ? kb * (KB / TROWS) : 0;   // causal: the Q tiles from the diagonal on (it0 * 64 = kb * 128 < len)
+    const float *lse_h = a.lse + (int64_t)hq * a.total_tokens + row0;
+    const float *dl_h = a.delta + (int64_t)hq * a.total_tokens + row0;
+    TileRegs tq, tdo;
+    float lse_r = 0.0f, dl_r = 0.0f;
+    auto load = [&](int it) {
+        tile_load_clamped(tq, q_seq, a.q_ss, it * TROWS, last, tid);
+        tile_load_clamped(tdo, do_seq, a.out_ss, it * TROWS, last, tid);
+        if (tid < TROWS) {
+            const int row = it * TROWS + tid;
+            const bool in = row < len;
+            lse_r = in ? lse_h[in ? row : 0] * lse_scale : -__builtin_inff();   // S = -inf, p = exp2(-inf) = 0
+            dl_r = in ? -dl_h[in ? row : 0] : 0.0f;
+        }
+    };
+    load(it0);
+    const bool key_edge = kb * KB + KB > len;   // a block that holds keys beyond the sequence
+    for (int j = 0; j < n_hq; ++j) {
+        for (int it = it0; it < n_it; ++it) {
+            __syncthreads();   // every wave is done with the previous tile's images
+            tile_store(img_q, tq, tid);
+            tile_store(img_do, tdo, tid);
+            if (tid < TROWS) {
+                lse_s[tid] = lse_r;
+                dl_s[tid] = dl_r;
+            }
+            __syncthreads();
+            if (it + 1 < n_it) {
+                load(it + 1);   // in flight under this tile's MFMAs
+            } else if (j + 1 < n_hq) {   // ... or the next query head's first tile
+                ++hq;
+                q_seq += a.q_hs;
+                do_seq += a.out_hs;
+                lse_h += a.total_tokens;
+                dl_h += a.total_tokens;
+                load(it0);
+            }
+            const bool diag = CAUSAL && it * TROWS < kb * KB + KB;   // a tile that holds queries before some key of the block
+            const bool edge = key_edge || it * TROWS + TROWS > len;  // ... or rows / keys beyond the sequence
+#pragma unroll
+            for (int mt = 0; mt < TROWS / 32; ++mt) {
+                const int rb = 32 * mt;
+                f32x16 S, dP;
+                // rows of registers 4g .. 4g + 3: rb + 8 g + 4 h + 0 .. 3
+#pragma unroll
+                for (int gg = 0; gg < 4; ++gg) {
+                    const f32x4 l4 = *(const f32x4 *)(lse_s + rb + 8 * gg + 4 * h);
+                    const f32x4 d4 = *(const f32x4 *)(dl_s + rb + 8 * gg + 4 * h);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        S[4 * gg + e] = l4[e];
+                        dP[4 * gg + e] = d4[e];
+                    }
+                }
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) S = E::mfma(row_read<vec8>(img_q, rb, ks, lane), Kb[ks], S);
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) dP = E::mfma(row_read<vec8>(img_do, rb, ks, lane), Vb[ks], dP);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    float p = __builtin_amdgcn_exp2f(c * S[i]);
+                    const int query = it * TROWS + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
+                    if constexpr (CAUSAL) {   // (plain: rows beyond the end have S = -inf, see load())
+                        if (diag) p = key > query ? 0.0f : p;
+                        if (edge) p = (key >= len || query >= len) ? 0.0f : p;
+                    }
+                    S[i] = p;                 // P
+                    dP[i] = p * dP[i];        // dS = P (dP - delta)
+                }
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const vec8 pb = acc_operand<DT>(S, s), db = acc_operand<DT>(dP, s);
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        dV[t] = E::mfma(tr_read<vec8>(img_do, rb, s, t, lane), pb, dV[t]);
+                        dK[t] = E::mfma(tr_read<vec8>(img_q, rb, s, t, lane), db, dK[t]);
+                    }
+                }
+            }
+        }
+    }
+    if (key >= len) return;   // (behind the last barrier and the last transposed read)
+    // dK^T / dV^T: column = this lane's key, rows d = 32 t + 8 gg + 4 h + 0 .. 3
+    if (a.split > 1) {   // the fp32 partials, unscaled: fa_bwd_dkdv_reduce_varlen_kernel rounds their sum
+        float *pk = a.part + (((int64_t)hk * a.split + sp) * a.total_tokens + row0 + key) * (2 * D) + 4 * h;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int gg = 0; gg < 4; ++gg) {
+                *(f32x4 *)(pk + 32 * t + 8 * gg) = f32x4{dK[t][4 * gg], dK[t][4 * gg + 1], dK[t][4 * gg + 2], dK[t][4 * gg + 3]};
+                *(f32x4 *)(pk + D + 32 * t + 8 * gg) = f32x4{dV[t][4 * gg], dV[t][4 * gg + 1], dV[t][4 * gg + 2], dV[t][4 * gg + 3]};
+            }
+        return;
+    }
+    const float inv_sqrt_d = 1.0f / __builtin_sqrtf((float)D);
+    const int64_t dkv_row = (int64_t)(row0 + key) * a.dkv_ss + (int64_t)hk * a.dkv_hs + 4 * h;
+    uint16_t *dk = a.dk + dkv_row;
+    uint16_t *dv = a.dv + dkv_row;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+            store4<DT>(dk + 32 * t + 8 * gg, dK[t], gg, inv_sqrt_d);
+            store4<DT>(dv + 32 * t + 8 * gg, dV[t], gg, 1.0f);
+        }
+}
+
+// split > 1: dK, dV of one (K / V head, token) row = the sum of its `split` partials in order, scaled and rounded once.
+// One thread per 8 elements of a dK or dV row.  Grid: n_kv_heads * total_tokens * 2 * 16 / 256 workgroups of 256 threads.
+// (every token belongs to a sequence -- cu_seqlens[0] = 0, [n_seqs] = total_tokens -- so every partial row was written)
+template <int DT>
+__global__ void __launch_bounds__(256) fa_bwd_dkdv_reduce_varlen_kernel(const BwdVarlenArgs a) {
+    using namespace bwd;
+    const int n_kv = a.n_heads / a.group;
+    const int64_t n = (int64_t)n_kv * a.total_tokens * 2 * (D / 8);
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const int c8 = (int)(idx % (D / 8)), which = (int)((idx / (D / 8)) & 1);   // 8-element chunk; 0 dK, 1 dV
+    const int64_t row = idx / (2 * (D / 8));   // hk * total_tokens + token
+    const int64_t hk = row / a.total_tokens, tok = row % a.total_tokens;
+    const int64_t plane = (int64_t)a.total_tokens * 2 * D;   // floats per partial
+    const float *src = a.part + (hk * a.split * a.total_tokens + tok) * (2 * D) + which * D + 8 * c8;
+    f32x4 lo = *(const f32x4 *)src, hi = *(const f32x4 *)(src + 4);
+    for (int s = 1; s < a.split; ++s) {
+        lo += *(const f32x4 *)(src + s * plane);
+        hi += *(const f32x4 *)(src + s * plane + 4);
+    }
+    const float scale = which ? 1.0f : 1.0f / __builtin_sqrtf((float)D);
+    float f[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        f[e] = lo[e] * scale;
+        f[4 + e] = hi[e] * scale;
+    }
+    uint16_t *dst = (which ? a.dv : a.dk) + hk * a.dkv_hs + tok * a.dkv_ss + 8 * c8;
+    *(typename Elem<DT>::vec8 *)dst = Elem<DT>::pack8(f);
+}
+
+// dQ of one 128-row Q block of one sequence, K / V of head h / group.  Grid: n_seqs * n_heads * n_blocks workgroups of 256 threads.
+template <int DT, bool CAUSAL>
+__global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const BwdVarlenArgs a) {
+    using namespace bwd;
+    using E = Elem<DT>;
+    using vec8 = typename E::vec8;
+    __shared__ __attribute__((aligned(16))) char img_k[TBYTES];
+    __shared__ __attribute__((aligned(16))) char img_v[TBYTES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    int sh, qb;   // sh = sequence * n_heads + head
+    block_coords(a.n_blocks, sh, qb);
+    if (CAUSAL) qb = a.n_blocks - 1 - qb;   // the longest sweeps first
+    const int seq = sh / a.n_heads, hq = sh % a.n_heads;
+    int row0, len;
+    seq_range(a, seq, row0, len);
+    if (qb * KB >= len) return;   // (workgroup-uniform, before any barrier)
+    const int last = len - 1;
+    const uint16_t *k_seq = a.k + (int64_t)row0 * a.kv_ss + (int64_t)(hq / a.group) * a.kv_hs;
+    const uint16_t *v_seq = a.v + (int64_t)row0 * a.kv_ss + (int64_t)(hq / a.group) * a.kv_hs;
+    const int query = qb * KB + 32 * wave + r;   // this lane's query (the accumulators' column)
+    const int query_c = query < last ? query : last;
+    // Q, dO of the wave's 32 rows: the B operands of S^T = K Q^T and dP^T = V dO^T
+    vec8 Qb[8], Ob[8];
+    {
+        const uint16_t *qr = a.q + (int64_t)(row0 + query_c) * a.q_ss + (int64_t)hq * a.q_hs + 8 * h;
+        const uint16_t *gr = a.dout + (int64_t)(row0 + query_c) * a.out_ss + (int64_t)hq * a.out_hs + 8 * h;
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            Qb[ks] = *(const vec8 *)(qr + 16 * ks);
+            Ob[ks] = *(const vec8 *)(gr + 16 * ks);
+        }
+    }
+    const float c = (float)((double)(1.0f / __builtin_sqrtf((float)D)) * 1.4426950408889634074);
+    const int64_t stat = (int64_t)hq * a.total_tokens + row0 + query_c;
+    const float lse_q = query < len ? a.lse[stat] * -log2e_over_c() : 0.0f;
+    const float dl_q = query < len ? -a.delta[stat] : 0.0f;
+    f32x16 dQ[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) dQ[t] = f32x16{};
+    const int n_all = (len + TROWS - 1) / TROWS;
+    const int n_kt = CAUSAL && (qb + 1) * (KB / TROWS) < n_all ? (qb + 1) * (KB / TROWS) : n_all;
+    TileRegs tk, tv;
+    auto load = [&](int kt) {
+        tile_load_clamped(tk, k_seq, a.kv_ss, kt * TROWS, last, tid);
+        tile_load_clamped(tv, v_seq, a.kv_ss, kt * TROWS, last, tid);
+    };
+    load(0);
+    const bool query_edge = qb * KB + KB > len;   // a block that holds rows beyond the sequence
+    for (int kt = 0; kt < n_kt; ++kt) {
+        __syncthreads();
+        tile_store(img_k, tk, tid);
+        tile_store(img_v, tv, tid);
+        __syncthreads();
+        if (kt + 1 < n_kt) load(kt + 1);
+        const bool diag = CAUSAL && kt * TROWS + TROWS > qb * KB;   // a tile that holds keys after some query of the block
+        const bool edge = query_edge || kt * TROWS + TROWS > len;   // ... or rows / keys beyond the sequence
+#pragma unroll
+        for (int mt = 0; mt < TROWS / 32; ++mt) {
+            const int rb = 32 * mt;
+            f32x16 S, dP;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                S[i] = lse_q;
+                dP[i] = dl_q;
+                if (!CAUSAL && edge) {   // keys beyond the end: S = -inf, p = exp2(-inf) = 0
+                    const int key = kt * TROWS + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
+                    S[i] = key >= len ? -__builtin_inff() : lse_q;
+                }
+            }
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) S = E::mfma(row_read<vec8>(img_k, rb, ks, lane), Qb[ks], S);
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) dP = E::mfma(row_read<vec8>(img_v, rb, ks, lane), Ob[ks], dP);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                float p = __builtin_amdgcn_exp2f(c * S[i]);
+                const int key = kt * TROWS + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
+                if constexpr (CAUSAL) {
+                    if (diag) p = key > query ? 0.0f : p;
+                    if (edge) p = (key >= len || query >= len) ? 0.0f : p;
+                }
+                dP[i] = p * dP[i];        // dS^T
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const vec8 db = acc_operand<DT>(dP, s);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) dQ[t] = E::mfma(tr_read<vec8>(img_k, rb, s, t, lane), db, dQ[t]);
+            }
+        }
+    }
+    if (query >= len) return;
+    const float inv_sqrt_d = 1.0f / __builtin_sqrtf((float)D);
+    uint16_t *dq = a.dq + (int64_t)(row0 + query) * a.out_ss + (int64_t)hq * a.out_hs + 4 * h;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) store4<DT>(dq + 32 * t + 8 * gg, dQ[t], gg, inv_sqrt_d);
+}
+
+}  // namespace fa

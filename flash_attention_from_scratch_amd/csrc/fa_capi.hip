@@ -18,6 +18,7 @@
 
 #include "../../include/fa_hip.h"
 #include "fa_bwd_gqa.hpp"
+#include "fa_bwd_varlen.hpp"
 #include "fa_registry.hpp"
 
 extern "C" {
@@ -38,6 +39,11 @@ kernel_fn_gqa gqa_kernel_dt5(bool masked, bool spec);
 // fa_bwd.hip: delta, dK / dV and dQ of one backward, enqueued on `s`
 hipError_t bwd_enqueue(const BwdArgs &a, int dtype, bool causal, hipStream_t s);
 hipError_t bwd_gqa_enqueue(const BwdGqaArgs &g, int dtype, bool causal, hipStream_t s);
+// fa_inst_varlen.hip / fa_bwd_varlen.hip: the packed variable-length forms
+kernel_fn_varlen varlen_kernel_dt15(bool first_block_skip);
+kernel_fn_varlen varlen_kernel_dt5(bool first_block_skip);
+int varlen_lds_bytes_dt15();
+hipError_t bwd_varlen_enqueue(const BwdVarlenArgs &a, int dtype, bool causal, hipStream_t s);
 }  // namespace fa
 
 namespace {
@@ -255,6 +261,17 @@ void do_init_body(int dev, DeviceState *st) {
         if (rc != hipSuccess) {
             st->status = FA_ERR_LAUNCH;
             snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, LSE form) on device %d: %s", fa::RingTraits<2>::kLdsBytes,
+                     dev, hipGetErrorString(rc));
+            return;
+        }
+    }
+    // the varlen forward (fa_fwd_launch_varlen): the 32-rows-per-wave kernel's 64 KiB
+    for (int i = 0; i < 4; ++i) {
+        const void *fn = (i & 2) ? (const void *)fa::varlen_kernel_dt5((i & 1) != 0) : (const void *)fa::varlen_kernel_dt15((i & 1) != 0);
+        const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, fa::varlen_lds_bytes_dt15());
+        if (rc != hipSuccess) {
+            st->status = FA_ERR_LAUNCH;
+            snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, varlen form) on device %d: %s", fa::varlen_lds_bytes_dt15(),
                      dev, hipGetErrorString(rc));
             return;
         }
@@ -895,6 +912,211 @@ int fa_fwd_launch_gqa(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_
         return fail(FA_ERR_SHAPE, "fa_fwd_launch_gqa needs seq_stride %% 128 == 0 (got %lld)", (long long)args->seq_stride);
     if ((uintptr_t)lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
     return launch_ex_impl(args, opts, stream, lse, kv);
+}
+
+// ---- packed variable-length sequences ------------------------------------------------------------------------------------
+namespace {
+int varlen_validate(const fa_varlen_layout *vl) {
+    if (!vl) return fail(FA_ERR_NULL, "null pointer argument");
+    if (vl->struct_size < sizeof(fa_varlen_layout))
+        return fail(FA_ERR_SHAPE, "fa_varlen_layout.struct_size (%u) is smaller than this library's (%zu)", vl->struct_size,
+                    sizeof(fa_varlen_layout));
+    if (!vl->cu_seqlens) return fail(FA_ERR_NULL, "cu_seqlens is null: a DEVICE pointer to n_seqs + 1 int32 row offsets is needed");
+    if ((uintptr_t)vl->cu_seqlens & 3) return fail(FA_ERR_ALIGN, "cu_seqlens must be 4-byte aligned");
+    if (vl->n_seqs < 1) return fail(FA_ERR_SHAPE, "n_seqs must be at least 1 (got %lld)", (long long)vl->n_seqs);
+    if (vl->total_tokens < 0) return fail(FA_ERR_SHAPE, "total_tokens must not be negative (got %lld)", (long long)vl->total_tokens);
+    if (vl->max_seqlen < 1) return fail(FA_ERR_SHAPE, "max_seqlen must be at least 1 (got %lld)", (long long)vl->max_seqlen);
+    if (vl->total_tokens > INT32_MAX / 2 || vl->max_seqlen > INT32_MAX / 2 || vl->n_seqs > INT32_MAX / 2)
+        return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
+    return FA_OK;
+}
+
+// one stride set of a packed tensor: token and head strides, positive multiples of 8, 32-bit offsets inside a 256-row block
+int check_strides_varlen(const char *which, int64_t n_heads, int64_t ss, int64_t hs) {
+    return check_strides(which, 1, n_heads, 0, ss, hs);
+}
+
+// every grid of a varlen launch: (sequences * heads * parts) workgroups per 128-row block of max_seqlen
+int varlen_grid_check(const fa_varlen_layout *vl, int64_t heads_times_parts) {
+    const int64_t blocks = (vl->max_seqlen + 127) / 128;
+    if (heads_times_parts > INT32_MAX || vl->n_seqs * heads_times_parts > INT32_MAX || vl->n_seqs * heads_times_parts * blocks > INT32_MAX)
+        return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
+    return FA_OK;
+}
+
+const fa::KernelEntry *varlen_entry(const fa_fwd_config *cfg, const char **why) {
+    Want w;
+    w.masked = true;
+    w.ragged = true;
+    const fa::KernelEntry *e = find_kernel(cfg, why, w);
+    if (e && !(e->rows_per_wave == 32 && e->n_waves == 4 && e->B_c == 64 && e->pipelined && e->async_copy && e->swizzled && e->eager &&
+               e->masked == 1 && e->d_head == 128))
+        e = nullptr;
+    return e;
+}
+const char *kNoVarlen = "packed variable-length sequences are served by the (B_r 128, B_c 64, 4 warps) + buffer configuration at d_head "
+                        "128 only, plain or causal, without speculative, prescaled_q and stats";
+
+int64_t bwd_varlen_split(const fa_bwd_varlen_args *a) {
+    const int64_t group = a->n_heads / a->n_kv_heads, wgs = a->varlen.n_seqs * a->n_kv_heads * ((a->varlen.max_seqlen + 127) / 128);
+    const int64_t want = a->causal ? 1024 : 256;
+    for (int64_t s = 1; s < group; ++s)
+        if (group % s == 0 && wgs * s >= want) return s;
+    return group;
+}
+int64_t bwd_varlen_delta_bytes(const fa_bwd_varlen_args *a) {   // (n_heads, total_tokens) fp32, rounded up to 16 bytes
+    return ((int64_t)sizeof(float) * a->n_heads * a->varlen.total_tokens + 15) & ~(int64_t)15;
+}
+
+int bwd_varlen_validate(const fa_bwd_varlen_args *a) {
+    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
+    if (a->dtype != FA_FP16 && a->dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
+    if (a->d_head != 128) return fail(FA_ERR_SHAPE, "the backward supports d_head = 128 only (got %lld)", (long long)a->d_head);
+    if (a->n_heads <= 0) return fail(FA_ERR_SHAPE, "n_heads must be positive");
+    int rc = varlen_validate(&a->varlen);
+    if (rc != FA_OK) return rc;
+    if (a->n_kv_heads < 1 || a->n_kv_heads > a->n_heads || a->n_heads % a->n_kv_heads != 0)
+        return fail(FA_ERR_SHAPE, "grouped-query attention needs n_kv_heads (%lld) to divide n_heads (%lld)", (long long)a->n_kv_heads,
+                    (long long)a->n_heads);
+    if ((rc = check_strides_varlen("q", a->n_heads, a->q_seq_stride, a->q_head_stride)) != FA_OK) return rc;
+    if ((rc = check_strides_varlen("out", a->n_heads, a->out_seq_stride, a->out_head_stride)) != FA_OK) return rc;
+    if ((rc = check_strides_varlen("kv", a->n_kv_heads, a->kv_seq_stride, a->kv_head_stride)) != FA_OK) return rc;
+    if ((rc = check_strides_varlen("dkv", a->n_kv_heads, a->dkv_seq_stride, a->dkv_head_stride)) != FA_OK) return rc;
+    if (a->n_heads * a->varlen.total_tokens > (int64_t)INT32_MAX * 8) return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
+    return varlen_grid_check(&a->varlen, a->n_heads);   // (n_kv_heads * split <= n_heads)
+}
+}  // namespace
+
+int fa_fwd_varlen_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) {
+    if (!cfg) return 0;
+    fa_fwd_opts o;
+    if (read_opts(opts, &o) != FA_OK) return 0;
+    if (o.speculative || o.prescaled_q || o.stats) return 0;
+    if (cfg->dtype != FA_BF16 && cfg->dtype != FA_FP16) return 0;
+    const char *why;
+    return varlen_entry(cfg, &why) ? 1 : 0;
+}
+
+int fa_fwd_launch_varlen(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vl, const fa_fwd_opts *opts, float *lse,
+                         void *stream) {
+    if (!args || !kv || !vl) return fail(FA_ERR_NULL, "null pointer argument");
+    if (!args->q || !args->k || !args->v || !args->o) return fail(FA_ERR_NULL, "null pointer argument");
+    if (!lse) return fail(FA_ERR_NULL, "lse is null: fa_fwd_launch_varlen needs a (n_heads, total_tokens) fp32 buffer");
+    if (args->cfg.dtype != FA_FP16 && args->cfg.dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
+    if (kv->struct_size < sizeof(fa_kv_layout))
+        return fail(FA_ERR_SHAPE, "fa_kv_layout.struct_size (%u) is smaller than this library's (%zu)", kv->struct_size, sizeof(fa_kv_layout));
+    fa_fwd_opts o;
+    int rc = read_opts(opts, &o);
+    if (rc != FA_OK) return rc;
+    if (!fa_fwd_varlen_supported(&args->cfg, opts)) return fail(FA_ERR_NO_KERNEL, "%s", kNoVarlen);
+    if (args->d_head != 128)
+        return fail(FA_ERR_SHAPE, "Tensor d_head (%lld) does not match kernel configuration d_head (%d)", (long long)args->d_head, 128);
+    if (args->n_heads <= 0) return fail(FA_ERR_SHAPE, "n_heads must be positive");
+    if ((rc = varlen_validate(vl)) != FA_OK) return rc;
+    if (kv->n_kv_heads < 1 || kv->n_kv_heads > args->n_heads || args->n_heads % kv->n_kv_heads != 0)
+        return fail(FA_ERR_SHAPE, "grouped-query attention needs n_kv_heads (%lld) to divide n_heads (%lld)", (long long)kv->n_kv_heads,
+                    (long long)args->n_heads);
+    if ((rc = check_strides_varlen("q", args->n_heads, args->seq_stride, args->head_stride)) != FA_OK) return rc;
+    if ((rc = check_strides_varlen("kv", kv->n_kv_heads, kv->kv_seq_stride, kv->kv_head_stride)) != FA_OK) return rc;
+    if ((rc = varlen_grid_check(vl, args->n_heads)) != FA_OK) return rc;
+    if (((uintptr_t)args->q | (uintptr_t)args->k | (uintptr_t)args->v | (uintptr_t)args->o) & 15)
+        return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
+    if ((uintptr_t)lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
+    if (vl->total_tokens == 0) {
+        if (o.ms) *o.ms = 0.0f;
+        return FA_OK;
+    }
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    const char *why;
+    const fa::KernelEntry *e = varlen_entry(&args->cfg, &why);
+    fa::KernelArgsVarlen va;
+    va.base.q = args->q;
+    va.base.k = args->k;
+    va.base.v = args->v;
+    va.base.o = args->o;
+    va.base.batch_stride = 0;
+    va.base.seq_stride = args->seq_stride;
+    va.base.head_stride = args->head_stride;
+    va.base.seq_len = 0;
+    va.base.n_heads = (int32_t)args->n_heads;
+    va.base.n_bh = (int32_t)(vl->n_seqs * args->n_heads);
+    va.base.n_q_blocks = (int32_t)((vl->max_seqlen + 127) / 128);
+    va.base.n_kv_blocks = 0;
+    va.base.causal = o.causal != 0;
+    va.cu_seqlens = vl->cu_seqlens;
+    va.lse = lse;
+    va.kv_seq_stride = kv->kv_seq_stride;
+    va.kv_head_stride = kv->kv_head_stride;
+    va.group = (int32_t)(args->n_heads / kv->n_kv_heads);
+    va.total_tokens = (int32_t)vl->total_tokens;
+    va.max_seqlen = (int32_t)vl->max_seqlen;
+    const bool fbs = e->softmax_mode == FA_SOFTMAX_FIRST_BLOCK_SKIP;
+    const void *fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kernel_dt15(fbs) : (const void *)fa::varlen_kernel_dt5(fbs);
+    const dim3 grid((unsigned)(va.base.n_bh * va.base.n_q_blocks)), block((unsigned)e->threads);
+    const hipStream_t s = (hipStream_t)stream;
+    return bwd_run([&] {
+        void *params[] = {&va};
+        return hipLaunchKernel(fn, grid, block, params, (size_t)e->lds_bytes, s);
+    }, s, o.ms);
+}
+
+int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *a) {
+    const int rc = bwd_varlen_validate(a);
+    if (rc != FA_OK) return rc;
+    const int64_t split = bwd_varlen_split(a);
+    return bwd_varlen_delta_bytes(a) + (split > 1 ? (int64_t)sizeof(float) * a->n_kv_heads * split * a->varlen.total_tokens * 2 * 128 : 0);
+}
+
+int fa_bwd_launch_varlen(const fa_bwd_varlen_args *a, void *stream, float *ms) {
+    int rc = bwd_varlen_validate(a);
+    if (rc != FA_OK) return rc;
+    if (!a->q || !a->k || !a->v || !a->o || !a->dout || !a->dq || !a->dk || !a->dv)
+        return fail(FA_ERR_NULL, "null tensor pointer (q, k, v, o, dout, dq, dk and dv are all needed)");
+    if (!a->lse) return fail(FA_ERR_NULL, "lse is null: the backward needs the forward's (n_heads, total_tokens) fp32 lse");
+    if (!a->workspace) return fail(FA_ERR_NULL, "workspace is null: allocate fa_bwd_varlen_workspace_bytes(args) bytes of device memory");
+    if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o | (uintptr_t)a->dout | (uintptr_t)a->dq |
+         (uintptr_t)a->dk | (uintptr_t)a->dv) & 15)
+        return fail(FA_ERR_ALIGN, "q, k, v, o, dout, dq, dk, dv must be 16-byte aligned");
+    if ((uintptr_t)a->lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
+    if ((uintptr_t)a->workspace & 15) return fail(FA_ERR_ALIGN, "workspace must be 16-byte aligned (it holds delta and the fp32 partials of dK / dV)");
+    if (a->varlen.total_tokens == 0) {
+        if (ms) *ms = 0.0f;
+        return FA_OK;
+    }
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    const int64_t split = bwd_varlen_split(a);
+    fa::BwdVarlenArgs va;
+    va.q = (const uint16_t *)a->q;
+    va.k = (const uint16_t *)a->k;
+    va.v = (const uint16_t *)a->v;
+    va.o = (const uint16_t *)a->o;
+    va.dout = (const uint16_t *)a->dout;
+    va.lse = a->lse;
+    va.delta = (float *)a->workspace;
+    va.dq = (uint16_t *)a->dq;
+    va.dk = (uint16_t *)a->dk;
+    va.dv = (uint16_t *)a->dv;
+    va.cu_seqlens = a->varlen.cu_seqlens;
+    va.part = split > 1 ? (float *)((char *)a->workspace + bwd_varlen_delta_bytes(a)) : nullptr;
+    va.q_ss = a->q_seq_stride;
+    va.q_hs = a->q_head_stride;
+    va.out_ss = a->out_seq_stride;
+    va.out_hs = a->out_head_stride;
+    va.kv_ss = a->kv_seq_stride;
+    va.kv_hs = a->kv_head_stride;
+    va.dkv_ss = a->dkv_seq_stride;
+    va.dkv_hs = a->dkv_head_stride;
+    va.n_seqs = (int32_t)a->varlen.n_seqs;
+    va.total_tokens = (int32_t)a->varlen.total_tokens;
+    va.max_seqlen = (int32_t)a->varlen.max_seqlen;
+    va.n_heads = (int32_t)a->n_heads;
+    va.group = (int32_t)(a->n_heads / a->n_kv_heads);
+    va.split = (int32_t)split;
+    va.n_blocks = (int32_t)((a->varlen.max_seqlen + 127) / 128);
+    const hipStream_t s = (hipStream_t)stream;
+    return bwd_run([&] { return fa::bwd_varlen_enqueue(va, a->dtype, a->causal != 0, s); }, s, ms);
 }
 
 static void add_slot(const AdaptiveState &ad, int idx, fa_adaptive_info *out) {

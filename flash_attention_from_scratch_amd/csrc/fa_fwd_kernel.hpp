@@ -405,6 +405,31 @@ struct FwdTraits {
                                                  : (kPlainBytes > kMergeBytes ? kPlainBytes : kMergeBytes);
 };
 
+// VARLEN (packed variable-length sequences, the training path: fa_fwd_launch_varlen): fa_fwd_kernel_varlen is the body of
+// fa_fwd_kernel whose workgroup finds its sequence's first row and length in cu_seqlens on the device, addresses K / V with a
+// head count and strides of their own (grouped-query attention) and also writes the row log-sum-exp.  Only fa_inst_varlen.hip
+// defines FA_KERNEL_VARLEN, and gets that kernel INSTEAD of fa_fwd_kernel (MASK forms only): the product's kernels keep their
+// names and, compiled from the same text, their code.  FA_KV_SS32 is the K / V seq stride in the body.
+struct KernelArgsVarlen {
+    KernelArgs base;             // q, k, v, o; Q's and O's seq (token) and head strides; n_heads; n_bh = n_seqs * n_heads;
+                                 // n_q_blocks = ceil(max_seqlen / B_r); causal.  batch_stride, seq_len, n_kv_blocks: unused
+    const int32_t *cu_seqlens;   // n_seqs + 1 row offsets (DEVICE); sequence i owns rows cu_seqlens[i] .. cu_seqlens[i + 1] - 1
+    float *lse;                  // (n_heads, total_tokens) fp32
+    int64_t kv_seq_stride, kv_head_stride;   // K, V: n_heads / group heads (elements)
+    int32_t group;               // query heads per K / V head
+    int32_t total_tokens, max_seqlen;
+};
+typedef void (*kernel_fn_varlen)(const KernelArgsVarlen);
+#ifdef FA_KERNEL_VARLEN
+#define FA_KV_SS32 kv_ss
+#define FA_SEQ_LEN v_seq_len
+#define FA_N_KV_BLOCKS ((v_seq_len + BC - 1) / BC)
+#else
+#define FA_KV_SS32 ss
+#define FA_SEQ_LEN args.seq_len
+#define FA_N_KV_BLOCKS args.n_kv_blocks
+#endif
+
 // ---------------------------------------------------------------------------------
 // The kernel.  d_head = 128 is the reference's scope (README.md:7-15); D = 64 is a widener.
 // ---------------------------------------------------------------------------------
@@ -423,8 +448,16 @@ struct FwdTraits {
 template <int DT, int QT, int NWAVES, int BC, bool SWZ, bool EAGER, bool OPT, bool PIPE, bool DMA = true,
           bool MASK = false, int D = 128, int ABL = 0, int KSPLIT = 1>
 __global__ void
+#ifdef FA_KERNEL_VARLEN
+// (one workgroup per SIMD set: with m live up to the LSE store the 256-register budget of two waves per SIMD spills)
+__launch_bounds__(NWAVES * 64, 1)
+fa_fwd_kernel_varlen(const KernelArgsVarlen va) {
+    static_assert(MASK && DMA && KSPLIT == 1 && ABL == 0, "the varlen form is the masked LDS-DMA kernel");
+    const KernelArgs &args = va.base;   // (seq_len and n_kv_blocks are the sequence's: FA_SEQ_LEN, FA_N_KV_BLOCKS)
+#else
 __launch_bounds__(NWAVES * 64, (QT == 1) ? 2 : 1)
 fa_fwd_kernel(const KernelArgs args) {
+#endif
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
     using TR = FwdTraits<DT, QT, NWAVES, BC, SWZ, EAGER, OPT, PIPE, DMA, MASK, D, KSPLIT>;
@@ -482,11 +515,32 @@ fa_fwd_kernel(const KernelArgs args) {
     if (MASK && args.causal) qb = nq - 1 - qb;  // longest rows first
     const int b = bh / args.n_heads, h = bh % args.n_heads;
     const int64_t ss = args.seq_stride;
+#ifdef FA_KERNEL_VARLEN
+    // b is the sequence: its first row and length from cu_seqlens, clamped so that every row this workgroup derives is a row
+    // of the tensors whatever cu_seqlens holds (first row in [0, total_tokens], length in [0, min(max_seqlen, what is left)])
+    int64_t v_row0 = va.cu_seqlens[b], v_len = va.cu_seqlens[b + 1];
+    v_row0 = v_row0 < 0 ? 0 : (v_row0 > va.total_tokens ? va.total_tokens : v_row0);
+    v_len -= v_row0;
+    {
+        const int64_t cap = va.total_tokens - v_row0 < va.max_seqlen ? va.total_tokens - v_row0 : va.max_seqlen;
+        v_len = v_len < 0 ? 0 : (v_len > cap ? cap : v_len);
+    }
+    if ((int64_t)qb * TR::kBr >= v_len) return;   // (workgroup-uniform; before any barrier or DMA)
+    const int v_seq_len = (int)v_len;
+    const int64_t kv_ss = va.kv_seq_stride;
+    const int64_t head_off = v_row0 * ss + (int64_t)h * args.head_stride;
+    const int64_t kv_head_off = v_row0 * kv_ss + (int64_t)(h / va.group) * va.kv_head_stride;
+    const uint16_t *Qg = (const uint16_t *)args.q + head_off;
+    const uint16_t *Kg = (const uint16_t *)args.k + kv_head_off;
+    const uint16_t *Vg = (const uint16_t *)args.v + kv_head_off;
+    uint16_t *Og = (uint16_t *)args.o + head_off;
+#else
     const int64_t head_off = (int64_t)b * args.batch_stride + (int64_t)h * args.head_stride;
     const uint16_t *Qg = (const uint16_t *)args.q + head_off;
     const uint16_t *Kg = (const uint16_t *)args.k + head_off;
     const uint16_t *Vg = (const uint16_t *)args.v + head_off;
     uint16_t *Og = (uint16_t *)args.o + head_off;
+#endif
 
     // ---- per-lane DMA source offsets (elements), invariant over tiles ------------
     // piece i (wave-uniform) covers LDS chunks [64 i, 64 i + 64) of a tile.
@@ -496,7 +550,7 @@ fa_fwd_kernel(const KernelArgs args) {
     const int k_row_in_piece = lane / CPR;                                 // 0..RPP-1
     // swizzle of tile row RPP*i + k_row_in_piece; i = wave + NWAVES*j and RPP*NWAVES % 16 == 0
     const int k_swz = SWZ ? swz_of(RPP * wave + k_row_in_piece) : 0;
-    const int64_t k_lane_off = (int64_t)k_row_in_piece * ss + (((lane & (CPR - 1)) ^ k_swz) << 3);
+    const int64_t k_lane_off = (int64_t)k_row_in_piece * FA_KV_SS32 + (((lane & (CPR - 1)) ^ k_swz) << 3);
     const int v_sub_in_piece = lane >> 5;                                  // 0..1
     const int v_w = lane & 31;
     const int64_t v_lane_row = (v_w >> 2);                                 // key & 7
@@ -505,9 +559,9 @@ fa_fwd_kernel(const KernelArgs args) {
     // KV blocks are visited last-to-first (forward_kernel.cuh:142,175-184): visit
     // index `it` is sequence block n_kv-1-it.
     // KV tiles this workgroup visits: all of them, or up to its last row's diagonal
-    const int S_len = args.seq_len;
+    const int S_len = FA_SEQ_LEN;
     const int wg_row0 = qb * TR::kBr;
-    int n_kv_ = args.n_kv_blocks;
+    int n_kv_ = FA_N_KV_BLOCKS;
     if (MASK && args.causal) {
         const int last_row = (wg_row0 + TR::kBr < S_len ? wg_row0 + TR::kBr : S_len) - 1;
         const int need = last_row / BC + 1;
@@ -521,11 +575,11 @@ fa_fwd_kernel(const KernelArgs args) {
 #pragma unroll
     for (int j = 0; j < DMA_PER_WAVE; ++j) {
         const int i = wave + NWAVES * j;  // piece index, wave-uniform; keys 4i .. 4i+3
-        k_off[j] = (unsigned)(((int64_t)(RPP * i) * ss + k_lane_off) * 2);
+        k_off[j] = (unsigned)(((int64_t)(RPP * i) * FA_KV_SS32 + k_lane_off) * 2);
         const int sub = 2 * i + v_sub_in_piece;  // subtiles 2i, 2i+1
-        v_off[j] = (unsigned)(((8 * (sub / DSUB) + v_lane_row) * ss + (sub % DSUB) * 32 + v_lane_d) * 2);
+        v_off[j] = (unsigned)(((8 * (sub / DSUB) + v_lane_row) * FA_KV_SS32 + (sub % DSUB) * 32 + v_lane_d) * 2);
     }
-    const int64_t tile_stride = (int64_t)BC * ss;  // elements between consecutive KV blocks
+    const int64_t tile_stride = (int64_t)BC * FA_KV_SS32;  // elements between consecutive KV blocks
     f32x4 abl_dummy[2 * DMA_PER_WAVE];  // ABL & 32 only: landing registers of plain loads
     // MASK: rows of the last sequence block that lie beyond seq_len are fetched from the last
     // valid row instead (their logits are masked, their P is exactly 0).
@@ -542,7 +596,7 @@ fa_fwd_kernel(const KernelArgs args) {
             for (int j = 0; j < DMA_PER_WAVE; ++j) {
                 int row = RPP * (wave + NWAVES * j) + k_row_in_piece;
                 row = row < valid ? row : valid - 1;
-                const unsigned off = (unsigned)(((int64_t)row * ss + (((lane & (CPR - 1)) ^ k_swz) << 3)) * 2);
+                const unsigned off = (unsigned)(((int64_t)row * FA_KV_SS32 + (((lane & (CPR - 1)) ^ k_swz) << 3)) * 2);
                 glds16_sv(base, off, kdst + (wave + NWAVES * j) * 1024);
             }
             return;
@@ -565,7 +619,7 @@ fa_fwd_kernel(const KernelArgs args) {
                 const int sub = 2 * (wave + NWAVES * j) + v_sub_in_piece;
                 int row = 8 * (sub / DSUB) + (int)v_lane_row;
                 row = row < valid ? row : valid - 1;
-                const unsigned off = (unsigned)(((int64_t)row * ss + (sub % DSUB) * 32 + v_lane_d) * 2);
+                const unsigned off = (unsigned)(((int64_t)row * FA_KV_SS32 + (sub % DSUB) * 32 + v_lane_d) * 2);
                 glds16_sv(base, off, vdst + (wave + NWAVES * j) * 1024);
             }
             return;
@@ -1102,6 +1156,20 @@ fa_fwd_kernel(const KernelArgs args) {
         attempt(FalseTag{});
     }
 
+#ifdef FA_KERNEL_VARLEN
+    // lse = ln l + m / sqrt d in the kernel's own units (m c is log2): one fp32 per valid row; both lane halves hold it
+    // (this (sequence, head)'s rows of lse, found again here rather than kept in registers across the loop)
+    int64_t l_row0 = va.cu_seqlens[b];
+    l_row0 = l_row0 < 0 ? 0 : (l_row0 > va.total_tokens ? va.total_tokens : l_row0);
+    float *lse_rows = va.lse + ((int64_t)h * va.total_tokens + l_row0);
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+        const float l_row = pair_sum(l[qt]);
+        const int row = wave_row0 + qt * 32 + r31;
+        if (hi == 0 && row < S_len)
+            lse_rows[row] = (__builtin_amdgcn_logf(l_row) + finite_or_zero(m[qt]) * c) * 0.693147180559945309f;
+    }
+#endif
     if ((ABL & 32) && args.seq_len < 0) {  // never true: keeps the landing registers allocated
 #pragma unroll
         for (int j = 0; j < 2 * DMA_PER_WAVE; ++j) *(f32x4 *)(Og + j * 8 + lane * 64) = abl_dummy[j];

@@ -88,3 +88,44 @@ def attention(q, k, v, causal=False):
     The forward is best_config(dtype, seq_len, masked=causal) with the row log-sum-exp; the backward is the HIP backward.
     Grouped-query attention: k and v may have n_kv_heads heads (dividing n_heads); their gradients then have as many."""
     return _Attention.apply(q, k, v, causal)
+
+
+def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False):
+    """Packed variable-length sequences: q (total_tokens, n_heads, 128), k / v (total_tokens, n_kv_heads, 128), cu_seqlens an
+    int32 device tensor of n_seqs + 1 row offsets, max_seqlen a Python int (no device sync) -> (o, lse[, ms]) with lse fp32
+    (n_heads, total_tokens).  A query attends to the keys of its own sequence (causal: at or before its position in it)."""
+    return flash_attention_kernels.forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=causal, timed=timed)
+
+
+def backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=False, timed=False):
+    """dQ, dK, dV over packed sequences from forward_varlen's o and lse -> (dq, dk, dv[, ms]).  Deterministic."""
+    return flash_attention_kernels.backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=causal, timed=timed)
+
+
+def _varlen_needs_copy(t):
+    return t.stride(2) != 1 or t.stride(0) % 8 != 0 or t.stride(1) % 8 != 0 or t.data_ptr() % 16 != 0
+
+
+class _AttentionVarlen(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens, max_seqlen, causal):
+        if _varlen_needs_copy(q):
+            q = q.contiguous()
+        if _varlen_needs_copy(k) or _varlen_needs_copy(v) or v.stride() != k.stride():
+            k, v = k.contiguous(), v.contiguous()
+        o, lse = forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=causal)
+        ctx.save_for_backward(q, k, v, o, lse, cu_seqlens)
+        ctx.max_seqlen, ctx.causal = max_seqlen, causal
+        return o
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, o, lse, cu_seqlens = ctx.saved_tensors
+        dq, dk, dv = backward_varlen(q, k, v, o, lse, dout.contiguous(), cu_seqlens, ctx.max_seqlen, causal=ctx.causal)
+        return dq, dk, dv, None, None, None
+
+
+def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False):
+    """softmax(q k^T / sqrt d) v over packed sequences, with gradients (flash-attn's flash_attn_varlen_func for self-attention):
+    the varlen forward with the row log-sum-exp and the varlen HIP backward.  k and v may have n_kv_heads heads."""
+    return _AttentionVarlen.apply(q, k, v, cu_seqlens, max_seqlen, causal)

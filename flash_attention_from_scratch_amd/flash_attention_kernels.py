@@ -289,3 +289,96 @@ def _backward_gqa(q, k, v, o, lse, dout, causal, timed):
         ms = ctypes.c_float(0.0)
         _capi.check(lib.fa_bwd_launch_gqa(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
     return (dq, dk, dv, float(ms.value)) if timed else (dq, dk, dv)
+
+
+# ---- packed variable-length sequences (fa_fwd_launch_varlen / fa_bwd_launch_varlen) ------------------------------------------
+
+def varlen_config(dtype):
+    """The configuration whose masked variant the varlen forward is the twin of: (B_r 128, B_c 64, 4 warps) + buffer."""
+    from .flash_helpers import kernel_configs as kc
+
+    name = kc.DType.BF16 if dtype == torch.bfloat16 else kc.DType.FP16
+    return kc.FlashForwardKernelConfig(name, 128, 128, 64, 4, True, True, True, 0, 0, 0, True, False)
+
+
+def _check_varlen(q, k, v, cu_seqlens, max_seqlen, others=()):
+    for t, name in ((q, "q"), (k, "k"), (v, "v"), (cu_seqlens, "cu_seqlens")) + tuple(others):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError("Only fp16 and bf16 are supported")
+    if any(t.dtype != q.dtype for t in (k, v) + tuple(t for t, name in others if name != "lse")):
+        raise RuntimeError("q, k, v (o and dout) must have the same data type")
+    if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2]:
+        raise RuntimeError("packed sequences: q must have shape (total_tokens, n_heads, d_head), k and v (total_tokens, n_kv_heads, d_head)")
+    if k.shape[1] < 1 or q.shape[1] % k.shape[1] != 0:
+        raise RuntimeError(f"grouped-query attention: the K / V heads ({k.shape[1]}) must divide the query heads ({q.shape[1]})")
+    if q.stride(2) != 1 or k.stride(2) != 1 or v.stride() != k.stride():
+        raise RuntimeError("packed sequences: q, k, v need a contiguous last dimension, k and v one stride set")
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2 or not cu_seqlens.is_contiguous():
+        raise RuntimeError("cu_seqlens must be a contiguous int32 tensor of n_seqs + 1 entries on q's device")
+    if not isinstance(max_seqlen, int) or isinstance(max_seqlen, bool):
+        raise RuntimeError("max_seqlen must be a Python int (a bound on every sequence's length; the device is not asked)")
+
+
+def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False):
+    """Attention over packed sequences with the row log-sum-exp (fa_fwd_launch_varlen): q (total_tokens, n_heads, 128), k and v
+    (total_tokens, n_kv_heads, 128), cu_seqlens an int32 device tensor of n_seqs + 1 row offsets, max_seqlen a Python int.
+    Strided views (a packed QKV buffer) pass as they are.  -> (o, lse[, ms]); o contiguous, lse fp32 (n_heads, total_tokens).
+    No device synchronisation unless timed."""
+    _check_varlen(q, k, v, cu_seqlens, max_seqlen)
+    total, n_heads, d_head = q.shape
+    lib = _capi.load()
+    cfg = _capi.make_config(varlen_config(q.dtype))
+    o = torch.empty((total, n_heads, d_head), dtype=q.dtype, device=q.device)
+    lse = torch.empty((n_heads, total), dtype=torch.float32, device=q.device)
+    if q.stride() != o.stride():   # (the launch has one stride set for q and o)
+        q = q.contiguous()
+    args = _capi.FaFwdArgs(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), o=o.data_ptr(), batch=1, seq_len=total, n_heads=n_heads,
+                           d_head=d_head, batch_stride=0, seq_stride=q.stride(0), head_stride=q.stride(1), cfg=cfg)
+    kv = _capi.make_kv_layout(k.shape[1], 0, k.stride(0), k.stride(1))
+    vl = _capi.make_varlen_layout(cu_seqlens.data_ptr(), cu_seqlens.numel() - 1, total, max_seqlen)
+    ms = ctypes.c_float(0.0)
+    opts = _capi.make_opts(causal=causal, ms=ms if timed else None)
+    with torch.cuda.device(q.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        _capi.check(lib.fa_fwd_launch_varlen(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(vl), ctypes.byref(opts),
+                                             ctypes.c_void_p(lse.data_ptr()), stream))
+    return (o, lse, float(ms.value)) if timed else (o, lse)
+
+
+def backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=False, timed=False):
+    """dQ, dK, dV over packed sequences from forward_varlen's o and lse and the gradient dout (fa_bwd_launch_varlen).  q, and
+    k / v (one stride set), may be strided views; o and dout are made contiguous; the gradients come back contiguous, dk and dv
+    with k's n_kv_heads heads.  -> (dq, dk, dv[, ms])."""
+    _check_varlen(q, k, v, cu_seqlens, max_seqlen, others=((o, "o"), (dout, "dout"), (lse, "lse")))
+    total, n_heads, d_head = q.shape
+    n_kv = k.shape[1]
+    if o.shape != q.shape or dout.shape != q.shape:
+        raise RuntimeError("q, o and dout must have one shape (total_tokens, n_heads, d_head)")
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (n_heads, total) or not lse.is_contiguous():
+        raise RuntimeError("lse must be a contiguous fp32 (n_heads, total_tokens) tensor")
+    o, dout = o.contiguous(), dout.contiguous()
+    dq = torch.empty_like(o)
+    dk = torch.empty((total, n_kv, d_head), dtype=q.dtype, device=q.device)
+    dv = torch.empty_like(dk)
+    lib = _capi.load()
+    args = _capi.FaBwdVarlenArgs(
+        q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), o=o.data_ptr(), dout=dout.data_ptr(),
+        lse=ctypes.cast(ctypes.c_void_p(lse.data_ptr()), ctypes.POINTER(ctypes.c_float)),
+        dq=dq.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), workspace=16,
+        n_heads=n_heads, n_kv_heads=n_kv, d_head=d_head,
+        q_seq_stride=q.stride(0), q_head_stride=q.stride(1), out_seq_stride=o.stride(0), out_head_stride=o.stride(1),
+        kv_seq_stride=k.stride(0), kv_head_stride=k.stride(1), dkv_seq_stride=dk.stride(0), dkv_head_stride=dk.stride(1),
+        dtype=15 if q.dtype == torch.bfloat16 else 5, causal=1 if causal else 0,
+        varlen=_capi.make_varlen_layout(cu_seqlens.data_ptr(), cu_seqlens.numel() - 1, total, max_seqlen),
+    )
+    nbytes = lib.fa_bwd_varlen_workspace_bytes(ctypes.byref(args))
+    _capi.check(nbytes if nbytes < 0 else 0)
+    with torch.cuda.device(q.device):
+        workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)   # (on the current stream's allocator)
+        args.workspace = workspace.data_ptr()
+        stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        ms = ctypes.c_float(0.0)
+        _capi.check(lib.fa_bwd_launch_varlen(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
+    return (dq, dk, dv, float(ms.value)) if timed else (dq, dk, dv)

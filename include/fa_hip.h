@@ -377,6 +377,73 @@ typedef struct fa_bwd_gqa_args {
 int64_t fa_bwd_gqa_workspace_bytes(const fa_bwd_gqa_args *args);      /* bytes, or a negative fa_status */
 int fa_bwd_launch_gqa(const fa_bwd_gqa_args *args, void *stream, float *ms);
 
+/*
+ * Packed variable-length sequences (flash-attn's varlen interface), forward with lse and backward, MHA and GQA / MQA, plain
+ * and causal, bf16 / fp16, d_head 128.  All tokens of all sequences lie in one (total_tokens, heads, 128) tensor; sequence i
+ * owns token rows cu_seqlens[i] .. cu_seqlens[i + 1] - 1; Q and K / V share cu_seqlens; a query attends to the keys of its
+ * own sequence only (causal: at or before its own position in it).  Any length >= 0 is valid.
+ *
+ * fa_varlen_layout: cu_seqlens is a DEVICE pointer to n_seqs + 1 int32 (4-byte aligned) which the host never reads: the
+ * launches stay asynchronous and graph-capturable.  The contract is the caller's -- non-decreasing, cu_seqlens[0] = 0,
+ * cu_seqlens[n_seqs] = total_tokens, every length <= max_seqlen (a loose bound only costs idle workgroups) -- but a
+ * violation cannot fault: every kernel clamps a sequence's first row to [0, total_tokens] and its length to [0, min(max_seqlen,
+ * total_tokens - first row)].  Results for a violated contract are unspecified; memory outside the tensors is never touched.
+ *
+ * fa_fwd_launch_varlen: args carries q, o (token stride seq_stride, head_stride), k, v, n_heads, d_head and cfg; args->batch,
+ * ->seq_len and ->batch_stride are IGNORED.  kv: K's and V's heads and strides (kv_batch_stride ignored; n_kv_heads = n_heads
+ * for MHA).  lse: (n_heads, total_tokens) fp32, contiguous (flash-attn's layout for packed input), required.  opts: causal and
+ * ms; speculative, prescaled_q and stats have no varlen form and are refused (FA_ERR_NO_KERNEL), allow_ragged is implied.
+ * Served (fa_fwd_varlen_supported): the configurations whose masked variant is the 32-rows-per-wave kernel of the
+ * (B_r 128, B_c 64, 4 warps) + buffer shape at d_head 128; O of sequence i is bit-identical to fa_fwd_launch_ex (allow_ragged)
+ * of that variant on the sequence alone.  total_tokens = 0 returns FA_OK without a launch.
+ *
+ * fa_bwd_launch_varlen: q_* are Q's strides, out_* those of O, dO and dQ, kv_* of K and V, dkv_* of dK and dV (elements,
+ * positive multiples of 8, token stride * 256 * 2 bytes within 32 bits).  The dK / dV kernel runs n_seqs * n_kv_heads * split *
+ * ceil(max_seqlen / 128) workgroups; split is the smallest divisor of n_heads / n_kv_heads for which that count reaches 256
+ * (1024 causal), else the whole group: a function of n_seqs, max_seqlen, the head counts and causal, never of what
+ * cu_seqlens holds.  workspace: fa_bwd_varlen_workspace_bytes bytes (delta, and the split's fp32 partials), 16-byte aligned.
+ * Deterministic like fa_bwd_launch; for sequences whose length is a multiple of 256 dQ has fa_bwd_launch's bits, dK / dV too
+ * where the two launches use the same split.
+ */
+typedef struct fa_varlen_layout {
+    uint32_t struct_size;
+    const int32_t *cu_seqlens;
+    int64_t n_seqs;
+    int64_t total_tokens;
+    int64_t max_seqlen;
+} fa_varlen_layout;
+int fa_fwd_varlen_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen, const fa_fwd_opts *opts,
+                         float *lse, void *stream);
+typedef struct fa_bwd_varlen_args {
+    const void *q;
+    const void *k;
+    const void *v;
+    const void *o;
+    const void *dout;
+    const float *lse;        /* (n_heads, total_tokens) fp32, contiguous */
+    void *dq;
+    void *dk;
+    void *dv;
+    void *workspace;
+    int64_t n_heads;
+    int64_t n_kv_heads;
+    int64_t d_head;
+    int64_t q_seq_stride;
+    int64_t q_head_stride;
+    int64_t out_seq_stride;
+    int64_t out_head_stride;
+    int64_t kv_seq_stride;
+    int64_t kv_head_stride;
+    int64_t dkv_seq_stride;
+    int64_t dkv_head_stride;
+    int32_t dtype;           /* fa_dtype */
+    int32_t causal;
+    fa_varlen_layout varlen;
+} fa_bwd_varlen_args;
+int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *args);   /* bytes, or a negative fa_status */
+int fa_bwd_launch_varlen(const fa_bwd_varlen_args *args, void *stream, float *ms);
+
 /* The adaptive speculative mode's record on `device` (fa_speculative_mode), and a reset of its demotion state (tests,
  * or a caller that knows its data has changed character). */
 int fa_adaptive_state(int device, fa_adaptive_info *out);
