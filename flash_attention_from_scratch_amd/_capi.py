@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_lse_supported", "fa_fwd_launch_lse", "fa_bwd_workspace_bytes", "fa_bwd_launch",
     "fa_fwd_gqa_supported", "fa_fwd_launch_gqa", "fa_bwd_gqa_workspace_bytes", "fa_bwd_launch_gqa",
     "fa_fwd_varlen_supported", "fa_fwd_launch_varlen", "fa_bwd_varlen_workspace_bytes", "fa_bwd_launch_varlen",
+    "fa_decode_supported", "fa_decode_num_splits", "fa_decode_workspace_bytes", "fa_decode_launch",
 )
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
 FA_ABI_VERSION = 6
@@ -130,6 +131,28 @@ class FaBwdVarlenArgs(ctypes.Structure):   # fa_bwd_varlen_args
         ("dtype", ctypes.c_int32), ("causal", ctypes.c_int32),
         ("varlen", FaVarlenLayout),
     ]
+
+
+class FaDecodeArgs(ctypes.Structure):   # fa_decode_args (KV-cache decode: contiguous or paged cache, lengths on the device)
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("causal", ctypes.c_int32), ("num_splits", ctypes.c_int32),
+        ("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p), ("o", ctypes.c_void_p), ("lse", ctypes.c_void_p),
+        ("cache_seqlens", ctypes.c_void_p), ("block_table", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+        ("batch", ctypes.c_int64), ("seqlen_q", ctypes.c_int64), ("n_heads", ctypes.c_int64), ("n_kv_heads", ctypes.c_int64),
+        ("d_head", ctypes.c_int64), ("seqlen_cache", ctypes.c_int64), ("num_pages", ctypes.c_int64), ("page_size", ctypes.c_int64),
+        ("max_pages_per_seq", ctypes.c_int64), ("block_table_stride", ctypes.c_int64), ("max_seqlen_k", ctypes.c_int64),
+        ("q_batch_stride", ctypes.c_int64), ("q_seq_stride", ctypes.c_int64), ("q_head_stride", ctypes.c_int64),
+        ("o_batch_stride", ctypes.c_int64), ("o_seq_stride", ctypes.c_int64), ("o_head_stride", ctypes.c_int64),
+        ("kv_batch_stride", ctypes.c_int64), ("kv_seq_stride", ctypes.c_int64), ("kv_head_stride", ctypes.c_int64),
+    ]
+
+
+def make_decode_args(**fields):
+    """fa_decode_args with struct_size set; d_head defaults to 128, everything not given to 0 / null."""
+    a = FaDecodeArgs(struct_size=ctypes.sizeof(FaDecodeArgs), d_head=128)
+    for name, value in fields.items():
+        setattr(a, name, value)
+    return a
 
 
 def make_varlen_layout(cu_seqlens_ptr, n_seqs, total_tokens, max_seqlen):
@@ -254,6 +277,14 @@ def load():
     lib.fa_bwd_varlen_workspace_bytes.argtypes = [ctypes.POINTER(FaBwdVarlenArgs)]
     lib.fa_bwd_launch_varlen.restype = ctypes.c_int
     lib.fa_bwd_launch_varlen.argtypes = [ctypes.POINTER(FaBwdVarlenArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    lib.fa_decode_supported.restype = ctypes.c_int
+    lib.fa_decode_supported.argtypes = [ctypes.POINTER(FaDecodeArgs)]
+    lib.fa_decode_num_splits.restype = ctypes.c_int
+    lib.fa_decode_num_splits.argtypes = [ctypes.POINTER(FaDecodeArgs)]
+    lib.fa_decode_workspace_bytes.restype = ctypes.c_int64
+    lib.fa_decode_workspace_bytes.argtypes = [ctypes.POINTER(FaDecodeArgs)]
+    lib.fa_decode_launch.restype = ctypes.c_int
+    lib.fa_decode_launch.argtypes = [ctypes.POINTER(FaDecodeArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p
     lib.fa_last_error.argtypes = []
     lib.fa_version.restype = ctypes.c_char_p

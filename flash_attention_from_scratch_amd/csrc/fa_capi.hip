@@ -19,6 +19,7 @@
 #include "../../include/fa_hip.h"
 #include "fa_bwd_gqa.hpp"
 #include "fa_bwd_varlen.hpp"
+#include "fa_decode_kernel.hpp"
 #include "fa_registry.hpp"
 
 extern "C" {
@@ -1117,6 +1118,154 @@ int fa_bwd_launch_varlen(const fa_bwd_varlen_args *a, void *stream, float *ms) {
     va.n_blocks = (int32_t)((a->varlen.max_seqlen + 127) / 128);
     const hipStream_t s = (hipStream_t)stream;
     return bwd_run([&] { return fa::bwd_varlen_enqueue(va, a->dtype, a->causal != 0, s); }, s, ms);
+}
+
+// ---- KV-cache decode ------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int64_t kDecodeMaxRows = 64, kDecodeWantWgs = 256, kDecodeKeysPerSplit = 256, kDecodeMaxSplits = 128, kDecodeMaxForced = 1024;
+
+int64_t decode_capacity(const fa_decode_args *a) { return a->block_table ? a->max_pages_per_seq * a->page_size : a->seqlen_cache; }
+
+// one stride set of the decode path: positive multiples of 8 elements (the kernels form 64-bit offsets)
+int decode_strides(const char *which, int64_t n0, int64_t n1, int64_t n2, int64_t bs, int64_t ss, int64_t hs) {
+    if (ss <= 0 || bs < 0 || hs < 0 || (n0 > 1 && bs == 0) || (n2 > 1 && hs == 0) || (n1 > 1 && ss == 0))
+        return fail(FA_ERR_SHAPE, "%s strides must be positive (batch %lld, seq %lld, head %lld elements)", which, (long long)bs,
+                    (long long)ss, (long long)hs);
+    if ((bs | ss | hs) & 7) return fail(FA_ERR_ALIGN, "%s strides must be multiples of 8 elements (16 bytes)", which);
+    return FA_OK;
+}
+
+// everything but the pointers' values: dtype, kernel, sizes, strides -- in the order of the statuses' numbers
+int decode_validate(const fa_decode_args *a) {
+    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
+    if (a->struct_size < sizeof(fa_decode_args))
+        return fail(FA_ERR_SHAPE, "fa_decode_args.struct_size (%u) is smaller than this library's (%zu)", a->struct_size, sizeof(fa_decode_args));
+    if (a->dtype != FA_FP16 && a->dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
+    if (a->d_head != 128) return fail(FA_ERR_SHAPE, "decode supports d_head = 128 only (got %lld)", (long long)a->d_head);
+    if (a->batch < 0 || a->seqlen_q <= 0 || a->n_heads <= 0) return fail(FA_ERR_SHAPE, "batch must not be negative, seqlen_q and n_heads must be positive");
+    if (a->batch > INT32_MAX / 2 || a->n_heads > INT32_MAX / 2) return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
+    if (a->n_kv_heads < 1 || a->n_kv_heads > a->n_heads || a->n_heads % a->n_kv_heads != 0)
+        return fail(FA_ERR_SHAPE, "grouped-query attention needs n_kv_heads (%lld) to divide n_heads (%lld)", (long long)a->n_kv_heads,
+                    (long long)a->n_heads);
+    const int64_t group = a->n_heads / a->n_kv_heads;
+    if (a->seqlen_q > kDecodeMaxRows || a->seqlen_q * group > kDecodeMaxRows)
+        return fail(FA_ERR_NO_KERNEL, "decode serves seqlen_q * (n_heads / n_kv_heads) <= 64 packed query rows (got %lld * %lld): use the "
+                                      "forward entry points for longer queries", (long long)a->seqlen_q, (long long)group);
+    if (a->block_table) {
+        if (a->page_size <= 0 || a->num_pages <= 0 || a->max_pages_per_seq <= 0)
+            return fail(FA_ERR_SHAPE, "paged cache: num_pages, page_size and max_pages_per_seq must be positive");
+        if (a->page_size % 64 != 0)
+            return fail(FA_ERR_NO_KERNEL, "paged cache: page_size must be a multiple of 64 (got %lld)", (long long)a->page_size);
+        if (a->block_table_stride < a->max_pages_per_seq)
+            return fail(FA_ERR_SHAPE, "block_table_stride (%lld) is smaller than max_pages_per_seq (%lld)", (long long)a->block_table_stride,
+                        (long long)a->max_pages_per_seq);
+        if (a->num_pages > INT32_MAX / 2 || a->page_size > INT32_MAX / 2 || a->max_pages_per_seq > INT32_MAX / 2)
+            return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
+    } else if (a->seqlen_cache <= 0) {
+        return fail(FA_ERR_SHAPE, "seqlen_cache must be positive (got %lld)", (long long)a->seqlen_cache);
+    }
+    const int64_t cap = decode_capacity(a);
+    if (cap > INT32_MAX / 2) return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
+    if (a->max_seqlen_k < 0 || a->max_seqlen_k > cap)
+        return fail(FA_ERR_SHAPE, "max_seqlen_k (%lld) must lie in [0, %lld] (0 = the cache's capacity)", (long long)a->max_seqlen_k, (long long)cap);
+    if (a->num_splits < 0 || a->num_splits > kDecodeMaxForced)
+        return fail(FA_ERR_SHAPE, "num_splits (%d) must lie in [0, %lld] (0 = the split rule)", a->num_splits, (long long)kDecodeMaxForced);
+    int rc = decode_strides("q", a->batch, a->seqlen_q, a->n_heads, a->q_batch_stride, a->q_seq_stride, a->q_head_stride);
+    if (rc != FA_OK) return rc;
+    if ((rc = decode_strides("o", a->batch, a->seqlen_q, a->n_heads, a->o_batch_stride, a->o_seq_stride, a->o_head_stride)) != FA_OK) return rc;
+    if ((rc = decode_strides("kv", a->block_table ? a->num_pages : a->batch, cap, a->n_kv_heads, a->kv_batch_stride, a->kv_seq_stride,
+                             a->kv_head_stride)) != FA_OK)
+        return rc;
+    if (a->batch * a->n_kv_heads * kDecodeMaxForced > INT32_MAX || a->batch * a->n_heads * a->seqlen_q > INT32_MAX)
+        return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
+    return FA_OK;
+}
+
+// The split rule: a pure function of batch, n_kv_heads and the host's key bound.  The smallest power of two that gives
+// the grid one workgroup per CU of an MI355X (256, the count the GQA backward's split uses), while a split keeps at
+// least 256 keys of the bound, at most 128.
+int64_t decode_splits(const fa_decode_args *a) {
+    if (a->num_splits > 0) return a->num_splits;
+    const int64_t max_k = a->max_seqlen_k > 0 ? a->max_seqlen_k : decode_capacity(a);
+    int64_t s = 1;
+    while (a->batch * a->n_kv_heads * s < kDecodeWantWgs && s < kDecodeMaxSplits) s *= 2;
+    const int64_t by_keys = (max_k + kDecodeKeysPerSplit - 1) / kDecodeKeysPerSplit;
+    return s < by_keys ? s : (by_keys < 1 ? 1 : by_keys);
+}
+
+int64_t decode_part_o_bytes(const fa_decode_args *a, int64_t splits) {
+    return (int64_t)sizeof(float) * splits * a->batch * a->n_kv_heads * (a->seqlen_q * (a->n_heads / a->n_kv_heads)) * 128;
+}
+}  // namespace
+
+int fa_decode_supported(const fa_decode_args *a) { return decode_validate(a) == FA_OK ? 1 : 0; }
+
+int fa_decode_num_splits(const fa_decode_args *a) {
+    const int rc = decode_validate(a);
+    return rc != FA_OK ? rc : (int)decode_splits(a);
+}
+
+int64_t fa_decode_workspace_bytes(const fa_decode_args *a) {
+    const int rc = decode_validate(a);
+    if (rc != FA_OK) return rc;
+    const int64_t splits = decode_splits(a);
+    if (splits == 1) return 0;
+    const int64_t po = decode_part_o_bytes(a, splits);   // (a multiple of 512), then the partial lse
+    return po + ((po / 128 + 15) & ~(int64_t)15);
+}
+
+int fa_decode_launch(const fa_decode_args *a, void *stream, float *ms) {
+    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
+    if (!a->q || !a->k || !a->v || !a->o) return fail(FA_ERR_NULL, "null tensor pointer (q, k, v and o are all needed)");
+    if (!a->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to batch int32 lengths is needed");
+    int rc = decode_validate(a);
+    if (rc != FA_OK) return rc;
+    if (a->batch == 0) {
+        if (ms) *ms = 0.0f;
+        return FA_OK;
+    }
+    const int64_t splits = decode_splits(a);
+    if (splits > 1 && !a->workspace)
+        return fail(FA_ERR_NULL, "workspace is null: allocate fa_decode_workspace_bytes(args) bytes of device memory");
+    if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) & 15) return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
+    if (((uintptr_t)a->cache_seqlens | (uintptr_t)a->block_table | (uintptr_t)a->lse) & 3)
+        return fail(FA_ERR_ALIGN, "cache_seqlens, block_table and lse must be 4-byte aligned");
+    if (splits > 1 && ((uintptr_t)a->workspace & 15)) return fail(FA_ERR_ALIGN, "workspace must be 16-byte aligned (it holds the splits' fp32 partials)");
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    fa::DecodeArgs d;
+    d.q = (const uint16_t *)a->q;
+    d.k = (const uint16_t *)a->k;
+    d.v = (const uint16_t *)a->v;
+    d.o = (uint16_t *)a->o;
+    d.lse = a->lse;
+    d.cache_seqlens = a->cache_seqlens;
+    d.block_table = a->block_table;
+    d.part_o = splits > 1 ? (float *)a->workspace : nullptr;
+    d.part_lse = splits > 1 ? (float *)((char *)a->workspace + decode_part_o_bytes(a, splits)) : nullptr;
+    d.q_bs = a->q_batch_stride;
+    d.q_ss = a->q_seq_stride;
+    d.q_hs = a->q_head_stride;
+    d.o_bs = a->o_batch_stride;
+    d.o_ss = a->o_seq_stride;
+    d.o_hs = a->o_head_stride;
+    d.kv_bs = a->kv_batch_stride;
+    d.kv_ss = a->kv_seq_stride;
+    d.kv_hs = a->kv_head_stride;
+    d.bt_bs = a->block_table ? a->block_table_stride : 0;
+    d.batch = (int32_t)a->batch;
+    d.seqlen_q = (int32_t)a->seqlen_q;
+    d.n_heads = (int32_t)a->n_heads;
+    d.n_kv_heads = (int32_t)a->n_kv_heads;
+    d.group = (int32_t)(a->n_heads / a->n_kv_heads);
+    d.rows = d.seqlen_q * d.group;
+    d.max_len = (int32_t)decode_capacity(a);
+    d.page_size = a->block_table ? (int32_t)a->page_size : 0;
+    d.num_pages = a->block_table ? (int32_t)a->num_pages : 0;
+    d.num_splits = (int32_t)splits;
+    d.causal = a->causal != 0;
+    const hipStream_t s = (hipStream_t)stream;
+    return bwd_run([&] { return fa::decode_enqueue(d, a->dtype, s); }, s, ms);
 }
 
 static void add_slot(const AdaptiveState &ad, int idx, fa_adaptive_info *out) {

@@ -97,6 +97,18 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False):
     return flash_attention_kernels.forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=causal, timed=timed)
 
 
+def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
+                    num_splits=0, timed=False):
+    """Decode attention against a K / V cache: q (batch, seqlen_q, n_heads, 128) against k_cache / v_cache
+    (batch, seqlen_cache, n_kv_heads, 128) -- or, with block_table (batch, max_pages_per_seq) int32, pages (num_pages,
+    page_size, n_kv_heads, 128) -- of which cache_seqlens (batch,) int32 ON THE DEVICE says how many keys are valid, the newest
+    tokens included.  seqlen_q * n_heads / n_kv_heads <= 64; causal is bottom-right aligned; a row without keys gives o = 0,
+    lse = -inf.  num_splits = 0 takes the split rule (a function of the shapes and max_seqlen_k alone).  -> o, or (o, lse) with
+    return_lse, each with ms appended if timed.  No device synchronisation unless timed; graph-capturable."""
+    return flash_attention_kernels.forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=block_table, causal=causal,
+                                                   return_lse=return_lse, max_seqlen_k=max_seqlen_k, num_splits=num_splits, timed=timed)
+
+
 def backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=False, timed=False):
     """dQ, dK, dV over packed sequences from forward_varlen's o and lse -> (dq, dk, dv[, ms]).  Deterministic."""
     return flash_attention_kernels.backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=causal, timed=timed)

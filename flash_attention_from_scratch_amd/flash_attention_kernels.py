@@ -382,3 +382,96 @@ def backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=False,
         ms = ctypes.c_float(0.0)
         _capi.check(lib.fa_bwd_launch_varlen(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
     return (dq, dk, dv, float(ms.value)) if timed else (dq, dk, dv)
+
+
+# ---- KV-cache decode (fa_decode_launch) ------------------------------------------------------------------------------------
+
+def _decode_needs_copy(t):
+    """A view the launch cannot take as it is: last dimension not contiguous, strides not multiples of 8 elements, or a base
+    that is not 16-byte aligned."""
+    return t.stride(-1) != 1 or any(s % 8 for s in t.stride()[:-1]) or t.data_ptr() % 16 != 0
+
+
+def kvcache_num_splits(q, k_cache, v_cache, cache_seqlens, block_table=None, max_seqlen_k=None, num_splits=0):
+    """The split count forward_kvcache uses for these arguments (fa_decode_num_splits): the same checks, nothing allocated, no
+    launch."""
+    _, args = _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, False, max_seqlen_k, num_splits)
+    return _capi.check(_capi.load().fa_decode_num_splits(ctypes.byref(args)))
+
+
+def _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_seqlen_k, num_splits):
+    """forward_kvcache's checks -> (q as the launch takes it, fa_decode_args still without o, lse and workspace)."""
+    tensors = [(q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cache_seqlens, "cache_seqlens")]
+    if block_table is not None:
+        tensors.append((block_table, "block_table"))
+    for t, name in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+        if t.device != q.device:
+            raise RuntimeError(f"{name} must be on q's device ({q.device}, got {t.device})")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError("Only fp16 and bf16 are supported")
+    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise RuntimeError("Input tensors must have the same data type")
+    if q.dim() != 4 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[3] != q.shape[3]:
+        raise RuntimeError("q must have shape (batch, seqlen_q, n_heads, d_head), k_cache and v_cache one shape (batch or "
+                           "num_pages, seqlen_cache or page_size, n_kv_heads, d_head)")
+    batch, seqlen_q, n_heads, d_head = q.shape
+    if block_table is None and k_cache.shape[0] != batch:
+        raise RuntimeError("a contiguous cache needs q's batch size (pass block_table for a paged cache)")
+    if cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (batch,) or not cache_seqlens.is_contiguous():
+        raise RuntimeError("cache_seqlens must be a contiguous int32 tensor of batch entries on q's device")
+    if block_table is not None and (block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != batch
+                                    or block_table.stride(1) != 1):
+        raise RuntimeError("block_table must be an int32 (batch, max_pages_per_seq) tensor on q's device with a contiguous last dimension")
+    if max_seqlen_k is not None and (not isinstance(max_seqlen_k, int) or isinstance(max_seqlen_k, bool)):
+        raise RuntimeError("max_seqlen_k must be a Python int (a bound on every length; the device is not asked)")
+    if _decode_needs_copy(q):
+        q = q.contiguous()
+    if _decode_needs_copy(k_cache) or _decode_needs_copy(v_cache) or k_cache.stride() != v_cache.stride():
+        # (a serving cache is gigabytes: copying it on every call would be silently slow)
+        raise RuntimeError("k_cache and v_cache need one stride set, a contiguous last dimension, strides that are multiples of 8 "
+                           "elements and a 16-byte aligned base")
+    args = _capi.make_decode_args(
+        dtype=15 if q.dtype == torch.bfloat16 else 5, causal=1 if causal else 0, num_splits=int(num_splits),
+        q=q.data_ptr(), k=k_cache.data_ptr(), v=v_cache.data_ptr(),
+        cache_seqlens=cache_seqlens.data_ptr(), block_table=block_table.data_ptr() if block_table is not None else None,
+        batch=batch, seqlen_q=seqlen_q, n_heads=n_heads, n_kv_heads=k_cache.shape[2], d_head=d_head,
+        seqlen_cache=k_cache.shape[1] if block_table is None else 0,
+        num_pages=k_cache.shape[0] if block_table is not None else 0, page_size=k_cache.shape[1] if block_table is not None else 0,
+        max_pages_per_seq=block_table.shape[1] if block_table is not None else 0,
+        block_table_stride=block_table.stride(0) if block_table is not None else 0,
+        max_seqlen_k=0 if max_seqlen_k is None else max_seqlen_k,
+        q_batch_stride=q.stride(0), q_seq_stride=q.stride(1), q_head_stride=q.stride(2),
+        o_batch_stride=seqlen_q * n_heads * d_head, o_seq_stride=n_heads * d_head, o_head_stride=d_head,   # (o: contiguous)
+        kv_batch_stride=k_cache.stride(0), kv_seq_stride=k_cache.stride(1), kv_head_stride=k_cache.stride(2),
+    )
+    return q, args
+
+
+def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
+                    num_splits=0, timed=False):
+    """Decode attention against a K / V cache (fa_decode_launch): q (batch, seqlen_q, n_heads, 128); k_cache, v_cache
+    (batch, seqlen_cache, n_kv_heads, 128), or with block_table (batch, max_pages_per_seq) int32 on the device
+    (num_pages, page_size, n_kv_heads, 128); cache_seqlens (batch,) int32 on the device, the valid keys of each entry (the
+    newest tokens included).  causal is bottom-right aligned.  -> o [, lse fp32 (batch, n_heads, seqlen_q)] [, ms].  The host
+    reads neither cache_seqlens nor block_table; no device synchronisation unless timed.  The caches pass as they are (strided
+    views included) and are refused if the launch cannot address them; q is copied if it has to be."""
+    q, args = _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_seqlen_k, num_splits)
+    batch, seqlen_q, n_heads, d_head = q.shape
+    o = torch.empty((batch, seqlen_q, n_heads, d_head), dtype=q.dtype, device=q.device)
+    lse = torch.empty((batch, n_heads, seqlen_q), dtype=torch.float32, device=q.device) if return_lse else None
+    args.o, args.lse = o.data_ptr(), (lse.data_ptr() if return_lse else None)
+    lib = _capi.load()
+    nbytes = lib.fa_decode_workspace_bytes(ctypes.byref(args))
+    _capi.check(nbytes if nbytes < 0 else 0)
+    with torch.cuda.device(q.device):
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes > 0 else None   # (on the current stream's allocator)
+        args.workspace = workspace.data_ptr() if workspace is not None else None
+        stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        ms = ctypes.c_float(0.0)
+        _capi.check(lib.fa_decode_launch(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
+    out = (o, lse) if return_lse else (o,)
+    if timed:
+        out = out + (float(ms.value),)
+    return out[0] if len(out) == 1 else out

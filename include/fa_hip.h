@@ -444,6 +444,76 @@ typedef struct fa_bwd_varlen_args {
 int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *args);   /* bytes, or a negative fa_status */
 int fa_bwd_launch_varlen(const fa_bwd_varlen_args *args, void *stream, float *ms);
 
+/*
+ * KV-cache decode attention (forward only): a few query rows per sequence against a long K / V cache whose valid length per
+ * batch entry lies in DEVICE memory.  bf16 / fp16, d_head 128, MHA and GQA / MQA (query head h reads K / V head
+ * h / (n_heads / n_kv_heads)), softmax scale 1 / sqrt(128).
+ *
+ * q, o: (batch, seqlen_q, n_heads, 128) with the q_* / o_* strides (elements).  k, v (one stride set, kv_*):
+ *   contiguous cache (block_table null):  (batch, seqlen_cache, n_kv_heads, 128); kv_batch_stride is the batch stride;
+ *   paged cache (block_table non-null):   (num_pages, page_size, n_kv_heads, 128); kv_batch_stride is the PAGE stride, and
+ *     block_table is a DEVICE (batch, max_pages_per_seq) int32 array, row stride block_table_stride: key j of batch entry b
+ *     is row j % page_size of page block_table[b][j / page_size].
+ * cache_seqlens: DEVICE (batch) int32, the number of valid keys of each entry, the newest tokens (which the caller has already
+ * written into the cache) included.  The host never reads it or block_table: launches are asynchronous and graph-capturable,
+ * and every grid and split count is a function of the host-visible arguments alone.
+ * causal: bottom-right aligned -- query row i sees keys j <= len - seqlen_q + i; else every row sees all len keys.  A row that
+ * sees no key gives o = 0 and lse = -inf.  lse (may be null): fp32 (batch, n_heads, seqlen_q), natural log, contiguous.
+ *
+ * Clamping: len is clamped to [0, capacity], capacity = seqlen_cache (paged: max_pages_per_seq * page_size);
+ * every block_table entry used is clamped to [0, num_pages), and only entries of pages below ceil(len / page_size) are read;
+ * cache rows at or beyond len are never fetched (their lanes fetch row len - 1 and are masked), so neither their contents
+ * nor unused pages nor unused block_table entries reach a result, and no address outside the tensors is formed.
+ *
+ * Served (fa_decode_supported = 1): seqlen_q * (n_heads / n_kv_heads) <= 64 packed rows and, paged, page_size % 64 == 0;
+ * anything else is FA_ERR_NO_KERNEL.  max_seqlen_k: the host's bound on every length, 0 = capacity; it only steers the split rule.
+ * num_splits: 0 = the rule -- the smallest power of two s with batch * n_kv_heads * s >= 256, at most ceil(max_seqlen_k / 256)
+ * and at most 128 (fa_decode_num_splits) -- or a forced count in [1, 1024].  With more than one split the workspace
+ * (fa_decode_workspace_bytes bytes of device memory, 16-byte aligned; 0 bytes for one split) holds fp32 partials that a second
+ * kernel combines in split order: no atomics, the same bits for the same arguments.
+ * Refused before any HIP call: null pointers (FA_ERR_NULL); dtype (FA_ERR_DTYPE); row count / page size (FA_ERR_NO_KERNEL);
+ * struct_size, sizes, strides not positive (FA_ERR_SHAPE); strides not multiples of 8, tensors not 16-byte aligned, int32
+ * arrays and lse not 4-byte aligned, workspace not 16-byte aligned (FA_ERR_ALIGN).  batch = 0 returns FA_OK without a device.
+ */
+typedef struct fa_decode_args {
+    uint32_t struct_size;      /* sizeof(fa_decode_args) */
+    int32_t dtype;             /* fa_dtype */
+    int32_t causal;
+    int32_t num_splits;        /* 0 = the rule */
+    const void *q;
+    const void *k;
+    const void *v;
+    void *o;
+    float *lse;                /* may be null */
+    const int32_t *cache_seqlens;
+    const int32_t *block_table;   /* null = contiguous cache */
+    void *workspace;           /* needed when fa_decode_workspace_bytes > 0 */
+    int64_t batch;
+    int64_t seqlen_q;
+    int64_t n_heads;
+    int64_t n_kv_heads;
+    int64_t d_head;
+    int64_t seqlen_cache;      /* contiguous cache: rows per batch entry (ignored when paged) */
+    int64_t num_pages;         /* paged cache only, like the next three */
+    int64_t page_size;
+    int64_t max_pages_per_seq;
+    int64_t block_table_stride;
+    int64_t max_seqlen_k;      /* 0 = capacity */
+    int64_t q_batch_stride;
+    int64_t q_seq_stride;
+    int64_t q_head_stride;
+    int64_t o_batch_stride;
+    int64_t o_seq_stride;
+    int64_t o_head_stride;
+    int64_t kv_batch_stride;   /* paged: the page stride */
+    int64_t kv_seq_stride;
+    int64_t kv_head_stride;
+} fa_decode_args;
+int fa_decode_supported(const fa_decode_args *args);
+int fa_decode_num_splits(const fa_decode_args *args);                 /* the split count the launch uses, or a negative fa_status */
+int64_t fa_decode_workspace_bytes(const fa_decode_args *args);        /* bytes, or a negative fa_status */
+int fa_decode_launch(const fa_decode_args *args, void *stream, float *ms);
+
 /* The adaptive speculative mode's record on `device` (fa_speculative_mode), and a reset of its demotion state (tests,
  * or a caller that knows its data has changed character). */
 int fa_adaptive_state(int device, fa_adaptive_info *out);
