@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_lse_supported", "fa_fwd_launch_lse", "fa_bwd_workspace_bytes", "fa_bwd_launch",
     "fa_fwd_gqa_supported", "fa_fwd_launch_gqa", "fa_bwd_gqa_workspace_bytes", "fa_bwd_launch_gqa",
     "fa_fwd_varlen_supported", "fa_fwd_launch_varlen", "fa_bwd_varlen_workspace_bytes", "fa_bwd_launch_varlen",
+    "fa_fwd_varlen_qk_supported", "fa_fwd_launch_varlen_qk", "fa_bwd_varlen_qk_workspace_bytes", "fa_bwd_launch_varlen_qk",
     "fa_decode_supported", "fa_decode_num_splits", "fa_decode_workspace_bytes", "fa_decode_launch",
 )
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -131,6 +132,10 @@ class FaBwdVarlenArgs(ctypes.Structure):   # fa_bwd_varlen_args
         ("dtype", ctypes.c_int32), ("causal", ctypes.c_int32),
         ("varlen", FaVarlenLayout),
     ]
+
+
+class FaBwdVarlenQKArgs(ctypes.Structure):   # fa_bwd_varlen_qk_args (varlen: the query rows; varlen_k: the key rows)
+    _fields_ = [("struct_size", ctypes.c_uint32)] + FaBwdVarlenArgs._fields_ + [("varlen_k", FaVarlenLayout)]
 
 
 class FaDecodeArgs(ctypes.Structure):   # fa_decode_args (KV-cache decode: contiguous or paged cache, lengths on the device)
@@ -277,6 +282,15 @@ def load():
     lib.fa_bwd_varlen_workspace_bytes.argtypes = [ctypes.POINTER(FaBwdVarlenArgs)]
     lib.fa_bwd_launch_varlen.restype = ctypes.c_int
     lib.fa_bwd_launch_varlen.argtypes = [ctypes.POINTER(FaBwdVarlenArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    lib.fa_fwd_varlen_qk_supported.restype = ctypes.c_int
+    lib.fa_fwd_varlen_qk_supported.argtypes = [cfg_p, ctypes.POINTER(FaFwdOpts)]
+    lib.fa_fwd_launch_varlen_qk.restype = ctypes.c_int
+    lib.fa_fwd_launch_varlen_qk.argtypes = [args_p, ctypes.POINTER(FaKvLayout), ctypes.POINTER(FaVarlenLayout), ctypes.POINTER(FaVarlenLayout),
+                                            ctypes.POINTER(FaFwdOpts), ctypes.c_void_p, ctypes.c_void_p]
+    lib.fa_bwd_varlen_qk_workspace_bytes.restype = ctypes.c_int64
+    lib.fa_bwd_varlen_qk_workspace_bytes.argtypes = [ctypes.POINTER(FaBwdVarlenQKArgs)]
+    lib.fa_bwd_launch_varlen_qk.restype = ctypes.c_int
+    lib.fa_bwd_launch_varlen_qk.argtypes = [ctypes.POINTER(FaBwdVarlenQKArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_decode_supported.restype = ctypes.c_int
     lib.fa_decode_supported.argtypes = [ctypes.POINTER(FaDecodeArgs)]
     lib.fa_decode_num_splits.restype = ctypes.c_int

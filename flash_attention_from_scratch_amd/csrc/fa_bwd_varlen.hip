@@ -29,6 +29,14 @@ static hipError_t bwd_varlen_enqueue_t(const BwdVarlenArgs &a, hipStream_t s) {
                            block, params, 0, s);
 }
 
+// the delta launch alone (fa_bwd_varlen_qk.hip: the same kernel over the query rows of a launch with separate K / V lengths)
+hipError_t bwd_varlen_delta_enqueue(const BwdVarlenArgs &a, int dtype, hipStream_t s) {
+    const int64_t rows = (int64_t)a.n_heads * a.total_tokens;
+    void *params[] = {(void *)&a};
+    const void *fn = dtype == 15 ? (const void *)&fa_bwd_delta_varlen_kernel<15> : (const void *)&fa_bwd_delta_varlen_kernel<5>;
+    return hipLaunchKernel(fn, dim3((unsigned)((rows + 15) / 16)), dim3(256), params, 0, s);
+}
+
 hipError_t bwd_varlen_enqueue(const BwdVarlenArgs &a, int dtype, bool causal, hipStream_t s) {
     if (dtype == 15) return causal ? bwd_varlen_enqueue_t<15, true>(a, s) : bwd_varlen_enqueue_t<15, false>(a, s);
     return causal ? bwd_varlen_enqueue_t<5, true>(a, s) : bwd_varlen_enqueue_t<5, false>(a, s);

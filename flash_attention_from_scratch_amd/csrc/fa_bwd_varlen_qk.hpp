@@ -1,0 +1,364 @@
+// fa_bwd_varlen_qk.hpp -- the backward over packed sequences with separate Q and K / V lengths (fa_bwd_launch_varlen_qk): Q,
+// dO, dQ, O are (total_q, n_heads, 128), K, V, dK, dV (total_k, n_kv_heads, 128); sequence i owns query rows cu_seqlens_q[i] ..
+// cu_seqlens_q[i + 1] - 1 and key rows cu_seqlens_k[i] .. cu_seqlens_k[i + 1] - 1 (both arrays on the DEVICE, never read by the
+// host).  The causal mask is bottom-right aligned: query r of a sequence sees keys j <= r + shift, shift = len_k - len_q.
+//
+// The kernels of fa_bwd_varlen.hpp written out again with the second range: the tile arithmetic (S, dP, dS, the five MFMA
+// products, the operand orientation, the LDS images, the order of the fp32 sums) is theirs, line for line, so that equal
+// ranges (shift = 0) give their bits.
+//   fa_bwd_delta_varlen_kernel           (fa_bwd_varlen.hpp, as it is) delta per (head, query token)
+//   fa_bwd_dkdv_varlen_qk_kernel         one workgroup per (sequence, K / V head, split part, 128-key block of max_seqlen_k)
+//   fa_bwd_dkdv_reduce_varlen_qk_kernel  split > 1 only: the sum of a key row's split partials, in order, over total_k
+//   fa_bwd_dq_varlen_qk_kernel           one workgroup per (sequence, head, 128-row Q block of max_seqlen_q)
+// Rows beyond either range's end are fetched from that range's LAST row and their p is exactly 0, as in fa_bwd_varlen.hpp; a
+// range of length 0 fetches nothing.  A query row that saw no key (len_k = 0, or causal r < len_q - len_k) has lse = -inf and is
+// treated as a row beyond the end (S starts at -inf, delta = 0): dq = 0, nothing of it in dK / dV.  A key no query sees
+// (len_q = 0) gets dk = dv = 0, written.  Both ranges are clamped by
+// seq_range's rule, each against its own total and max_seqlen, so a cu_seqlens that violates its contract cannot fault.
+// No float atomics, no waiting between workgroups, no scratch: the same inputs give the same bits.
+#pragma once
+#include "fa_bwd_varlen.hpp"
+
+namespace fa {
+
+struct BwdVarlenQKArgs {
+    const uint16_t *q, *k, *v;        // q_* / kv_* strides
+    const uint16_t *o, *dout;         // out_* strides
+    const float *lse;                 // (n_heads, total_tokens), contiguous
+    float *delta;                     // workspace: (n_heads, total_tokens)
+    uint16_t *dq, *dk, *dv;           // dq: out_* strides; dk, dv: dkv_*
+    const int32_t *cu_seqlens;        // n_seqs + 1 entries: the query rows
+    const int32_t *cu_seqlens_k;      // n_seqs + 1 entries: the key rows
+    float *part;                      // split > 1: (n_kv_heads * split, total_k, 2, 128) fp32 dK^T | dV^T, unscaled
+    int64_t q_ss, q_hs;               // elements
+    int64_t out_ss, out_hs;
+    int64_t kv_ss, kv_hs;
+    int64_t dkv_ss, dkv_hs;
+    int32_t n_seqs, total_tokens, max_seqlen, n_heads;   // total_tokens, max_seqlen: the query side
+    int32_t total_k, max_seqlen_k;
+    int32_t group, split;             // query heads per K / V head; workgroups per (K / V head, key block), divides group
+    int32_t n_blocks, n_blocks_k;     // ceil(max_seqlen / 128), ceil(max_seqlen_k / 128): blocks of the grids
+};
+
+namespace bwd {
+
+// sequence -> first row and length of one range, clamped so that every row0 + i, 0 <= i < len, is a row of that side's tensors
+FA_DEV void seq_range_of(const int32_t *cu, int64_t total, int64_t max_len, int seq, int &row0, int &len) {
+    const int64_t lo = cu[seq], hi = cu[seq + 1];
+    const int64_t r0 = lo < 0 ? 0 : (lo > total ? total : lo);
+    int64_t n = hi - r0;
+    const int64_t cap = total - r0 < max_len ? total - r0 : max_len;
+    n = n < 0 ? 0 : (n > cap ? cap : n);
+    row0 = (int)r0;
+    len = (int)n;
+}
+FA_DEV void seq_range_q(const BwdVarlenQKArgs &a, int seq, int &row0, int &len) {
+    seq_range_of(a.cu_seqlens, a.total_tokens, a.max_seqlen, seq, row0, len);
+}
+FA_DEV void seq_range_k(const BwdVarlenQKArgs &a, int seq, int &row0, int &len) {
+    seq_range_of(a.cu_seqlens_k, a.total_k, a.max_seqlen_k, seq, row0, len);
+}
+
+}  // namespace bwd
+
+// dK, dV of one 128-key block of one K / V head of one sequence, summed over group / split query heads.
+// Grid: n_seqs * n_kv_heads * split * n_blocks_k workgroups of 256 threads.  The sweep runs over the Q tiles of len_q; a block
+// no query sees (len_q = 0) sweeps nothing and stores zeros.
+template <int DT, bool CAUSAL>
+__global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_qk_kernel(const BwdVarlenQKArgs a) {
+    using namespace bwd;
+    using E = Elem<DT>;
+    using vec8 = typename E::vec8;
+    __shared__ __attribute__((aligned(16))) char img_q[TBYTES];
+    __shared__ __attribute__((aligned(16))) char img_do[TBYTES];
+    __shared__ __attribute__((aligned(16))) float lse_s[TROWS];   // -lse sqrt(d) of the tile's rows
+    __shared__ __attribute__((aligned(16))) float dl_s[TROWS];    // -delta
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    int wg, kb;   // wg = (sequence * n_kv_heads + K / V head) * split + part
+    block_coords(a.n_blocks_k, wg, kb);
+    const int n_kv = a.n_heads / a.group, skv = wg / a.split, seq = skv / n_kv, hk = skv % n_kv, sp = wg % a.split;
+    int row0, len, krow0, klen;   // the sequence's query rows and key rows
+    seq_range_q(a, seq, row0, len);
+    seq_range_k(a, seq, krow0, klen);
+    if (kb * KB >= klen) return;   // (workgroup-uniform, before any barrier)
+    const int last = len - 1, klast = klen - 1;
+    const int shift = klen - len;   // causal, bottom-right: query r sees keys <= r + shift
+    const int n_hq = a.group / a.split;   // query heads of the sweep: hk * group + part * n_hq + 0 .. n_hq - 1
+    int hq = hk * a.group + sp * n_hq;
+    const uint16_t *q_seq = a.q + (int64_t)row0 * a.q_ss + (int64_t)hq * a.q_hs;
+    const uint16_t *do_seq = a.dout + (int64_t)row0 * a.out_ss + (int64_t)hq * a.out_hs;
+    const int key = kb * KB + 32 * wave + r;   // this lane's key (the accumulators' column)
+    const int key_c = key < klast ? key : klast;
+    // K, V of the wave's 32 keys: the B operands of S = Q K^T and dP = dO V^T, resident for the whole sweep
+    vec8 Kb[8], Vb[8];
+    {
+        const int64_t kv_row = (int64_t)(krow0 + key_c) * a.kv_ss + (int64_t)hk * a.kv_hs + 8 * h;
+        const uint16_t *kr = a.k + kv_row;
+        const uint16_t *vr = a.v + kv_row;
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            Kb[ks] = *(const vec8 *)(kr + 16 * ks);
+            Vb[ks] = *(const vec8 *)(vr + 16 * ks);
+        }
+    }
+    const float c = (float)((double)(1.0f / __builtin_sqrtf((float)D)) * 1.4426950408889634074);
+    const float lse_scale = -log2e_over_c();
+    f32x16 dV[4], dK[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        dV[t] = f32x16{};
+        dK[t] = f32x16{};
+    }
+    const int n_it = (len + TROWS - 1) / TROWS;
+    // causal: the Q tiles from the first one that can see the block on (it0 >= n_it: no query sees it)
+    const int it0 = CAUSAL ? (kb * KB - shift > 0 ? kb * KB - shift : 0) / TROWS : 0;
+    const float *lse_h = a.lse + (int64_t)hq * a.total_tokens + row0;
+    const float *dl_h = a.delta + (int64_t)hq * a.total_tokens + row0;
+    TileRegs tq, tdo;
+    float lse_r = 0.0f, dl_r = 0.0f;
+    auto load = [&](int it) {
+        tile_load_clamped(tq, q_seq, a.q_ss, it * TROWS, last, tid);
+        tile_load_clamped(tdo, do_seq, a.out_ss, it * TROWS, last, tid);
+        if (tid < TROWS) {
+            const int row = it * TROWS + tid;
+            const bool in = row < len;
+            // (a row that saw no key has lse = -inf: a row beyond the end, or lse * lse_scale = +inf would reach dK / dV as NaN)
+            const float lse_v = in ? lse_h[in ? row : 0] : -__builtin_inff();
+            const bool live = in && lse_v != -__builtin_inff();
+            lse_r = live ? lse_v * lse_scale : -__builtin_inff();   // S = -inf, p = exp2(-inf) = 0
+            dl_r = live ? -dl_h[in ? row : 0] : 0.0f;
+        }
+    };
+    if (it0 < n_it) load(it0);   // (len_q = 0 has no row to fetch)
+    const bool key_edge = kb * KB + KB > klen;   // a block that holds keys beyond the sequence
+    for (int j = 0; j < n_hq; ++j) {
+        for (int it = it0; it < n_it; ++it) {
+            __syncthreads();   // every wave is done with the previous tile's images
+            tile_store(img_q, tq, tid);
+            tile_store(img_do, tdo, tid);
+            if (tid < TROWS) {
+                lse_s[tid] = lse_r;
+                dl_s[tid] = dl_r;
+            }
+            __syncthreads();
+            if (it + 1 < n_it) {
+                load(it + 1);   // in flight under this tile's MFMAs
+            } else if (j + 1 < n_hq) {   // ... or the next query head's first tile
+                ++hq;
+                q_seq += a.q_hs;
+                do_seq += a.out_hs;
+                lse_h += a.total_tokens;
+                dl_h += a.total_tokens;
+                load(it0);
+            }
+            const bool diag = CAUSAL && it * TROWS + shift < kb * KB + KB;   // a tile that holds queries before some key of the block
+            const bool edge = key_edge || it * TROWS + TROWS > len;  // ... or rows / keys beyond the sequence
+#pragma unroll
+            for (int mt = 0; mt < TROWS / 32; ++mt) {
+                const int rb = 32 * mt;
+                f32x16 S, dP;
+                // rows of registers 4g .. 4g + 3: rb + 8 g + 4 h + 0 .. 3
+#pragma unroll
+                for (int gg = 0; gg < 4; ++gg) {
+                    const f32x4 l4 = *(const f32x4 *)(lse_s + rb + 8 * gg + 4 * h);
+                    const f32x4 d4 = *(const f32x4 *)(dl_s + rb + 8 * gg + 4 * h);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        S[4 * gg + e] = l4[e];
+                        dP[4 * gg + e] = d4[e];
+                    }
+                }
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) S = E::mfma(row_read<vec8>(img_q, rb, ks, lane), Kb[ks], S);
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) dP = E::mfma(row_read<vec8>(img_do, rb, ks, lane), Vb[ks], dP);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    float p = __builtin_amdgcn_exp2f(c * S[i]);
+                    const int query = it * TROWS + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
+                    if constexpr (CAUSAL) {   // (plain: rows beyond the end have S = -inf, see load())
+                        if (diag) p = key > query + shift ? 0.0f : p;
+                        if (edge) p = (key >= klen || query >= len) ? 0.0f : p;
+                    }
+                    S[i] = p;                 // P
+                    dP[i] = p * dP[i];        // dS = P (dP - delta)
+                }
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const vec8 pb = acc_operand<DT>(S, s), db = acc_operand<DT>(dP, s);
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        dV[t] = E::mfma(tr_read<vec8>(img_do, rb, s, t, lane), pb, dV[t]);
+                        dK[t] = E::mfma(tr_read<vec8>(img_q, rb, s, t, lane), db, dK[t]);
+                    }
+                }
+            }
+        }
+    }
+    if (key >= klen) return;   // (behind the last barrier and the last transposed read)
+    // dK^T / dV^T: column = this lane's key, rows d = 32 t + 8 gg + 4 h + 0 .. 3
+    if (a.split > 1) {   // the fp32 partials, unscaled: fa_bwd_dkdv_reduce_varlen_kernel rounds their sum
+        float *pk = a.part + (((int64_t)hk * a.split + sp) * a.total_k + krow0 + key) * (2 * D) + 4 * h;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int gg = 0; gg < 4; ++gg) {
+                *(f32x4 *)(pk + 32 * t + 8 * gg) = f32x4{dK[t][4 * gg], dK[t][4 * gg + 1], dK[t][4 * gg + 2], dK[t][4 * gg + 3]};
+                *(f32x4 *)(pk + D + 32 * t + 8 * gg) = f32x4{dV[t][4 * gg], dV[t][4 * gg + 1], dV[t][4 * gg + 2], dV[t][4 * gg + 3]};
+            }
+        return;
+    }
+    const float inv_sqrt_d = 1.0f / __builtin_sqrtf((float)D);
+    const int64_t dkv_row = (int64_t)(krow0 + key) * a.dkv_ss + (int64_t)hk * a.dkv_hs + 4 * h;
+    uint16_t *dk = a.dk + dkv_row;
+    uint16_t *dv = a.dv + dkv_row;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+            store4<DT>(dk + 32 * t + 8 * gg, dK[t], gg, inv_sqrt_d);
+            store4<DT>(dv + 32 * t + 8 * gg, dV[t], gg, 1.0f);
+        }
+}
+
+// split > 1: dK, dV of one (K / V head, token) row = the sum of its `split` partials in order, scaled and rounded once.
+// One thread per 8 elements of a dK or dV row.  Grid: n_kv_heads * total_k * 2 * 16 / 256 workgroups of 256 threads.
+// (every key row belongs to a sequence -- cu_seqlens_k[0] = 0, [n_seqs] = total_k -- so every partial row was written)
+template <int DT>
+__global__ void __launch_bounds__(256) fa_bwd_dkdv_reduce_varlen_qk_kernel(const BwdVarlenQKArgs a) {
+    using namespace bwd;
+    const int n_kv = a.n_heads / a.group;
+    const int64_t n = (int64_t)n_kv * a.total_k * 2 * (D / 8);
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const int c8 = (int)(idx % (D / 8)), which = (int)((idx / (D / 8)) & 1);   // 8-element chunk; 0 dK, 1 dV
+    const int64_t row = idx / (2 * (D / 8));   // hk * total_k + token
+    const int64_t hk = row / a.total_k, tok = row % a.total_k;
+    const int64_t plane = (int64_t)a.total_k * 2 * D;   // floats per partial
+    const float *src = a.part + (hk * a.split * a.total_k + tok) * (2 * D) + which * D + 8 * c8;
+    f32x4 lo = *(const f32x4 *)src, hi = *(const f32x4 *)(src + 4);
+    for (int s = 1; s < a.split; ++s) {
+        lo += *(const f32x4 *)(src + s * plane);
+        hi += *(const f32x4 *)(src + s * plane + 4);
+    }
+    const float scale = which ? 1.0f : 1.0f / __builtin_sqrtf((float)D);
+    float f[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        f[e] = lo[e] * scale;
+        f[4 + e] = hi[e] * scale;
+    }
+    uint16_t *dst = (which ? a.dv : a.dk) + hk * a.dkv_hs + tok * a.dkv_ss + 8 * c8;
+    *(typename Elem<DT>::vec8 *)dst = Elem<DT>::pack8(f);
+}
+
+// dQ of one 128-row Q block of one sequence, K / V of head h / group.  Grid: n_seqs * n_heads * n_blocks workgroups of 256 threads.
+// The sweep runs over the key tiles of len_k; a block that sees no key (len_k = 0, or causal rows above the shifted diagonal)
+// sweeps nothing and stores zeros.
+template <int DT, bool CAUSAL>
+__global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_qk_kernel(const BwdVarlenQKArgs a) {
+    using namespace bwd;
+    using E = Elem<DT>;
+    using vec8 = typename E::vec8;
+    __shared__ __attribute__((aligned(16))) char img_k[TBYTES];
+    __shared__ __attribute__((aligned(16))) char img_v[TBYTES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    int sh, qb;   // sh = sequence * n_heads + head
+    block_coords(a.n_blocks, sh, qb);
+    if (CAUSAL) qb = a.n_blocks - 1 - qb;   // the longest sweeps first
+    const int seq = sh / a.n_heads, hq = sh % a.n_heads;
+    int row0, len, krow0, klen;   // the sequence's query rows and key rows
+    seq_range_q(a, seq, row0, len);
+    seq_range_k(a, seq, krow0, klen);
+    if (qb * KB >= len) return;   // (workgroup-uniform, before any barrier)
+    const int last = len - 1, klast = klen - 1;
+    const int shift = klen - len;   // causal, bottom-right: query r sees keys <= r + shift
+    const uint16_t *k_seq = a.k + (int64_t)krow0 * a.kv_ss + (int64_t)(hq / a.group) * a.kv_hs;
+    const uint16_t *v_seq = a.v + (int64_t)krow0 * a.kv_ss + (int64_t)(hq / a.group) * a.kv_hs;
+    const int query = qb * KB + 32 * wave + r;   // this lane's query (the accumulators' column)
+    const int query_c = query < last ? query : last;
+    // Q, dO of the wave's 32 rows: the B operands of S^T = K Q^T and dP^T = V dO^T
+    vec8 Qb[8], Ob[8];
+    {
+        const uint16_t *qr = a.q + (int64_t)(row0 + query_c) * a.q_ss + (int64_t)hq * a.q_hs + 8 * h;
+        const uint16_t *gr = a.dout + (int64_t)(row0 + query_c) * a.out_ss + (int64_t)hq * a.out_hs + 8 * h;
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            Qb[ks] = *(const vec8 *)(qr + 16 * ks);
+            Ob[ks] = *(const vec8 *)(gr + 16 * ks);
+        }
+    }
+    const float c = (float)((double)(1.0f / __builtin_sqrtf((float)D)) * 1.4426950408889634074);
+    const int64_t stat = (int64_t)hq * a.total_tokens + row0 + query_c;
+    // (a row that saw no key has lse = -inf: its S starts at -inf, p = exp2(-inf) = 0, rather than at lse * scale = +inf)
+    const float lse_v = a.lse[stat];
+    const bool dead = lse_v == -__builtin_inff();
+    const float lse_q = query < len ? (dead ? -__builtin_inff() : lse_v * -log2e_over_c()) : 0.0f;
+    const float dl_q = query < len && !dead ? -a.delta[stat] : 0.0f;
+    f32x16 dQ[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) dQ[t] = f32x16{};
+    const int n_all = (klen + TROWS - 1) / TROWS;
+    // causal: cut at the block's last row's diagonal, (qb + 1) * 128 - 1 + shift; no tile when that lies before key 0
+    const int n_diag = (qb + 1) * KB + shift > 0 ? ((qb + 1) * KB + shift + TROWS - 1) / TROWS : 0;
+    const int n_kt = CAUSAL && n_diag < n_all ? n_diag : n_all;
+    TileRegs tk, tv;
+    auto load = [&](int kt) {
+        tile_load_clamped(tk, k_seq, a.kv_ss, kt * TROWS, klast, tid);
+        tile_load_clamped(tv, v_seq, a.kv_ss, kt * TROWS, klast, tid);
+    };
+    if (n_kt > 0) load(0);   // (len_k = 0 has no row to fetch)
+    const bool query_edge = qb * KB + KB > len;   // a block that holds rows beyond the sequence
+    for (int kt = 0; kt < n_kt; ++kt) {
+        __syncthreads();
+        tile_store(img_k, tk, tid);
+        tile_store(img_v, tv, tid);
+        __syncthreads();
+        if (kt + 1 < n_kt) load(kt + 1);
+        const bool diag = CAUSAL && kt * TROWS + TROWS > qb * KB + shift;   // a tile that holds keys after some query of the block
+        const bool edge = query_edge || kt * TROWS + TROWS > klen;   // ... or rows / keys beyond the sequence
+#pragma unroll
+        for (int mt = 0; mt < TROWS / 32; ++mt) {
+            const int rb = 32 * mt;
+            f32x16 S, dP;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                S[i] = lse_q;
+                dP[i] = dl_q;
+                if (!CAUSAL && edge) {   // keys beyond the end: S = -inf, p = exp2(-inf) = 0
+                    const int key = kt * TROWS + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
+                    S[i] = key >= klen ? -__builtin_inff() : lse_q;
+                }
+            }
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) S = E::mfma(row_read<vec8>(img_k, rb, ks, lane), Qb[ks], S);
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) dP = E::mfma(row_read<vec8>(img_v, rb, ks, lane), Ob[ks], dP);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                float p = __builtin_amdgcn_exp2f(c * S[i]);
+                const int key = kt * TROWS + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
+                if constexpr (CAUSAL) {
+                    if (diag) p = key > query + shift ? 0.0f : p;
+                    if (edge) p = (key >= klen || query >= len) ? 0.0f : p;
+                }
+                dP[i] = p * dP[i];        // dS^T
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const vec8 db = acc_operand<DT>(dP, s);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) dQ[t] = E::mfma(tr_read<vec8>(img_k, rb, s, t, lane), db, dQ[t]);
+            }
+        }
+    }
+    if (query >= len) return;
+    const float inv_sqrt_d = 1.0f / __builtin_sqrtf((float)D);
+    uint16_t *dq = a.dq + (int64_t)(row0 + query) * a.out_ss + (int64_t)hq * a.out_hs + 4 * h;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) store4<DT>(dq + 32 * t + 8 * gg, dQ[t], gg, inv_sqrt_d);
+}
+
+}  // namespace fa

@@ -420,6 +420,27 @@ struct KernelArgsVarlen {
     int32_t total_tokens, max_seqlen;
 };
 typedef void (*kernel_fn_varlen)(const KernelArgsVarlen);
+// VARLEN_QK (separate Q and K / V lengths: fa_fwd_launch_varlen_qk): fa_fwd_kernel_varlen_qk is the varlen body with a second
+// range.  Sequence i owns query rows cu_seqlens[i] .. of q / o / lse (the range KernelArgsVarlen describes) and key rows
+// cu_seqlens_k[i] .. of k / v; both ranges are clamped by the one rule above.  The causal diagonal is bottom-right aligned:
+// query r sees keys j <= r + (len_k - len_q) -- FA_SHIFTED(row) is the last key a row sees.  A row that sees no key gives
+// o = 0, lse = -inf.  Only fa_inst_varlen_qk.hip defines FA_KERNEL_VARLEN_QK, and gets that kernel INSTEAD of the other two.
+struct KernelArgsVarlenQK {
+    KernelArgsVarlen v;            // cu_seqlens, total_tokens, max_seqlen: the QUERY side; n_q_blocks = ceil(max_seqlen_q / B_r)
+    const int32_t *cu_seqlens_k;   // n_seqs + 1 row offsets of k / v (DEVICE)
+    int32_t total_k, max_seqlen_k;
+};
+typedef void (*kernel_fn_varlen_qk)(const KernelArgsVarlenQK);
+#ifdef FA_KERNEL_VARLEN_QK
+#define FA_KERNEL_VARLEN
+#define FA_Q_LEN q_len
+#define FA_Q_LEN_END q_len_v
+#define FA_SHIFTED(row) ((row) + kq_shift)
+#else
+#define FA_Q_LEN S_len
+#define FA_Q_LEN_END S_len
+#define FA_SHIFTED(row) (row)
+#endif
 #ifdef FA_KERNEL_VARLEN
 #define FA_KV_SS32 kv_ss
 #define FA_SEQ_LEN v_seq_len
@@ -448,7 +469,13 @@ typedef void (*kernel_fn_varlen)(const KernelArgsVarlen);
 template <int DT, int QT, int NWAVES, int BC, bool SWZ, bool EAGER, bool OPT, bool PIPE, bool DMA = true,
           bool MASK = false, int D = 128, int ABL = 0, int KSPLIT = 1>
 __global__ void
-#ifdef FA_KERNEL_VARLEN
+#if defined(FA_KERNEL_VARLEN_QK)
+__launch_bounds__(NWAVES * 64, 1)
+fa_fwd_kernel_varlen_qk(const KernelArgsVarlenQK qa) {
+    static_assert(MASK && DMA && KSPLIT == 1 && ABL == 0 && QT == 1, "the varlen form is the masked LDS-DMA kernel");
+    const KernelArgsVarlen &va = qa.v;  // (the query side)
+    const KernelArgs &args = va.base;
+#elif defined(FA_KERNEL_VARLEN)
 // (one workgroup per SIMD set: with m live up to the LSE store the 256-register budget of two waves per SIMD spills)
 __launch_bounds__(NWAVES * 64, 1)
 fa_fwd_kernel_varlen(const KernelArgsVarlen va) {
@@ -526,10 +553,29 @@ fa_fwd_kernel(const KernelArgs args) {
         v_len = v_len < 0 ? 0 : (v_len > cap ? cap : v_len);
     }
     if ((int64_t)qb * TR::kBr >= v_len) return;   // (workgroup-uniform; before any barrier or DMA)
+#ifdef FA_KERNEL_VARLEN_QK
+    // ... and its key rows from cu_seqlens_k, by the same rule against total_k and max_seqlen_k
+    const int q_len = (int)v_len;
+    int64_t k_row0 = qa.cu_seqlens_k[b], k_len = qa.cu_seqlens_k[b + 1];
+    k_row0 = k_row0 < 0 ? 0 : (k_row0 > qa.total_k ? qa.total_k : k_row0);
+    k_len -= k_row0;
+    {
+        const int64_t cap = qa.total_k - k_row0 < qa.max_seqlen_k ? qa.total_k - k_row0 : qa.max_seqlen_k;
+        k_len = k_len < 0 ? 0 : (k_len > cap ? cap : k_len);
+    }
+    const int v_seq_len = (int)k_len;          // FA_SEQ_LEN, FA_N_KV_BLOCKS, ragged_rows and the key clamp: the K range
+    const int kq_shift = v_seq_len - q_len;    // bottom-right diagonal: query r sees keys <= r + kq_shift
+    // len_q for the epilogue's row tests, parked in a vector register across the loop (the scalar file is full there: held
+    // as a scalar it is spilled to a lane and back; 372 of 512 vector registers are in use)
+    int q_len_v;
+    asm("v_mov_b32 %0, %1" : "=v"(q_len_v) : "s"(q_len));
+#else
+    const int64_t k_row0 = v_row0;
     const int v_seq_len = (int)v_len;
+#endif
     const int64_t kv_ss = va.kv_seq_stride;
     const int64_t head_off = v_row0 * ss + (int64_t)h * args.head_stride;
-    const int64_t kv_head_off = v_row0 * kv_ss + (int64_t)(h / va.group) * va.kv_head_stride;
+    const int64_t kv_head_off = k_row0 * kv_ss + (int64_t)(h / va.group) * va.kv_head_stride;
     const uint16_t *Qg = (const uint16_t *)args.q + head_off;
     const uint16_t *Kg = (const uint16_t *)args.k + kv_head_off;
     const uint16_t *Vg = (const uint16_t *)args.v + kv_head_off;
@@ -563,11 +609,31 @@ fa_fwd_kernel(const KernelArgs args) {
     const int wg_row0 = qb * TR::kBr;
     int n_kv_ = FA_N_KV_BLOCKS;
     if (MASK && args.causal) {
-        const int last_row = (wg_row0 + TR::kBr < S_len ? wg_row0 + TR::kBr : S_len) - 1;
+        const int last_row = (wg_row0 + TR::kBr < FA_Q_LEN ? wg_row0 + TR::kBr : FA_Q_LEN) - 1;
+#ifdef FA_KERNEL_VARLEN_QK
+        const int need = FA_SHIFTED(last_row) < 0 ? 0 : FA_SHIFTED(last_row) / BC + 1;   // (no key at all: len_q - len_k rows or more above)
+#else
         const int need = last_row / BC + 1;
+#endif
         n_kv_ = need < n_kv_ ? need : n_kv_;
     }
     const int n_kv = n_kv_;
+#ifdef FA_KERNEL_VARLEN_QK
+    if (n_kv == 0) {
+        // no tile to visit (len_k = 0, or causal rows that all lie above the shifted diagonal): o = 0 and lse = -inf for the
+        // workgroup's valid rows, whole 256-B rows as the epilogue stores them.  Workgroup-uniform, before any DMA or barrier.
+        const int64_t z_row0 = (int64_t)wg_row0 + wave * TR::kRowsPerWave;
+        const int z_rsub = lane / CPR, z_chunk = lane & (CPR - 1);
+        float *z_lse = va.lse + ((int64_t)h * va.total_tokens + v_row0);
+#pragma unroll
+        for (int i = 0; i < TR::kRowsPerWave / RPP; ++i) {
+            const int64_t row = z_row0 + RPP * i + z_rsub;
+            if (row < q_len) *(s16x8 *)(Og + row * ss + z_chunk * 8) = s16x8{};
+        }
+        if (lane < TR::kRowsPerWave && z_row0 + lane < q_len) z_lse[z_row0 + lane] = -__builtin_inff();
+        return;
+    }
+#endif
     const unsigned smem_base = __builtin_amdgcn_readfirstlane(lds_addr(smem));
     // DMA addressing: SGPR base = head base + tile offset (scalar ALU), VGPR = 32-bit
     // per-lane byte offset of this wave's piece inside a tile (invariant over tiles).
@@ -697,7 +763,7 @@ fa_fwd_kernel(const KernelArgs args) {
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
         int64_t row = (int64_t)qb * TR::kBr + wave_r * TR::kRowsPerWave + qt * 32 + r31;
-        if (MASK && row >= S_len) row = S_len - 1;  // rows past the end are computed, never stored
+        if (MASK && row >= FA_Q_LEN) row = FA_Q_LEN - 1;  // rows past the end are computed, never stored
         const uint16_t *qp = Qg + row * ss + hi * 8;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) Qr[qt][ks] = *(const vec8 *)(qp + ks * 16);
@@ -733,14 +799,14 @@ fa_fwd_kernel(const KernelArgs args) {
     const int wave_row0 = wg_row0 + wave_r * TR::kRowsPerWave;
     auto tile_needs_mask = [&](int it) -> bool {  // wave-uniform
         const int kv0 = (n_kv - 1 - it) * BC;
-        return MASK && (kv0 + BC > S_len || (args.causal && kv0 + BC - 1 > wave_row0));
+        return MASK && (kv0 + BC > S_len || (args.causal && kv0 + BC - 1 > FA_SHIFTED(wave_row0)));
     };
     auto mask_S = [&](f32x16 (&S)[QT][NTW], int it) {
         const int kv0 = (n_kv - 1 - it) * BC;
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
             const int q_row = wave_row0 + qt * 32 + r31;
-            const int limit = args.causal ? (q_row < S_len - 1 ? q_row : S_len - 1) : S_len - 1;  // last live key
+            const int limit = args.causal ? (FA_SHIFTED(q_row) < S_len - 1 ? FA_SHIFTED(q_row) : S_len - 1) : S_len - 1;  // last live key
 #pragma unroll
             for (int nt = 0; nt < NTW; ++nt)
 #pragma unroll
@@ -1166,7 +1232,7 @@ fa_fwd_kernel(const KernelArgs args) {
     for (int qt = 0; qt < QT; ++qt) {
         const float l_row = pair_sum(l[qt]);
         const int row = wave_row0 + qt * 32 + r31;
-        if (hi == 0 && row < S_len)
+        if (hi == 0 && row < FA_Q_LEN_END)   // (a row without keys: l = 0, m = -inf -> ln 0 + 0 = -inf)
             lse_rows[row] = (__builtin_amdgcn_logf(l_row) + finite_or_zero(m[qt]) * c) * 0.693147180559945309f;
     }
 #endif
@@ -1219,7 +1285,12 @@ fa_fwd_kernel(const KernelArgs args) {
         char *stage_o = smem + wave_r * (TR::kRowsPerWave * ROWB);
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
+#ifdef FA_KERNEL_VARLEN_QK
+            const float l_all = pair_sum(l[qt]);
+            const float inv = l_all == 0.0f ? 0.0f : 1.0f / l_all;   // a row that saw no key: o = 0, not 0 / 0
+#else
             const float inv = 1.0f / pair_sum(l[qt]);
+#endif
             const int row = qt * 32 + r31;
             char *wp = stage_o + row * ROWB + hi * 8;
 #pragma unroll
@@ -1242,7 +1313,7 @@ fa_fwd_kernel(const KernelArgs args) {
         for (int i = 0; i < TR::kRowsPerWave / RPP; ++i) {
             const int row = RPP * i + rsub;
             const s16x8 v = *(const s16x8 *)(stage_o + row * ROWB + ((chunk ^ swz_of(row)) << 4));
-            if (!MASK || row0 + row < S_len) *(s16x8 *)(Og + (row0 + row) * ss + chunk * 8) = v;
+            if (!MASK || row0 + row < FA_Q_LEN_END) *(s16x8 *)(Og + (row0 + row) * ss + chunk * 8) = v;
         }
     }
 }

@@ -90,11 +90,17 @@ def attention(q, k, v, causal=False):
     return _Attention.apply(q, k, v, causal)
 
 
-def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False):
+def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None):
     """Packed variable-length sequences: q (total_tokens, n_heads, 128), k / v (total_tokens, n_kv_heads, 128), cu_seqlens an
     int32 device tensor of n_seqs + 1 row offsets, max_seqlen a Python int (no device sync) -> (o, lse[, ms]) with lse fp32
-    (n_heads, total_tokens).  A query attends to the keys of its own sequence (causal: at or before its position in it)."""
-    return flash_attention_kernels.forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=causal, timed=timed)
+    (n_heads, total_tokens).  A query attends to the keys of its own sequence (causal: at or before its position in it).
+
+    With cu_seqlens_k and max_seqlen_k (both or neither: one alone is a ValueError) Q and K / V have lengths of their own:
+    cu_seqlens / max_seqlen are Q's, k / v are (total_k, n_kv_heads, 128) with sequence i's keys at rows cu_seqlens_k[i] ..
+    cu_seqlens_k[i + 1] - 1, any lengths >= 0 on either side.  causal is then bottom-right aligned (forward_kvcache's and
+    flash-attn's rule): query r sees keys j <= r + (len_k - len_q); a row that sees no key gives o = 0, lse = -inf."""
+    return flash_attention_kernels.forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=causal, timed=timed,
+                                                  cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
 
 
 def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
@@ -109,9 +115,12 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
                                                    return_lse=return_lse, max_seqlen_k=max_seqlen_k, num_splits=num_splits, timed=timed)
 
 
-def backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=False, timed=False):
-    """dQ, dK, dV over packed sequences from forward_varlen's o and lse -> (dq, dk, dv[, ms]).  Deterministic."""
-    return flash_attention_kernels.backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=causal, timed=timed)
+def backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None):
+    """dQ, dK, dV over packed sequences from forward_varlen's o and lse -> (dq, dk, dv[, ms]).  Deterministic.
+    cu_seqlens_k / max_seqlen_k (both or neither): separate K / V lengths as in forward_varlen, causal bottom-right aligned; a
+    row that saw no key gets dq = 0, a key no query sees gets dk = dv = 0 (written, not skipped)."""
+    return flash_attention_kernels.backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=causal, timed=timed,
+                                                   cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
 
 
 def _varlen_needs_copy(t):
@@ -120,24 +129,37 @@ def _varlen_needs_copy(t):
 
 class _AttentionVarlen(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, cu_seqlens, max_seqlen, causal):
+    def forward(ctx, q, k, v, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k):
         if _varlen_needs_copy(q):
             q = q.contiguous()
         if _varlen_needs_copy(k) or _varlen_needs_copy(v) or v.stride() != k.stride():
             k, v = k.contiguous(), v.contiguous()
-        o, lse = forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=causal)
-        ctx.save_for_backward(q, k, v, o, lse, cu_seqlens)
-        ctx.max_seqlen, ctx.causal = max_seqlen, causal
+        o, lse = forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=causal, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
+        ctx.qk = cu_seqlens_k is not None
+        if ctx.qk:
+            ctx.save_for_backward(q, k, v, o, lse, cu_seqlens, cu_seqlens_k)
+        else:
+            ctx.save_for_backward(q, k, v, o, lse, cu_seqlens)
+        ctx.max_seqlen, ctx.max_seqlen_k, ctx.causal = max_seqlen, max_seqlen_k, causal
         return o
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, o, lse, cu_seqlens = ctx.saved_tensors
-        dq, dk, dv = backward_varlen(q, k, v, o, lse, dout.contiguous(), cu_seqlens, ctx.max_seqlen, causal=ctx.causal)
-        return dq, dk, dv, None, None, None
+        q, k, v, o, lse, cu_seqlens = ctx.saved_tensors[:6]
+        cu_seqlens_k = ctx.saved_tensors[6] if ctx.qk else None
+        dq, dk, dv = backward_varlen(q, k, v, o, lse, dout.contiguous(), cu_seqlens, ctx.max_seqlen, causal=ctx.causal,
+                                     cu_seqlens_k=cu_seqlens_k, max_seqlen_k=ctx.max_seqlen_k)
+        return dq, dk, dv, None, None, None, None, None
 
 
-def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False):
-    """softmax(q k^T / sqrt d) v over packed sequences, with gradients (flash-attn's flash_attn_varlen_func for self-attention):
-    the varlen forward with the row log-sum-exp and the varlen HIP backward.  k and v may have n_kv_heads heads."""
-    return _AttentionVarlen.apply(q, k, v, cu_seqlens, max_seqlen, causal)
+def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, cu_seqlens_k=None, max_seqlen_k=None):
+    """softmax(q k^T / sqrt d) v over packed sequences, with gradients (flash-attn's flash_attn_varlen_func): the varlen forward
+    with the row log-sum-exp and the varlen HIP backward.  k and v may have n_kv_heads heads.
+
+    cu_seqlens_k / max_seqlen_k (both or neither: one alone is a ValueError) give K / V lengths of their own -- cross-attention,
+    chunked prefill behind a prefix: cu_seqlens / max_seqlen are then Q's, k / v are (total_k, n_kv_heads, 128), and causal is
+    bottom-right aligned: query r of a sequence sees keys j <= r + (len_k - len_q).  A row that sees no key gives o = 0 and
+    dq = 0; a key no query sees gets dk = dv = 0.  Both offset arrays are saved for the backward."""
+    if (cu_seqlens_k is None) != (max_seqlen_k is None):
+        raise ValueError("cu_seqlens_k and max_seqlen_k go together: give both (separate Q and K / V lengths) or neither")
+    return _AttentionVarlen.apply(q, k, v, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k)

@@ -445,6 +445,61 @@ int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *args);   /* byte
 int fa_bwd_launch_varlen(const fa_bwd_varlen_args *args, void *stream, float *ms);
 
 /*
+ * Packed sequences with SEPARATE Q and K / V lengths (flash-attn's cu_seqlens_q / cu_seqlens_k): cross-attention, chunked
+ * prefill behind a prefix, verification of many speculative rows -- forward with lse and backward.  q, o, dout, dq are
+ * (total_q, n_heads, 128), k, v, dk, dv (total_k, n_kv_heads, 128); sequence i owns query rows varlen_q.cu_seqlens[i] ..
+ * [i + 1] - 1 and key rows varlen_k.cu_seqlens[i] .. [i + 1] - 1.  Two fa_varlen_layout, one per side: n_seqs must match,
+ * total_tokens and max_seqlen are that side's; each is clamped by the rule above against its own bounds.  Any lengths >= 0
+ * are valid, independently.  causal is BOTTOM-RIGHT aligned, as in fa_decode_launch: query r of a sequence sees keys
+ * j <= r + (len_k - len_q).  A row that sees no key (len_k = 0; causal rows r < len_q - len_k) gives o = 0, lse = -inf,
+ * dq = 0; a key no query sees (len_q = 0: under the bottom-right mask the last row sees every key) gets dk = dv = 0, written.
+ * lse is (n_heads, total_q) fp32.
+ *
+ * fa_fwd_launch_varlen_qk / fa_fwd_varlen_qk_supported: the arguments, the served configurations and the refusals of
+ * fa_fwd_launch_varlen.  total_q = 0 returns FA_OK without a launch; total_k = 0 with total_q > 0 launches and writes the
+ * zeros and -inf.  With varlen_k equal to varlen_q, o and lse are bit-identical to fa_fwd_launch_varlen's.
+ *
+ * fa_bwd_varlen_qk_args: the fields of fa_bwd_varlen_args (varlen: the QUERY side) behind a struct_size, and varlen_k.  The
+ * dK / dV kernel runs n_seqs * n_kv_heads * split * ceil(max_seqlen_k / 128) workgroups, split by fa_bwd_launch_varlen's rule
+ * with max_seqlen_k in place of max_seqlen; partials and their sum run over total_k.  The dQ kernel runs n_seqs * n_heads *
+ * ceil(max_seqlen_q / 128) workgroups.  workspace: fa_bwd_varlen_qk_workspace_bytes bytes, 16-byte aligned.  Deterministic;
+ * with equal sides dq, dk, dv are bit-identical to fa_bwd_launch_varlen's and the workspace size is the same.
+ */
+int fa_fwd_varlen_qk_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_qk(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                            const fa_varlen_layout *varlen_k, const fa_fwd_opts *opts, float *lse, void *stream);
+typedef struct fa_bwd_varlen_qk_args {
+    uint32_t struct_size;    /* sizeof(fa_bwd_varlen_qk_args) */
+    const void *q;
+    const void *k;
+    const void *v;
+    const void *o;
+    const void *dout;
+    const float *lse;        /* (n_heads, total_q) fp32, contiguous */
+    void *dq;
+    void *dk;
+    void *dv;
+    void *workspace;
+    int64_t n_heads;
+    int64_t n_kv_heads;
+    int64_t d_head;
+    int64_t q_seq_stride;
+    int64_t q_head_stride;
+    int64_t out_seq_stride;
+    int64_t out_head_stride;
+    int64_t kv_seq_stride;
+    int64_t kv_head_stride;
+    int64_t dkv_seq_stride;
+    int64_t dkv_head_stride;
+    int32_t dtype;           /* fa_dtype */
+    int32_t causal;          /* bottom-right aligned */
+    fa_varlen_layout varlen;     /* the query rows */
+    fa_varlen_layout varlen_k;   /* the key rows */
+} fa_bwd_varlen_qk_args;
+int64_t fa_bwd_varlen_qk_workspace_bytes(const fa_bwd_varlen_qk_args *args);   /* bytes, or a negative fa_status */
+int fa_bwd_launch_varlen_qk(const fa_bwd_varlen_qk_args *args, void *stream, float *ms);
+
+/*
  * KV-cache decode attention (forward only): a few query rows per sequence against a long K / V cache whose valid length per
  * batch entry lies in DEVICE memory.  bf16 / fp16, d_head 128, MHA and GQA / MQA (query head h reads K / V head
  * h / (n_heads / n_kv_heads)), softmax scale 1 / sqrt(128).
