@@ -41,14 +41,12 @@ kernel_fn_gqa gqa_kernel_dt5(bool masked, bool spec);
 // fa_bwd.hip: delta, dK / dV and dQ of one backward, enqueued on `s`
 hipError_t bwd_enqueue(const BwdArgs &a, int dtype, bool causal, hipStream_t s);
 hipError_t bwd_gqa_enqueue(const BwdGqaArgs &g, int dtype, bool causal, hipStream_t s);
-// fa_inst_varlen.hip / fa_bwd_varlen.hip: the packed variable-length forms
+// fa_inst_varlen.hip: the packed variable-length forward (equal or separate Q and K / V lengths)
 kernel_fn_varlen varlen_kernel_dt15(bool first_block_skip);
 kernel_fn_varlen varlen_kernel_dt5(bool first_block_skip);
 int varlen_lds_bytes_dt15();
+// fa_bwd_varlen.hip / fa_bwd_varlen_qk.hip: the packed backward, and its form with separate Q and K / V lengths
 hipError_t bwd_varlen_enqueue(const BwdVarlenArgs &a, int dtype, bool causal, hipStream_t s);
-// fa_inst_varlen_qk.hip / fa_bwd_varlen_qk.hip: the packed forms with separate Q and K / V lengths
-kernel_fn_varlen_qk varlen_qk_kernel_dt15(bool first_block_skip);
-kernel_fn_varlen_qk varlen_qk_kernel_dt5(bool first_block_skip);
 hipError_t bwd_varlen_qk_enqueue(const BwdVarlenQKArgs &a, int dtype, bool causal, hipStream_t s);
 }  // namespace fa
 
@@ -271,24 +269,13 @@ void do_init_body(int dev, DeviceState *st) {
             return;
         }
     }
-    // the varlen forward (fa_fwd_launch_varlen): the 32-rows-per-wave kernel's 64 KiB
+    // the varlen forward (fa_fwd_launch_varlen, fa_fwd_launch_varlen_qk): the 32-rows-per-wave kernel's 64 KiB
     for (int i = 0; i < 4; ++i) {
         const void *fn = (i & 2) ? (const void *)fa::varlen_kernel_dt5((i & 1) != 0) : (const void *)fa::varlen_kernel_dt15((i & 1) != 0);
         const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, fa::varlen_lds_bytes_dt15());
         if (rc != hipSuccess) {
             st->status = FA_ERR_LAUNCH;
             snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, varlen form) on device %d: %s", fa::varlen_lds_bytes_dt15(),
-                     dev, hipGetErrorString(rc));
-            return;
-        }
-    }
-    // ... and its form with separate Q and K / V lengths (fa_fwd_launch_varlen_qk): the same LDS
-    for (int i = 0; i < 4; ++i) {
-        const void *fn = (i & 2) ? (const void *)fa::varlen_qk_kernel_dt5((i & 1) != 0) : (const void *)fa::varlen_qk_kernel_dt15((i & 1) != 0);
-        const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, fa::varlen_lds_bytes_dt15());
-        if (rc != hipSuccess) {
-            st->status = FA_ERR_LAUNCH;
-            snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, varlen_qk form) on device %d: %s", fa::varlen_lds_bytes_dt15(),
                      dev, hipGetErrorString(rc));
             return;
         }
@@ -842,16 +829,19 @@ int bwd_gqa_validate(const fa_bwd_gqa_args *g) {
     return check_strides("dkv", a.batch, g->n_kv_heads, g->dkv_batch_stride, g->dkv_seq_stride, g->dkv_head_stride);
 }
 
-// Workgroups per (K / V head, key block) of the dK / dV kernel: the smallest divisor of the group that gives the grid at least
+// Workgroups per (K / V head, key block) of a dK / dV kernel: the smallest divisor of the group that gives the grid at least
 // 256 workgroups (one per CU of an MI355X), 1024 causal (a causal block's sweep is 1 .. seq_len / 128 tiles long: the
-// dispatcher evens that out only with several workgroups per CU).  A function of the shape alone.
+// dispatcher evens that out only with several workgroups per CU).  `workgroups`: the grid without a split.  A function of the
+// shape alone.
+int64_t bwd_dkdv_split(int64_t group, int64_t workgroups, bool causal) {
+    const int64_t want = causal ? 1024 : 256;
+    for (int64_t s = 1; s < group; ++s)
+        if (group % s == 0 && workgroups * s >= want) return s;
+    return group;
+}
 int64_t bwd_gqa_split(const fa_bwd_gqa_args *g) {
     const fa_bwd_args &a = g->base;
-    const int64_t group = a.n_heads / g->n_kv_heads, wgs = a.batch * g->n_kv_heads * (a.seq_len / 128);
-    const int64_t want = a.causal ? 1024 : 256;
-    for (int64_t s = 1; s < group; ++s)
-        if (group % s == 0 && wgs * s >= want) return s;
-    return group;
+    return bwd_dkdv_split(a.n_heads / g->n_kv_heads, a.batch * g->n_kv_heads * (a.seq_len / 128), a.causal != 0);
 }
 
 int64_t bwd_gqa_part_bytes(const fa_bwd_gqa_args *g, int64_t split) {   // the split's fp32 partials
@@ -931,7 +921,11 @@ int fa_fwd_launch_gqa(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_
     return launch_ex_impl(args, opts, stream, lse, kv);
 }
 
-// ---- packed variable-length sequences ------------------------------------------------------------------------------------
+// ---- packed variable-length sequences: one range for Q and K / V (fa_*_varlen) or one each (fa_*_varlen_qk) ------------------
+// One host path, of two ranges; the entry points with one fa_varlen_layout pass it for both sides.  Each entry point keeps its
+// own name, and its name for the query side's total, in its messages.  The forward has one kernel; the backward keeps the
+// single-range kernels beside the two-range ones (theirs are faster), so the two backward entries share the
+// checks, the split and the argument fill and differ in the kernels they enqueue.
 namespace {
 int varlen_validate(const fa_varlen_layout *vl) {
     if (!vl) return fail(FA_ERR_NULL, "null pointer argument");
@@ -945,6 +939,17 @@ int varlen_validate(const fa_varlen_layout *vl) {
     if (vl->max_seqlen < 1) return fail(FA_ERR_SHAPE, "max_seqlen must be at least 1 (got %lld)", (long long)vl->max_seqlen);
     if (vl->total_tokens > INT32_MAX / 2 || vl->max_seqlen > INT32_MAX / 2 || vl->n_seqs > INT32_MAX / 2)
         return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
+    return FA_OK;
+}
+
+// the two layouts of one launch: each valid by itself, one sequence count
+int varlen_qk_validate(const fa_varlen_layout *vq, const fa_varlen_layout *vk) {
+    int rc = varlen_validate(vq);
+    if (rc != FA_OK) return rc;
+    if ((rc = varlen_validate(vk)) != FA_OK) return rc;
+    if (vq->n_seqs != vk->n_seqs)
+        return fail(FA_ERR_SHAPE, "n_seqs mismatch: the query side has %lld sequences, the key side %lld", (long long)vq->n_seqs,
+                    (long long)vk->n_seqs);
     return FA_OK;
 }
 
@@ -974,51 +979,12 @@ const fa::KernelEntry *varlen_entry(const fa_fwd_config *cfg, const char **why) 
 const char *kNoVarlen = "packed variable-length sequences are served by the (B_r 128, B_c 64, 4 warps) + buffer configuration at d_head "
                         "128 only, plain or causal, without speculative, prescaled_q and stats";
 
-int64_t bwd_varlen_split(const fa_bwd_varlen_args *a) {
-    const int64_t group = a->n_heads / a->n_kv_heads, wgs = a->varlen.n_seqs * a->n_kv_heads * ((a->varlen.max_seqlen + 127) / 128);
-    const int64_t want = a->causal ? 1024 : 256;
-    for (int64_t s = 1; s < group; ++s)
-        if (group % s == 0 && wgs * s >= want) return s;
-    return group;
-}
-int64_t bwd_varlen_delta_bytes(const fa_bwd_varlen_args *a) {   // (n_heads, total_tokens) fp32, rounded up to 16 bytes
-    return ((int64_t)sizeof(float) * a->n_heads * a->varlen.total_tokens + 15) & ~(int64_t)15;
-}
-
-int bwd_varlen_validate(const fa_bwd_varlen_args *a) {
-    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
-    if (a->dtype != FA_FP16 && a->dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
-    if (a->d_head != 128) return fail(FA_ERR_SHAPE, "the backward supports d_head = 128 only (got %lld)", (long long)a->d_head);
-    if (a->n_heads <= 0) return fail(FA_ERR_SHAPE, "n_heads must be positive");
-    int rc = varlen_validate(&a->varlen);
-    if (rc != FA_OK) return rc;
-    if (a->n_kv_heads < 1 || a->n_kv_heads > a->n_heads || a->n_heads % a->n_kv_heads != 0)
-        return fail(FA_ERR_SHAPE, "grouped-query attention needs n_kv_heads (%lld) to divide n_heads (%lld)", (long long)a->n_kv_heads,
-                    (long long)a->n_heads);
-    if ((rc = check_strides_varlen("q", a->n_heads, a->q_seq_stride, a->q_head_stride)) != FA_OK) return rc;
-    if ((rc = check_strides_varlen("out", a->n_heads, a->out_seq_stride, a->out_head_stride)) != FA_OK) return rc;
-    if ((rc = check_strides_varlen("kv", a->n_kv_heads, a->kv_seq_stride, a->kv_head_stride)) != FA_OK) return rc;
-    if ((rc = check_strides_varlen("dkv", a->n_kv_heads, a->dkv_seq_stride, a->dkv_head_stride)) != FA_OK) return rc;
-    if (a->n_heads * a->varlen.total_tokens > (int64_t)INT32_MAX * 8) return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
-    return varlen_grid_check(&a->varlen, a->n_heads);   // (n_kv_heads * split <= n_heads)
-}
-}  // namespace
-
-int fa_fwd_varlen_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) {
-    if (!cfg) return 0;
-    fa_fwd_opts o;
-    if (read_opts(opts, &o) != FA_OK) return 0;
-    if (o.speculative || o.prescaled_q || o.stats) return 0;
-    if (cfg->dtype != FA_BF16 && cfg->dtype != FA_FP16) return 0;
-    const char *why;
-    return varlen_entry(cfg, &why) ? 1 : 0;
-}
-
-int fa_fwd_launch_varlen(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vl, const fa_fwd_opts *opts, float *lse,
-                         void *stream) {
-    if (!args || !kv || !vl) return fail(FA_ERR_NULL, "null pointer argument");
+// the forward of `entry` (a public entry point; `total`: its name for the query side's total)
+int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
+                      const fa_varlen_layout *vk, const fa_fwd_opts *opts, float *lse, void *stream) {
+    if (!args || !kv || !vq || !vk) return fail(FA_ERR_NULL, "null pointer argument");
     if (!args->q || !args->k || !args->v || !args->o) return fail(FA_ERR_NULL, "null pointer argument");
-    if (!lse) return fail(FA_ERR_NULL, "lse is null: fa_fwd_launch_varlen needs a (n_heads, total_tokens) fp32 buffer");
+    if (!lse) return fail(FA_ERR_NULL, "lse is null: %s needs a (n_heads, %s) fp32 buffer", entry, total);
     if (args->cfg.dtype != FA_FP16 && args->cfg.dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
     if (kv->struct_size < sizeof(fa_kv_layout))
         return fail(FA_ERR_SHAPE, "fa_kv_layout.struct_size (%u) is smaller than this library's (%zu)", kv->struct_size, sizeof(fa_kv_layout));
@@ -1026,179 +992,6 @@ int fa_fwd_launch_varlen(const fa_fwd_args *args, const fa_kv_layout *kv, const 
     int rc = read_opts(opts, &o);
     if (rc != FA_OK) return rc;
     if (!fa_fwd_varlen_supported(&args->cfg, opts)) return fail(FA_ERR_NO_KERNEL, "%s", kNoVarlen);
-    if (args->d_head != 128)
-        return fail(FA_ERR_SHAPE, "Tensor d_head (%lld) does not match kernel configuration d_head (%d)", (long long)args->d_head, 128);
-    if (args->n_heads <= 0) return fail(FA_ERR_SHAPE, "n_heads must be positive");
-    if ((rc = varlen_validate(vl)) != FA_OK) return rc;
-    if (kv->n_kv_heads < 1 || kv->n_kv_heads > args->n_heads || args->n_heads % kv->n_kv_heads != 0)
-        return fail(FA_ERR_SHAPE, "grouped-query attention needs n_kv_heads (%lld) to divide n_heads (%lld)", (long long)kv->n_kv_heads,
-                    (long long)args->n_heads);
-    if ((rc = check_strides_varlen("q", args->n_heads, args->seq_stride, args->head_stride)) != FA_OK) return rc;
-    if ((rc = check_strides_varlen("kv", kv->n_kv_heads, kv->kv_seq_stride, kv->kv_head_stride)) != FA_OK) return rc;
-    if ((rc = varlen_grid_check(vl, args->n_heads)) != FA_OK) return rc;
-    if (((uintptr_t)args->q | (uintptr_t)args->k | (uintptr_t)args->v | (uintptr_t)args->o) & 15)
-        return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
-    if ((uintptr_t)lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
-    if (vl->total_tokens == 0) {
-        if (o.ms) *o.ms = 0.0f;
-        return FA_OK;
-    }
-    DeviceState *dev = current_device(&rc);
-    if (!dev) return rc;
-    const char *why;
-    const fa::KernelEntry *e = varlen_entry(&args->cfg, &why);
-    fa::KernelArgsVarlen va;
-    va.base.q = args->q;
-    va.base.k = args->k;
-    va.base.v = args->v;
-    va.base.o = args->o;
-    va.base.batch_stride = 0;
-    va.base.seq_stride = args->seq_stride;
-    va.base.head_stride = args->head_stride;
-    va.base.seq_len = 0;
-    va.base.n_heads = (int32_t)args->n_heads;
-    va.base.n_bh = (int32_t)(vl->n_seqs * args->n_heads);
-    va.base.n_q_blocks = (int32_t)((vl->max_seqlen + 127) / 128);
-    va.base.n_kv_blocks = 0;
-    va.base.causal = o.causal != 0;
-    va.cu_seqlens = vl->cu_seqlens;
-    va.lse = lse;
-    va.kv_seq_stride = kv->kv_seq_stride;
-    va.kv_head_stride = kv->kv_head_stride;
-    va.group = (int32_t)(args->n_heads / kv->n_kv_heads);
-    va.total_tokens = (int32_t)vl->total_tokens;
-    va.max_seqlen = (int32_t)vl->max_seqlen;
-    const bool fbs = e->softmax_mode == FA_SOFTMAX_FIRST_BLOCK_SKIP;
-    const void *fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kernel_dt15(fbs) : (const void *)fa::varlen_kernel_dt5(fbs);
-    const dim3 grid((unsigned)(va.base.n_bh * va.base.n_q_blocks)), block((unsigned)e->threads);
-    const hipStream_t s = (hipStream_t)stream;
-    return bwd_run([&] {
-        void *params[] = {&va};
-        return hipLaunchKernel(fn, grid, block, params, (size_t)e->lds_bytes, s);
-    }, s, o.ms);
-}
-
-int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *a) {
-    const int rc = bwd_varlen_validate(a);
-    if (rc != FA_OK) return rc;
-    const int64_t split = bwd_varlen_split(a);
-    return bwd_varlen_delta_bytes(a) + (split > 1 ? (int64_t)sizeof(float) * a->n_kv_heads * split * a->varlen.total_tokens * 2 * 128 : 0);
-}
-
-int fa_bwd_launch_varlen(const fa_bwd_varlen_args *a, void *stream, float *ms) {
-    int rc = bwd_varlen_validate(a);
-    if (rc != FA_OK) return rc;
-    if (!a->q || !a->k || !a->v || !a->o || !a->dout || !a->dq || !a->dk || !a->dv)
-        return fail(FA_ERR_NULL, "null tensor pointer (q, k, v, o, dout, dq, dk and dv are all needed)");
-    if (!a->lse) return fail(FA_ERR_NULL, "lse is null: the backward needs the forward's (n_heads, total_tokens) fp32 lse");
-    if (!a->workspace) return fail(FA_ERR_NULL, "workspace is null: allocate fa_bwd_varlen_workspace_bytes(args) bytes of device memory");
-    if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o | (uintptr_t)a->dout | (uintptr_t)a->dq |
-         (uintptr_t)a->dk | (uintptr_t)a->dv) & 15)
-        return fail(FA_ERR_ALIGN, "q, k, v, o, dout, dq, dk, dv must be 16-byte aligned");
-    if ((uintptr_t)a->lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
-    if ((uintptr_t)a->workspace & 15) return fail(FA_ERR_ALIGN, "workspace must be 16-byte aligned (it holds delta and the fp32 partials of dK / dV)");
-    if (a->varlen.total_tokens == 0) {
-        if (ms) *ms = 0.0f;
-        return FA_OK;
-    }
-    DeviceState *dev = current_device(&rc);
-    if (!dev) return rc;
-    const int64_t split = bwd_varlen_split(a);
-    fa::BwdVarlenArgs va;
-    va.q = (const uint16_t *)a->q;
-    va.k = (const uint16_t *)a->k;
-    va.v = (const uint16_t *)a->v;
-    va.o = (const uint16_t *)a->o;
-    va.dout = (const uint16_t *)a->dout;
-    va.lse = a->lse;
-    va.delta = (float *)a->workspace;
-    va.dq = (uint16_t *)a->dq;
-    va.dk = (uint16_t *)a->dk;
-    va.dv = (uint16_t *)a->dv;
-    va.cu_seqlens = a->varlen.cu_seqlens;
-    va.part = split > 1 ? (float *)((char *)a->workspace + bwd_varlen_delta_bytes(a)) : nullptr;
-    va.q_ss = a->q_seq_stride;
-    va.q_hs = a->q_head_stride;
-    va.out_ss = a->out_seq_stride;
-    va.out_hs = a->out_head_stride;
-    va.kv_ss = a->kv_seq_stride;
-    va.kv_hs = a->kv_head_stride;
-    va.dkv_ss = a->dkv_seq_stride;
-    va.dkv_hs = a->dkv_head_stride;
-    va.n_seqs = (int32_t)a->varlen.n_seqs;
-    va.total_tokens = (int32_t)a->varlen.total_tokens;
-    va.max_seqlen = (int32_t)a->varlen.max_seqlen;
-    va.n_heads = (int32_t)a->n_heads;
-    va.group = (int32_t)(a->n_heads / a->n_kv_heads);
-    va.split = (int32_t)split;
-    va.n_blocks = (int32_t)((a->varlen.max_seqlen + 127) / 128);
-    const hipStream_t s = (hipStream_t)stream;
-    return bwd_run([&] { return fa::bwd_varlen_enqueue(va, a->dtype, a->causal != 0, s); }, s, ms);
-}
-
-// ---- packed variable-length sequences with separate Q and K / V lengths -------------------------------------------------------
-namespace {
-// the two layouts of one launch: each valid by itself, one sequence count
-int varlen_qk_validate(const fa_varlen_layout *vq, const fa_varlen_layout *vk) {
-    int rc = varlen_validate(vq);
-    if (rc != FA_OK) return rc;
-    if ((rc = varlen_validate(vk)) != FA_OK) return rc;
-    if (vq->n_seqs != vk->n_seqs)
-        return fail(FA_ERR_SHAPE, "n_seqs mismatch: the query side has %lld sequences, the key side %lld", (long long)vq->n_seqs,
-                    (long long)vk->n_seqs);
-    return FA_OK;
-}
-
-// fa_bwd_launch_varlen's rule with max_seqlen_k in place of max_seqlen: host-visible arguments only
-int64_t bwd_varlen_qk_split(const fa_bwd_varlen_qk_args *a) {
-    const int64_t group = a->n_heads / a->n_kv_heads, wgs = a->varlen.n_seqs * a->n_kv_heads * ((a->varlen_k.max_seqlen + 127) / 128);
-    const int64_t want = a->causal ? 1024 : 256;
-    for (int64_t s = 1; s < group; ++s)
-        if (group % s == 0 && wgs * s >= want) return s;
-    return group;
-}
-int64_t bwd_varlen_qk_delta_bytes(const fa_bwd_varlen_qk_args *a) {   // (n_heads, total_q) fp32, rounded up to 16 bytes
-    return ((int64_t)sizeof(float) * a->n_heads * a->varlen.total_tokens + 15) & ~(int64_t)15;
-}
-
-int bwd_varlen_qk_validate(const fa_bwd_varlen_qk_args *a) {
-    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
-    if (a->struct_size < sizeof(fa_bwd_varlen_qk_args))
-        return fail(FA_ERR_SHAPE, "fa_bwd_varlen_qk_args.struct_size (%u) is smaller than this library's (%zu)", a->struct_size,
-                    sizeof(fa_bwd_varlen_qk_args));
-    if (a->dtype != FA_FP16 && a->dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
-    if (a->d_head != 128) return fail(FA_ERR_SHAPE, "the backward supports d_head = 128 only (got %lld)", (long long)a->d_head);
-    if (a->n_heads <= 0) return fail(FA_ERR_SHAPE, "n_heads must be positive");
-    int rc = varlen_qk_validate(&a->varlen, &a->varlen_k);
-    if (rc != FA_OK) return rc;
-    if (a->n_kv_heads < 1 || a->n_kv_heads > a->n_heads || a->n_heads % a->n_kv_heads != 0)
-        return fail(FA_ERR_SHAPE, "grouped-query attention needs n_kv_heads (%lld) to divide n_heads (%lld)", (long long)a->n_kv_heads,
-                    (long long)a->n_heads);
-    if ((rc = check_strides_varlen("q", a->n_heads, a->q_seq_stride, a->q_head_stride)) != FA_OK) return rc;
-    if ((rc = check_strides_varlen("out", a->n_heads, a->out_seq_stride, a->out_head_stride)) != FA_OK) return rc;
-    if ((rc = check_strides_varlen("kv", a->n_kv_heads, a->kv_seq_stride, a->kv_head_stride)) != FA_OK) return rc;
-    if ((rc = check_strides_varlen("dkv", a->n_kv_heads, a->dkv_seq_stride, a->dkv_head_stride)) != FA_OK) return rc;
-    if (a->n_heads * a->varlen.total_tokens > (int64_t)INT32_MAX * 8 || a->n_kv_heads * a->varlen_k.total_tokens > (int64_t)INT32_MAX / 2)
-        return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
-    if ((rc = varlen_grid_check(&a->varlen, a->n_heads)) != FA_OK) return rc;
-    return varlen_grid_check(&a->varlen_k, a->n_heads);   // (n_kv_heads * split <= n_heads)
-}
-}  // namespace
-
-int fa_fwd_varlen_qk_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
-
-int fa_fwd_launch_varlen_qk(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_varlen_layout *vk,
-                            const fa_fwd_opts *opts, float *lse, void *stream) {
-    if (!args || !kv || !vq || !vk) return fail(FA_ERR_NULL, "null pointer argument");
-    if (!args->q || !args->k || !args->v || !args->o) return fail(FA_ERR_NULL, "null pointer argument");
-    if (!lse) return fail(FA_ERR_NULL, "lse is null: fa_fwd_launch_varlen_qk needs a (n_heads, total_q) fp32 buffer");
-    if (args->cfg.dtype != FA_FP16 && args->cfg.dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
-    if (kv->struct_size < sizeof(fa_kv_layout))
-        return fail(FA_ERR_SHAPE, "fa_kv_layout.struct_size (%u) is smaller than this library's (%zu)", kv->struct_size, sizeof(fa_kv_layout));
-    fa_fwd_opts o;
-    int rc = read_opts(opts, &o);
-    if (rc != FA_OK) return rc;
-    if (!fa_fwd_varlen_qk_supported(&args->cfg, opts)) return fail(FA_ERR_NO_KERNEL, "%s", kNoVarlen);
     if (args->d_head != 128)
         return fail(FA_ERR_SHAPE, "Tensor d_head (%lld) does not match kernel configuration d_head (%d)", (long long)args->d_head, 128);
     if (args->n_heads <= 0) return fail(FA_ERR_SHAPE, "n_heads must be positive");
@@ -1212,7 +1005,7 @@ int fa_fwd_launch_varlen_qk(const fa_fwd_args *args, const fa_kv_layout *kv, con
     if (((uintptr_t)args->q | (uintptr_t)args->k | (uintptr_t)args->v | (uintptr_t)args->o) & 15)
         return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
     if ((uintptr_t)lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
-    if (vq->total_tokens == 0) {
+    if (vq->total_tokens == 0) {   // (no query rows: nothing to write)
         if (o.ms) *o.ms = 0.0f;
         return FA_OK;
     }
@@ -1246,7 +1039,7 @@ int fa_fwd_launch_varlen_qk(const fa_fwd_args *args, const fa_kv_layout *kv, con
     qa.total_k = (int32_t)vk->total_tokens;
     qa.max_seqlen_k = (int32_t)vk->max_seqlen;
     const bool fbs = e->softmax_mode == FA_SOFTMAX_FIRST_BLOCK_SKIP;
-    const void *fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_qk_kernel_dt15(fbs) : (const void *)fa::varlen_qk_kernel_dt5(fbs);
+    const void *fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kernel_dt15(fbs) : (const void *)fa::varlen_kernel_dt5(fbs);
     const dim3 grid((unsigned)(va.base.n_bh * va.base.n_q_blocks)), block((unsigned)e->threads);
     const hipStream_t s = (hipStream_t)stream;
     return bwd_run([&] {
@@ -1255,33 +1048,98 @@ int fa_fwd_launch_varlen_qk(const fa_fwd_args *args, const fa_kv_layout *kv, con
     }, s, o.ms);
 }
 
-int64_t fa_bwd_varlen_qk_workspace_bytes(const fa_bwd_varlen_qk_args *a) {
-    const int rc = bwd_varlen_qk_validate(a);
-    if (rc != FA_OK) return rc;
-    const int64_t split = bwd_varlen_qk_split(a);
-    return bwd_varlen_qk_delta_bytes(a) + (split > 1 ? (int64_t)sizeof(float) * a->n_kv_heads * split * a->varlen_k.total_tokens * 2 * 128 : 0);
+// fa_bwd_varlen_args as the arguments of two ranges: its one layout on both sides
+fa_bwd_varlen_qk_args both_sides(const fa_bwd_varlen_args *a) {
+    fa_bwd_varlen_qk_args b;
+    b.struct_size = sizeof(b);
+    b.q = a->q;
+    b.k = a->k;
+    b.v = a->v;
+    b.o = a->o;
+    b.dout = a->dout;
+    b.lse = a->lse;
+    b.dq = a->dq;
+    b.dk = a->dk;
+    b.dv = a->dv;
+    b.workspace = a->workspace;
+    b.n_heads = a->n_heads;
+    b.n_kv_heads = a->n_kv_heads;
+    b.d_head = a->d_head;
+    b.q_seq_stride = a->q_seq_stride;
+    b.q_head_stride = a->q_head_stride;
+    b.out_seq_stride = a->out_seq_stride;
+    b.out_head_stride = a->out_head_stride;
+    b.kv_seq_stride = a->kv_seq_stride;
+    b.kv_head_stride = a->kv_head_stride;
+    b.dkv_seq_stride = a->dkv_seq_stride;
+    b.dkv_head_stride = a->dkv_head_stride;
+    b.dtype = a->dtype;
+    b.causal = a->causal;
+    b.varlen = b.varlen_k = a->varlen;
+    return b;
 }
 
-int fa_bwd_launch_varlen_qk(const fa_bwd_varlen_qk_args *a, void *stream, float *ms) {
-    int rc = bwd_varlen_qk_validate(a);
+// the dK / dV split: bwd_dkdv_split on the key side's grid -- host-visible arguments only, never what cu_seqlens holds
+int64_t bwd_varlen_split(const fa_bwd_varlen_qk_args *a) {
+    return bwd_dkdv_split(a->n_heads / a->n_kv_heads, a->varlen.n_seqs * a->n_kv_heads * ((a->varlen_k.max_seqlen + 127) / 128),
+                          a->causal != 0);
+}
+int64_t bwd_varlen_delta_bytes(const fa_bwd_varlen_qk_args *a) {   // (n_heads, total_q) fp32, rounded up to 16 bytes
+    return ((int64_t)sizeof(float) * a->n_heads * a->varlen.total_tokens + 15) & ~(int64_t)15;
+}
+
+// own_key_side: the caller gave varlen_k (fa_*_varlen_qk), whose rows the reduce kernel's grid runs over
+int bwd_varlen_validate(const fa_bwd_varlen_qk_args *a, bool own_key_side) {
+    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
+    if (a->struct_size < sizeof(fa_bwd_varlen_qk_args))
+        return fail(FA_ERR_SHAPE, "fa_bwd_varlen_qk_args.struct_size (%u) is smaller than this library's (%zu)", a->struct_size,
+                    sizeof(fa_bwd_varlen_qk_args));
+    if (a->dtype != FA_FP16 && a->dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
+    if (a->d_head != 128) return fail(FA_ERR_SHAPE, "the backward supports d_head = 128 only (got %lld)", (long long)a->d_head);
+    if (a->n_heads <= 0) return fail(FA_ERR_SHAPE, "n_heads must be positive");
+    int rc = varlen_qk_validate(&a->varlen, &a->varlen_k);
+    if (rc != FA_OK) return rc;
+    if (a->n_kv_heads < 1 || a->n_kv_heads > a->n_heads || a->n_heads % a->n_kv_heads != 0)
+        return fail(FA_ERR_SHAPE, "grouped-query attention needs n_kv_heads (%lld) to divide n_heads (%lld)", (long long)a->n_kv_heads,
+                    (long long)a->n_heads);
+    if ((rc = check_strides_varlen("q", a->n_heads, a->q_seq_stride, a->q_head_stride)) != FA_OK) return rc;
+    if ((rc = check_strides_varlen("out", a->n_heads, a->out_seq_stride, a->out_head_stride)) != FA_OK) return rc;
+    if ((rc = check_strides_varlen("kv", a->n_kv_heads, a->kv_seq_stride, a->kv_head_stride)) != FA_OK) return rc;
+    if ((rc = check_strides_varlen("dkv", a->n_kv_heads, a->dkv_seq_stride, a->dkv_head_stride)) != FA_OK) return rc;
+    if (a->n_heads * a->varlen.total_tokens > (int64_t)INT32_MAX * 8 ||
+        (own_key_side && a->n_kv_heads * a->varlen_k.total_tokens > (int64_t)INT32_MAX / 2))
+        return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
+    if ((rc = varlen_grid_check(&a->varlen, a->n_heads)) != FA_OK) return rc;
+    return varlen_grid_check(&a->varlen_k, a->n_heads);   // (n_kv_heads * split <= n_heads)
+}
+
+int64_t bwd_varlen_workspace_bytes(const fa_bwd_varlen_qk_args *a, bool own_key_side) {
+    const int rc = bwd_varlen_validate(a, own_key_side);
+    if (rc != FA_OK) return rc;
+    const int64_t split = bwd_varlen_split(a);
+    return bwd_varlen_delta_bytes(a) + (split > 1 ? (int64_t)sizeof(float) * a->n_kv_heads * split * a->varlen_k.total_tokens * 2 * 128 : 0);
+}
+
+// what a backward entry point refuses before it looks at the device; in its messages `total` is its name for the query side's
+// total, `workspace_fn` its workspace function
+int bwd_varlen_checks(const fa_bwd_varlen_qk_args *a, bool own_key_side, const char *total, const char *workspace_fn) {
+    int rc = bwd_varlen_validate(a, own_key_side);
     if (rc != FA_OK) return rc;
     if (!a->q || !a->k || !a->v || !a->o || !a->dout || !a->dq || !a->dk || !a->dv)
         return fail(FA_ERR_NULL, "null tensor pointer (q, k, v, o, dout, dq, dk and dv are all needed)");
-    if (!a->lse) return fail(FA_ERR_NULL, "lse is null: the backward needs the forward's (n_heads, total_q) fp32 lse");
-    if (!a->workspace) return fail(FA_ERR_NULL, "workspace is null: allocate fa_bwd_varlen_qk_workspace_bytes(args) bytes of device memory");
+    if (!a->lse) return fail(FA_ERR_NULL, "lse is null: the backward needs the forward's (n_heads, %s) fp32 lse", total);
+    if (!a->workspace) return fail(FA_ERR_NULL, "workspace is null: allocate %s(args) bytes of device memory", workspace_fn);
     if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o | (uintptr_t)a->dout | (uintptr_t)a->dq |
          (uintptr_t)a->dk | (uintptr_t)a->dv) & 15)
         return fail(FA_ERR_ALIGN, "q, k, v, o, dout, dq, dk, dv must be 16-byte aligned");
     if ((uintptr_t)a->lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
     if ((uintptr_t)a->workspace & 15) return fail(FA_ERR_ALIGN, "workspace must be 16-byte aligned (it holds delta and the fp32 partials of dK / dV)");
-    if (a->varlen.total_tokens == 0 && a->varlen_k.total_tokens == 0) {
-        if (ms) *ms = 0.0f;
-        return FA_OK;
-    }
-    DeviceState *dev = current_device(&rc);
-    if (!dev) return rc;
-    const int64_t split = bwd_varlen_qk_split(a);
-    fa::BwdVarlenQKArgs va;
+    return FA_OK;
+}
+
+// the kernels' arguments of two ranges from the host's
+void bwd_varlen_fill(fa::BwdVarlenQKArgs &va, const fa_bwd_varlen_qk_args *a) {
+    const int64_t split = bwd_varlen_split(a);
     va.q = (const uint16_t *)a->q;
     va.k = (const uint16_t *)a->k;
     va.v = (const uint16_t *)a->v;
@@ -1293,8 +1151,7 @@ int fa_bwd_launch_varlen_qk(const fa_bwd_varlen_qk_args *a, void *stream, float 
     va.dk = (uint16_t *)a->dk;
     va.dv = (uint16_t *)a->dv;
     va.cu_seqlens = a->varlen.cu_seqlens;
-    va.cu_seqlens_k = a->varlen_k.cu_seqlens;
-    va.part = split > 1 ? (float *)((char *)a->workspace + bwd_varlen_qk_delta_bytes(a)) : nullptr;
+    va.part = split > 1 ? (float *)((char *)a->workspace + bwd_varlen_delta_bytes(a)) : nullptr;
     va.q_ss = a->q_seq_stride;
     va.q_hs = a->q_head_stride;
     va.out_ss = a->out_seq_stride;
@@ -1307,12 +1164,78 @@ int fa_bwd_launch_varlen_qk(const fa_bwd_varlen_qk_args *a, void *stream, float 
     va.total_tokens = (int32_t)a->varlen.total_tokens;
     va.max_seqlen = (int32_t)a->varlen.max_seqlen;
     va.n_heads = (int32_t)a->n_heads;
-    va.total_k = (int32_t)a->varlen_k.total_tokens;
-    va.max_seqlen_k = (int32_t)a->varlen_k.max_seqlen;
     va.group = (int32_t)(a->n_heads / a->n_kv_heads);
     va.split = (int32_t)split;
     va.n_blocks = (int32_t)((a->varlen.max_seqlen + 127) / 128);
+    va.cu_seqlens_k = a->varlen_k.cu_seqlens;
+    va.total_k = (int32_t)a->varlen_k.total_tokens;
+    va.max_seqlen_k = (int32_t)a->varlen_k.max_seqlen;
     va.n_blocks_k = (int32_t)((a->varlen_k.max_seqlen + 127) / 128);
+}
+// ... and what the kernels of one range take of them (fa::BwdVarlenArgs, in its field order)
+fa::BwdVarlenArgs one_range(const fa::BwdVarlenQKArgs &w) {
+    return {w.q,    w.k,    w.v,     w.o,     w.dout,  w.lse,   w.delta,  w.dq,      w.dk,           w.dv,         w.cu_seqlens, w.part,
+            w.q_ss, w.q_hs, w.out_ss, w.out_hs, w.kv_ss, w.kv_hs, w.dkv_ss, w.dkv_hs, w.n_seqs,       w.total_tokens, w.max_seqlen,
+            w.n_heads, w.group, w.split, w.n_blocks};
+}
+}  // namespace
+
+int fa_fwd_varlen_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) {
+    if (!cfg) return 0;
+    fa_fwd_opts o;
+    if (read_opts(opts, &o) != FA_OK) return 0;
+    if (o.speculative || o.prescaled_q || o.stats) return 0;
+    if (cfg->dtype != FA_BF16 && cfg->dtype != FA_FP16) return 0;
+    const char *why;
+    return varlen_entry(cfg, &why) ? 1 : 0;
+}
+int fa_fwd_varlen_qk_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
+
+int fa_fwd_launch_varlen(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vl, const fa_fwd_opts *opts, float *lse,
+                         void *stream) {
+    return fwd_launch_varlen("fa_fwd_launch_varlen", "total_tokens", args, kv, vl, vl, opts, lse, stream);
+}
+int fa_fwd_launch_varlen_qk(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_varlen_layout *vk,
+                            const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen("fa_fwd_launch_varlen_qk", "total_q", args, kv, vq, vk, opts, lse, stream);
+}
+
+int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *a) {
+    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
+    const fa_bwd_varlen_qk_args b = both_sides(a);
+    return bwd_varlen_workspace_bytes(&b, false);
+}
+int64_t fa_bwd_varlen_qk_workspace_bytes(const fa_bwd_varlen_qk_args *a) { return bwd_varlen_workspace_bytes(a, true); }
+
+int fa_bwd_launch_varlen(const fa_bwd_varlen_args *args, void *stream, float *ms) {
+    if (!args) return fail(FA_ERR_NULL, "null pointer argument");
+    const fa_bwd_varlen_qk_args b = both_sides(args), *a = &b;
+    int rc = bwd_varlen_checks(a, false, "total_tokens", "fa_bwd_varlen_workspace_bytes");
+    if (rc != FA_OK) return rc;
+    if (a->varlen.total_tokens == 0) {
+        if (ms) *ms = 0.0f;
+        return FA_OK;
+    }
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    fa::BwdVarlenQKArgs both;
+    bwd_varlen_fill(both, a);
+    const fa::BwdVarlenArgs va = one_range(both);
+    const hipStream_t s = (hipStream_t)stream;
+    return bwd_run([&] { return fa::bwd_varlen_enqueue(va, a->dtype, a->causal != 0, s); }, s, ms);
+}
+
+int fa_bwd_launch_varlen_qk(const fa_bwd_varlen_qk_args *a, void *stream, float *ms) {
+    int rc = bwd_varlen_checks(a, true, "total_q", "fa_bwd_varlen_qk_workspace_bytes");
+    if (rc != FA_OK) return rc;
+    if (a->varlen.total_tokens == 0 && a->varlen_k.total_tokens == 0) {
+        if (ms) *ms = 0.0f;
+        return FA_OK;
+    }
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    fa::BwdVarlenQKArgs va;
+    bwd_varlen_fill(va, a);
     const hipStream_t s = (hipStream_t)stream;
     return bwd_run([&] { return fa::bwd_varlen_qk_enqueue(va, a->dtype, a->causal != 0, s); }, s, ms);
 }

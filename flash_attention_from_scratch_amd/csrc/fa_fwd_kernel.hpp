@@ -405,11 +405,17 @@ struct FwdTraits {
                                                  : (kPlainBytes > kMergeBytes ? kPlainBytes : kMergeBytes);
 };
 
-// VARLEN (packed variable-length sequences, the training path: fa_fwd_launch_varlen): fa_fwd_kernel_varlen is the body of
-// fa_fwd_kernel whose workgroup finds its sequence's first row and length in cu_seqlens on the device, addresses K / V with a
-// head count and strides of their own (grouped-query attention) and also writes the row log-sum-exp.  Only fa_inst_varlen.hip
-// defines FA_KERNEL_VARLEN, and gets that kernel INSTEAD of fa_fwd_kernel (MASK forms only): the product's kernels keep their
-// names and, compiled from the same text, their code.  FA_KV_SS32 is the K / V seq stride in the body.
+// VARLEN (packed variable-length sequences, the training path: fa_fwd_launch_varlen, fa_fwd_launch_varlen_qk):
+// fa_fwd_kernel_varlen is the body of fa_fwd_kernel whose workgroup finds its sequence's rows in cu_seqlens on the device,
+// addresses K / V with a head count and strides of their own (grouped-query attention) and also writes the row log-sum-exp.
+// Only fa_inst_varlen.hip defines FA_KERNEL_VARLEN, and gets that kernel INSTEAD of fa_fwd_kernel (MASK forms only): the
+// product's kernels keep their names and, compiled from the same text, their code.  FA_KV_SS32 is the K / V seq stride in
+// the body.
+// Sequence i owns query rows cu_seqlens[i] .. of q / o / lse (the range KernelArgsVarlen describes) and key rows
+// cu_seqlens_k[i] .. of k / v; each range is clamped against its own total and max_seqlen (first row in [0, total], length in
+// [0, min(max_seqlen, what is left)]).  The causal diagonal is bottom-right aligned: query r sees keys j <= r + (len_k -
+// len_q) -- FA_SHIFTED(row) is the last key a row sees.  A row that sees no key gives o = 0, lse = -inf.
+// fa_fwd_launch_varlen is the launch whose two ranges are one.
 struct KernelArgsVarlen {
     KernelArgs base;             // q, k, v, o; Q's and O's seq (token) and head strides; n_heads; n_bh = n_seqs * n_heads;
                                  // n_q_blocks = ceil(max_seqlen / B_r); causal.  batch_stride, seq_len, n_kv_blocks: unused
@@ -419,36 +425,26 @@ struct KernelArgsVarlen {
     int32_t group;               // query heads per K / V head
     int32_t total_tokens, max_seqlen;
 };
-typedef void (*kernel_fn_varlen)(const KernelArgsVarlen);
-// VARLEN_QK (separate Q and K / V lengths: fa_fwd_launch_varlen_qk): fa_fwd_kernel_varlen_qk is the varlen body with a second
-// range.  Sequence i owns query rows cu_seqlens[i] .. of q / o / lse (the range KernelArgsVarlen describes) and key rows
-// cu_seqlens_k[i] .. of k / v; both ranges are clamped by the one rule above.  The causal diagonal is bottom-right aligned:
-// query r sees keys j <= r + (len_k - len_q) -- FA_SHIFTED(row) is the last key a row sees.  A row that sees no key gives
-// o = 0, lse = -inf.  Only fa_inst_varlen_qk.hip defines FA_KERNEL_VARLEN_QK, and gets that kernel INSTEAD of the other two.
 struct KernelArgsVarlenQK {
     KernelArgsVarlen v;            // cu_seqlens, total_tokens, max_seqlen: the QUERY side; n_q_blocks = ceil(max_seqlen_q / B_r)
     const int32_t *cu_seqlens_k;   // n_seqs + 1 row offsets of k / v (DEVICE)
     int32_t total_k, max_seqlen_k;
 };
-typedef void (*kernel_fn_varlen_qk)(const KernelArgsVarlenQK);
-#ifdef FA_KERNEL_VARLEN_QK
-#define FA_KERNEL_VARLEN
-#define FA_Q_LEN q_len
-#define FA_Q_LEN_END q_len_v
-#define FA_SHIFTED(row) ((row) + kq_shift)
-#else
-#define FA_Q_LEN S_len
-#define FA_Q_LEN_END S_len
-#define FA_SHIFTED(row) (row)
-#endif
+typedef void (*kernel_fn_varlen)(const KernelArgsVarlenQK);
 #ifdef FA_KERNEL_VARLEN
 #define FA_KV_SS32 kv_ss
 #define FA_SEQ_LEN v_seq_len
 #define FA_N_KV_BLOCKS ((v_seq_len + BC - 1) / BC)
+#define FA_Q_LEN q_len
+#define FA_Q_LEN_END q_len_v
+#define FA_SHIFTED(row) ((row) + kq_shift)
 #else
 #define FA_KV_SS32 ss
 #define FA_SEQ_LEN args.seq_len
 #define FA_N_KV_BLOCKS args.n_kv_blocks
+#define FA_Q_LEN S_len
+#define FA_Q_LEN_END S_len
+#define FA_SHIFTED(row) (row)
 #endif
 
 // ---------------------------------------------------------------------------------
@@ -469,17 +465,12 @@ typedef void (*kernel_fn_varlen_qk)(const KernelArgsVarlenQK);
 template <int DT, int QT, int NWAVES, int BC, bool SWZ, bool EAGER, bool OPT, bool PIPE, bool DMA = true,
           bool MASK = false, int D = 128, int ABL = 0, int KSPLIT = 1>
 __global__ void
-#if defined(FA_KERNEL_VARLEN_QK)
-__launch_bounds__(NWAVES * 64, 1)
-fa_fwd_kernel_varlen_qk(const KernelArgsVarlenQK qa) {
-    static_assert(MASK && DMA && KSPLIT == 1 && ABL == 0 && QT == 1, "the varlen form is the masked LDS-DMA kernel");
-    const KernelArgsVarlen &va = qa.v;  // (the query side)
-    const KernelArgs &args = va.base;
-#elif defined(FA_KERNEL_VARLEN)
+#ifdef FA_KERNEL_VARLEN
 // (one workgroup per SIMD set: with m live up to the LSE store the 256-register budget of two waves per SIMD spills)
 __launch_bounds__(NWAVES * 64, 1)
-fa_fwd_kernel_varlen(const KernelArgsVarlen va) {
-    static_assert(MASK && DMA && KSPLIT == 1 && ABL == 0, "the varlen form is the masked LDS-DMA kernel");
+fa_fwd_kernel_varlen(const KernelArgsVarlenQK qa) {
+    static_assert(MASK && DMA && KSPLIT == 1 && ABL == 0 && QT == 1, "the varlen form is the masked LDS-DMA kernel");
+    const KernelArgsVarlen &va = qa.v;  // (the query side)
     const KernelArgs &args = va.base;   // (seq_len and n_kv_blocks are the sequence's: FA_SEQ_LEN, FA_N_KV_BLOCKS)
 #else
 __launch_bounds__(NWAVES * 64, (QT == 1) ? 2 : 1)
@@ -553,7 +544,6 @@ fa_fwd_kernel(const KernelArgs args) {
         v_len = v_len < 0 ? 0 : (v_len > cap ? cap : v_len);
     }
     if ((int64_t)qb * TR::kBr >= v_len) return;   // (workgroup-uniform; before any barrier or DMA)
-#ifdef FA_KERNEL_VARLEN_QK
     // ... and its key rows from cu_seqlens_k, by the same rule against total_k and max_seqlen_k
     const int q_len = (int)v_len;
     int64_t k_row0 = qa.cu_seqlens_k[b], k_len = qa.cu_seqlens_k[b + 1];
@@ -569,10 +559,6 @@ fa_fwd_kernel(const KernelArgs args) {
     // as a scalar it is spilled to a lane and back; 372 of 512 vector registers are in use)
     int q_len_v;
     asm("v_mov_b32 %0, %1" : "=v"(q_len_v) : "s"(q_len));
-#else
-    const int64_t k_row0 = v_row0;
-    const int v_seq_len = (int)v_len;
-#endif
     const int64_t kv_ss = va.kv_seq_stride;
     const int64_t head_off = v_row0 * ss + (int64_t)h * args.head_stride;
     const int64_t kv_head_off = k_row0 * kv_ss + (int64_t)(h / va.group) * va.kv_head_stride;
@@ -610,7 +596,7 @@ fa_fwd_kernel(const KernelArgs args) {
     int n_kv_ = FA_N_KV_BLOCKS;
     if (MASK && args.causal) {
         const int last_row = (wg_row0 + TR::kBr < FA_Q_LEN ? wg_row0 + TR::kBr : FA_Q_LEN) - 1;
-#ifdef FA_KERNEL_VARLEN_QK
+#ifdef FA_KERNEL_VARLEN
         const int need = FA_SHIFTED(last_row) < 0 ? 0 : FA_SHIFTED(last_row) / BC + 1;   // (no key at all: len_q - len_k rows or more above)
 #else
         const int need = last_row / BC + 1;
@@ -618,7 +604,7 @@ fa_fwd_kernel(const KernelArgs args) {
         n_kv_ = need < n_kv_ ? need : n_kv_;
     }
     const int n_kv = n_kv_;
-#ifdef FA_KERNEL_VARLEN_QK
+#ifdef FA_KERNEL_VARLEN
     if (n_kv == 0) {
         // no tile to visit (len_k = 0, or causal rows that all lie above the shifted diagonal): o = 0 and lse = -inf for the
         // workgroup's valid rows, whole 256-B rows as the epilogue stores them.  Workgroup-uniform, before any DMA or barrier.
@@ -1285,7 +1271,7 @@ fa_fwd_kernel(const KernelArgs args) {
         char *stage_o = smem + wave_r * (TR::kRowsPerWave * ROWB);
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
-#ifdef FA_KERNEL_VARLEN_QK
+#ifdef FA_KERNEL_VARLEN
             const float l_all = pair_sum(l[qt]);
             const float inv = l_all == 0.0f ? 0.0f : 1.0f / l_all;   // a row that saw no key: o = 0, not 0 / 0
 #else

@@ -1,9 +1,9 @@
-// fa_inst_varlen.hip -- the forward over packed variable-length sequences (fa_fwd_kernel_varlen; fa_fwd_launch_varlen), one
-// translation unit per dtype (-DFA_INST_DT=<5|15>).  FA_KERNEL_VARLEN makes fa_fwd_kernel.hpp define fa_fwd_kernel_varlen from
-// the body of fa_fwd_kernel (which this unit then does not have): the masked 32-rows-per-wave kernel at the
-// (B_r 128, B_c 64, 4 warps) + buffer shape, with and without the first-block skip -- the twins of the two masked entries of
-// that shape.  Compiled with the flags of the slice that builds those entries, so that one contraction pattern gives one
-// set of bits.  Not in the registry, like fa_inst_lse.hip.
+// fa_inst_varlen.hip -- the forward over packed variable-length sequences (fa_fwd_kernel_varlen; fa_fwd_launch_varlen,
+// fa_fwd_launch_varlen_qk), one translation unit per dtype (-DFA_INST_DT=<5|15>).  FA_KERNEL_VARLEN makes fa_fwd_kernel.hpp
+// define fa_fwd_kernel_varlen from the body of fa_fwd_kernel (which this unit then does not have): the masked
+// 32-rows-per-wave kernel at the (B_r 128, B_c 64, 4 warps) + buffer shape, with and without the first-block skip -- the twins
+// of the two masked entries of that shape.  Compiled with the flags of the slice that builds those entries, so that one
+// contraction pattern gives one set of bits.  Not in the registry, like fa_inst_lse.hip.
 #define FA_KERNEL_VARLEN
 #include "fa_fwd_kernel.hpp"
 

@@ -336,6 +336,15 @@ def _check_varlen(q, k, v, cu_seqlens, max_seqlen, others=(), cu_seqlens_k=None,
             raise RuntimeError("max_seqlen_k must be a Python int (a bound on every sequence's K / V length; the device is not asked)")
 
 
+def _varlen_layouts(q, k, cu_seqlens, max_seqlen, cu_seqlens_k, max_seqlen_k):
+    """-> the launch's fa_varlen_layout(s): one for Q and K / V, or with the key side given (query side, key side)"""
+    n_seqs = cu_seqlens.numel() - 1
+    if cu_seqlens_k is None:
+        return (_capi.make_varlen_layout(cu_seqlens.data_ptr(), n_seqs, q.shape[0], max_seqlen),)
+    return (_capi.make_varlen_layout(cu_seqlens.data_ptr(), n_seqs, q.shape[0], max(max_seqlen, 1)),   # (a bound of 0: nothing but empties)
+            _capi.make_varlen_layout(cu_seqlens_k.data_ptr(), n_seqs, k.shape[0], max(max_seqlen_k, 1)))
+
+
 def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None):
     """Attention over packed sequences with the row log-sum-exp (fa_fwd_launch_varlen): q (total_tokens, n_heads, 128), k and v
     (total_tokens, n_kv_heads, 128), cu_seqlens an int32 device tensor of n_seqs + 1 row offsets, max_seqlen a Python int.
@@ -346,11 +355,10 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
     and max_seqlen are then Q's -- q is (total_q, n_heads, 128), lse (n_heads, total_q) -- and k, v are (total_k, n_kv_heads, 128)
     with sequence i's keys at rows cu_seqlens_k[i] .. cu_seqlens_k[i + 1] - 1.  Any lengths >= 0 on either side.  causal is then
     BOTTOM-RIGHT aligned, as in forward_kvcache and flash-attn: query r of a sequence sees keys j <= r + (len_k - len_q).  A row
-    that sees no key (len_k = 0; causal rows r < len_q - len_k) gives o = 0 and lse = -inf.  Left at None: today's call, same
-    kernels, same bits."""
-    if _qk_sides(cu_seqlens_k, max_seqlen_k):
-        return _forward_varlen_qk(q, k, v, cu_seqlens, cu_seqlens_k, max_seqlen, max_seqlen_k, causal, timed)
-    _check_varlen(q, k, v, cu_seqlens, max_seqlen)
+    that sees no key (len_k = 0; causal rows r < len_q - len_k) gives o = 0 and lse = -inf.  Left at None: k and v share
+    cu_seqlens and max_seqlen (the same kernel with one range for both sides)."""
+    qk = _qk_sides(cu_seqlens_k, max_seqlen_k)
+    _check_varlen(q, k, v, cu_seqlens, max_seqlen, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
     total, n_heads, d_head = q.shape
     lib = _capi.load()
     cfg = _capi.make_config(varlen_config(q.dtype))
@@ -361,76 +369,15 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
     args = _capi.FaFwdArgs(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), o=o.data_ptr(), batch=1, seq_len=total, n_heads=n_heads,
                            d_head=d_head, batch_stride=0, seq_stride=q.stride(0), head_stride=q.stride(1), cfg=cfg)
     kv = _capi.make_kv_layout(k.shape[1], 0, k.stride(0), k.stride(1))
-    vl = _capi.make_varlen_layout(cu_seqlens.data_ptr(), cu_seqlens.numel() - 1, total, max_seqlen)
+    sides = _varlen_layouts(q, k, cu_seqlens, max_seqlen, cu_seqlens_k, max_seqlen_k)
     ms = ctypes.c_float(0.0)
     opts = _capi.make_opts(causal=causal, ms=ms if timed else None)
     with torch.cuda.device(q.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        _capi.check(lib.fa_fwd_launch_varlen(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(vl), ctypes.byref(opts),
-                                             ctypes.c_void_p(lse.data_ptr()), stream))
+        launch = lib.fa_fwd_launch_varlen_qk if qk else lib.fa_fwd_launch_varlen
+        _capi.check(launch(ctypes.byref(args), ctypes.byref(kv), *(ctypes.byref(s) for s in sides), ctypes.byref(opts),
+                           ctypes.c_void_p(lse.data_ptr()), stream))
     return (o, lse, float(ms.value)) if timed else (o, lse)
-
-
-def _forward_varlen_qk(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, timed):
-    _check_varlen(q, k, v, cu_seqlens_q, max_seqlen_q, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
-    total, n_heads, d_head = q.shape
-    lib = _capi.load()
-    cfg = _capi.make_config(varlen_config(q.dtype))
-    o = torch.empty((total, n_heads, d_head), dtype=q.dtype, device=q.device)
-    lse = torch.empty((n_heads, total), dtype=torch.float32, device=q.device)
-    if q.stride() != o.stride():   # (the launch has one stride set for q and o)
-        q = q.contiguous()
-    args = _capi.FaFwdArgs(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), o=o.data_ptr(), batch=1, seq_len=total, n_heads=n_heads,
-                           d_head=d_head, batch_stride=0, seq_stride=q.stride(0), head_stride=q.stride(1), cfg=cfg)
-    kv = _capi.make_kv_layout(k.shape[1], 0, k.stride(0), k.stride(1))
-    n_seqs = cu_seqlens_q.numel() - 1
-    vq = _capi.make_varlen_layout(cu_seqlens_q.data_ptr(), n_seqs, total, max(max_seqlen_q, 1))   # (a bound of 0: nothing but empties)
-    vk = _capi.make_varlen_layout(cu_seqlens_k.data_ptr(), n_seqs, k.shape[0], max(max_seqlen_k, 1))
-    ms = ctypes.c_float(0.0)
-    opts = _capi.make_opts(causal=causal, ms=ms if timed else None)
-    with torch.cuda.device(q.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        _capi.check(lib.fa_fwd_launch_varlen_qk(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(vq), ctypes.byref(vk), ctypes.byref(opts),
-                                                ctypes.c_void_p(lse.data_ptr()), stream))
-    return (o, lse, float(ms.value)) if timed else (o, lse)
-
-
-def _backward_varlen_qk(q, k, v, o, lse, dout, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, timed):
-    _check_varlen(q, k, v, cu_seqlens_q, max_seqlen_q, others=((o, "o"), (dout, "dout"), (lse, "lse")),
-                  cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
-    total, n_heads, d_head = q.shape
-    total_k, n_kv = k.shape[0], k.shape[1]
-    if o.shape != q.shape or dout.shape != q.shape:
-        raise RuntimeError("q, o and dout must have one shape (total_q, n_heads, d_head)")
-    if lse.dtype != torch.float32 or tuple(lse.shape) != (n_heads, total) or not lse.is_contiguous():
-        raise RuntimeError("lse must be a contiguous fp32 (n_heads, total_q) tensor")
-    o, dout = o.contiguous(), dout.contiguous()
-    dq = torch.empty_like(o)
-    dk = torch.empty((total_k, n_kv, d_head), dtype=q.dtype, device=q.device)
-    dv = torch.empty_like(dk)
-    lib = _capi.load()
-    n_seqs = cu_seqlens_q.numel() - 1
-    args = _capi.FaBwdVarlenQKArgs(
-        struct_size=ctypes.sizeof(_capi.FaBwdVarlenQKArgs),
-        q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), o=o.data_ptr(), dout=dout.data_ptr(),
-        lse=ctypes.cast(ctypes.c_void_p(lse.data_ptr()), ctypes.POINTER(ctypes.c_float)),
-        dq=dq.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), workspace=16,
-        n_heads=n_heads, n_kv_heads=n_kv, d_head=d_head,
-        q_seq_stride=q.stride(0), q_head_stride=q.stride(1), out_seq_stride=o.stride(0), out_head_stride=o.stride(1),
-        kv_seq_stride=k.stride(0), kv_head_stride=k.stride(1), dkv_seq_stride=dk.stride(0), dkv_head_stride=dk.stride(1),
-        dtype=15 if q.dtype == torch.bfloat16 else 5, causal=1 if causal else 0,
-        varlen=_capi.make_varlen_layout(cu_seqlens_q.data_ptr(), n_seqs, total, max(max_seqlen_q, 1)),
-        varlen_k=_capi.make_varlen_layout(cu_seqlens_k.data_ptr(), n_seqs, total_k, max(max_seqlen_k, 1)),
-    )
-    nbytes = lib.fa_bwd_varlen_qk_workspace_bytes(ctypes.byref(args))
-    _capi.check(nbytes if nbytes < 0 else 0)
-    with torch.cuda.device(q.device):
-        workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)   # (on the current stream's allocator)
-        args.workspace = workspace.data_ptr()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        ms = ctypes.c_float(0.0)
-        _capi.check(lib.fa_bwd_launch_varlen_qk(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
-    return (dq, dk, dv, float(ms.value)) if timed else (dq, dk, dv)
 
 
 def backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None):
@@ -441,38 +388,45 @@ def backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=False,
     cu_seqlens_k / max_seqlen_k (both or neither, else ValueError): separate K / V lengths as in forward_varlen
     (fa_bwd_launch_varlen_qk), causal bottom-right aligned.  A row that saw no key (lse = -inf) gets dq = 0; a key no query
     sees (len_q = 0: under the bottom-right mask the last row sees every key) gets dk = dv = 0, written."""
-    if _qk_sides(cu_seqlens_k, max_seqlen_k):
-        return _backward_varlen_qk(q, k, v, o, lse, dout, cu_seqlens, cu_seqlens_k, max_seqlen, max_seqlen_k, causal, timed)
-    _check_varlen(q, k, v, cu_seqlens, max_seqlen, others=((o, "o"), (dout, "dout"), (lse, "lse")))
+    qk = _qk_sides(cu_seqlens_k, max_seqlen_k)
+    _check_varlen(q, k, v, cu_seqlens, max_seqlen, others=((o, "o"), (dout, "dout"), (lse, "lse")),
+                  cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
     total, n_heads, d_head = q.shape
-    n_kv = k.shape[1]
+    total_k, n_kv = k.shape[0], k.shape[1]
+    total_name = "total_q" if qk else "total_tokens"
     if o.shape != q.shape or dout.shape != q.shape:
-        raise RuntimeError("q, o and dout must have one shape (total_tokens, n_heads, d_head)")
+        raise RuntimeError(f"q, o and dout must have one shape ({total_name}, n_heads, d_head)")
     if lse.dtype != torch.float32 or tuple(lse.shape) != (n_heads, total) or not lse.is_contiguous():
-        raise RuntimeError("lse must be a contiguous fp32 (n_heads, total_tokens) tensor")
+        raise RuntimeError(f"lse must be a contiguous fp32 (n_heads, {total_name}) tensor")
     o, dout = o.contiguous(), dout.contiguous()
     dq = torch.empty_like(o)
-    dk = torch.empty((total, n_kv, d_head), dtype=q.dtype, device=q.device)
+    dk = torch.empty((total_k, n_kv, d_head), dtype=q.dtype, device=q.device)
     dv = torch.empty_like(dk)
     lib = _capi.load()
-    args = _capi.FaBwdVarlenArgs(
+    sides = _varlen_layouts(q, k, cu_seqlens, max_seqlen, cu_seqlens_k, max_seqlen_k)
+    fields = dict(
         q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), o=o.data_ptr(), dout=dout.data_ptr(),
         lse=ctypes.cast(ctypes.c_void_p(lse.data_ptr()), ctypes.POINTER(ctypes.c_float)),
         dq=dq.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), workspace=16,
         n_heads=n_heads, n_kv_heads=n_kv, d_head=d_head,
         q_seq_stride=q.stride(0), q_head_stride=q.stride(1), out_seq_stride=o.stride(0), out_head_stride=o.stride(1),
         kv_seq_stride=k.stride(0), kv_head_stride=k.stride(1), dkv_seq_stride=dk.stride(0), dkv_head_stride=dk.stride(1),
-        dtype=15 if q.dtype == torch.bfloat16 else 5, causal=1 if causal else 0,
-        varlen=_capi.make_varlen_layout(cu_seqlens.data_ptr(), cu_seqlens.numel() - 1, total, max_seqlen),
+        dtype=15 if q.dtype == torch.bfloat16 else 5, causal=1 if causal else 0, varlen=sides[0],
     )
-    nbytes = lib.fa_bwd_varlen_workspace_bytes(ctypes.byref(args))
+    if qk:
+        args = _capi.FaBwdVarlenQKArgs(struct_size=ctypes.sizeof(_capi.FaBwdVarlenQKArgs), varlen_k=sides[1], **fields)
+        workspace_bytes, launch = lib.fa_bwd_varlen_qk_workspace_bytes, lib.fa_bwd_launch_varlen_qk
+    else:
+        args = _capi.FaBwdVarlenArgs(**fields)
+        workspace_bytes, launch = lib.fa_bwd_varlen_workspace_bytes, lib.fa_bwd_launch_varlen
+    nbytes = workspace_bytes(ctypes.byref(args))
     _capi.check(nbytes if nbytes < 0 else 0)
     with torch.cuda.device(q.device):
         workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)   # (on the current stream's allocator)
         args.workspace = workspace.data_ptr()
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
         ms = ctypes.c_float(0.0)
-        _capi.check(lib.fa_bwd_launch_varlen(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
+        _capi.check(launch(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
     return (dq, dk, dv, float(ms.value)) if timed else (dq, dk, dv)
 
 

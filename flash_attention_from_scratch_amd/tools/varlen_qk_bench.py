@@ -1,8 +1,10 @@
 """Packed sequences with separate Q and K / V lengths, timing (the sibling of varlen_bench.py).  One JSON line per case; all arms
 of a case alternate in one process, event-timed medians after two warm-up rounds:
-  - "parity":  equal sides through the new entry points against forward_varlen / backward_varlen on the same tensors -- the
-               uniform 16 x 4096 batch and varlen_bench.py's mixed batch.  The existing arm runs TWICE per round; the spread
-               between its two medians is the margin the new / existing ratio is read against (`*_margin`).
+  - "parity":  the backward on equal sides with the key side given (the two-range kernels) against backward_varlen without it
+               (the one-range kernels) on the same tensors -- the uniform 16 x 4096 batch and varlen_bench.py's mixed batch.
+               The arm without the key side runs TWICE per round; the spread between its two medians is the margin the
+               ratio is read against (`bwd_margin`).  The forward is one kernel either way and is not timed here
+               (profiles/training/varlen_fold_parity_bf16.jsonl: the run, forward included, on which it was folded).
   - "prefill": chunked prefill, len_q in {512, 2048} against len_k in {8192, 32768}, causal (bottom-right), batch 8, H / Hkv =
                32 / 8 and 16 / 16: ms and useful TFLOP/s on the shifted-causal FLOP count (4 d per visible (query, key) pair
                forward, 10 d backward), forward and forward + backward.
@@ -50,24 +52,21 @@ def parity(case, lengths, H, Hkv, causal, dtype, reps):
     T, m = sum(lengths), max(lengths)
     q, k, v, dout = _tensors(T, T, H, Hkv, dtype)
     cu, cuk = _cu(lengths), _cu(lengths)
-    t = {name: [] for name in ("fwd_old_a", "fwd_new", "fwd_old_b", "bwd_old_a", "bwd_new", "bwd_old_b")}
+    t = {name: [] for name in ("bwd_old_a", "bwd_new", "bwd_old_b")}
+    o, lse = flash_attention.forward_varlen(q, k, v, cu, m, causal=causal)
     for i in range(reps + 2):
-        o, lse, f0 = flash_attention.forward_varlen(q, k, v, cu, m, causal=causal, timed=True)
-        o2, lse2, f1 = flash_attention.forward_varlen(q, k, v, cu, m, causal=causal, timed=True, cu_seqlens_k=cuk, max_seqlen_k=m)
-        *_, f2 = flash_attention.forward_varlen(q, k, v, cu, m, causal=causal, timed=True)
         *_, b0 = flash_attention.backward_varlen(q, k, v, o, lse, dout, cu, m, causal=causal, timed=True)
-        *_, b1 = flash_attention.backward_varlen(q, k, v, o2, lse2, dout, cu, m, causal=causal, timed=True, cu_seqlens_k=cuk, max_seqlen_k=m)
+        *_, b1 = flash_attention.backward_varlen(q, k, v, o, lse, dout, cu, m, causal=causal, timed=True, cu_seqlens_k=cuk, max_seqlen_k=m)
         *_, b2 = flash_attention.backward_varlen(q, k, v, o, lse, dout, cu, m, causal=causal, timed=True)
         if i > 1:
-            for name, ms in zip(t, (f0, f1, f2, b0, b1, b2)):
+            for name, ms in zip(t, (b0, b1, b2)):
                 t[name].append(ms)
     med = {name: _median(x) for name, x in t.items()}
     line = {"arm": "parity", "case": case, "n_seqs": len(lengths), "total_tokens": T, "n_heads": H, "n_kv_heads": Hkv,
             "dtype": str(dtype).replace("torch.", ""), "causal": causal, "reps": reps, **{name + "_ms": ms for name, ms in med.items()}}
-    for p in ("fwd", "bwd"):
-        old = 0.5 * (med[p + "_old_a"] + med[p + "_old_b"])
-        line[p + "_new_over_old"] = med[p + "_new"] / old
-        line[p + "_margin"] = abs(med[p + "_old_a"] - med[p + "_old_b"]) / old   # the existing arm against itself
+    old = 0.5 * (med["bwd_old_a"] + med["bwd_old_b"])
+    line["bwd_new_over_old"] = med["bwd_new"] / old
+    line["bwd_margin"] = abs(med["bwd_old_a"] - med["bwd_old_b"]) / old   # the one-range arm against itself
     return line
 
 

@@ -457,13 +457,15 @@ int fa_bwd_launch_varlen(const fa_bwd_varlen_args *args, void *stream, float *ms
  *
  * fa_fwd_launch_varlen_qk / fa_fwd_varlen_qk_supported: the arguments, the served configurations and the refusals of
  * fa_fwd_launch_varlen.  total_q = 0 returns FA_OK without a launch; total_k = 0 with total_q > 0 launches and writes the
- * zeros and -inf.  With varlen_k equal to varlen_q, o and lse are bit-identical to fa_fwd_launch_varlen's.
+ * zeros and -inf.  One kernel serves both: fa_fwd_launch_varlen is this launch with its one layout on both sides, so with
+ * varlen_k equal to varlen_q, o and lse are bit-identical to fa_fwd_launch_varlen's.
  *
  * fa_bwd_varlen_qk_args: the fields of fa_bwd_varlen_args (varlen: the QUERY side) behind a struct_size, and varlen_k.  The
  * dK / dV kernel runs n_seqs * n_kv_heads * split * ceil(max_seqlen_k / 128) workgroups, split by fa_bwd_launch_varlen's rule
  * with max_seqlen_k in place of max_seqlen; partials and their sum run over total_k.  The dQ kernel runs n_seqs * n_heads *
  * ceil(max_seqlen_q / 128) workgroups.  workspace: fa_bwd_varlen_qk_workspace_bytes bytes, 16-byte aligned.  Deterministic;
- * with equal sides dq, dk, dv are bit-identical to fa_bwd_launch_varlen's and the workspace size is the same.
+ * with equal sides dq, dk, dv are bit-identical to fa_bwd_launch_varlen's and the workspace size is the same (kernels of
+ * its own beside fa_bwd_launch_varlen's, which are the faster ones for one range: checks, split and workspace are shared).
  */
 int fa_fwd_varlen_qk_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
 int fa_fwd_launch_varlen_qk(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,

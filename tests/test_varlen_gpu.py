@@ -14,6 +14,8 @@ Against the existing kernels, bit for bit:
     bwd_varlen_split(n_seqs, max_seqlen, ...) == bwd_gqa_split(1, len_i, ...), computed in the test from the workspace sizes.
     The other cases fall under the fp32 rule."""
 import ctypes
+import json
+import os
 
 import pytest
 import torch
@@ -21,6 +23,8 @@ import torch
 import flash_attention
 from flash_attention_from_scratch_amd import _capi
 from flash_attention_from_scratch_amd import flash_attention_kernels as fak
+from flash_attention_from_scratch_amd.tools import record_varlen_bits as rec
+from tests.conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
@@ -28,6 +32,7 @@ DEV = "cuda:0"
 DTYPES = [torch.bfloat16, torch.float16]
 O_TOL = {torch.bfloat16: 2.0 ** -6, torch.float16: 2.0 ** -9}
 H = 4
+HEADS = [(4, 4), (8, 2), (4, 1)]
 LENGTH_SETS = {
     "aligned": ([256, 1024, 512], None),
     "edges": ([1, 63, 64, 65, 127, 129, 257, 1000], None),
@@ -366,3 +371,29 @@ def test_varlen_launches_replay_from_a_graph(dtype):
     torch.cuda.synchronize()
     for x, y in zip((o_e, lse_e) + tuple(g_e), (o_g, lse_g) + tuple(g_g)):
         assert _same(x, y)
+
+
+@pytest.fixture(scope="module")
+def recorded_bits():
+    return json.load(open(os.path.join(GOLDEN, "varlen_equal_sides_bits.json")))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("heads", HEADS)
+@pytest.mark.parametrize("name", list(LENGTH_SETS))
+def test_varlen_reproduces_the_recorded_bits(recorded_bits, dtype, causal, heads, name):
+    """tests/golden/varlen_equal_sides_bits.json: SHA-256 of o, lse, dq, dk, dv as forward_varlen / backward_varlen without the
+    key side gave them before the forward with one range was folded into the forward with two (tools/record_varlen_bits.py;
+    the bits of one hipcc, regenerated with profiles/r06/toolchain.json).  Both spellings of the call reproduce every hash."""
+    lengths, max_seqlen = LENGTH_SETS[name]
+    max_seqlen = max_seqlen or max(lengths)
+    q, k, v, dout = _inputs(lengths, heads[0], heads[1], dtype, seed=recorded_bits["seed"])
+    cu_t, _ = _cu(lengths)
+    want = recorded_bits["cases"][rec.case_id(dtype, causal, heads, name)]
+    for key_side in ({}, dict(cu_seqlens_k=cu_t.clone(), max_seqlen_k=max_seqlen)):
+        o, lse = flash_attention.forward_varlen(q, k, v, cu_t, max_seqlen, causal=causal, **key_side)
+        grads = flash_attention.backward_varlen(q, k, v, o, lse, dout, cu_t, max_seqlen, causal=causal, **key_side)
+        torch.cuda.synchronize()
+        for nm, x in zip(rec.NAMES, (o, lse) + tuple(grads)):
+            assert rec.sha256_of(x) == want[nm], (nm, sorted(key_side))

@@ -293,12 +293,12 @@ def _no_scratch_no_spills(text):
 
 
 def test_varlen_qk_slices_have_mfma_and_no_scratch():
+    """the forward comes from the varlen slice, which serves both entry-point families; the backward has a slice of its own"""
     for dt, mfma in ((15, "v_mfma_f32_32x32x16_bf16"), (5, "v_mfma_f32_32x32x16_f16")):
-        text = _isa(f"varlen_qk_dt{dt}", "fa_inst_varlen_qk")
+        text = _isa(f"varlen_dt{dt}", "fa_inst_varlen")
         assert mfma in text and "ds_read_b64_tr_b16" in text and "global_load_lds_dwordx4" in text
-        # the two forms (with and without the first-block skip) of the new kernel, and neither of the kernels it is built from
-        assert len(re.findall(r"^_ZN2fa23fa_fwd_kernel_varlen_qk\w+:", text, flags=re.M)) == 2
-        assert re.search(r"^_ZN2fa20fa_fwd_kernel_varlenI", text, flags=re.M) is None
+        # the two forms (with and without the first-block skip) of the varlen kernel, and not the kernel it is built from
+        assert len(re.findall(r"^_ZN2fa20fa_fwd_kernel_varlenI\w+:", text, flags=re.M)) == 2
         assert re.search(r"^_ZN2fa13fa_fwd_kernelI", text, flags=re.M) is None
         _no_scratch_no_spills(text)
     text = _isa("bwd_varlen_qk", "fa_bwd_varlen_qk")
