@@ -33,7 +33,9 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_varlen_supported", "fa_fwd_launch_varlen", "fa_bwd_varlen_workspace_bytes", "fa_bwd_launch_varlen",
     "fa_fwd_varlen_qk_supported", "fa_fwd_launch_varlen_qk", "fa_bwd_varlen_qk_workspace_bytes", "fa_bwd_launch_varlen_qk",
     "fa_decode_supported", "fa_decode_num_splits", "fa_decode_workspace_bytes", "fa_decode_launch",
+    "fa_decode_fp8_supported", "fa_decode_fp8_num_splits", "fa_decode_fp8_workspace_bytes", "fa_decode_fp8_launch",
 )
+FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
 FA_ABI_VERSION = 6
 SOFTMAX_MODES = ("eager", "first_block_skip", "lazy", "speculative")  # fa_softmax_mode
@@ -155,6 +157,21 @@ class FaDecodeArgs(ctypes.Structure):   # fa_decode_args (KV-cache decode: conti
 def make_decode_args(**fields):
     """fa_decode_args with struct_size set; d_head defaults to 128, everything not given to 0 / null."""
     a = FaDecodeArgs(struct_size=ctypes.sizeof(FaDecodeArgs), d_head=128)
+    for name, value in fields.items():
+        setattr(a, name, value)
+    return a
+
+
+class FaDecodeFp8Args(ctypes.Structure):   # fa_decode_fp8_args (fa_decode_args' fields, then the fp8 cache's descales and encoding)
+    _fields_ = FaDecodeArgs._fields_ + [
+        ("k_descale", ctypes.c_void_p), ("v_descale", ctypes.c_void_p), ("descale_batch_stride", ctypes.c_int64),
+        ("kv_dtype", ctypes.c_int32),
+    ]
+
+
+def make_decode_fp8_args(**fields):
+    """fa_decode_fp8_args with struct_size set; d_head defaults to 128, kv_dtype to e4m3fn, everything not given to 0 / null."""
+    a = FaDecodeFp8Args(struct_size=ctypes.sizeof(FaDecodeFp8Args), d_head=128, kv_dtype=FA_KV_FP8_E4M3FN)
     for name, value in fields.items():
         setattr(a, name, value)
     return a
@@ -299,6 +316,14 @@ def load():
     lib.fa_decode_workspace_bytes.argtypes = [ctypes.POINTER(FaDecodeArgs)]
     lib.fa_decode_launch.restype = ctypes.c_int
     lib.fa_decode_launch.argtypes = [ctypes.POINTER(FaDecodeArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    lib.fa_decode_fp8_supported.restype = ctypes.c_int
+    lib.fa_decode_fp8_supported.argtypes = [ctypes.POINTER(FaDecodeFp8Args)]
+    lib.fa_decode_fp8_num_splits.restype = ctypes.c_int
+    lib.fa_decode_fp8_num_splits.argtypes = [ctypes.POINTER(FaDecodeFp8Args)]
+    lib.fa_decode_fp8_workspace_bytes.restype = ctypes.c_int64
+    lib.fa_decode_fp8_workspace_bytes.argtypes = [ctypes.POINTER(FaDecodeFp8Args)]
+    lib.fa_decode_fp8_launch.restype = ctypes.c_int
+    lib.fa_decode_fp8_launch.argtypes = [ctypes.POINTER(FaDecodeFp8Args), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p
     lib.fa_last_error.argtypes = []
     lib.fa_version.restype = ctypes.c_char_p

@@ -21,6 +21,7 @@
 #include "fa_bwd_varlen.hpp"
 #include "fa_bwd_varlen_qk.hpp"
 #include "fa_decode_kernel.hpp"
+#include "fa_decode_fp8_kernel.hpp"
 #include "fa_registry.hpp"
 
 extern "C" {
@@ -1316,6 +1317,63 @@ int64_t decode_splits(const fa_decode_args *a) {
 int64_t decode_part_o_bytes(const fa_decode_args *a, int64_t splits) {
     return (int64_t)sizeof(float) * splits * a->batch * a->n_kv_heads * (a->seqlen_q * (a->n_heads / a->n_kv_heads)) * 128;
 }
+
+// the kernels' arguments from validated ones
+void decode_fill(fa::DecodeArgs &d, const fa_decode_args *a, int64_t splits) {
+    d.q = (const uint16_t *)a->q;
+    d.k = (const uint16_t *)a->k;
+    d.v = (const uint16_t *)a->v;
+    d.o = (uint16_t *)a->o;
+    d.lse = a->lse;
+    d.cache_seqlens = a->cache_seqlens;
+    d.block_table = a->block_table;
+    d.part_o = splits > 1 ? (float *)a->workspace : nullptr;
+    d.part_lse = splits > 1 ? (float *)((char *)a->workspace + decode_part_o_bytes(a, splits)) : nullptr;
+    d.q_bs = a->q_batch_stride;
+    d.q_ss = a->q_seq_stride;
+    d.q_hs = a->q_head_stride;
+    d.o_bs = a->o_batch_stride;
+    d.o_ss = a->o_seq_stride;
+    d.o_hs = a->o_head_stride;
+    d.kv_bs = a->kv_batch_stride;
+    d.kv_ss = a->kv_seq_stride;
+    d.kv_hs = a->kv_head_stride;
+    d.bt_bs = a->block_table ? a->block_table_stride : 0;
+    d.batch = (int32_t)a->batch;
+    d.seqlen_q = (int32_t)a->seqlen_q;
+    d.n_heads = (int32_t)a->n_heads;
+    d.n_kv_heads = (int32_t)a->n_kv_heads;
+    d.group = (int32_t)(a->n_heads / a->n_kv_heads);
+    d.rows = d.seqlen_q * d.group;
+    d.max_len = (int32_t)decode_capacity(a);
+    d.page_size = a->block_table ? (int32_t)a->page_size : 0;
+    d.num_pages = a->block_table ? (int32_t)a->num_pages : 0;
+    d.num_splits = (int32_t)splits;
+    d.causal = a->causal != 0;
+}
+
+// ---- ... against an fp8 cache: fa_decode_args' leading fields, validated as such, and the fp8 rules ------------------------
+static_assert(offsetof(fa_decode_fp8_args, kv_head_stride) == offsetof(fa_decode_args, kv_head_stride) &&
+              offsetof(fa_decode_fp8_args, k_descale) == sizeof(fa_decode_args), "fa_decode_fp8_args begins with fa_decode_args' fields");
+
+int decode_fp8_validate(const fa_decode_fp8_args *a, fa_decode_args *base) {
+    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
+    if (a->struct_size < sizeof(fa_decode_fp8_args))
+        return fail(FA_ERR_SHAPE, "fa_decode_fp8_args.struct_size (%u) is smaller than this library's (%zu)", a->struct_size,
+                    sizeof(fa_decode_fp8_args));
+    if (a->kv_dtype != FA_KV_FP8_E4M3FN)
+        return fail(FA_ERR_DTYPE, "kv_dtype (%d) is not served: the fp8 cache is e4m3fn (FA_KV_FP8_E4M3FN)", a->kv_dtype);
+    memcpy(base, a, sizeof(fa_decode_args));
+    base->struct_size = sizeof(fa_decode_args);
+    const int rc = decode_validate(base);
+    if (rc != FA_OK) return rc;
+    if ((a->k_descale || a->v_descale) && a->descale_batch_stride < a->n_kv_heads)
+        return fail(FA_ERR_SHAPE, "descale_batch_stride (%lld) is smaller than n_kv_heads (%lld)", (long long)a->descale_batch_stride,
+                    (long long)a->n_kv_heads);
+    if ((a->kv_batch_stride | a->kv_seq_stride | a->kv_head_stride) & 15)
+        return fail(FA_ERR_ALIGN, "kv strides of an fp8 cache must be multiples of 16 bytes");
+    return FA_OK;
+}
 }  // namespace
 
 int fa_decode_supported(const fa_decode_args *a) { return decode_validate(a) == FA_OK ? 1 : 0; }
@@ -1354,38 +1412,56 @@ int fa_decode_launch(const fa_decode_args *a, void *stream, float *ms) {
     DeviceState *dev = current_device(&rc);
     if (!dev) return rc;
     fa::DecodeArgs d;
-    d.q = (const uint16_t *)a->q;
-    d.k = (const uint16_t *)a->k;
-    d.v = (const uint16_t *)a->v;
-    d.o = (uint16_t *)a->o;
-    d.lse = a->lse;
-    d.cache_seqlens = a->cache_seqlens;
-    d.block_table = a->block_table;
-    d.part_o = splits > 1 ? (float *)a->workspace : nullptr;
-    d.part_lse = splits > 1 ? (float *)((char *)a->workspace + decode_part_o_bytes(a, splits)) : nullptr;
-    d.q_bs = a->q_batch_stride;
-    d.q_ss = a->q_seq_stride;
-    d.q_hs = a->q_head_stride;
-    d.o_bs = a->o_batch_stride;
-    d.o_ss = a->o_seq_stride;
-    d.o_hs = a->o_head_stride;
-    d.kv_bs = a->kv_batch_stride;
-    d.kv_ss = a->kv_seq_stride;
-    d.kv_hs = a->kv_head_stride;
-    d.bt_bs = a->block_table ? a->block_table_stride : 0;
-    d.batch = (int32_t)a->batch;
-    d.seqlen_q = (int32_t)a->seqlen_q;
-    d.n_heads = (int32_t)a->n_heads;
-    d.n_kv_heads = (int32_t)a->n_kv_heads;
-    d.group = (int32_t)(a->n_heads / a->n_kv_heads);
-    d.rows = d.seqlen_q * d.group;
-    d.max_len = (int32_t)decode_capacity(a);
-    d.page_size = a->block_table ? (int32_t)a->page_size : 0;
-    d.num_pages = a->block_table ? (int32_t)a->num_pages : 0;
-    d.num_splits = (int32_t)splits;
-    d.causal = a->causal != 0;
+    decode_fill(d, a, splits);
     const hipStream_t s = (hipStream_t)stream;
     return bwd_run([&] { return fa::decode_enqueue(d, a->dtype, s); }, s, ms);
+}
+
+int fa_decode_fp8_supported(const fa_decode_fp8_args *a) {
+    fa_decode_args base;
+    return decode_fp8_validate(a, &base) == FA_OK ? 1 : 0;
+}
+
+int fa_decode_fp8_num_splits(const fa_decode_fp8_args *a) {
+    fa_decode_args base;
+    const int rc = decode_fp8_validate(a, &base);
+    return rc != FA_OK ? rc : (int)decode_splits(&base);
+}
+
+int64_t fa_decode_fp8_workspace_bytes(const fa_decode_fp8_args *a) {
+    fa_decode_args base;
+    const int rc = decode_fp8_validate(a, &base);
+    return rc != FA_OK ? rc : fa_decode_workspace_bytes(&base);
+}
+
+int fa_decode_fp8_launch(const fa_decode_fp8_args *a, void *stream, float *ms) {
+    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
+    if (!a->q || !a->k || !a->v || !a->o) return fail(FA_ERR_NULL, "null tensor pointer (q, k, v and o are all needed)");
+    if (!a->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to batch int32 lengths is needed");
+    fa_decode_args base;
+    int rc = decode_fp8_validate(a, &base);
+    if (rc != FA_OK) return rc;
+    if (a->batch == 0) {
+        if (ms) *ms = 0.0f;
+        return FA_OK;
+    }
+    const int64_t splits = decode_splits(&base);
+    if (splits > 1 && !a->workspace)
+        return fail(FA_ERR_NULL, "workspace is null: allocate fa_decode_fp8_workspace_bytes(args) bytes of device memory");
+    if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) & 15) return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
+    if (((uintptr_t)a->cache_seqlens | (uintptr_t)a->block_table | (uintptr_t)a->lse) & 3)
+        return fail(FA_ERR_ALIGN, "cache_seqlens, block_table and lse must be 4-byte aligned");
+    if (((uintptr_t)a->k_descale | (uintptr_t)a->v_descale) & 3) return fail(FA_ERR_ALIGN, "k_descale and v_descale must be 4-byte aligned");
+    if (splits > 1 && ((uintptr_t)a->workspace & 15)) return fail(FA_ERR_ALIGN, "workspace must be 16-byte aligned (it holds the splits' fp32 partials)");
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    fa::DecodeFp8Args d;
+    decode_fill(d.d, &base, splits);
+    d.k_descale = a->k_descale;
+    d.v_descale = a->v_descale;
+    d.ds_bs = a->descale_batch_stride;
+    const hipStream_t s = (hipStream_t)stream;
+    return bwd_run([&] { return fa::decode_fp8_enqueue(d, a->dtype, s); }, s, ms);
 }
 
 static void add_slot(const AdaptiveState &ad, int idx, fa_adaptive_info *out) {

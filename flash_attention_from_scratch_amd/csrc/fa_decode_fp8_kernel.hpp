@@ -1,0 +1,297 @@
+// fa_decode_fp8_kernel.hpp -- the decode path of fa_decode_kernel.hpp against an fp8 (OCP e4m3fn) K / V cache with one fp32
+// descale per (batch entry, K / V head) and tensor.  Q, O, the partials and the combine kernel are the 16-bit
+// path's; so are the grid, the four waves, the row packing, the split of the key tiles, the clamping and the merge of the waves.
+// What differs:
+//  * K and V are fetched as fp8, 16 bytes per lane and load, 8 loads per 32-key unit (the 16-bit form: 16):
+//        K   lane (li, g), load (kt, j): key 16 kt + li, d 64 j + 16 g .. + 15 -- 64-byte row segments, as in the 16-bit form.
+//            Bytes 8 h .. 8 h + 7 of the load are the lane's A operand of MFMA k-step s = 2 j + h, so k-step s, lane group g,
+//            element e multiplies d = 64 (s >> 1) + 16 g + 8 (s & 1) + e; Q^T is loaded in the same permutation of d (a dot
+//            product does not mind the order of its terms)
+//        V   lane (r = lane >> 3, c = lane & 7), load i: key 8 i + r, d 16 c .. + 15 -- whole 128-byte rows
+//    K stays fp8 in the prefetch registers and is converted to Q's type (v_cvt_scalef32_pk_{bf16,f16}_fp8, scale 1: every finite
+//    e4m3 value is exact in both) right before its MFMAs; V is converted before it is written to the wave's 16-bit LDS image,
+//    whose layout and transposed reads are unchanged.
+//  * k_descale is folded into the exponent's constant c = k_descale / sqrt(128) * log2(e): S and the running maximum m stay in
+//    raw (undescaled) logit units, and lse = m * k_descale / sqrt(128) + log(l).  (A positive descale keeps the maximum the maximum.)
+//    v_descale is folded into the final 1 / l.  Both are one scalar per workgroup; no address depends on either.
+//  * A prefetch register set is 32 VGPRs instead of 64, so the 64-row form holds V a unit ahead as the others do.
+#pragma once
+#include "fa_decode_kernel.hpp"
+
+namespace fa {
+
+// the 16-bit path's arguments (k, v: the fp8 bytes; kv_*: strides in bytes = elements) and the descales
+struct DecodeFp8Args {
+    DecodeArgs d;
+    const float *k_descale, *v_descale;   // (batch, n_kv_heads), row stride ds_bs; null = 1
+    int64_t ds_bs;
+};
+
+namespace decode {
+// eight e4m3fn values (two dwords, lowest byte first) as eight values of Q's type
+template <int DT>
+static FA_DEV typename Elem<DT>::vec8 cvt_fp8x8(unsigned w0, unsigned w1) {
+    u32x4 r;
+    if constexpr (DT == 15) {
+        r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false));
+        r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true));
+        r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false));
+        r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true));
+    } else {
+        r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, false));
+        r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, true));
+        r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, false));
+        r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, true));
+    }
+    return __builtin_bit_cast(typename Elem<DT>::vec8, r);
+}
+}  // namespace decode
+
+template <int DT, int NT, bool PAGED>
+__global__ void __launch_bounds__(decode::THREADS) fa_decode_fp8_split_kernel(const DecodeFp8Args a8) {
+    using E = Elem<DT>;
+    using vec8 = typename E::vec8;
+    using namespace decode;
+    constexpr int KS = D / 32, DT16 = D / 16;
+    constexpr int MERGE = NT * DT16 * 64 * 16;   // one wave's accumulators
+    constexpr int MAIN = NWAVES * VBYTES > MERGE ? NWAVES * VBYTES : MERGE;
+    __shared__ __attribute__((aligned(16))) char smem[MAIN + (NWAVES + 1) * NT * 16 * 4];
+    const DecodeArgs &a = a8.d;
+    const uint8_t *const k8 = (const uint8_t *)a.k, *const v8 = (const uint8_t *)a.v;
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int li = lane & 15, g = lane >> 4;
+    const int vr = lane >> 3, vc = lane & 7;   // V's load shape
+    const int nsp = a.num_splits;
+    const int split = blockIdx.x % nsp, kvh = (blockIdx.x / nsp) % a.n_kv_heads, b = blockIdx.x / (nsp * a.n_kv_heads);
+
+    int len = a.cache_seqlens[b];
+    len = len < 0 ? 0 : (len > a.max_len ? a.max_len : len);
+    const int n_tiles = (len + TILE - 1) / TILE;
+    const int t0 = (int)((int64_t)n_tiles * split / nsp), t1 = (int)((int64_t)n_tiles * (split + 1) / nsp);
+    const int n_units = (len + UNIT - 1) / UNIT;
+    const int u_end = 2 * t1 < n_units ? 2 * t1 : n_units;
+    const float kd = a8.k_descale ? a8.k_descale[(int64_t)b * a8.ds_bs + kvh] : 1.0f;
+    const float vd = a8.v_descale ? a8.v_descale[(int64_t)b * a8.ds_bs + kvh] : 1.0f;
+
+    // Q^T, resident, in K's permutation of d; lim: the first key a row does not see
+    vec8 Qr[NT][KS];
+    int lim[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int r = nt * 16 + li;
+        const bool valid = r < a.rows;
+        const int rr = valid ? r : 0, qi = rr / a.group, qh = kvh * a.group + rr % a.group;
+        const uint16_t *qp = a.q + (int64_t)b * a.q_bs + (int64_t)qi * a.q_ss + (int64_t)qh * a.q_hs + g * 16;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) Qr[nt][ks] = *(const vec8 *)(qp + (ks >> 1) * 64 + (ks & 1) * 8);
+        lim[nt] = !valid ? 0 : (a.causal ? len - a.seqlen_q + qi + 1 : len);
+    }
+
+    const float scale = kd / __builtin_sqrtf((float)D);   // raw logits -> logits
+    const float c = scale * 1.4426950408889634074f;
+    const float ninf = -__builtin_inff();
+
+    f32x4 O[NT][DT16];
+    float m[NT], l[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+        for (int t = 0; t < DT16; ++t) O[nt][t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        m[nt] = ninf;
+        l[nt] = 0.0f;
+    }
+
+    // one 32-key unit's K and V, 16 bytes per lane and load (shapes: the head of this file); keys at or beyond len come from
+    // key len - 1.  A unit at or beyond u_end (the prefetch behind a wave's last unit) is still loaded, every lane from the
+    // first row of unit `u_valid`: one cached row instead of 8 KiB, and the number of loads in flight stays the same on every
+    // path, so the waits can be counted
+    auto load_unit = [&](int u, int u_valid, u32x4 (&Kr)[2][2], u32x4 (&Vr)[4]) {
+        const bool real = u < u_end;
+        const int key0 = (real ? u : u_valid) * UNIT;
+        int64_t base;
+        int row0;
+        if constexpr (PAGED) {
+            const int page = key0 / a.page_size;
+            // a scalar load (the compiler's own would be a vector load behind the unit's 8: waiting for it would drain them all)
+            int p;
+            asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(p) : "s"(a.block_table + (int64_t)b * a.bt_bs + page) : "memory");
+            p = p < 0 ? 0 : (p >= a.num_pages ? a.num_pages - 1 : p);
+            base = (int64_t)p * a.kv_bs + (int64_t)kvh * a.kv_hs;
+            row0 = key0 - page * a.page_size;
+        } else {
+            base = (int64_t)b * a.kv_bs + (int64_t)kvh * a.kv_hs;
+            row0 = key0;
+        }
+        const int last = real ? len - 1 - key0 : 0;
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) {
+            const int ko = kt * 16 + li < last ? kt * 16 + li : last;
+            const uint8_t *kp = k8 + base + (int64_t)(row0 + ko) * a.kv_ss + g * 16;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) Kr[kt][j] = *(const u32x4 *)(kp + j * 64);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int ko = i * 8 + vr < last ? i * 8 + vr : last;
+            Vr[i] = *(const u32x4 *)(v8 + base + (int64_t)(row0 + ko) * a.kv_ss + vc * 16);
+        }
+    };
+
+    char *vs = smem + wave * VBYTES;
+    const char *vrd = vs + (4 * g + (li >> 2)) * VROW + (li & 3) * 8;   // T10: lane 4q + p of a group: row q, columns 4p ..
+    auto compute_unit = [&](int u, const u32x4 (&Kr)[2][2], const u32x4 (&Vr)[4]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            char *wp = vs + (i * 8 + vr) * VROW + vc * 32;
+            *(vec8 *)wp = cvt_fp8x8<DT>(Vr[i][0], Vr[i][1]);
+            *(vec8 *)(wp + 16) = cvt_fp8x8<DT>(Vr[i][2], Vr[i][3]);
+        }
+        f32x4 S[NT][2];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) S[nt][0] = S[nt][1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt) {
+                const vec8 ka = cvt_fp8x8<DT>(Kr[kt][ks >> 1][2 * (ks & 1)], Kr[kt][ks >> 1][2 * (ks & 1) + 1]);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) S[nt][kt] = E::mfma16(ka, Qr[nt][ks], S[nt][kt]);
+            }
+        vec8 Pb[NT];
+        const int key_g = u * UNIT + 4 * g;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            float s[8];
+            float mx = ninf;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {   // element j: key 16 (j >> 2) + 4 g + (j & 3) of the unit
+                s[j] = key_g + 16 * (j >> 2) + (j & 3) < lim[nt] ? S[nt][j >> 2][j & 3] : ninf;
+                mx = fmaxf(mx, s[j]);
+            }
+            const float m_new = fmaxf(m[nt], quad_max(mx));
+            const float m_ref = m_new == ninf ? 0.0f : m_new;   // a row that has seen no key yet: no inf - inf
+            const float alpha = __builtin_amdgcn_exp2f((m[nt] - m_ref) * c);
+            m[nt] = m_new;
+            l[nt] *= alpha;
+#pragma unroll
+            for (int t = 0; t < DT16; ++t) O[nt][t] *= alpha;
+            const float neg_mc = -(m_ref * c);
+            float p[8], rowsum = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                p[j] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[j], c, neg_mc));
+                rowsum += p[j];
+            }
+            l[nt] += rowsum;
+            Pb[nt] = E::pack8(p);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave's V image is written
+#pragma unroll
+        for (int t = 0; t < DT16; ++t) {
+            s16x8 av;
+            av.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((FA_LDS(s16x4) *)(vrd + t * 32));
+            av.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((FA_LDS(s16x4) *)(vrd + t * 32 + 16 * VROW));
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) O[nt][t] = E::mfma16(__builtin_bit_cast(vec8, av), Pb[nt], O[nt][t]);
+        }
+        asm volatile("" ::: "memory");   // ... and read before the next unit's is written
+    };
+
+    // Two register sets, A and B, taken in turn (the loop is unrolled by two, so no set is ever copied into the other): a
+    // unit's 8 loads are issued before the previous unit's work and waited for with the next unit's 8 still in flight.
+    {
+        u32x4 Ka[2][2], Kb[2][2], Va[4], Vb[4];
+        int u = 2 * t0 + wave;
+        if (u < u_end) load_unit(u, u, Ka, Va);
+        while (u < u_end) {
+            load_unit(u + NWAVES, u, Kb, Vb);
+            __builtin_amdgcn_sched_barrier(0);   // the requests go out before the unit's work, not where the scheduler finds room
+            compute_unit(u, Ka, Va);
+            u += NWAVES;
+            if (u >= u_end) break;
+            load_unit(u + NWAVES, u, Ka, Va);
+            __builtin_amdgcn_sched_barrier(0);
+            compute_unit(u, Kb, Vb);
+            u += NWAVES;
+        }
+    }
+
+    // the four waves' states into wave 0: one reference per row for all of them, then plain sums in wave order
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) l[nt] = quad_sum(l[nt]);
+    float *m_sh = (float *)(smem + MAIN), *l_sh = m_sh + NWAVES * NT * 16, *o_sh = (float *)smem;
+    __syncthreads();   // every wave is done with its V image
+    if (g == 0) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) m_sh[(wave * NT + nt) * 16 + li] = m[nt];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        float m_all = ninf;
+#pragma unroll
+        for (int w = 0; w < NWAVES; ++w) m_all = fmaxf(m_all, m_sh[(w * NT + nt) * 16 + li]);
+        const float m_ref = m_all == ninf ? 0.0f : m_all;
+        const float alpha = __builtin_amdgcn_exp2f((m[nt] - m_ref) * c);
+        m[nt] = m_all;
+        l[nt] *= alpha;
+#pragma unroll
+        for (int t = 0; t < DT16; ++t) O[nt][t] *= alpha;
+    }
+    for (int w = 1; w < NWAVES; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+                for (int t = 0; t < DT16; ++t) *(f32x4 *)(o_sh + ((nt * DT16 + t) * 64 + lane) * 4) = O[nt][t];
+                if (g == 0) l_sh[nt * 16 + li] = l[nt];
+            }
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+                for (int t = 0; t < DT16; ++t) O[nt][t] += *(const f32x4 *)(o_sh + ((nt * DT16 + t) * 64 + lane) * 4);
+                l[nt] += l_sh[nt * 16 + li];
+            }
+        }
+        __syncthreads();
+    }
+    if (wave != 0) return;
+
+    // lane (li, g) holds row 16 nt + li, d 16 t + 4 g .. + 3; m is a raw logit, l a sum of undescaled V's weights
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int r = nt * 16 + li;
+        if (r >= a.rows) continue;
+        const bool any = l[nt] > 0.0f;
+        const float inv = any ? vd / l[nt] : 0.0f;
+        const float lse = any ? m[nt] * scale + __logf(l[nt]) : ninf;
+        const int qi = r / a.group, qh = kvh * a.group + r % a.group;
+        if (nsp == 1) {
+            uint16_t *op = a.o + (int64_t)b * a.o_bs + (int64_t)qi * a.o_ss + (int64_t)qh * a.o_hs + 4 * g;
+#pragma unroll
+            for (int t = 0; t < DT16; ++t) {
+                u32x2 w;
+                w[0] = E::pack2(O[nt][t][0] * inv, O[nt][t][1] * inv);
+                w[1] = E::pack2(O[nt][t][2] * inv, O[nt][t][3] * inv);
+                *(u32x2 *)(op + 16 * t) = w;
+            }
+            if (a.lse && g == 0) a.lse[((int64_t)b * a.n_heads + qh) * a.seqlen_q + qi] = lse;
+        } else {
+            const int64_t row = (((int64_t)split * a.batch + b) * a.n_kv_heads + kvh) * a.rows + r;
+            float *pp = a.part_o + row * D + 4 * g;
+#pragma unroll
+            for (int t = 0; t < DT16; ++t) *(f32x4 *)(pp + 16 * t) = O[nt][t] * inv;
+            if (g == 0) a.part_lse[row] = lse;
+        }
+    }
+}
+
+// the fp8 split kernel and, for num_splits > 1, the 16-bit path's combine kernel on stream s (fa_decode_fp8.hip)
+hipError_t decode_fp8_enqueue(const DecodeFp8Args &a, int dtype, hipStream_t s);
+
+}  // namespace fa

@@ -104,15 +104,28 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
 
 
 def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
-                    num_splits=0, timed=False):
+                    num_splits=0, timed=False, k_descale=None, v_descale=None):
     """Decode attention against a K / V cache: q (batch, seqlen_q, n_heads, 128) against k_cache / v_cache
     (batch, seqlen_cache, n_kv_heads, 128) -- or, with block_table (batch, max_pages_per_seq) int32, pages (num_pages,
     page_size, n_kv_heads, 128) -- of which cache_seqlens (batch,) int32 ON THE DEVICE says how many keys are valid, the newest
     tokens included.  seqlen_q * n_heads / n_kv_heads <= 64; causal is bottom-right aligned; a row without keys gives o = 0,
     lse = -inf.  num_splits = 0 takes the split rule (a function of the shapes and max_seqlen_k alone).  -> o, or (o, lse) with
-    return_lse, each with ms appended if timed.  No device synchronisation unless timed; graph-capturable."""
+    return_lse, each with ms appended if timed.  No device synchronisation unless timed; graph-capturable.
+
+    An fp8 cache: k_cache / v_cache of dtype torch.float8_e4m3fn in the same shapes, q and o still bf16 / fp16.
+    k_descale, v_descale: fp32 (batch, n_kv_heads) ON THE DEVICE, None = 1, finite and positive; key j of entry b and K / V head
+    h stands for float(k8[j]) * k_descale[b, h], likewise V (quantize_kvcache_fp8 makes such a cache).  Other float8 dtypes,
+    K and V of different dtypes, and descales with a 16-bit cache are refused."""
     return flash_attention_kernels.forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=block_table, causal=causal,
-                                                   return_lse=return_lse, max_seqlen_k=max_seqlen_k, num_splits=num_splits, timed=timed)
+                                                   return_lse=return_lse, max_seqlen_k=max_seqlen_k, num_splits=num_splits, timed=timed,
+                                                   k_descale=k_descale, v_descale=v_descale)
+
+
+def quantize_kvcache_fp8(k, v):
+    """A contiguous 16-bit cache (batch, seqlen_cache, n_kv_heads, 128) -> (k8, v8, k_descale, v_descale) for forward_kvcache:
+    torch.float8_e4m3fn caches and fp32 (batch, n_kv_heads) descales, amax / 448 per (batch entry, K / V head), 1 for an all-zero
+    head.  Plain torch."""
+    return flash_attention_kernels.quantize_kvcache_fp8(k, v)
 
 
 def backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None):

@@ -438,18 +438,24 @@ def _decode_needs_copy(t):
     return t.stride(-1) != 1 or any(s % 8 for s in t.stride()[:-1]) or t.data_ptr() % 16 != 0
 
 
+_FLOAT8_DTYPES = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
+
+
 def kvcache_num_splits(q, k_cache, v_cache, cache_seqlens, block_table=None, max_seqlen_k=None, num_splits=0):
-    """The split count forward_kvcache uses for these arguments (fa_decode_num_splits): the same checks, nothing allocated, no
-    launch."""
-    _, args = _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, False, max_seqlen_k, num_splits)
-    return _capi.check(_capi.load().fa_decode_num_splits(ctypes.byref(args)))
+    """The split count forward_kvcache uses for these arguments (fa_decode_num_splits, or fa_decode_fp8_num_splits for an fp8
+    cache: the same rule): the same checks, nothing allocated, no launch."""
+    _, args, fp8 = _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, False, max_seqlen_k, num_splits, None, None)
+    lib = _capi.load()
+    return _capi.check((lib.fa_decode_fp8_num_splits if fp8 else lib.fa_decode_num_splits)(ctypes.byref(args)))
 
 
-def _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_seqlen_k, num_splits):
-    """forward_kvcache's checks -> (q as the launch takes it, fa_decode_args still without o, lse and workspace)."""
+def _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_seqlen_k, num_splits, k_descale, v_descale):
+    """forward_kvcache's checks -> (q as the launch takes it, fa_decode_args or fa_decode_fp8_args still without o, lse and
+    workspace, whether the cache is fp8)."""
     tensors = [(q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cache_seqlens, "cache_seqlens")]
     if block_table is not None:
         tensors.append((block_table, "block_table"))
+    tensors += [(t, name) for t, name in ((k_descale, "k_descale"), (v_descale, "v_descale")) if t is not None]
     for t, name in tensors:
         if not t.is_cuda:
             raise RuntimeError(f"{name} must be a CUDA tensor")
@@ -457,8 +463,15 @@ def _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_se
             raise RuntimeError(f"{name} must be on q's device ({q.device}, got {t.device})")
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise RuntimeError("Only fp16 and bf16 are supported")
-    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+    fp8 = k_cache.dtype in _FLOAT8_DTYPES or v_cache.dtype in _FLOAT8_DTYPES
+    if fp8 and k_cache.dtype != v_cache.dtype:
+        raise RuntimeError(f"k_cache and v_cache must have one data type (got {k_cache.dtype} and {v_cache.dtype})")
+    if fp8 and k_cache.dtype != torch.float8_e4m3fn:
+        raise RuntimeError(f"an fp8 cache must be torch.float8_e4m3fn (got {k_cache.dtype})")
+    if not fp8 and k_cache.dtype != q.dtype:
         raise RuntimeError("Input tensors must have the same data type")
+    if not fp8 and (k_descale is not None or v_descale is not None):
+        raise RuntimeError("k_descale / v_descale belong to an fp8 (torch.float8_e4m3fn) cache; this cache is 16-bit")
     if q.dim() != 4 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[3] != q.shape[3]:
         raise RuntimeError("q must have shape (batch, seqlen_q, n_heads, d_head), k_cache and v_cache one shape (batch or "
                            "num_pages, seqlen_cache or page_size, n_kv_heads, d_head)")
@@ -472,13 +485,18 @@ def _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_se
         raise RuntimeError("block_table must be an int32 (batch, max_pages_per_seq) tensor on q's device with a contiguous last dimension")
     if max_seqlen_k is not None and (not isinstance(max_seqlen_k, int) or isinstance(max_seqlen_k, bool)):
         raise RuntimeError("max_seqlen_k must be a Python int (a bound on every length; the device is not asked)")
+    for t, name in ((k_descale, "k_descale"), (v_descale, "v_descale")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (batch, k_cache.shape[2]) or not t.is_contiguous()):
+            raise RuntimeError(f"{name} must be a contiguous fp32 (batch, n_kv_heads) = ({batch}, {k_cache.shape[2]}) tensor on q's device")
     if _decode_needs_copy(q):
         q = q.contiguous()
-    if _decode_needs_copy(k_cache) or _decode_needs_copy(v_cache) or k_cache.stride() != v_cache.stride():
+    kv_unit = 16 if fp8 else 8   # 16 bytes
+    if (_decode_needs_copy(k_cache) or _decode_needs_copy(v_cache) or k_cache.stride() != v_cache.stride()
+            or any(s % kv_unit for s in k_cache.stride()[:-1])):
         # (a serving cache is gigabytes: copying it on every call would be silently slow)
-        raise RuntimeError("k_cache and v_cache need one stride set, a contiguous last dimension, strides that are multiples of 8 "
+        raise RuntimeError(f"k_cache and v_cache need one stride set, a contiguous last dimension, strides that are multiples of {kv_unit} "
                            "elements and a 16-byte aligned base")
-    args = _capi.make_decode_args(
+    fields = dict(
         dtype=15 if q.dtype == torch.bfloat16 else 5, causal=1 if causal else 0, num_splits=int(num_splits),
         q=q.data_ptr(), k=k_cache.data_ptr(), v=v_cache.data_ptr(),
         cache_seqlens=cache_seqlens.data_ptr(), block_table=block_table.data_ptr() if block_table is not None else None,
@@ -492,32 +510,59 @@ def _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_se
         o_batch_stride=seqlen_q * n_heads * d_head, o_seq_stride=n_heads * d_head, o_head_stride=d_head,   # (o: contiguous)
         kv_batch_stride=k_cache.stride(0), kv_seq_stride=k_cache.stride(1), kv_head_stride=k_cache.stride(2),
     )
-    return q, args
+    if not fp8:
+        return q, _capi.make_decode_args(**fields), False
+    args = _capi.make_decode_fp8_args(
+        k_descale=k_descale.data_ptr() if k_descale is not None else None,
+        v_descale=v_descale.data_ptr() if v_descale is not None else None,
+        descale_batch_stride=k_cache.shape[2], **fields)
+    return q, args, True
 
 
 def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
-                    num_splits=0, timed=False):
+                    num_splits=0, timed=False, k_descale=None, v_descale=None):
     """Decode attention against a K / V cache (fa_decode_launch): q (batch, seqlen_q, n_heads, 128); k_cache, v_cache
     (batch, seqlen_cache, n_kv_heads, 128), or with block_table (batch, max_pages_per_seq) int32 on the device
     (num_pages, page_size, n_kv_heads, 128); cache_seqlens (batch,) int32 on the device, the valid keys of each entry (the
     newest tokens included).  causal is bottom-right aligned.  -> o [, lse fp32 (batch, n_heads, seqlen_q)] [, ms].  The host
     reads neither cache_seqlens nor block_table; no device synchronisation unless timed.  The caches pass as they are (strided
-    views included) and are refused if the launch cannot address them; q is copied if it has to be."""
-    q, args = _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_seqlen_k, num_splits)
+    views included) and are refused if the launch cannot address them; q is copied if it has to be.
+    A torch.float8_e4m3fn cache takes fa_decode_fp8_launch: k_descale, v_descale (fp32 (batch, n_kv_heads) on the device, None = 1;
+    never read by the host) scale the cache's values, key j of entry b and K / V head h standing for float(k8[j]) * k_descale[b, h]."""
+    q, args, fp8 = _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_seqlen_k, num_splits, k_descale, v_descale)
     batch, seqlen_q, n_heads, d_head = q.shape
     o = torch.empty((batch, seqlen_q, n_heads, d_head), dtype=q.dtype, device=q.device)
     lse = torch.empty((batch, n_heads, seqlen_q), dtype=torch.float32, device=q.device) if return_lse else None
     args.o, args.lse = o.data_ptr(), (lse.data_ptr() if return_lse else None)
     lib = _capi.load()
-    nbytes = lib.fa_decode_workspace_bytes(ctypes.byref(args))
+    workspace_bytes, launch = ((lib.fa_decode_fp8_workspace_bytes, lib.fa_decode_fp8_launch) if fp8 else
+                               (lib.fa_decode_workspace_bytes, lib.fa_decode_launch))
+    nbytes = workspace_bytes(ctypes.byref(args))
     _capi.check(nbytes if nbytes < 0 else 0)
     with torch.cuda.device(q.device):
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes > 0 else None   # (on the current stream's allocator)
         args.workspace = workspace.data_ptr() if workspace is not None else None
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
         ms = ctypes.c_float(0.0)
-        _capi.check(lib.fa_decode_launch(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
+        _capi.check(launch(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
     out = (o, lse) if return_lse else (o,)
     if timed:
         out = out + (float(ms.value),)
     return out[0] if len(out) == 1 else out
+
+
+def quantize_kvcache_fp8(k, v):
+    """A contiguous 16-bit (or fp32) cache (batch, seqlen_cache, n_kv_heads, d_head) -> (k8, v8, k_descale, v_descale): e4m3fn
+    caches of the same shape and fp32 (batch, n_kv_heads) descales, amax / 448 per (batch entry, K / V head) -- 448 is e4m3fn's
+    largest finite value -- and 1 for an all-zero head.  Plain torch (callers, tests, the bench); value ~ float(x8) * descale."""
+    def one(t):
+        if t.dim() != 4:
+            raise RuntimeError("quantize_kvcache_fp8 takes (batch, seqlen_cache, n_kv_heads, d_head) tensors")
+        x = t.float()
+        amax = x.abs().amax(dim=(1, 3))
+        descale = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+        x8 = (x / descale[:, None, :, None]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+        return x8, descale.contiguous()
+    k8, k_descale = one(k)
+    v8, v_descale = one(v)
+    return k8, v8, k_descale, v_descale

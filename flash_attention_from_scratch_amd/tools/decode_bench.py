@@ -10,7 +10,13 @@ without the causal mask (for seqlen_q 1 it is the same problem).  `gbps_*` is ac
 valid + Q + O) / time.  Clocks are whatever the device runs at.
 Kernel times of their own: run it under `rocprofv3 --kernel-trace --stats -- python .../decode_bench.py`.
 
-    python flash_attention_from_scratch_amd/tools/decode_bench.py [--reps N] [--quick] [--out FILE]
+--kv-dtype fp8: the same cases with two arms instead, alternating in one process, both with the split rule's num_splits:
+  - "fp8":   forward_kvcache on the cache quantized to e4m3fn with per (batch, K / V head) descales (quantize_kvcache_fp8);
+  - "16bit": forward_kvcache on the 16-bit cache the fp8 one was quantized from (the yardstick).
+`gbps_fp8` counts K and V at 1 byte per element, `gbps_16bit` at 2; `fp8_over_16bit` is the time ratio.  Written to
+profiles/inference/decode_fp8_bench_<dtype>.jsonl unless --out says otherwise.
+
+    python flash_attention_from_scratch_amd/tools/decode_bench.py [--reps N] [--quick] [--kv-dtype {16bit,fp8}] [--out FILE]
 """
 import argparse
 import json
@@ -40,6 +46,49 @@ def _timed(fn):
     stop.record()
     stop.synchronize()
     return start.elapsed_time(stop)
+
+
+def _quantize(k, v, chunk=4):
+    """quantize_kvcache_fp8 a few batch entries at a time (its fp32 temporaries are several times a 64k cache's size)"""
+    parts = [flash_attention.quantize_kvcache_fp8(k[b:b + chunk], v[b:b + chunk]) for b in range(0, k.shape[0], chunk)]
+    return tuple(torch.cat([p[i] for p in parts]) for i in range(4))
+
+
+def run_fp8(case, lengths, cache_len, H, Hkv, Sq, page_size, dtype, reps):
+    B = len(lengths)
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    q = torch.randn((B, Sq, H, 128), generator=gen, device="cuda").to(dtype)
+    k = torch.randn((B, cache_len, Hkv, 128), generator=gen, device="cuda").to(dtype)
+    v = torch.randn((B, cache_len, Hkv, 128), generator=gen, device="cuda").to(dtype)
+    lens = torch.tensor(lengths, dtype=torch.int32, device="cuda")
+    k8, v8, kd, vd = _quantize(k, v)
+    kw = {}
+    if page_size:
+        per_seq = cache_len // page_size
+        perm = torch.randperm(B * per_seq, generator=torch.Generator().manual_seed(1)).to("cuda")
+
+        def paginate(t):
+            out = torch.empty((B * per_seq, page_size, Hkv, 128), dtype=torch.uint8 if t.dtype == torch.float8_e4m3fn else t.dtype, device="cuda")
+            out[perm] = (t.view(torch.uint8) if t.dtype == torch.float8_e4m3fn else t).view(B * per_seq, page_size, Hkv, 128)
+            return out.view(t.dtype)
+        k, v, k8, v8 = paginate(k), paginate(v), paginate(k8), paginate(v8)
+        kw["block_table"] = perm.view(B, per_seq).to(torch.int32)
+    t_8, t_16 = [], []
+    for i in range(reps + 2):   # (two warm-up rounds)
+        t0 = _timed(lambda: flash_attention.forward_kvcache(q, k8, v8, lens, k_descale=kd, v_descale=vd, **kw))
+        t1 = _timed(lambda: flash_attention.forward_kvcache(q, k, v, lens, **kw))
+        if i > 1:
+            t_8.append(t0), t_16.append(t1)
+    uniform = len(set(lengths)) == 1
+    kv_elems, qo_bytes = 2 * sum(lengths) * Hkv * 128, 2 * 2 * B * Sq * H * 128
+    line = {"case": case, "batch": B, "cache_len": cache_len, "lengths": lengths if not uniform else lengths[0], "n_heads": H,
+            "n_kv_heads": Hkv, "seqlen_q": Sq, "page_size": page_size, "dtype": str(dtype).replace("torch.", ""), "kv_dtype": "fp8_e4m3fn",
+            "reps": reps, "num_splits_rule": fak.kvcache_num_splits(q, k8, v8, lens, **kw),
+            "bytes_fp8": kv_elems + qo_bytes, "bytes_16bit": 2 * kv_elems + qo_bytes, "fp8_ms": _median(t_8), "16bit_ms": _median(t_16)}
+    line["gbps_fp8"] = line["bytes_fp8"] / (line["fp8_ms"] * 1e-3) / 1e9
+    line["gbps_16bit"] = line["bytes_16bit"] / (line["16bit_ms"] * 1e-3) / 1e9
+    line["fp8_over_16bit"] = line["fp8_ms"] / line["16bit_ms"]
+    return line
 
 
 def run(case, lengths, cache_len, H, Hkv, Sq, page_size, dtype, reps):
@@ -114,13 +163,17 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--quick", action="store_true", help="seqlen_q 1, contiguous, 1k and 64k caches only")
     ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "inference", "decode_bench_bf16.jsonl"))
+    ap.add_argument("--kv-dtype", choices=("16bit", "fp8"), default="16bit", help="fp8: the e4m3fn cache against the 16-bit one")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    fp8 = a.kv_dtype == "fp8"
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "inference", f"decode_fp8_bench_{a.dtype}.jsonl" if fp8 else "decode_bench_bf16.jsonl")
     assert torch.cuda.is_available(), "decode_bench.py needs the GPU"
     dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float16
     lines = []
     for c in cases(a.quick):
-        lines.append(run(*c, dtype, a.reps))
+        lines.append((run_fp8 if fp8 else run)(*c, dtype, a.reps))
         print(json.dumps(lines[-1]), flush=True)
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

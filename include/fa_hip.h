@@ -571,6 +571,70 @@ int fa_decode_num_splits(const fa_decode_args *args);                 /* the spl
 int64_t fa_decode_workspace_bytes(const fa_decode_args *args);        /* bytes, or a negative fa_status */
 int fa_decode_launch(const fa_decode_args *args, void *stream, float *ms);
 
+/*
+ * The same decode against an fp8 K / V cache.  k and v hold OCP e4m3fn bytes (torch.float8_e4m3fn; not MI300's fnuz
+ * encoding) in the shapes and addressings of fa_decode_args, one byte per element, so the kv_* strides count bytes; q and o
+ * stay bf16 / fp16 (dtype).  kv_dtype names the cache's encoding: FA_KV_FP8_E4M3FN is the only value served, anything else
+ * is FA_ERR_DTYPE.
+ * k_descale, v_descale (either may be null, which means 1): fp32 DEVICE arrays (batch, n_kv_heads), row stride
+ * descale_batch_stride elements.  Key j of entry b, K / V head h stands for float(k8[j]) * k_descale[b][h], likewise V; the
+ * result is softmax(q k^T / sqrt(128)) v on those values, with lse from the same logits.  The host never reads the descales
+ * (like cache_seqlens they may change between graph replays).  They must be finite and positive: the caller's contract, not
+ * checked; whatever they hold, no address depends on them.  An e4m3 NaN (0x7f, 0xff) in a valid row propagates as a 16-bit
+ * NaN does; at or beyond len it is never fetched.
+ * Everything else -- causal, empty rows, the clamping, the split rule (the same function of the same arguments, the same
+ * constants), the workspace size and format, the fixed-order combine, determinism -- is fa_decode_launch's.
+ * Refused before any HIP call, as fa_decode_launch does, and additionally: kv_dtype (FA_ERR_DTYPE); kv_* strides not
+ * multiples of 16 bytes, k / v not 16-byte aligned, descale pointers not 4-byte aligned (FA_ERR_ALIGN);
+ * descale_batch_stride < n_kv_heads with a descale given (FA_ERR_SHAPE).
+ */
+typedef enum fa_kv_dtype {
+    FA_KV_FP8_E4M3FN = 1
+} fa_kv_dtype;
+
+typedef struct fa_decode_fp8_args {
+    uint32_t struct_size;      /* sizeof(fa_decode_fp8_args) */
+    int32_t dtype;             /* fa_dtype of q and o */
+    int32_t causal;
+    int32_t num_splits;        /* 0 = the rule */
+    const void *q;
+    const void *k;             /* fp8 bytes */
+    const void *v;
+    void *o;
+    float *lse;                /* may be null */
+    const int32_t *cache_seqlens;
+    const int32_t *block_table;   /* null = contiguous cache */
+    void *workspace;           /* needed when fa_decode_fp8_workspace_bytes > 0 */
+    int64_t batch;
+    int64_t seqlen_q;
+    int64_t n_heads;
+    int64_t n_kv_heads;
+    int64_t d_head;
+    int64_t seqlen_cache;
+    int64_t num_pages;
+    int64_t page_size;
+    int64_t max_pages_per_seq;
+    int64_t block_table_stride;
+    int64_t max_seqlen_k;      /* 0 = capacity */
+    int64_t q_batch_stride;
+    int64_t q_seq_stride;
+    int64_t q_head_stride;
+    int64_t o_batch_stride;
+    int64_t o_seq_stride;
+    int64_t o_head_stride;
+    int64_t kv_batch_stride;   /* bytes = elements; paged: the page stride */
+    int64_t kv_seq_stride;
+    int64_t kv_head_stride;
+    const float *k_descale;    /* DEVICE (batch, n_kv_heads) fp32, may be null (= 1) */
+    const float *v_descale;
+    int64_t descale_batch_stride;   /* elements; >= n_kv_heads when a descale is given */
+    int32_t kv_dtype;          /* fa_kv_dtype */
+} fa_decode_fp8_args;
+int fa_decode_fp8_supported(const fa_decode_fp8_args *args);
+int fa_decode_fp8_num_splits(const fa_decode_fp8_args *args);          /* the split count the launch uses, or a negative fa_status */
+int64_t fa_decode_fp8_workspace_bytes(const fa_decode_fp8_args *args); /* bytes, or a negative fa_status */
+int fa_decode_fp8_launch(const fa_decode_fp8_args *args, void *stream, float *ms);
+
 /* The adaptive speculative mode's record on `device` (fa_speculative_mode), and a reset of its demotion state (tests,
  * or a caller that knows its data has changed character). */
 int fa_adaptive_state(int device, fa_adaptive_info *out);
