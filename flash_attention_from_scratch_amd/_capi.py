@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_varlen_qk_supported", "fa_fwd_launch_varlen_qk", "fa_bwd_varlen_qk_workspace_bytes", "fa_bwd_launch_varlen_qk",
     "fa_decode_supported", "fa_decode_num_splits", "fa_decode_workspace_bytes", "fa_decode_launch",
     "fa_decode_fp8_supported", "fa_decode_fp8_num_splits", "fa_decode_fp8_workspace_bytes", "fa_decode_fp8_launch",
+    "fa_kvcache_append_launch",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -172,6 +173,34 @@ class FaDecodeFp8Args(ctypes.Structure):   # fa_decode_fp8_args (fa_decode_args'
 def make_decode_fp8_args(**fields):
     """fa_decode_fp8_args with struct_size set; d_head defaults to 128, kv_dtype to e4m3fn, everything not given to 0 / null."""
     a = FaDecodeFp8Args(struct_size=ctypes.sizeof(FaDecodeFp8Args), d_head=128, kv_dtype=FA_KV_FP8_E4M3FN)
+    for name, value in fields.items():
+        setattr(a, name, value)
+    return a
+
+
+class FaKvcacheAppendArgs(ctypes.Structure):   # fa_kvcache_append_args (the append / rotary / quantize / advance step in front of a decode)
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("kv_dtype", ctypes.c_int32), ("causal", ctypes.c_int32),
+        ("rotary_interleaved", ctypes.c_int32),
+        ("k_new", ctypes.c_void_p), ("v_new", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p),
+        ("q", ctypes.c_void_p), ("q_out", ctypes.c_void_p), ("rotary_cos", ctypes.c_void_p), ("rotary_sin", ctypes.c_void_p),
+        ("cache_seqlens", ctypes.c_void_p), ("seqlens_out", ctypes.c_void_p), ("block_table", ctypes.c_void_p),
+        ("k_descale", ctypes.c_void_p), ("v_descale", ctypes.c_void_p),
+        ("batch", ctypes.c_int64), ("seqlen_new", ctypes.c_int64), ("seqlen_q", ctypes.c_int64), ("n_heads", ctypes.c_int64),
+        ("n_kv_heads", ctypes.c_int64), ("d_head", ctypes.c_int64), ("seqlen_cache", ctypes.c_int64), ("num_pages", ctypes.c_int64),
+        ("page_size", ctypes.c_int64), ("max_pages_per_seq", ctypes.c_int64), ("block_table_stride", ctypes.c_int64),
+        ("rotary_dim", ctypes.c_int64), ("seqlen_ro", ctypes.c_int64), ("rotary_seq_stride", ctypes.c_int64),
+        ("new_batch_stride", ctypes.c_int64), ("new_seq_stride", ctypes.c_int64), ("new_head_stride", ctypes.c_int64),
+        ("q_batch_stride", ctypes.c_int64), ("q_seq_stride", ctypes.c_int64), ("q_head_stride", ctypes.c_int64),
+        ("qo_batch_stride", ctypes.c_int64), ("qo_seq_stride", ctypes.c_int64), ("qo_head_stride", ctypes.c_int64),
+        ("kv_batch_stride", ctypes.c_int64), ("kv_seq_stride", ctypes.c_int64), ("kv_head_stride", ctypes.c_int64),
+        ("descale_batch_stride", ctypes.c_int64),
+    ]
+
+
+def make_kvcache_append_args(**fields):
+    """fa_kvcache_append_args with struct_size set; d_head defaults to 128, everything not given to 0 / null."""
+    a = FaKvcacheAppendArgs(struct_size=ctypes.sizeof(FaKvcacheAppendArgs), d_head=128)
     for name, value in fields.items():
         setattr(a, name, value)
     return a
@@ -324,6 +353,8 @@ def load():
     lib.fa_decode_fp8_workspace_bytes.argtypes = [ctypes.POINTER(FaDecodeFp8Args)]
     lib.fa_decode_fp8_launch.restype = ctypes.c_int
     lib.fa_decode_fp8_launch.argtypes = [ctypes.POINTER(FaDecodeFp8Args), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    lib.fa_kvcache_append_launch.restype = ctypes.c_int
+    lib.fa_kvcache_append_launch.argtypes = [ctypes.POINTER(FaKvcacheAppendArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p
     lib.fa_last_error.argtypes = []
     lib.fa_version.restype = ctypes.c_char_p

@@ -22,6 +22,7 @@
 #include "fa_bwd_varlen_qk.hpp"
 #include "fa_decode_kernel.hpp"
 #include "fa_decode_fp8_kernel.hpp"
+#include "fa_kvcache_append_kernel.hpp"
 #include "fa_registry.hpp"
 
 extern "C" {
@@ -1462,6 +1463,162 @@ int fa_decode_fp8_launch(const fa_decode_fp8_args *a, void *stream, float *ms) {
     d.ds_bs = a->descale_batch_stride;
     const hipStream_t s = (hipStream_t)stream;
     return bwd_run([&] { return fa::decode_fp8_enqueue(d, a->dtype, s); }, s, ms);
+}
+
+// ---- the KV-cache append in front of a decode --------------------------------------------------------------------------------
+namespace {
+// one stride set of the append: positive where the size asks for it, multiples of `unit` elements (16 bytes)
+int append_strides(const char *which, int64_t unit, int64_t n0, int64_t n1, int64_t n2, int64_t bs, int64_t ss, int64_t hs) {
+    if (ss <= 0 || bs < 0 || hs < 0 || (n0 > 1 && bs == 0) || (n2 > 1 && hs == 0) || (n1 > 1 && ss == 0))
+        return fail(FA_ERR_SHAPE, "%s strides must be positive (batch %lld, seq %lld, head %lld elements)", which, (long long)bs,
+                    (long long)ss, (long long)hs);
+    if ((bs | ss | hs) & (unit - 1)) return fail(FA_ERR_ALIGN, "%s strides must be multiples of %lld elements (16 bytes)", which, (long long)unit);
+    return FA_OK;
+}
+
+// the bytes [p, p + extent) a (n0, n1, n2, 128) tensor of 16-bit elements spans
+int64_t append_extent(int64_t n0, int64_t n1, int64_t n2, int64_t bs, int64_t ss, int64_t hs) {
+    return 2 * ((n0 - 1) * bs + (n1 - 1) * ss + (n2 - 1) * hs + 128);
+}
+
+int append_validate(const fa_kvcache_append_args *a) {
+    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
+    if (a->struct_size < sizeof(fa_kvcache_append_args))
+        return fail(FA_ERR_SHAPE, "fa_kvcache_append_args.struct_size (%u) is smaller than this library's (%zu)", a->struct_size,
+                    sizeof(fa_kvcache_append_args));
+    if (!a->k || !a->v) return fail(FA_ERR_NULL, "null cache pointer (k and v are both needed)");
+    if (a->seqlen_new > 0 && (!a->k_new || !a->v_new)) return fail(FA_ERR_NULL, "null new-row pointer (k_new and v_new are both needed)");
+    if (!a->cache_seqlens || !a->seqlens_out)
+        return fail(FA_ERR_NULL, "cache_seqlens or seqlens_out is null: DEVICE pointers to batch int32 lengths are needed (they may be one pointer)");
+    if (a->q && !a->q_out) return fail(FA_ERR_NULL, "q_out is null: q is rotated into a separate tensor");
+    if (a->dtype != FA_FP16 && a->dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
+    if (a->kv_dtype != 0 && a->kv_dtype != FA_KV_FP8_E4M3FN)
+        return fail(FA_ERR_DTYPE, "kv_dtype (%d) is not served: 0 (the cache has dtype) or FA_KV_FP8_E4M3FN", a->kv_dtype);
+    const bool fp8 = a->kv_dtype == FA_KV_FP8_E4M3FN;
+    if (a->block_table && a->page_size > 0 && a->page_size % 64 != 0)
+        return fail(FA_ERR_NO_KERNEL, "paged cache: page_size must be a multiple of 64 (got %lld)", (long long)a->page_size);
+    if (a->d_head != 128) return fail(FA_ERR_SHAPE, "the append supports d_head = 128 only (got %lld)", (long long)a->d_head);
+    if (a->batch < 0 || a->seqlen_new < 0 || a->n_kv_heads <= 0)
+        return fail(FA_ERR_SHAPE, "batch and seqlen_new must not be negative, n_kv_heads must be positive");
+    if (a->batch > INT32_MAX / 2 || a->seqlen_new > INT32_MAX / 2 || a->n_kv_heads > INT32_MAX / 2 || a->seqlen_new * a->n_kv_heads > INT32_MAX / 64)
+        return fail(FA_ERR_SHAPE, "problem too large: the append's item counts are 32-bit");
+    int64_t cap;
+    if (a->block_table) {
+        if (a->page_size <= 0 || a->num_pages <= 0 || a->max_pages_per_seq <= 0)
+            return fail(FA_ERR_SHAPE, "paged cache: num_pages, page_size and max_pages_per_seq must be positive");
+        if (a->block_table_stride < a->max_pages_per_seq)
+            return fail(FA_ERR_SHAPE, "block_table_stride (%lld) is smaller than max_pages_per_seq (%lld)", (long long)a->block_table_stride,
+                        (long long)a->max_pages_per_seq);
+        if (a->num_pages > INT32_MAX / 2 || a->page_size > INT32_MAX / 2 || a->max_pages_per_seq > INT32_MAX / 2)
+            return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
+        cap = a->max_pages_per_seq * a->page_size;
+    } else {
+        if (a->seqlen_cache <= 0) return fail(FA_ERR_SHAPE, "seqlen_cache must be positive (got %lld)", (long long)a->seqlen_cache);
+        cap = a->seqlen_cache;
+    }
+    if (cap > INT32_MAX / 2) return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
+    const bool rotary = a->rotary_cos || a->rotary_sin;
+    if (rotary) {
+        if (!a->rotary_cos || !a->rotary_sin) return fail(FA_ERR_SHAPE, "rotary_cos and rotary_sin come together (one of them is null)");
+        if (a->rotary_dim < 16 || a->rotary_dim > 128 || a->rotary_dim % 16 != 0)
+            return fail(FA_ERR_SHAPE, "rotary_dim (%lld) must be a multiple of 16 in [16, 128]", (long long)a->rotary_dim);
+        if (a->seqlen_ro <= 0 || a->seqlen_ro > INT32_MAX / 2) return fail(FA_ERR_SHAPE, "seqlen_ro (%lld) must be positive", (long long)a->seqlen_ro);
+        if (a->rotary_seq_stride < a->rotary_dim / 2)
+            return fail(FA_ERR_SHAPE, "rotary_seq_stride (%lld) is smaller than rotary_dim / 2 (%lld)", (long long)a->rotary_seq_stride,
+                        (long long)a->rotary_dim / 2);
+    }
+    if (a->q) {
+        if (!rotary) return fail(FA_ERR_SHAPE, "q is given without rotary tables: there is nothing to do to it");
+        if (a->seqlen_q <= 0 || a->n_heads <= 0) return fail(FA_ERR_SHAPE, "seqlen_q and n_heads must be positive when q is given");
+        if (a->seqlen_q > INT32_MAX / 2 || a->n_heads > INT32_MAX / 2 || a->seqlen_q * a->n_heads > INT32_MAX / 64)
+            return fail(FA_ERR_SHAPE, "problem too large: the append's item counts are 32-bit");
+    }
+    if (!fp8 && (a->k_descale || a->v_descale))
+        return fail(FA_ERR_SHAPE, "k_descale / v_descale belong to an fp8 cache (kv_dtype FA_KV_FP8_E4M3FN); this cache is 16-bit");
+    if (fp8 && (a->k_descale || a->v_descale) && a->descale_batch_stride < a->n_kv_heads)
+        return fail(FA_ERR_SHAPE, "descale_batch_stride (%lld) is smaller than n_kv_heads (%lld)", (long long)a->descale_batch_stride,
+                    (long long)a->n_kv_heads);
+    int rc;
+    if (a->seqlen_new > 0 &&
+        (rc = append_strides("new", 8, a->batch, a->seqlen_new, a->n_kv_heads, a->new_batch_stride, a->new_seq_stride, a->new_head_stride)) != FA_OK)
+        return rc;
+    if ((rc = append_strides("kv", fp8 ? 16 : 8, a->block_table ? a->num_pages : a->batch, cap, a->n_kv_heads, a->kv_batch_stride, a->kv_seq_stride,
+                             a->kv_head_stride)) != FA_OK)
+        return rc;
+    if (a->q) {
+        if ((rc = append_strides("q", 8, a->batch, a->seqlen_q, a->n_heads, a->q_batch_stride, a->q_seq_stride, a->q_head_stride)) != FA_OK) return rc;
+        if ((rc = append_strides("q_out", 8, a->batch, a->seqlen_q, a->n_heads, a->qo_batch_stride, a->qo_seq_stride, a->qo_head_stride)) != FA_OK)
+            return rc;
+        if (a->batch > 0) {
+            const uintptr_t q0 = (uintptr_t)a->q, o0 = (uintptr_t)a->q_out;
+            const uintptr_t q1 = q0 + (uintptr_t)append_extent(a->batch, a->seqlen_q, a->n_heads, a->q_batch_stride, a->q_seq_stride, a->q_head_stride);
+            const uintptr_t o1 = o0 + (uintptr_t)append_extent(a->batch, a->seqlen_q, a->n_heads, a->qo_batch_stride, a->qo_seq_stride, a->qo_head_stride);
+            if (q0 < o1 && o0 < q1) return fail(FA_ERR_SHAPE, "q_out overlaps q: the rotated query needs a tensor of its own");
+        }
+    }
+    if (rotary && (a->rotary_seq_stride & 7)) return fail(FA_ERR_ALIGN, "rotary_seq_stride must be a multiple of 8 elements (16 bytes)");
+    if (((uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->k_new | (uintptr_t)a->v_new | (uintptr_t)a->q | (uintptr_t)a->q_out |
+         (uintptr_t)a->rotary_cos | (uintptr_t)a->rotary_sin) & 15)
+        return fail(FA_ERR_ALIGN, "k, v, k_new, v_new, q, q_out, rotary_cos and rotary_sin must be 16-byte aligned");
+    if (((uintptr_t)a->cache_seqlens | (uintptr_t)a->seqlens_out | (uintptr_t)a->block_table | (uintptr_t)a->k_descale | (uintptr_t)a->v_descale) & 3)
+        return fail(FA_ERR_ALIGN, "cache_seqlens, seqlens_out, block_table, k_descale and v_descale must be 4-byte aligned");
+    return FA_OK;
+}
+}  // namespace
+
+int fa_kvcache_append_launch(const fa_kvcache_append_args *a, void *stream, float *ms) {
+    int rc = append_validate(a);
+    if (rc != FA_OK) return rc;
+    if (a->batch == 0) {
+        if (ms) *ms = 0.0f;
+        return FA_OK;
+    }
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    const bool rotary = a->rotary_cos != nullptr, fp8 = a->kv_dtype == FA_KV_FP8_E4M3FN, with_q = rotary && a->q;
+    fa::AppendArgs d;
+    d.k_new = (const uint16_t *)a->k_new;
+    d.v_new = (const uint16_t *)a->v_new;
+    d.k = a->k;
+    d.v = a->v;
+    d.q = with_q ? (const uint16_t *)a->q : nullptr;
+    d.q_out = with_q ? (uint16_t *)a->q_out : nullptr;
+    d.cos = (const uint16_t *)a->rotary_cos;
+    d.sin = (const uint16_t *)a->rotary_sin;
+    d.cache_seqlens = a->cache_seqlens;
+    d.seqlens_out = a->seqlens_out;
+    d.block_table = a->block_table;
+    d.k_descale = fp8 ? a->k_descale : nullptr;
+    d.v_descale = fp8 ? a->v_descale : nullptr;
+    d.new_bs = a->new_batch_stride;
+    d.new_ss = a->new_seq_stride;
+    d.new_hs = a->new_head_stride;
+    d.q_bs = a->q_batch_stride;
+    d.q_ss = a->q_seq_stride;
+    d.q_hs = a->q_head_stride;
+    d.qo_bs = a->qo_batch_stride;
+    d.qo_ss = a->qo_seq_stride;
+    d.qo_hs = a->qo_head_stride;
+    d.kv_bs = a->kv_batch_stride;
+    d.kv_ss = a->kv_seq_stride;
+    d.kv_hs = a->kv_head_stride;
+    d.bt_bs = a->block_table ? a->block_table_stride : 0;
+    d.ds_bs = a->descale_batch_stride;
+    d.ro_ss = rotary ? a->rotary_seq_stride : 0;
+    d.seqlen_new = (int32_t)a->seqlen_new;
+    d.seqlen_q = with_q ? (int32_t)a->seqlen_q : 0;
+    d.n_heads = with_q ? (int32_t)a->n_heads : 0;
+    d.n_kv_heads = (int32_t)a->n_kv_heads;
+    d.max_len = (int32_t)(a->block_table ? a->max_pages_per_seq * a->page_size : a->seqlen_cache);
+    d.page_size = a->block_table ? (int32_t)a->page_size : 0;
+    d.num_pages = a->block_table ? (int32_t)a->num_pages : 0;
+    d.rotary_dim = rotary ? (int32_t)a->rotary_dim : 0;
+    d.seqlen_ro = rotary ? (int32_t)a->seqlen_ro : 0;
+    d.interleaved = a->rotary_interleaved != 0;
+    d.causal = a->causal != 0;
+    const hipStream_t s = (hipStream_t)stream;
+    const int batch = (int)a->batch;
+    return bwd_run([&] { return fa::kvcache_append_enqueue(d, batch, a->dtype, fp8, s); }, s, ms);
 }
 
 static void add_slot(const AdaptiveState &ad, int idx, fa_adaptive_info *out) {

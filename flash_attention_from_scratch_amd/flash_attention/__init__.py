@@ -104,7 +104,8 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
 
 
 def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
-                    num_splits=0, timed=False, k_descale=None, v_descale=None):
+                    num_splits=0, timed=False, k_descale=None, v_descale=None, k=None, v=None, rotary_cos=None, rotary_sin=None,
+                    rotary_interleaved=False, advance_seqlens=False):
     """Decode attention against a K / V cache: q (batch, seqlen_q, n_heads, 128) against k_cache / v_cache
     (batch, seqlen_cache, n_kv_heads, 128) -- or, with block_table (batch, max_pages_per_seq) int32, pages (num_pages,
     page_size, n_kv_heads, 128) -- of which cache_seqlens (batch,) int32 ON THE DEVICE says how many keys are valid, the newest
@@ -115,10 +116,33 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
     An fp8 cache: k_cache / v_cache of dtype torch.float8_e4m3fn in the same shapes, q and o still bf16 / fp16.
     k_descale, v_descale: fp32 (batch, n_kv_heads) ON THE DEVICE, None = 1, finite and positive; key j of entry b and K / V head
     h stands for float(k8[j]) * k_descale[b, h], likewise V (quantize_kvcache_fp8 makes such a cache).  Other float8 dtypes,
-    K and V of different dtypes, and descales with a 16-bit cache are refused."""
+    K and V of different dtypes, and descales with a 16-bit cache are refused.
+
+    A fused decode step: with k, v (batch, seqlen_new, n_kv_heads, 128), cache_seqlens counts the keys BEFORE
+    the call (flash-attn's flash_attn_with_kvcache); the new rows are appended in place first (append_kvcache: rotated with
+    rotary_cos / rotary_sin (seqlen_ro, rotary_dim / 2) like q, quantized for an fp8 cache) and the attention covers
+    cache_seqlens + seqlen_new keys.  advance_seqlens=True also writes the new lengths into cache_seqlens.  max_seqlen_k bounds the
+    lengths after the append.  Rotary without k / v, k without v, and rotary under causal with seqlen_new != seqlen_q are refused."""
     return flash_attention_kernels.forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=block_table, causal=causal,
                                                    return_lse=return_lse, max_seqlen_k=max_seqlen_k, num_splits=num_splits, timed=timed,
-                                                   k_descale=k_descale, v_descale=v_descale)
+                                                   k_descale=k_descale, v_descale=v_descale, k=k, v=v, rotary_cos=rotary_cos,
+                                                   rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved,
+                                                   advance_seqlens=advance_seqlens)
+
+
+def append_kvcache(k_cache, v_cache, k, v, cache_seqlens, block_table=None, q=None, rotary_cos=None, rotary_sin=None,
+                   rotary_interleaved=False, causal=False, k_descale=None, v_descale=None, seqlens_out=None):
+    """The step in front of a decode, one HIP kernel: write the new rows k, v (batch, seqlen_new, n_kv_heads, 128)
+    into the cache IN PLACE at positions cache_seqlens[b] + t -- contiguous, or paged through block_table; a token past the
+    capacity is dropped -- rotating the new keys, and q into a new tensor, with rotary_cos / rotary_sin (seqlen_ro, rotary_dim / 2;
+    rotary_interleaved pairs (2 i, 2 i + 1), else (i, i + rotary_dim / 2); bit-identical to fp32 eager torch rounded once), and
+    quantizing for a torch.float8_e4m3fn cache with k_descale / v_descale (the bytes quantize_kvcache_fp8's expression gives).
+    q row i takes position cache_seqlens[b] + i with causal, else cache_seqlens[b].  min(cache_seqlens + seqlen_new, capacity) goes to
+    seqlens_out: None allocates it, cache_seqlens itself advances in place.  -> (seqlens_out, q_rot or None).  The host reads no
+    device array; graph-capturable."""
+    return flash_attention_kernels.append_kvcache(k_cache, v_cache, k, v, cache_seqlens, block_table=block_table, q=q,
+                                                  rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved,
+                                                  causal=causal, k_descale=k_descale, v_descale=v_descale, seqlens_out=seqlens_out)
 
 
 def quantize_kvcache_fp8(k, v):

@@ -519,8 +519,119 @@ def _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_se
     return q, args, True
 
 
+def append_kvcache(k_cache, v_cache, k, v, cache_seqlens, block_table=None, q=None, rotary_cos=None, rotary_sin=None,
+                   rotary_interleaved=False, causal=False, k_descale=None, v_descale=None, seqlens_out=None):
+    """The step in front of a decode (fa_kvcache_append_launch): write the new rows k, v (batch, seqlen_new, n_kv_heads, 128) into
+    the cache IN PLACE at positions cache_seqlens[b] + t (contiguous, or paged through block_table; a token past the capacity is
+    dropped), rotate the new keys -- and q, into a new tensor -- with rotary_cos / rotary_sin (seqlen_ro, rotary_dim / 2) of q's
+    dtype, quantize for a torch.float8_e4m3fn cache with k_descale / v_descale (the bytes of quantize_kvcache_fp8's expression), and
+    write min(cache_seqlens + seqlen_new, capacity) to seqlens_out (None: a new tensor; cache_seqlens itself: in place).
+    q row i is rotated at position cache_seqlens[b] + i with causal, else at cache_seqlens[b].  -> (seqlens_out, q_rot or None).
+    One kernel on the current stream; the host reads no device array; graph-capturable."""
+    for t, name in ((k_cache, "k_cache"), (v_cache, "v_cache"), (k, "k"), (v, "v"), (cache_seqlens, "cache_seqlens")):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{name} must be a tensor")
+    rotary = rotary_cos is not None or rotary_sin is not None
+    if rotary and (rotary_cos is None or rotary_sin is None):
+        raise RuntimeError("rotary_cos and rotary_sin come together")
+    if q is not None and not rotary:
+        raise RuntimeError("q is given without rotary_cos / rotary_sin: there is nothing to do to it")
+    dev = k_cache.device
+    named = [(k_cache, "k_cache"), (v_cache, "v_cache"), (k, "k"), (v, "v"), (cache_seqlens, "cache_seqlens"), (block_table, "block_table"),
+             (q, "q"), (rotary_cos, "rotary_cos"), (rotary_sin, "rotary_sin"), (k_descale, "k_descale"), (v_descale, "v_descale"),
+             (seqlens_out, "seqlens_out")]
+    for t, name in named:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+        if t.device != dev:
+            raise RuntimeError(f"{name} must be on k_cache's device ({dev}, got {t.device})")
+    if k.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError("Only fp16 and bf16 are supported")
+    if v.dtype != k.dtype or any(t is not None and t.dtype != k.dtype for t in (q, rotary_cos, rotary_sin)):
+        raise RuntimeError("Input tensors must have the same data type (k, v, q, rotary_cos, rotary_sin)")
+    fp8 = k_cache.dtype in _FLOAT8_DTYPES or v_cache.dtype in _FLOAT8_DTYPES
+    if k_cache.dtype != v_cache.dtype:
+        raise RuntimeError(f"k_cache and v_cache must have one data type (got {k_cache.dtype} and {v_cache.dtype})")
+    if fp8 and k_cache.dtype != torch.float8_e4m3fn:
+        raise RuntimeError(f"an fp8 cache must be torch.float8_e4m3fn (got {k_cache.dtype})")
+    if not fp8 and k_cache.dtype != k.dtype:
+        raise RuntimeError("Input tensors must have the same data type")
+    if not fp8 and (k_descale is not None or v_descale is not None):
+        raise RuntimeError("k_descale / v_descale belong to an fp8 (torch.float8_e4m3fn) cache; this cache is 16-bit")
+    if k.dim() != 4 or k.shape != v.shape or k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[2:] != k.shape[2:]:
+        raise RuntimeError("k and v must have one shape (batch, seqlen_new, n_kv_heads, d_head), k_cache and v_cache one shape (batch or "
+                           "num_pages, seqlen_cache or page_size, n_kv_heads, d_head)")
+    batch, seqlen_new, n_kv_heads, d_head = k.shape
+    if block_table is None and k_cache.shape[0] != batch:
+        raise RuntimeError("a contiguous cache needs k's batch size (pass block_table for a paged cache)")
+    if cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (batch,) or not cache_seqlens.is_contiguous():
+        raise RuntimeError("cache_seqlens must be a contiguous int32 tensor of batch entries on the cache's device")
+    if seqlens_out is not None and (seqlens_out.dtype != torch.int32 or tuple(seqlens_out.shape) != (batch,) or not seqlens_out.is_contiguous()):
+        raise RuntimeError("seqlens_out must be a contiguous int32 tensor of batch entries on the cache's device (or cache_seqlens itself)")
+    if block_table is not None and (block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != batch
+                                    or block_table.stride(1) != 1):
+        raise RuntimeError("block_table must be an int32 (batch, max_pages_per_seq) tensor on the cache's device with a contiguous last dimension")
+    for t, name in ((k_descale, "k_descale"), (v_descale, "v_descale")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (batch, n_kv_heads) or not t.is_contiguous()):
+            raise RuntimeError(f"{name} must be a contiguous fp32 (batch, n_kv_heads) = ({batch}, {n_kv_heads}) tensor on the cache's device")
+    if rotary:
+        if rotary_cos.dim() != 2 or rotary_cos.shape != rotary_sin.shape or rotary_cos.shape[0] < 1:
+            raise RuntimeError("rotary_cos and rotary_sin must have one shape (seqlen_ro, rotary_dim / 2)")
+        rotary_dim = 2 * rotary_cos.shape[1]
+        if rotary_dim % 16 != 0 or not 16 <= rotary_dim <= d_head:
+            raise RuntimeError(f"rotary_dim (2 * rotary_cos.shape[1] = {rotary_dim}) must be a multiple of 16 in [16, {d_head}]")
+        if _decode_needs_copy(rotary_cos) or _decode_needs_copy(rotary_sin) or rotary_cos.stride() != rotary_sin.stride():
+            rotary_cos, rotary_sin = rotary_cos.contiguous(), rotary_sin.contiguous()
+    if q is not None:
+        if q.dim() != 4 or q.shape[0] != batch or q.shape[3] != d_head or q.shape[2] % n_kv_heads != 0:
+            raise RuntimeError("q must have shape (batch, seqlen_q, n_heads, d_head) with k's batch and d_head and n_heads a multiple of n_kv_heads")
+        if _decode_needs_copy(q):
+            q = q.contiguous()
+    if _decode_needs_copy(k) or _decode_needs_copy(v) or k.stride() != v.stride():
+        k, v = k.contiguous(), v.contiguous()
+    kv_unit = 16 if fp8 else 8   # 16 bytes
+    if (_decode_needs_copy(k_cache) or _decode_needs_copy(v_cache) or k_cache.stride() != v_cache.stride()
+            or any(s % kv_unit for s in k_cache.stride()[:-1])):
+        raise RuntimeError(f"k_cache and v_cache need one stride set, a contiguous last dimension, strides that are multiples of {kv_unit} "
+                           "elements and a 16-byte aligned base")
+    with torch.cuda.device(dev):
+        if seqlens_out is None:
+            seqlens_out = torch.empty_like(cache_seqlens)
+        q_out = torch.empty(q.shape, dtype=q.dtype, device=dev) if q is not None else None
+        paged = block_table is not None
+        args = _capi.make_kvcache_append_args(
+            dtype=15 if k.dtype == torch.bfloat16 else 5, kv_dtype=_capi.FA_KV_FP8_E4M3FN if fp8 else 0, causal=1 if causal else 0,
+            rotary_interleaved=1 if rotary_interleaved else 0,
+            k_new=k.data_ptr(), v_new=v.data_ptr(), k=k_cache.data_ptr(), v=v_cache.data_ptr(),
+            q=q.data_ptr() if q is not None else None, q_out=q_out.data_ptr() if q is not None else None,
+            rotary_cos=rotary_cos.data_ptr() if rotary else None, rotary_sin=rotary_sin.data_ptr() if rotary else None,
+            cache_seqlens=cache_seqlens.data_ptr(), seqlens_out=seqlens_out.data_ptr(),
+            block_table=block_table.data_ptr() if paged else None,
+            k_descale=k_descale.data_ptr() if k_descale is not None else None,
+            v_descale=v_descale.data_ptr() if v_descale is not None else None,
+            batch=batch, seqlen_new=seqlen_new, seqlen_q=q.shape[1] if q is not None else 0, n_heads=q.shape[2] if q is not None else 0,
+            n_kv_heads=n_kv_heads, d_head=d_head, seqlen_cache=0 if paged else k_cache.shape[1],
+            num_pages=k_cache.shape[0] if paged else 0, page_size=k_cache.shape[1] if paged else 0,
+            max_pages_per_seq=block_table.shape[1] if paged else 0, block_table_stride=block_table.stride(0) if paged else 0,
+            rotary_dim=rotary_dim if rotary else 0, seqlen_ro=rotary_cos.shape[0] if rotary else 0,
+            rotary_seq_stride=rotary_cos.stride(0) if rotary else 0,
+            new_batch_stride=k.stride(0), new_seq_stride=k.stride(1), new_head_stride=k.stride(2),
+            kv_batch_stride=k_cache.stride(0), kv_seq_stride=k_cache.stride(1), kv_head_stride=k_cache.stride(2),
+            descale_batch_stride=n_kv_heads,
+        )
+        if q is not None:
+            args.q_batch_stride, args.q_seq_stride, args.q_head_stride = q.stride(0), q.stride(1), q.stride(2)
+            args.qo_batch_stride, args.qo_seq_stride, args.qo_head_stride = q_out.stride(0), q_out.stride(1), q_out.stride(2)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _capi.check(_capi.load().fa_kvcache_append_launch(ctypes.byref(args), stream, None))
+    return seqlens_out, q_out
+
+
 def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
-                    num_splits=0, timed=False, k_descale=None, v_descale=None):
+                    num_splits=0, timed=False, k_descale=None, v_descale=None, k=None, v=None, rotary_cos=None, rotary_sin=None,
+                    rotary_interleaved=False, advance_seqlens=False):
     """Decode attention against a K / V cache (fa_decode_launch): q (batch, seqlen_q, n_heads, 128); k_cache, v_cache
     (batch, seqlen_cache, n_kv_heads, 128), or with block_table (batch, max_pages_per_seq) int32 on the device
     (num_pages, page_size, n_kv_heads, 128); cache_seqlens (batch,) int32 on the device, the valid keys of each entry (the
@@ -528,7 +639,27 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
     reads neither cache_seqlens nor block_table; no device synchronisation unless timed.  The caches pass as they are (strided
     views included) and are refused if the launch cannot address them; q is copied if it has to be.
     A torch.float8_e4m3fn cache takes fa_decode_fp8_launch: k_descale, v_descale (fp32 (batch, n_kv_heads) on the device, None = 1;
-    never read by the host) scale the cache's values, key j of entry b and K / V head h standing for float(k8[j]) * k_descale[b, h]."""
+    never read by the host) scale the cache's values, key j of entry b and K / V head h standing for float(k8[j]) * k_descale[b, h].
+    With k, v (batch, seqlen_new, n_kv_heads, 128): cache_seqlens counts the keys BEFORE this call (flash-attn's meaning);
+    append_kvcache writes the new rows first (rotating them and q with rotary_cos / rotary_sin, quantizing for an fp8 cache), and
+    the attention runs over cache_seqlens + seqlen_new keys with the rotated q, on the same stream.  advance_seqlens writes the new
+    lengths into cache_seqlens in place (one captured graph is then a whole decode step).  max_seqlen_k bounds the lengths after
+    the append; timed's ms stays the decode's alone."""
+    if k is not None or v is not None or rotary_cos is not None or rotary_sin is not None or advance_seqlens:
+        if k is None or v is None:
+            raise RuntimeError("k and v come together; rotary_cos / rotary_sin and advance_seqlens need them (the append is what they act on)")
+        rotary = rotary_cos is not None or rotary_sin is not None
+        if rotary and causal and k.dim() == 4 and q.dim() == 4 and k.shape[1] != q.shape[1]:
+            raise RuntimeError(f"rotary with causal needs seqlen_new == seqlen_q (got {k.shape[1]} and {q.shape[1]}): query row i is "
+                               "rotated at the position of new key i")
+        if q.dim() == 4 and k.dim() == 4 and q.shape[0] != k.shape[0]:
+            raise RuntimeError("k and v need q's batch size")
+        cache_seqlens, q_rot = append_kvcache(k_cache, v_cache, k, v, cache_seqlens, block_table=block_table, q=q if rotary else None,
+                                              rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved,
+                                              causal=causal, k_descale=k_descale, v_descale=v_descale,
+                                              seqlens_out=cache_seqlens if advance_seqlens else None)
+        if rotary:
+            q = q_rot
     q, args, fp8 = _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_seqlen_k, num_splits, k_descale, v_descale)
     batch, seqlen_q, n_heads, d_head = q.shape
     o = torch.empty((batch, seqlen_q, n_heads, d_head), dtype=q.dtype, device=q.device)

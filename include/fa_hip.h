@@ -512,7 +512,7 @@ int fa_bwd_launch_varlen_qk(const fa_bwd_varlen_qk_args *args, void *stream, flo
  *     block_table is a DEVICE (batch, max_pages_per_seq) int32 array, row stride block_table_stride: key j of batch entry b
  *     is row j % page_size of page block_table[b][j / page_size].
  * cache_seqlens: DEVICE (batch) int32, the number of valid keys of each entry, the newest tokens (which the caller has already
- * written into the cache) included.  The host never reads it or block_table: launches are asynchronous and graph-capturable,
+ * written into the cache, with fa_kvcache_append_launch for one) included.  The host never reads it or block_table: launches are asynchronous and graph-capturable,
  * and every grid and split count is a function of the host-visible arguments alone.
  * causal: bottom-right aligned -- query row i sees keys j <= len - seqlen_q + i; else every row sees all len keys.  A row that
  * sees no key gives o = 0 and lse = -inf.  lse (may be null): fp32 (batch, n_heads, seqlen_q), natural log, contiguous.
@@ -634,6 +634,86 @@ int fa_decode_fp8_supported(const fa_decode_fp8_args *args);
 int fa_decode_fp8_num_splits(const fa_decode_fp8_args *args);          /* the split count the launch uses, or a negative fa_status */
 int64_t fa_decode_fp8_workspace_bytes(const fa_decode_fp8_args *args); /* bytes, or a negative fa_status */
 int fa_decode_fp8_launch(const fa_decode_fp8_args *args, void *stream, float *ms);
+
+/*
+ * The step in front of a decode: append seqlen_new new K / V rows per batch entry to the cache IN PLACE, at the positions the
+ * device-side lengths name, optionally rotate the new keys and the query (rotary embedding), quantize for an fp8 cache, and
+ * advance the lengths.  One kernel on `stream`; the host reads none of the device arrays, so the launch is asynchronous and
+ * graph-capturable, and fa_decode_launch / fa_decode_fp8_launch behind it on the same stream sees the appended cache.
+ *
+ * Per batch entry b, len = clamp(cache_seqlens[b], 0, capacity) (capacity as in fa_decode_args):
+ *  - k_new, v_new (batch, seqlen_new, n_kv_heads, 128), dtype, one stride set (new_*): row t goes to cache position len + t,
+ *    addressed as fa_decode_args addresses the cache (contiguous, or paged through block_table with every entry used clamped to
+ *    [0, num_pages)); a token whose position is >= capacity is dropped.  kv_dtype 0: the cache has q's dtype and the kv_*
+ *    strides count its elements; FA_KV_FP8_E4M3FN: e4m3fn bytes, strides in bytes, and the row is stored as
+ *    e4m3fn(clamp(x / descale[b][h], -448, 448)) -- IEEE fp32 division, round to nearest even, NaN stays NaN (0x7f / 0xff): the
+ *    bytes of torch's (x.float() / descale).clamp(-448, 448).to(torch.float8_e4m3fn).  k_descale / v_descale as in
+ *    fa_decode_fp8_args (null = 1); they belong to an fp8 cache only.
+ *  - rotary_cos, rotary_sin (both or neither): (seqlen_ro, rotary_dim / 2) tables of dtype, row stride rotary_seq_stride;
+ *    rotary_dim a multiple of 16 in [16, 128], elements at or beyond it pass through.  rotary_interleaved 0 pairs element i with
+ *    i + rotary_dim / 2, 1 pairs 2 i with 2 i + 1; o1 = x1 c - x2 s, o2 = x1 s + x2 c in fp32 with unfused multiplies and adds,
+ *    rounded once to dtype (the bits of the same expression in eager torch).  The key at position p uses table row
+ *    min(p, seqlen_ro - 1).  V is never rotated; without tables K is copied bit for bit.
+ *  - q (batch, seqlen_q, n_heads, 128), with tables only, is rotated into q_out (same shape, its own strides; must not overlap
+ *    q): row i uses position len + i with causal, else len (flash-attn's rule).  q may be null (keys only).
+ *  - seqlens_out[b] = min(len + seqlen_new, capacity).  seqlens_out may be cache_seqlens itself (in-place advance): entry b is
+ *    read and written by one workgroup, the store behind a barrier.
+ * Two batch entries that map to one page are the caller's contract violation: the result there is undefined, the addresses
+ * stay in range.  seqlen_new = 0 is served (a given q is rotated, the lengths are copied); k_new / v_new may then be null.
+ * Refused before any HIP call: null pointers, q without q_out (FA_ERR_NULL); dtype, kv_dtype (FA_ERR_DTYPE); page_size % 64 != 0
+ * (FA_ERR_NO_KERNEL); struct_size, sizes, strides not positive, rotary_dim not a multiple of 16 in [16, 128], one table
+ * without the other, q without tables, q_out overlapping q, descales with a 16-bit cache (FA_ERR_SHAPE);
+ * strides not multiples of 16 bytes, tensors and tables not 16-byte aligned, int32 / fp32 arrays not 4-byte aligned
+ * (FA_ERR_ALIGN).  batch = 0 returns FA_OK without a device.
+ */
+typedef struct fa_kvcache_append_args {
+    uint32_t struct_size;      /* sizeof(fa_kvcache_append_args) */
+    int32_t dtype;             /* fa_dtype of k_new, v_new, q, q_out and the tables */
+    int32_t kv_dtype;          /* 0 = the cache has dtype; or fa_kv_dtype */
+    int32_t causal;            /* only the position rule of q */
+    int32_t rotary_interleaved;
+    const void *k_new;
+    const void *v_new;
+    void *k;                   /* the cache, written in place */
+    void *v;
+    const void *q;             /* may be null */
+    void *q_out;
+    const void *rotary_cos;    /* both null = no rotary */
+    const void *rotary_sin;
+    const int32_t *cache_seqlens;
+    int32_t *seqlens_out;      /* may be cache_seqlens */
+    const int32_t *block_table;   /* null = contiguous cache */
+    const float *k_descale;    /* fp8 cache only; DEVICE (batch, n_kv_heads) fp32, may be null (= 1) */
+    const float *v_descale;
+    int64_t batch;
+    int64_t seqlen_new;
+    int64_t seqlen_q;          /* ignored without q */
+    int64_t n_heads;           /* ignored without q */
+    int64_t n_kv_heads;
+    int64_t d_head;
+    int64_t seqlen_cache;      /* contiguous cache: rows per batch entry (ignored when paged) */
+    int64_t num_pages;         /* paged cache only, like the next three */
+    int64_t page_size;
+    int64_t max_pages_per_seq;
+    int64_t block_table_stride;
+    int64_t rotary_dim;        /* with tables only */
+    int64_t seqlen_ro;
+    int64_t rotary_seq_stride;
+    int64_t new_batch_stride;
+    int64_t new_seq_stride;
+    int64_t new_head_stride;
+    int64_t q_batch_stride;
+    int64_t q_seq_stride;
+    int64_t q_head_stride;
+    int64_t qo_batch_stride;   /* q_out's */
+    int64_t qo_seq_stride;
+    int64_t qo_head_stride;
+    int64_t kv_batch_stride;   /* elements of the cache's type; paged: the page stride */
+    int64_t kv_seq_stride;
+    int64_t kv_head_stride;
+    int64_t descale_batch_stride;   /* elements; >= n_kv_heads when a descale is given */
+} fa_kvcache_append_args;
+int fa_kvcache_append_launch(const fa_kvcache_append_args *args, void *stream, float *ms);
 
 /* The adaptive speculative mode's record on `device` (fa_speculative_mode), and a reset of its demotion state (tests,
  * or a caller that knows its data has changed character). */
