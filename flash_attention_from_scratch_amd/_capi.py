@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "fa_decode_supported", "fa_decode_num_splits", "fa_decode_workspace_bytes", "fa_decode_launch",
     "fa_decode_fp8_supported", "fa_decode_fp8_num_splits", "fa_decode_fp8_workspace_bytes", "fa_decode_fp8_launch",
     "fa_kvcache_append_launch",
+    "fa_fwd_varlen_kvcache_supported", "fa_fwd_launch_varlen_kvcache",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -206,6 +207,23 @@ def make_kvcache_append_args(**fields):
     return a
 
 
+class FaKvcacheLayout(ctypes.Structure):   # fa_kvcache_layout (the key side of a prefill: a contiguous or paged cache, lengths on the device)
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("cache_seqlens", ctypes.c_void_p), ("block_table", ctypes.c_void_p),
+        ("seqlen_cache", ctypes.c_int64), ("num_pages", ctypes.c_int64), ("page_size", ctypes.c_int64),
+        ("max_pages_per_seq", ctypes.c_int64), ("block_table_stride", ctypes.c_int64), ("max_seqlen_k", ctypes.c_int64),
+        ("batch", ctypes.c_int64),
+    ]
+
+
+def make_kvcache_layout(**fields):
+    """fa_kvcache_layout with struct_size set; everything not given is 0 / null."""
+    a = FaKvcacheLayout(struct_size=ctypes.sizeof(FaKvcacheLayout))
+    for name, value in fields.items():
+        setattr(a, name, value)
+    return a
+
+
 def make_varlen_layout(cu_seqlens_ptr, n_seqs, total_tokens, max_seqlen):
     return FaVarlenLayout(struct_size=ctypes.sizeof(FaVarlenLayout), cu_seqlens=cu_seqlens_ptr, n_seqs=n_seqs,
                           total_tokens=total_tokens, max_seqlen=max_seqlen)
@@ -333,6 +351,11 @@ def load():
     lib.fa_fwd_launch_varlen_qk.restype = ctypes.c_int
     lib.fa_fwd_launch_varlen_qk.argtypes = [args_p, ctypes.POINTER(FaKvLayout), ctypes.POINTER(FaVarlenLayout), ctypes.POINTER(FaVarlenLayout),
                                             ctypes.POINTER(FaFwdOpts), ctypes.c_void_p, ctypes.c_void_p]
+    lib.fa_fwd_varlen_kvcache_supported.restype = ctypes.c_int
+    lib.fa_fwd_varlen_kvcache_supported.argtypes = [cfg_p, ctypes.POINTER(FaFwdOpts)]
+    lib.fa_fwd_launch_varlen_kvcache.restype = ctypes.c_int
+    lib.fa_fwd_launch_varlen_kvcache.argtypes = [args_p, ctypes.POINTER(FaKvLayout), ctypes.POINTER(FaVarlenLayout),
+                                                 ctypes.POINTER(FaKvcacheLayout), ctypes.POINTER(FaFwdOpts), ctypes.c_void_p, ctypes.c_void_p]
     lib.fa_bwd_varlen_qk_workspace_bytes.restype = ctypes.c_int64
     lib.fa_bwd_varlen_qk_workspace_bytes.argtypes = [ctypes.POINTER(FaBwdVarlenQKArgs)]
     lib.fa_bwd_launch_varlen_qk.restype = ctypes.c_int

@@ -47,6 +47,9 @@ hipError_t bwd_gqa_enqueue(const BwdGqaArgs &g, int dtype, bool causal, hipStrea
 kernel_fn_varlen varlen_kernel_dt15(bool first_block_skip);
 kernel_fn_varlen varlen_kernel_dt5(bool first_block_skip);
 int varlen_lds_bytes_dt15();
+// fa_inst_varlen_kvcache.hip: the same forward with its keys taken from a KV cache (the varlen form's LDS)
+kernel_fn_varlen_kvcache varlen_kvcache_kernel_dt15(bool first_block_skip);
+kernel_fn_varlen_kvcache varlen_kvcache_kernel_dt5(bool first_block_skip);
 // fa_bwd_varlen.hip / fa_bwd_varlen_qk.hip: the packed backward, and its form with separate Q and K / V lengths
 hipError_t bwd_varlen_enqueue(const BwdVarlenArgs &a, int dtype, bool causal, hipStream_t s);
 hipError_t bwd_varlen_qk_enqueue(const BwdVarlenQKArgs &a, int dtype, bool causal, hipStream_t s);
@@ -279,6 +282,17 @@ void do_init_body(int dev, DeviceState *st) {
             st->status = FA_ERR_LAUNCH;
             snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, varlen form) on device %d: %s", fa::varlen_lds_bytes_dt15(),
                      dev, hipGetErrorString(rc));
+            return;
+        }
+    }
+    // ... and its form against a KV cache (fa_fwd_launch_varlen_kvcache)
+    for (int i = 0; i < 4; ++i) {
+        const void *fn = (i & 2) ? (const void *)fa::varlen_kvcache_kernel_dt5((i & 1) != 0) : (const void *)fa::varlen_kvcache_kernel_dt15((i & 1) != 0);
+        const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, fa::varlen_lds_bytes_dt15());
+        if (rc != hipSuccess) {
+            st->status = FA_ERR_LAUNCH;
+            snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, varlen KV-cache form) on device %d: %s",
+                     fa::varlen_lds_bytes_dt15(), dev, hipGetErrorString(rc));
             return;
         }
     }
@@ -981,10 +995,51 @@ const fa::KernelEntry *varlen_entry(const fa_fwd_config *cfg, const char **why) 
 const char *kNoVarlen = "packed variable-length sequences are served by the (B_r 128, B_c 64, 4 warps) + buffer configuration at d_head "
                         "128 only, plain or causal, without speculative, prescaled_q and stats";
 
+// the cache side of fa_fwd_launch_varlen_kvcache: fa_decode_launch's rules for the same fields (kv and vq: already validated)
+int64_t kvcache_capacity(const fa_kvcache_layout *kc) { return kc->block_table ? kc->max_pages_per_seq * kc->page_size : kc->seqlen_cache; }
+int kvcache_validate(const fa_kvcache_layout *kc, const fa_kv_layout *kv, const fa_varlen_layout *vq) {
+    if (kc->struct_size < sizeof(fa_kvcache_layout))
+        return fail(FA_ERR_SHAPE, "fa_kvcache_layout.struct_size (%u) is smaller than this library's (%zu)", kc->struct_size,
+                    sizeof(fa_kvcache_layout));
+    if (!kc->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to n_seqs int32 lengths is needed");
+    if (kc->block_table) {
+        if (kc->page_size <= 0 || kc->num_pages <= 0 || kc->max_pages_per_seq <= 0)
+            return fail(FA_ERR_SHAPE, "paged cache: num_pages, page_size and max_pages_per_seq must be positive");
+        if (kc->page_size % 64 != 0)
+            return fail(FA_ERR_NO_KERNEL, "paged cache: page_size must be a multiple of 64 (got %lld)", (long long)kc->page_size);
+        if (kc->block_table_stride < kc->max_pages_per_seq)
+            return fail(FA_ERR_SHAPE, "block_table_stride (%lld) is smaller than max_pages_per_seq (%lld)", (long long)kc->block_table_stride,
+                        (long long)kc->max_pages_per_seq);
+        if (kc->num_pages > INT32_MAX / 2 || kc->page_size > INT32_MAX / 2 || kc->max_pages_per_seq > INT32_MAX / 2 ||
+            kc->block_table_stride > INT32_MAX / 2)
+            return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
+    } else if (kc->seqlen_cache <= 0) {
+        return fail(FA_ERR_SHAPE, "seqlen_cache must be positive (got %lld)", (long long)kc->seqlen_cache);
+    } else if (kc->batch != vq->n_seqs) {
+        return fail(FA_ERR_SHAPE, "a contiguous cache needs one batch entry per sequence: batch (%lld) must equal n_seqs (%lld)",
+                    (long long)kc->batch, (long long)vq->n_seqs);
+    }
+    const int64_t cap = kvcache_capacity(kc);
+    if (cap > INT32_MAX / 2) return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
+    if (kc->max_seqlen_k < 0 || kc->max_seqlen_k > cap)
+        return fail(FA_ERR_SHAPE, "max_seqlen_k (%lld) must lie in [0, %lld] (0 = the cache's capacity)", (long long)kc->max_seqlen_k, (long long)cap);
+    const int64_t entries = kc->block_table ? kc->num_pages : vq->n_seqs;
+    if (kv->kv_batch_stride < 0 || (entries > 1 && kv->kv_batch_stride == 0))
+        return fail(FA_ERR_SHAPE, "kv strides must be positive (the cache's %s stride is %lld elements)", kc->block_table ? "page" : "batch",
+                    (long long)kv->kv_batch_stride);
+    if (kv->kv_batch_stride & 7) return fail(FA_ERR_ALIGN, "kv strides must be multiples of 8 elements (16 bytes)");
+    if (((uintptr_t)kc->cache_seqlens | (uintptr_t)kc->block_table) & 3)
+        return fail(FA_ERR_ALIGN, "cache_seqlens and block_table must be 4-byte aligned");
+    return FA_OK;
+}
+
 // the forward of `entry` (a public entry point; `total`: its name for the query side's total)
+// `kc` non-null: the key side is a KV cache (fa_fwd_launch_varlen_kvcache), and vk is not used
 int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
-                      const fa_varlen_layout *vk, const fa_fwd_opts *opts, float *lse, void *stream) {
-    if (!args || !kv || !vq || !vk) return fail(FA_ERR_NULL, "null pointer argument");
+                      const fa_varlen_layout *vk, const fa_fwd_opts *opts, float *lse, void *stream, const fa_kvcache_layout *kc = nullptr,
+                      bool cache_side = false) {
+    if (cache_side) vk = vq;   // (one valid layout for the checks both launches share)
+    if (!args || !kv || !vq || !vk || (cache_side && !kc)) return fail(FA_ERR_NULL, "null pointer argument");
     if (!args->q || !args->k || !args->v || !args->o) return fail(FA_ERR_NULL, "null pointer argument");
     if (!lse) return fail(FA_ERR_NULL, "lse is null: %s needs a (n_heads, %s) fp32 buffer", entry, total);
     if (args->cfg.dtype != FA_FP16 && args->cfg.dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
@@ -1007,6 +1062,7 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
     if (((uintptr_t)args->q | (uintptr_t)args->k | (uintptr_t)args->v | (uintptr_t)args->o) & 15)
         return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
     if ((uintptr_t)lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
+    if (cache_side && (rc = kvcache_validate(kc, kv, vq)) != FA_OK) return rc;
     if (vq->total_tokens == 0) {   // (no query rows: nothing to write)
         if (o.ms) *o.ms = 0.0f;
         return FA_OK;
@@ -1015,8 +1071,9 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
     if (!dev) return rc;
     const char *why;
     const fa::KernelEntry *e = varlen_entry(&args->cfg, &why);
+    fa::KernelArgsVarlenKVCache ca;
     fa::KernelArgsVarlenQK qa;
-    fa::KernelArgsVarlen &va = qa.v;
+    fa::KernelArgsVarlen &va = cache_side ? ca.v : qa.v;
     va.base.q = args->q;
     va.base.k = args->k;
     va.base.v = args->v;
@@ -1042,10 +1099,23 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
     qa.max_seqlen_k = (int32_t)vk->max_seqlen;
     const bool fbs = e->softmax_mode == FA_SOFTMAX_FIRST_BLOCK_SKIP;
     const void *fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kernel_dt15(fbs) : (const void *)fa::varlen_kernel_dt5(fbs);
+    void *kernel_args = &qa;
+    if (cache_side) {
+        const int64_t cap = kvcache_capacity(kc);
+        ca.cache_seqlens = kc->cache_seqlens;
+        ca.block_table = kc->block_table;
+        ca.page_stride = kv->kv_batch_stride;
+        ca.bt_stride = kc->block_table ? (int32_t)kc->block_table_stride : 0;
+        ca.num_pages = kc->block_table ? (int32_t)kc->num_pages : (int32_t)vq->n_seqs;
+        ca.tiles_per_page = (int32_t)(kc->block_table ? kc->page_size / 64 : (cap + 63) / 64);   // (contiguous: one "page" per entry)
+        ca.max_len = (int32_t)(kc->max_seqlen_k > 0 ? kc->max_seqlen_k : cap);
+        fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kvcache_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_kernel_dt5(fbs);
+        kernel_args = &ca;
+    }
     const dim3 grid((unsigned)(va.base.n_bh * va.base.n_q_blocks)), block((unsigned)e->threads);
     const hipStream_t s = (hipStream_t)stream;
     return bwd_run([&] {
-        void *params[] = {&qa};
+        void *params[] = {kernel_args};
         return hipLaunchKernel(fn, grid, block, params, (size_t)e->lds_bytes, s);
     }, s, o.ms);
 }
@@ -1200,6 +1270,13 @@ int fa_fwd_launch_varlen(const fa_fwd_args *args, const fa_kv_layout *kv, const 
 int fa_fwd_launch_varlen_qk(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_varlen_layout *vk,
                             const fa_fwd_opts *opts, float *lse, void *stream) {
     return fwd_launch_varlen("fa_fwd_launch_varlen_qk", "total_q", args, kv, vq, vk, opts, lse, stream);
+}
+
+int fa_fwd_varlen_kvcache_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
+
+int fa_fwd_launch_varlen_kvcache(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_kvcache_layout *kc,
+                                 const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true);
 }
 
 int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *a) {

@@ -431,6 +431,26 @@ struct KernelArgsVarlenQK {
     int32_t total_k, max_seqlen_k;
 };
 typedef void (*kernel_fn_varlen)(const KernelArgsVarlenQK);
+// VARLEN against a KV cache (prefill behind a cached prefix: fa_fwd_launch_varlen_kvcache): fa_fwd_kernel_varlen_kvcache is
+// fa_fwd_kernel_varlen whose sequence b takes its key rows from a cache instead of a packed range.  Only
+// fa_inst_varlen_kvcache.hip defines FA_KERNEL_VARLEN_KVCACHE (beside FA_KERNEL_VARLEN) and gets that kernel INSTEAD of
+// fa_fwd_kernel_varlen.  len_k = cache_seqlens[b], clamped to [0, max_len]; tile t (keys 64 t ..) lies at
+//   page_stride * entry + (t % tiles_per_page) * 64 * kv_seq_stride + kv_head * kv_head_stride      (elements from k / v)
+// with entry = clamp(block_table[b][t / tiles_per_page], 0, num_pages - 1), or = b for a contiguous cache (block_table null:
+// page_stride is the batch stride and tiles_per_page covers the whole cache, so the page index is always 0).  A tile lies in one
+// page (page_size % 64 == 0), so only this workgroup-uniform base differs from the packed kernel; the per-lane offsets, the
+// ragged-tile rule (rows beyond len_k are fetched from row len_k - 1, the same tile, the same page), the masks, the MFMA /
+// softmax body and the epilogue are its text.  Only table entries of pages below ceil(len_k / page_size) are read.
+struct KernelArgsVarlenKVCache {
+    KernelArgsVarlen v;            // the QUERY side, as in KernelArgsVarlenQK; kv_seq_stride, kv_head_stride: the cache's
+    const int32_t *cache_seqlens;  // (n_seqs) valid keys per sequence (DEVICE)
+    const int32_t *block_table;    // (n_seqs, bt_stride) page numbers (DEVICE), or null: contiguous cache
+    int64_t page_stride;           // elements between pages (contiguous cache: between batch entries)
+    int32_t bt_stride, num_pages;
+    int32_t tiles_per_page;        // page_size / 64 (contiguous cache: ceil(seqlen_cache / 64))
+    int32_t max_len;               // min(capacity, max_seqlen_k)
+};
+typedef void (*kernel_fn_varlen_kvcache)(const KernelArgsVarlenKVCache);
 #ifdef FA_KERNEL_VARLEN
 #define FA_KV_SS32 kv_ss
 #define FA_SEQ_LEN v_seq_len
@@ -468,7 +488,11 @@ __global__ void
 #ifdef FA_KERNEL_VARLEN
 // (one workgroup per SIMD set: with m live up to the LSE store the 256-register budget of two waves per SIMD spills)
 __launch_bounds__(NWAVES * 64, 1)
+#ifdef FA_KERNEL_VARLEN_KVCACHE
+fa_fwd_kernel_varlen_kvcache(const KernelArgsVarlenKVCache qa) {
+#else
 fa_fwd_kernel_varlen(const KernelArgsVarlenQK qa) {
+#endif
     static_assert(MASK && DMA && KSPLIT == 1 && ABL == 0 && QT == 1, "the varlen form is the masked LDS-DMA kernel");
     const KernelArgsVarlen &va = qa.v;  // (the query side)
     const KernelArgs &args = va.base;   // (seq_len and n_kv_blocks are the sequence's: FA_SEQ_LEN, FA_N_KV_BLOCKS)
@@ -546,6 +570,11 @@ fa_fwd_kernel(const KernelArgs args) {
     if ((int64_t)qb * TR::kBr >= v_len) return;   // (workgroup-uniform; before any barrier or DMA)
     // ... and its key rows from cu_seqlens_k, by the same rule against total_k and max_seqlen_k
     const int q_len = (int)v_len;
+#ifdef FA_KERNEL_VARLEN_KVCACHE
+    // ... and its key count from cache_seqlens, clamped to [0, max_len]; the rows themselves are found tile by tile (kc_*)
+    int64_t k_row0 = 0, k_len = qa.cache_seqlens[b];
+    k_len = k_len < 0 ? 0 : (k_len > qa.max_len ? qa.max_len : k_len);
+#else
     int64_t k_row0 = qa.cu_seqlens_k[b], k_len = qa.cu_seqlens_k[b + 1];
     k_row0 = k_row0 < 0 ? 0 : (k_row0 > qa.total_k ? qa.total_k : k_row0);
     k_len -= k_row0;
@@ -553,6 +582,7 @@ fa_fwd_kernel(const KernelArgs args) {
         const int64_t cap = qa.total_k - k_row0 < qa.max_seqlen_k ? qa.total_k - k_row0 : qa.max_seqlen_k;
         k_len = k_len < 0 ? 0 : (k_len > cap ? cap : k_len);
     }
+#endif
     const int v_seq_len = (int)k_len;          // FA_SEQ_LEN, FA_N_KV_BLOCKS, ragged_rows and the key clamp: the K range
     const int kq_shift = v_seq_len - q_len;    // bottom-right diagonal: query r sees keys <= r + kq_shift
     // len_q for the epilogue's row tests, parked in a vector register across the loop (the scalar file is full there: held
@@ -632,6 +662,38 @@ fa_fwd_kernel(const KernelArgs args) {
         v_off[j] = (unsigned)(((8 * (sub / DSUB) + v_lane_row) * FA_KV_SS32 + (sub % DSUB) * 32 + v_lane_d) * 2);
     }
     const int64_t tile_stride = (int64_t)BC * FA_KV_SS32;  // elements between consecutive KV blocks
+#ifdef FA_KERNEL_VARLEN_KVCACHE
+    // The walk over the cache's tiles, last to first, by counters (no division in the loop): kc_page / kc_tip are the page and
+    // the tile inside it of the next K tile to request, kc_cur that page's table entry.  When the walk leaves a page, the entry
+    // of the page below is requested behind the DMA pieces of that K request: a whole visit before the next K request uses it.  The
+    // table is read through the constant address space (nothing writes it while the kernel runs): a workgroup-uniform SCALAR
+    // load whose wait the compiler places at the first use -- as a global load between the DMA's inline asm it becomes a vector
+    // load that is waited for (vmcnt(0): the K tile just requested) on the spot.  K is requested one tile ahead of V, so V's
+    // base is the last K base or the one before it (kc_last, kc_prev).
+    typedef const __attribute__((address_space(4))) int32_t *kc_table_ptr;
+    const int kc_tpp = qa.tiles_per_page;
+    int kc_page = (n_kv - 1) / kc_tpp;
+    int kc_tip = (n_kv - 1) - kc_page * kc_tpp;
+    const bool kc_paged = qa.block_table != nullptr;
+    const kc_table_ptr kc_row = (kc_table_ptr)(unsigned long long)(qa.block_table + (int64_t)b * qa.bt_stride);
+    int kc_cur = kc_paged ? kc_row[kc_page] : b;   // (contiguous cache: the "page" is the batch entry)
+    int64_t kc_last = 0, kc_prev = 0;
+    auto kc_offset = [&]() {   // the next K tile's offset (elements): the entry clamped to a page of the cache
+        const int p = kc_cur < 0 ? 0 : (kc_cur >= qa.num_pages ? qa.num_pages - 1 : kc_cur);
+        kc_prev = kc_last;
+        kc_last = (int64_t)p * qa.page_stride + (int64_t)kc_tip * tile_stride;
+        return kc_last;
+    };
+    auto kc_step = [&]() {     // ... and on to the tile below it
+        if (kc_tip != 0) {
+            --kc_tip;
+            return;
+        }
+        kc_tip = kc_tpp - 1;
+        --kc_page;
+        if (kc_paged && kc_page >= 0) kc_cur = kc_row[kc_page];
+    };
+#endif
     f32x4 abl_dummy[2 * DMA_PER_WAVE];  // ABL & 32 only: landing registers of plain loads
     // MASK: rows of the last sequence block that lie beyond seq_len are fetched from the last
     // valid row instead (their logits are masked, their P is exactly 0).
@@ -640,7 +702,11 @@ fa_fwd_kernel(const KernelArgs args) {
         return (MASK && kv0 + BC > S_len) ? S_len - kv0 : 0;
     };
     auto issue_k = [&](int it, int stage) {
+#ifdef FA_KERNEL_VARLEN_KVCACHE
+        const uint16_t *base = Kg + kc_offset();   // (K tiles are requested in visit order, each once)
+#else
         const uint16_t *base = Kg + (int64_t)(n_kv - 1 - it) * tile_stride;
+#endif
         const unsigned kdst = smem_base + stage * TILE;
         if (ABL & 16) return;
         if (const int valid = ragged_rows(it)) {
@@ -651,6 +717,9 @@ fa_fwd_kernel(const KernelArgs args) {
                 const unsigned off = (unsigned)(((int64_t)row * FA_KV_SS32 + (((lane & (CPR - 1)) ^ k_swz) << 3)) * 2);
                 glds16_sv(base, off, kdst + (wave + NWAVES * j) * 1024);
             }
+#ifdef FA_KERNEL_VARLEN_KVCACHE
+            kc_step();
+#endif
             return;
         }
 #pragma unroll
@@ -660,9 +729,17 @@ fa_fwd_kernel(const KernelArgs args) {
             else
                 glds16_sv(base, k_off[j], kdst + (wave + NWAVES * j) * 1024);
         }
+#ifdef FA_KERNEL_VARLEN_KVCACHE
+        kc_step();
+#endif
     };
     auto issue_v = [&](int it, int stage) {
+#ifdef FA_KERNEL_VARLEN_KVCACHE
+        // V(it) follows K(it + 1) except in the prologue and at the last tile: then K(it) was the last K request
+        const uint16_t *base = Vg + ((it > 0 && it + 1 < n_kv) ? kc_prev : kc_last);
+#else
         const uint16_t *base = Vg + (int64_t)(n_kv - 1 - it) * tile_stride;
+#endif
         const unsigned vdst = smem_base + V_BASE + stage * TILE;
         if (ABL & 16) return;
         if (const int valid = ragged_rows(it)) {

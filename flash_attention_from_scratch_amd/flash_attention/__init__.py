@@ -130,6 +130,23 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
                                                    advance_seqlens=advance_seqlens)
 
 
+def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table=None, causal=False,
+                           max_seqlen_k=None, timed=False):
+    """Prefill against a K / V cache (flash-attn's flash_attn_varlen_func(..., block_table=)): chunked prefill
+    behind a cached prefix, prompts behind a shared prefix, verification of more rows than forward_kvcache serves.  q
+    (total_q, n_heads, 128) holds the query rows of all sequences packed, sequence i's at rows cu_seqlens_q[i] ..
+    cu_seqlens_q[i + 1] - 1 (int32, n_seqs + 1 entries ON THE DEVICE), at most max_seqlen_q (a Python int) each.  The keys are
+    read from the cache in place: k_cache / v_cache (n_seqs, seqlen_cache, n_kv_heads, 128) -- or, with block_table
+    (n_seqs, max_pages_per_seq) int32, pages (num_pages, page_size, n_kv_heads, 128), page_size a multiple of 64 -- of which
+    cache_seqlens (n_seqs,) int32 ON THE DEVICE says how many are valid, the chunk's own keys (appended before this call, with
+    append_kvcache for one) included.  causal is bottom-right aligned: query r sees keys j <= r + (len_k - len_q); a row that sees
+    no key gives o = 0, lse = -inf.  max_seqlen_k (a Python int) bounds every length, None = the capacity.
+    -> (o, lse[, ms]) with lse fp32 (n_heads, total_q): bit for bit forward_varlen(cu_seqlens_k=) on the same keys packed.  bf16 /
+    fp16; an fp8 cache is refused.  No device synchronisation unless timed; graph-capturable; the same inputs give the same bits."""
+    return flash_attention_kernels.forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens,
+                                                          block_table=block_table, causal=causal, max_seqlen_k=max_seqlen_k, timed=timed)
+
+
 def append_kvcache(k_cache, v_cache, k, v, cache_seqlens, block_table=None, q=None, rotary_cos=None, rotary_sin=None,
                    rotary_interleaved=False, causal=False, k_descale=None, v_descale=None, seqlens_out=None):
     """The step in front of a decode, one HIP kernel: write the new rows k, v (batch, seqlen_new, n_kv_heads, 128)

@@ -682,6 +682,86 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
     return out[0] if len(out) == 1 else out
 
 
+def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table=None, causal=False,
+                           max_seqlen_k=None, timed=False):
+    """Prefill against a K / V cache (fa_fwd_launch_varlen_kvcache): forward_varlen(cu_seqlens_k=) whose keys are read from the
+    cache in place.  q (total_q, n_heads, 128) packed, cu_seqlens_q an int32 device tensor of n_seqs + 1 row offsets, max_seqlen_q
+    a Python int; k_cache, v_cache (n_seqs, seqlen_cache, n_kv_heads, 128), or with block_table (n_seqs, max_pages_per_seq) int32 on
+    the device (num_pages, page_size, n_kv_heads, 128); cache_seqlens (n_seqs,) int32 on the device, the valid keys of each
+    sequence, the chunk's own (already appended) included.  causal is bottom-right aligned.  -> (o, lse[, ms]); o contiguous, lse
+    fp32 (n_heads, total_q).  The host reads no device array; no device synchronisation unless timed.  The caches pass as they
+    are and are refused if the launch cannot address them; an fp8 cache is refused."""
+    tensors = [(q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cu_seqlens_q, "cu_seqlens_q"), (cache_seqlens, "cache_seqlens")]
+    if block_table is not None:
+        tensors.append((block_table, "block_table"))
+    for t, name in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{name} must be a tensor")
+    if k_cache.dtype in _FLOAT8_DTYPES or v_cache.dtype in _FLOAT8_DTYPES:
+        raise RuntimeError("forward_varlen_kvcache reads a bf16 / fp16 cache: an fp8 cache is not served here (forward_kvcache "
+                           "decodes against one)")
+    for t, name in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+        if t.device != q.device:
+            raise RuntimeError(f"{name} must be on q's device ({q.device}, got {t.device})")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError("Only fp16 and bf16 are supported")
+    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise RuntimeError("Input tensors must have the same data type")
+    if q.dim() != 3 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[3] != q.shape[2]:
+        raise RuntimeError("q must have shape (total_q, n_heads, d_head), k_cache and v_cache one shape (n_seqs or num_pages, "
+                           "seqlen_cache or page_size, n_kv_heads, d_head)")
+    total, n_heads, d_head = q.shape
+    n_kv = k_cache.shape[2]
+    if n_kv < 1 or n_heads % n_kv != 0:
+        raise RuntimeError(f"grouped-query attention: the K / V heads ({n_kv}) must divide the query heads ({n_heads})")
+    if cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or not cu_seqlens_q.is_contiguous():
+        raise RuntimeError("cu_seqlens_q must be a contiguous int32 tensor of n_seqs + 1 entries on q's device")
+    n_seqs = cu_seqlens_q.numel() - 1
+    if not isinstance(max_seqlen_q, int) or isinstance(max_seqlen_q, bool):
+        raise RuntimeError("max_seqlen_q must be a Python int (a bound on every sequence's query rows; the device is not asked)")
+    if block_table is None and k_cache.shape[0] != n_seqs:
+        raise RuntimeError("a contiguous cache needs one batch entry per sequence (pass block_table for a paged cache)")
+    if cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (n_seqs,) or not cache_seqlens.is_contiguous():
+        raise RuntimeError("cache_seqlens must be a contiguous int32 tensor of n_seqs entries on q's device")
+    if block_table is not None and (block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != n_seqs
+                                    or block_table.stride(1) != 1):
+        raise RuntimeError("block_table must be an int32 (n_seqs, max_pages_per_seq) tensor on q's device with a contiguous last dimension")
+    if max_seqlen_k is not None and (not isinstance(max_seqlen_k, int) or isinstance(max_seqlen_k, bool)):
+        raise RuntimeError("max_seqlen_k must be a Python int (a bound on every length; the device is not asked)")
+    if q.stride(2) != 1:
+        raise RuntimeError("packed sequences: q needs a contiguous last dimension")
+    if (_decode_needs_copy(k_cache) or _decode_needs_copy(v_cache) or k_cache.stride() != v_cache.stride()):
+        # (a serving cache is gigabytes: copying it on every call would be silently slow)
+        raise RuntimeError("k_cache and v_cache need one stride set, a contiguous last dimension, strides that are multiples of 8 "
+                           "elements and a 16-byte aligned base")
+    paged = block_table is not None
+    lib = _capi.load()
+    cfg = _capi.make_config(varlen_config(q.dtype))
+    with torch.cuda.device(q.device):
+        o = torch.empty((total, n_heads, d_head), dtype=q.dtype, device=q.device)
+        lse = torch.empty((n_heads, total), dtype=torch.float32, device=q.device)
+        if q.stride() != o.stride():   # (the launch has one stride set for q and o)
+            q = q.contiguous()
+        args = _capi.FaFwdArgs(q=q.data_ptr(), k=k_cache.data_ptr(), v=v_cache.data_ptr(), o=o.data_ptr(), batch=1, seq_len=total,
+                               n_heads=n_heads, d_head=d_head, batch_stride=0, seq_stride=q.stride(0), head_stride=q.stride(1), cfg=cfg)
+        kv = _capi.make_kv_layout(n_kv, k_cache.stride(0), k_cache.stride(1), k_cache.stride(2))
+        vq = _capi.make_varlen_layout(cu_seqlens_q.data_ptr(), n_seqs, total, max(max_seqlen_q, 1))   # (a bound of 0: nothing but empties)
+        kc = _capi.make_kvcache_layout(
+            cache_seqlens=cache_seqlens.data_ptr(), block_table=block_table.data_ptr() if paged else None,
+            seqlen_cache=0 if paged else k_cache.shape[1], batch=0 if paged else k_cache.shape[0],
+            num_pages=k_cache.shape[0] if paged else 0, page_size=k_cache.shape[1] if paged else 0,
+            max_pages_per_seq=block_table.shape[1] if paged else 0, block_table_stride=block_table.stride(0) if paged else 0,
+            max_seqlen_k=0 if max_seqlen_k is None else max_seqlen_k)
+        ms = ctypes.c_float(0.0)
+        opts = _capi.make_opts(causal=causal, ms=ms if timed else None)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        _capi.check(lib.fa_fwd_launch_varlen_kvcache(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(vq), ctypes.byref(kc),
+                                                     ctypes.byref(opts), ctypes.c_void_p(lse.data_ptr()), stream))
+    return (o, lse, float(ms.value)) if timed else (o, lse)
+
+
 def quantize_kvcache_fp8(k, v):
     """A contiguous 16-bit (or fp32) cache (batch, seqlen_cache, n_kv_heads, d_head) -> (k8, v8, k_descale, v_descale): e4m3fn
     caches of the same shape and fp32 (batch, n_kv_heads) descales, amax / 448 per (batch entry, K / V head) -- 448 is e4m3fn's

@@ -502,6 +502,53 @@ int64_t fa_bwd_varlen_qk_workspace_bytes(const fa_bwd_varlen_qk_args *args);   /
 int fa_bwd_launch_varlen_qk(const fa_bwd_varlen_qk_args *args, void *stream, float *ms);
 
 /*
+ * Prefill against a KV cache (flash-attn's flash_attn_varlen_func(..., block_table=)): fa_fwd_launch_varlen_qk whose key side is
+ * a cache, contiguous or paged, instead of a packed tensor -- chunked prefill behind a cached prefix, prompt processing behind a
+ * shared prefix, verification of more speculative rows than fa_decode_launch serves.  Forward only, with lse.
+ *
+ * args, kv, varlen_q, opts, lse, stream: as for fa_fwd_launch_varlen_qk; args->k, ->v are the caches and kv their strides:
+ *   contiguous cache (block_table null):  (n_seqs, seqlen_cache, n_kv_heads, 128); kv_batch_stride is the batch stride;
+ *   paged cache (block_table non-null):   (num_pages, page_size, n_kv_heads, 128); kv_batch_stride is the PAGE stride, and
+ *     block_table is a DEVICE (n_seqs, max_pages_per_seq) int32 array, row stride block_table_stride: key j of sequence b
+ *     is row j % page_size of page block_table[b][j / page_size]             (the two shapes of fa_decode_args).
+ * fa_kvcache_layout: struct_size = sizeof(fa_kvcache_layout).  cache_seqlens: DEVICE (n_seqs) int32, the valid keys of each
+ * sequence, the chunk's own keys (which the caller has already written, with fa_kvcache_append_launch for one) included.  The
+ * host reads neither it nor block_table: launches are asynchronous and graph-capturable.  max_seqlen_k: the host's bound on
+ * every length, 0 = the capacity.
+ * causal is BOTTOM-RIGHT aligned: query r of sequence b sees keys j <= r + (len_k - len_q).  A row that sees no key gives
+ * o = 0, lse = -inf.  The grid is n_seqs * n_heads * ceil(max_seqlen_q / 128) workgroups: no split, no workspace, no atomics,
+ * the same bits for the same inputs -- and the bits of fa_fwd_launch_varlen_qk on the same keys packed.
+ *
+ * Clamping: len_k to [0, min(capacity, max_seqlen_k)], capacity = seqlen_cache (paged: max_pages_per_seq * page_size); the
+ * query range by fa_varlen_layout's rule; every block_table entry used to [0, num_pages), and only entries of pages below
+ * ceil(len_k / page_size) are read; cache rows at or beyond len_k are never fetched (their lanes fetch row len_k - 1, which
+ * lies in the same page, and are masked).  So neither stale rows nor unused pages nor unused block_table entries reach a
+ * result, and no address outside the tensors is formed, whatever the three device arrays hold.
+ *
+ * Served (fa_fwd_varlen_kvcache_supported): the configurations and options of fa_fwd_launch_varlen.  Refused before any HIP
+ * call: what fa_fwd_launch_varlen refuses, and null cache_seqlens (FA_ERR_NULL); page_size % 64 != 0 (FA_ERR_NO_KERNEL);
+ * struct_size, sizes that are not positive, block_table_stride < max_pages_per_seq, max_seqlen_k outside [0, capacity], a
+ * contiguous cache whose kv_batch_stride is not positive with n_seqs > 1, lengths beyond 32 bits (FA_ERR_SHAPE); strides not
+ * multiples of 8, cache_seqlens or block_table not 4-byte aligned (FA_ERR_ALIGN); a contiguous cache whose batch is not
+ * n_seqs (FA_ERR_SHAPE: sequence b reads batch entry b).  total_q = 0 returns FA_OK without a launch.
+ */
+typedef struct fa_kvcache_layout {
+    uint32_t struct_size;         /* sizeof(fa_kvcache_layout) */
+    const int32_t *cache_seqlens;
+    const int32_t *block_table;   /* null = contiguous cache */
+    int64_t seqlen_cache;         /* contiguous cache: rows per batch entry (ignored when paged) */
+    int64_t num_pages;            /* paged cache only, like the next three */
+    int64_t page_size;
+    int64_t max_pages_per_seq;
+    int64_t block_table_stride;
+    int64_t max_seqlen_k;         /* 0 = capacity */
+    int64_t batch;                /* contiguous cache: its batch entries, which must be n_seqs (ignored when paged) */
+} fa_kvcache_layout;
+int fa_fwd_varlen_kvcache_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_kvcache(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                 const fa_kvcache_layout *cache, const fa_fwd_opts *opts, float *lse, void *stream);
+
+/*
  * KV-cache decode attention (forward only): a few query rows per sequence against a long K / V cache whose valid length per
  * batch entry lies in DEVICE memory.  bf16 / fp16, d_head 128, MHA and GQA / MQA (query head h reads K / V head
  * h / (n_heads / n_kv_heads)), softmax scale 1 / sqrt(128).
