@@ -1,6 +1,7 @@
-// fa_bwd_varlen.hip -- the varlen backward's translation unit: the kernels of fa_bwd_varlen.hpp for both dtypes and both masks,
-// and the enqueue of one backward over packed sequences (three or four launches on one stream).  Shapes and pointers are
-// validated by the caller (fa_bwd_launch_varlen, fa_capi.hip).  The flags of fa_bwd.hip: same contraction, same bits.
+// fa_bwd_varlen.hip -- the varlen backward's translation unit: the kernels of fa_bwd_varlen.hpp in their one-range form
+// (BwdVarlenArgs) for both dtypes and both masks, and the enqueue of one backward over packed sequences (three or four launches
+// on one stream).  Shapes and pointers are validated by the caller (fa_bwd_launch_varlen, fa_capi.hip).  The flags of
+// fa_bwd.hip: same contraction, same bits.
 #include <hip/hip_runtime.h>
 
 #include "fa_bwd_varlen.hpp"
@@ -17,15 +18,15 @@ static hipError_t bwd_varlen_enqueue_t(const BwdVarlenArgs &a, hipStream_t s) {
     if (rc != hipSuccess) return rc;
     const int64_t n_kv = a.n_heads / a.group;
     const dim3 block(bwd::THREADS);
-    rc = hipLaunchKernel((const void *)&fa_bwd_dkdv_varlen_kernel<DT, CAUSAL>,
+    rc = hipLaunchKernel((const void *)&fa_bwd_dkdv_varlen_kernel<BwdVarlenArgs, DT, CAUSAL>,
                          dim3((unsigned)((int64_t)a.n_seqs * n_kv * a.split * a.n_blocks)), block, params, 0, s);
     if (rc != hipSuccess) return rc;
     if (a.split > 1) {
         const int64_t n = n_kv * a.total_tokens * 2 * (bwd::D / 8);
-        rc = hipLaunchKernel((const void *)&fa_bwd_dkdv_reduce_varlen_kernel<DT>, dim3((unsigned)((n + 255) / 256)), dim3(256), params, 0, s);
+        rc = hipLaunchKernel((const void *)&fa_bwd_dkdv_reduce_varlen_kernel<BwdVarlenArgs, DT>, dim3((unsigned)((n + 255) / 256)), dim3(256), params, 0, s);
         if (rc != hipSuccess) return rc;
     }
-    return hipLaunchKernel((const void *)&fa_bwd_dq_varlen_kernel<DT, CAUSAL>, dim3((unsigned)((int64_t)a.n_seqs * a.n_heads * a.n_blocks)),
+    return hipLaunchKernel((const void *)&fa_bwd_dq_varlen_kernel<BwdVarlenArgs, DT, CAUSAL>, dim3((unsigned)((int64_t)a.n_seqs * a.n_heads * a.n_blocks)),
                            block, params, 0, s);
 }
 

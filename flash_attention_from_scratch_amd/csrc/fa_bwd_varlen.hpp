@@ -1,13 +1,19 @@
-// fa_bwd_varlen.hpp -- the backward over packed variable-length sequences (fa_bwd_launch_varlen): Q, dO, dQ, O are
-// (total_tokens, n_heads, 128), K, V, dK, dV (total_tokens, n_kv_heads, 128), and sequence i owns token rows
-// cu_seqlens[i] .. cu_seqlens[i + 1] - 1 (cu_seqlens on the DEVICE: the host never reads it, the launch stays asynchronous).
+// fa_bwd_varlen.hpp -- the backward over packed variable-length sequences, with one range per sequence (fa_bwd_launch_varlen,
+// BwdVarlenArgs) or with separate Q and K / V ranges (fa_bwd_launch_varlen_qk, BwdVarlenQKArgs).  One text of each kernel
+// serves both: ARGS names the form, `if constexpr (QK)` marks every site where they differ, and each form is instantiated in
+// a translation unit of its own (fa_bwd_varlen.hip, fa_bwd_varlen_qk.hip), so the one-range kernels carry none of the second
+// range's code.
+//
+// One range: Q, dO, dQ, O are (total_tokens, n_heads, 128), K, V, dK, dV (total_tokens, n_kv_heads, 128), and sequence i owns
+// token rows cu_seqlens[i] .. cu_seqlens[i + 1] - 1 (cu_seqlens on the DEVICE: the host never reads it, the launch stays
+// asynchronous).
 //
 // The kernels of fa_bwd_gqa.hpp (MHA is their group = 1 case) with the workgroup -> (sequence, head, 128-row block) lookup in
 // front; the tile arithmetic (S, dP, dS, the five MFMA products, the operand orientation, the LDS images, the order of the
 // fp32 sums) is theirs, line for line, so that a sequence whose length is a multiple of 256 gets the dense kernels' bits.
-//   fa_bwd_delta_varlen_kernel        delta per (head, token): no sequence lookup at all
+//   fa_bwd_delta_varlen_kernel        delta per (head, query token): no sequence lookup at all, one form
 //   fa_bwd_dkdv_varlen_kernel         one workgroup per (sequence, K / V head, split part, 128-key block of max_seqlen)
-//   fa_bwd_dkdv_reduce_varlen_kernel  split > 1 only: the sum of a row's split partials, in order, scaled and rounded once
+//   fa_bwd_dkdv_reduce_varlen_kernel  split > 1 only: the sum of a key row's split partials, in order, scaled and rounded once
 //   fa_bwd_dq_varlen_kernel           one workgroup per (sequence, head, 128-row Q block of max_seqlen)
 // A workgroup whose block starts at or beyond its sequence's length returns at once (before any barrier).  Rows of a tile,
 // and resident K / V or Q / dO rows, beyond the sequence's end are fetched from the sequence's LAST row (never from another
@@ -19,7 +25,20 @@
 // cu_seqlens is the caller's (non-decreasing, [0] = 0, [n_seqs] = total_tokens, lengths <= max_seqlen), but a violation
 // cannot fault: seq_range() clamps the first row to [0, total_tokens] and the length to [0, min(max_seqlen, what is left)].
 // No float atomics, no waiting between workgroups, no scratch: the same inputs give the same bits.
+//
+// What the second range adds: K, V, dK, dV are (total_k, n_kv_heads, 128) and sequence i owns key rows cu_seqlens_k[i] ..
+// cu_seqlens_k[i + 1] - 1 (on the device too); the dK / dV grid and the partials run over max_seqlen_k and total_k.
+//  * The causal mask is bottom-right aligned: query r of a sequence sees keys j <= r + shift, shift = len_k - len_q.  Equal
+//    ranges (shift = 0) give the one-range kernels' bits.
+//  * A query row that saw no key (len_k = 0, or causal r < len_q - len_k) has lse = -inf and is treated as a row beyond the
+//    end (S starts at -inf, delta = 0): dq = 0, nothing of it in dK / dV.
+//  * A range of length 0 fetches nothing (the first tile's load is guarded).  A key no query sees (len_q = 0) gets
+//    dk = dv = 0, written.
+//  * Rows beyond either range's end are fetched from THAT range's last row; both ranges are clamped by seq_range's rule, each
+//    against its own total and max_seqlen.
 #pragma once
+#include <type_traits>
+
 #include "fa_bwd_kernel.hpp"
 
 namespace fa {
@@ -41,6 +60,25 @@ struct BwdVarlenArgs {
     int32_t n_blocks;                 // ceil(max_seqlen / 128): blocks of the grid per (sequence, head)
 };
 
+struct BwdVarlenQKArgs {
+    const uint16_t *q, *k, *v;        // q_* / kv_* strides
+    const uint16_t *o, *dout;         // out_* strides
+    const float *lse;                 // (n_heads, total_tokens), contiguous
+    float *delta;                     // workspace: (n_heads, total_tokens)
+    uint16_t *dq, *dk, *dv;           // dq: out_* strides; dk, dv: dkv_*
+    const int32_t *cu_seqlens;        // n_seqs + 1 entries: the query rows
+    const int32_t *cu_seqlens_k;      // n_seqs + 1 entries: the key rows
+    float *part;                      // split > 1: (n_kv_heads * split, total_k, 2, 128) fp32 dK^T | dV^T, unscaled
+    int64_t q_ss, q_hs;               // elements
+    int64_t out_ss, out_hs;
+    int64_t kv_ss, kv_hs;
+    int64_t dkv_ss, dkv_hs;
+    int32_t n_seqs, total_tokens, max_seqlen, n_heads;   // total_tokens, max_seqlen: the query side
+    int32_t total_k, max_seqlen_k;
+    int32_t group, split;             // query heads per K / V head; workgroups per (K / V head, key block), divides group
+    int32_t n_blocks, n_blocks_k;     // ceil(max_seqlen / 128), ceil(max_seqlen_k / 128): blocks of the grids
+};
+
 namespace bwd {
 
 // sequence -> first row and length, clamped so that every row0 + i, 0 <= i < len, is a row of the tensors
@@ -54,6 +92,29 @@ FA_DEV void seq_range(const BwdVarlenArgs &a, int seq, int &row0, int &len) {
     row0 = (int)r0;
     len = (int)n;
 }
+
+// ... of one of two ranges, by the same rule against that side's total and max_seqlen
+FA_DEV void seq_range_of(const int32_t *cu, int64_t total, int64_t max_len, int seq, int &row0, int &len) {
+    const int64_t lo = cu[seq], hi = cu[seq + 1];
+    const int64_t r0 = lo < 0 ? 0 : (lo > total ? total : lo);
+    int64_t n = hi - r0;
+    const int64_t cap = total - r0 < max_len ? total - r0 : max_len;
+    n = n < 0 ? 0 : (n > cap ? cap : n);
+    row0 = (int)r0;
+    len = (int)n;
+}
+FA_DEV void seq_range_q(const BwdVarlenQKArgs &a, int seq, int &row0, int &len) {
+    seq_range_of(a.cu_seqlens, a.total_tokens, a.max_seqlen, seq, row0, len);
+}
+FA_DEV void seq_range_k(const BwdVarlenQKArgs &a, int seq, int &row0, int &len) {
+    seq_range_of(a.cu_seqlens_k, a.total_k, a.max_seqlen_k, seq, row0, len);
+}
+
+// the key side's rows and 128-key blocks: the one range's, or the second range's
+__host__ __device__ inline int32_t total_k(const BwdVarlenArgs &a) { return a.total_tokens; }
+__host__ __device__ inline int32_t total_k(const BwdVarlenQKArgs &a) { return a.total_k; }
+__host__ __device__ inline int32_t n_blocks_k(const BwdVarlenArgs &a) { return a.n_blocks; }
+__host__ __device__ inline int32_t n_blocks_k(const BwdVarlenQKArgs &a) { return a.n_blocks_k; }
 
 // tile_load with the tile's rows clamped to the sequence: row first + r comes from row min(first + r, last)
 FA_DEV void tile_load_clamped(TileRegs &t, const uint16_t *seq_rows, int64_t ss, int first, int last, int tid) {
@@ -90,34 +151,44 @@ __global__ void __launch_bounds__(256) fa_bwd_delta_varlen_kernel(const BwdVarle
 }
 
 // dK, dV of one 128-key block of one K / V head of one sequence, summed over group / split query heads.
-// Grid: n_seqs * n_kv_heads * split * n_blocks workgroups of 256 threads.
-template <int DT, bool CAUSAL>
-__global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(const BwdVarlenArgs a) {
+// Grid: n_seqs * n_kv_heads * split * n_blocks_k workgroups of 256 threads.  The sweep runs over the Q tiles of len_q; two
+// ranges: a block no query sees (len_q = 0) sweeps nothing and stores zeros.
+template <class ARGS, int DT, bool CAUSAL>
+__global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(const ARGS a) {
     using namespace bwd;
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
+    constexpr bool QK = std::is_same_v<ARGS, BwdVarlenQKArgs>;
     __shared__ __attribute__((aligned(16))) char img_q[TBYTES];
     __shared__ __attribute__((aligned(16))) char img_do[TBYTES];
     __shared__ __attribute__((aligned(16))) float lse_s[TROWS];   // -lse sqrt(d) of the tile's rows
     __shared__ __attribute__((aligned(16))) float dl_s[TROWS];    // -delta
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     int wg, kb;   // wg = (sequence * n_kv_heads + K / V head) * split + part
-    block_coords(a.n_blocks, wg, kb);
+    block_coords(n_blocks_k(a), wg, kb);
     const int n_kv = a.n_heads / a.group, skv = wg / a.split, seq = skv / n_kv, hk = skv % n_kv, sp = wg % a.split;
-    int row0, len;
-    seq_range(a, seq, row0, len);
-    if (kb * KB >= len) return;   // (workgroup-uniform, before any barrier)
-    const int last = len - 1;
+    int row0, len, krow0, klen;   // the sequence's query rows and key rows
+    if constexpr (QK) {
+        seq_range_q(a, seq, row0, len);
+        seq_range_k(a, seq, krow0, klen);
+    } else {
+        seq_range(a, seq, row0, len);
+        krow0 = row0;
+        klen = len;
+    }
+    if (kb * KB >= klen) return;   // (workgroup-uniform, before any barrier)
+    const int last = len - 1, klast = klen - 1;
+    const int shift = QK ? klen - len : 0;   // causal, bottom-right: query r sees keys <= r + shift
     const int n_hq = a.group / a.split;   // query heads of the sweep: hk * group + part * n_hq + 0 .. n_hq - 1
     int hq = hk * a.group + sp * n_hq;
     const uint16_t *q_seq = a.q + (int64_t)row0 * a.q_ss + (int64_t)hq * a.q_hs;
     const uint16_t *do_seq = a.dout + (int64_t)row0 * a.out_ss + (int64_t)hq * a.out_hs;
     const int key = kb * KB + 32 * wave + r;   // this lane's key (the accumulators' column)
-    const int key_c = key < last ? key : last;
+    const int key_c = key < klast ? key : klast;
     // K, V of the wave's 32 keys: the B operands of S = Q K^T and dP = dO V^T, resident for the whole sweep
     vec8 Kb[8], Vb[8];
     {
-        const int64_t kv_row = (int64_t)(row0 + key_c) * a.kv_ss + (int64_t)hk * a.kv_hs + 8 * h;
+        const int64_t kv_row = (int64_t)(krow0 + key_c) * a.kv_ss + (int64_t)hk * a.kv_hs + 8 * h;
         const uint16_t *kr = a.k + kv_row;
         const uint16_t *vr = a.v + kv_row;
 #pragma unroll
@@ -135,7 +206,11 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
         dK[t] = f32x16{};
     }
     const int n_it = (len + TROWS - 1) / TROWS;
-    const int it0 = CAUSAL ? kb * (KB / TROWS) : 0;   // causal: the Q tiles from the diagonal on (it0 * 64 = kb * 128 < len)
+    // causal: the Q tiles from the diagonal on (one range: it0 * 64 = kb * 128 < len), that is from the first one that can see
+    // the block (two ranges; it0 >= n_it: no query sees it)
+    int it0 = 0;
+    if constexpr (CAUSAL && QK) it0 = (kb * KB - shift > 0 ? kb * KB - shift : 0) / TROWS;
+    else if constexpr (CAUSAL) it0 = kb * (KB / TROWS);
     const float *lse_h = a.lse + (int64_t)hq * a.total_tokens + row0;
     const float *dl_h = a.delta + (int64_t)hq * a.total_tokens + row0;
     TileRegs tq, tdo;
@@ -146,12 +221,20 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
         if (tid < TROWS) {
             const int row = it * TROWS + tid;
             const bool in = row < len;
-            lse_r = in ? lse_h[in ? row : 0] * lse_scale : -__builtin_inff();   // S = -inf, p = exp2(-inf) = 0
-            dl_r = in ? -dl_h[in ? row : 0] : 0.0f;
+            if constexpr (QK) {
+                // (a row that saw no key has lse = -inf: a row beyond the end, or lse * lse_scale = +inf would reach dK / dV as NaN)
+                const float lse_v = in ? lse_h[in ? row : 0] : -__builtin_inff();
+                const bool live = in && lse_v != -__builtin_inff();
+                lse_r = live ? lse_v * lse_scale : -__builtin_inff();   // S = -inf, p = exp2(-inf) = 0
+                dl_r = live ? -dl_h[in ? row : 0] : 0.0f;
+            } else {
+                lse_r = in ? lse_h[in ? row : 0] * lse_scale : -__builtin_inff();   // S = -inf, p = exp2(-inf) = 0
+                dl_r = in ? -dl_h[in ? row : 0] : 0.0f;
+            }
         }
     };
-    load(it0);
-    const bool key_edge = kb * KB + KB > len;   // a block that holds keys beyond the sequence
+    if (!QK || it0 < n_it) load(it0);   // (two ranges: len_q = 0 has no row to fetch)
+    const bool key_edge = kb * KB + KB > klen;   // a block that holds keys beyond the sequence
     for (int j = 0; j < n_hq; ++j) {
         for (int it = it0; it < n_it; ++it) {
             __syncthreads();   // every wave is done with the previous tile's images
@@ -172,7 +255,7 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
                 dl_h += a.total_tokens;
                 load(it0);
             }
-            const bool diag = CAUSAL && it * TROWS < kb * KB + KB;   // a tile that holds queries before some key of the block
+            const bool diag = CAUSAL && it * TROWS + shift < kb * KB + KB;   // a tile that holds queries before some key of the block
             const bool edge = key_edge || it * TROWS + TROWS > len;  // ... or rows / keys beyond the sequence
 #pragma unroll
             for (int mt = 0; mt < TROWS / 32; ++mt) {
@@ -198,8 +281,8 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
                     float p = __builtin_amdgcn_exp2f(c * S[i]);
                     const int query = it * TROWS + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
                     if constexpr (CAUSAL) {   // (plain: rows beyond the end have S = -inf, see load())
-                        if (diag) p = key > query ? 0.0f : p;
-                        if (edge) p = (key >= len || query >= len) ? 0.0f : p;
+                        if (diag) p = key > query + shift ? 0.0f : p;
+                        if (edge) p = (key >= klen || query >= len) ? 0.0f : p;
                     }
                     S[i] = p;                 // P
                     dP[i] = p * dP[i];        // dS = P (dP - delta)
@@ -216,10 +299,10 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
             }
         }
     }
-    if (key >= len) return;   // (behind the last barrier and the last transposed read)
+    if (key >= klen) return;   // (behind the last barrier and the last transposed read)
     // dK^T / dV^T: column = this lane's key, rows d = 32 t + 8 gg + 4 h + 0 .. 3
     if (a.split > 1) {   // the fp32 partials, unscaled: fa_bwd_dkdv_reduce_varlen_kernel rounds their sum
-        float *pk = a.part + (((int64_t)hk * a.split + sp) * a.total_tokens + row0 + key) * (2 * D) + 4 * h;
+        float *pk = a.part + (((int64_t)hk * a.split + sp) * total_k(a) + krow0 + key) * (2 * D) + 4 * h;
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -230,7 +313,7 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
         return;
     }
     const float inv_sqrt_d = 1.0f / __builtin_sqrtf((float)D);
-    const int64_t dkv_row = (int64_t)(row0 + key) * a.dkv_ss + (int64_t)hk * a.dkv_hs + 4 * h;
+    const int64_t dkv_row = (int64_t)(krow0 + key) * a.dkv_ss + (int64_t)hk * a.dkv_hs + 4 * h;
     uint16_t *dk = a.dk + dkv_row;
     uint16_t *dv = a.dv + dkv_row;
 #pragma unroll
@@ -242,21 +325,21 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
         }
 }
 
-// split > 1: dK, dV of one (K / V head, token) row = the sum of its `split` partials in order, scaled and rounded once.
-// One thread per 8 elements of a dK or dV row.  Grid: n_kv_heads * total_tokens * 2 * 16 / 256 workgroups of 256 threads.
-// (every token belongs to a sequence -- cu_seqlens[0] = 0, [n_seqs] = total_tokens -- so every partial row was written)
-template <int DT>
-__global__ void __launch_bounds__(256) fa_bwd_dkdv_reduce_varlen_kernel(const BwdVarlenArgs a) {
+// split > 1: dK, dV of one (K / V head, key token) row = the sum of its `split` partials in order, scaled and rounded once.
+// One thread per 8 elements of a dK or dV row.  Grid: n_kv_heads * total_k * 2 * 16 / 256 workgroups of 256 threads.
+// (every key row belongs to a sequence -- cu_seqlens[0] = 0, [n_seqs] = total, on the key side -- so every partial row was written)
+template <class ARGS, int DT>
+__global__ void __launch_bounds__(256) fa_bwd_dkdv_reduce_varlen_kernel(const ARGS a) {
     using namespace bwd;
     const int n_kv = a.n_heads / a.group;
-    const int64_t n = (int64_t)n_kv * a.total_tokens * 2 * (D / 8);
+    const int64_t n = (int64_t)n_kv * total_k(a) * 2 * (D / 8);
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= n) return;
     const int c8 = (int)(idx % (D / 8)), which = (int)((idx / (D / 8)) & 1);   // 8-element chunk; 0 dK, 1 dV
-    const int64_t row = idx / (2 * (D / 8));   // hk * total_tokens + token
-    const int64_t hk = row / a.total_tokens, tok = row % a.total_tokens;
-    const int64_t plane = (int64_t)a.total_tokens * 2 * D;   // floats per partial
-    const float *src = a.part + (hk * a.split * a.total_tokens + tok) * (2 * D) + which * D + 8 * c8;
+    const int64_t row = idx / (2 * (D / 8));   // hk * total_k + token
+    const int64_t hk = row / total_k(a), tok = row % total_k(a);
+    const int64_t plane = (int64_t)total_k(a) * 2 * D;   // floats per partial
+    const float *src = a.part + (hk * a.split * total_k(a) + tok) * (2 * D) + which * D + 8 * c8;
     f32x4 lo = *(const f32x4 *)src, hi = *(const f32x4 *)(src + 4);
     for (int s = 1; s < a.split; ++s) {
         lo += *(const f32x4 *)(src + s * plane);
@@ -274,11 +357,14 @@ __global__ void __launch_bounds__(256) fa_bwd_dkdv_reduce_varlen_kernel(const Bw
 }
 
 // dQ of one 128-row Q block of one sequence, K / V of head h / group.  Grid: n_seqs * n_heads * n_blocks workgroups of 256 threads.
-template <int DT, bool CAUSAL>
-__global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const BwdVarlenArgs a) {
+// The sweep runs over the key tiles of len_k; two ranges: a block that sees no key (len_k = 0, or causal rows above the shifted
+// diagonal) sweeps nothing and stores zeros.
+template <class ARGS, int DT, bool CAUSAL>
+__global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const ARGS a) {
     using namespace bwd;
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
+    constexpr bool QK = std::is_same_v<ARGS, BwdVarlenQKArgs>;
     __shared__ __attribute__((aligned(16))) char img_k[TBYTES];
     __shared__ __attribute__((aligned(16))) char img_v[TBYTES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
@@ -286,12 +372,20 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
     block_coords(a.n_blocks, sh, qb);
     if (CAUSAL) qb = a.n_blocks - 1 - qb;   // the longest sweeps first
     const int seq = sh / a.n_heads, hq = sh % a.n_heads;
-    int row0, len;
-    seq_range(a, seq, row0, len);
+    int row0, len, krow0, klen;   // the sequence's query rows and key rows
+    if constexpr (QK) {
+        seq_range_q(a, seq, row0, len);
+        seq_range_k(a, seq, krow0, klen);
+    } else {
+        seq_range(a, seq, row0, len);
+        krow0 = row0;
+        klen = len;
+    }
     if (qb * KB >= len) return;   // (workgroup-uniform, before any barrier)
-    const int last = len - 1;
-    const uint16_t *k_seq = a.k + (int64_t)row0 * a.kv_ss + (int64_t)(hq / a.group) * a.kv_hs;
-    const uint16_t *v_seq = a.v + (int64_t)row0 * a.kv_ss + (int64_t)(hq / a.group) * a.kv_hs;
+    const int last = len - 1, klast = klen - 1;
+    const int shift = QK ? klen - len : 0;   // causal, bottom-right: query r sees keys <= r + shift
+    const uint16_t *k_seq = a.k + (int64_t)krow0 * a.kv_ss + (int64_t)(hq / a.group) * a.kv_hs;
+    const uint16_t *v_seq = a.v + (int64_t)krow0 * a.kv_ss + (int64_t)(hq / a.group) * a.kv_hs;
     const int query = qb * KB + 32 * wave + r;   // this lane's query (the accumulators' column)
     const int query_c = query < last ? query : last;
     // Q, dO of the wave's 32 rows: the B operands of S^T = K Q^T and dP^T = V dO^T
@@ -307,19 +401,31 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
     }
     const float c = (float)((double)(1.0f / __builtin_sqrtf((float)D)) * 1.4426950408889634074);
     const int64_t stat = (int64_t)hq * a.total_tokens + row0 + query_c;
-    const float lse_q = query < len ? a.lse[stat] * -log2e_over_c() : 0.0f;
-    const float dl_q = query < len ? -a.delta[stat] : 0.0f;
+    float lse_q, dl_q;
+    if constexpr (QK) {
+        // (a row that saw no key has lse = -inf: its S starts at -inf, p = exp2(-inf) = 0, rather than at lse * scale = +inf)
+        const float lse_v = a.lse[stat];
+        const bool dead = lse_v == -__builtin_inff();
+        lse_q = query < len ? (dead ? -__builtin_inff() : lse_v * -log2e_over_c()) : 0.0f;
+        dl_q = query < len && !dead ? -a.delta[stat] : 0.0f;
+    } else {
+        lse_q = query < len ? a.lse[stat] * -log2e_over_c() : 0.0f;
+        dl_q = query < len ? -a.delta[stat] : 0.0f;
+    }
     f32x16 dQ[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) dQ[t] = f32x16{};
-    const int n_all = (len + TROWS - 1) / TROWS;
-    const int n_kt = CAUSAL && (qb + 1) * (KB / TROWS) < n_all ? (qb + 1) * (KB / TROWS) : n_all;
+    const int n_all = (klen + TROWS - 1) / TROWS;
+    // causal: cut at the block's last row's diagonal, (qb + 1) * 128 - 1 + shift; two ranges: no tile when that lies before key 0
+    int n_diag = (qb + 1) * (KB / TROWS);
+    if constexpr (QK) n_diag = (qb + 1) * KB + shift > 0 ? ((qb + 1) * KB + shift + TROWS - 1) / TROWS : 0;
+    const int n_kt = CAUSAL && n_diag < n_all ? n_diag : n_all;
     TileRegs tk, tv;
     auto load = [&](int kt) {
-        tile_load_clamped(tk, k_seq, a.kv_ss, kt * TROWS, last, tid);
-        tile_load_clamped(tv, v_seq, a.kv_ss, kt * TROWS, last, tid);
+        tile_load_clamped(tk, k_seq, a.kv_ss, kt * TROWS, klast, tid);
+        tile_load_clamped(tv, v_seq, a.kv_ss, kt * TROWS, klast, tid);
     };
-    load(0);
+    if (!QK || n_kt > 0) load(0);   // (two ranges: len_k = 0 has no row to fetch)
     const bool query_edge = qb * KB + KB > len;   // a block that holds rows beyond the sequence
     for (int kt = 0; kt < n_kt; ++kt) {
         __syncthreads();
@@ -327,8 +433,8 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
         tile_store(img_v, tv, tid);
         __syncthreads();
         if (kt + 1 < n_kt) load(kt + 1);
-        const bool diag = CAUSAL && kt * TROWS + TROWS > qb * KB;   // a tile that holds keys after some query of the block
-        const bool edge = query_edge || kt * TROWS + TROWS > len;   // ... or rows / keys beyond the sequence
+        const bool diag = CAUSAL && kt * TROWS + TROWS > qb * KB + shift;   // a tile that holds keys after some query of the block
+        const bool edge = query_edge || kt * TROWS + TROWS > klen;   // ... or rows / keys beyond the sequence
 #pragma unroll
         for (int mt = 0; mt < TROWS / 32; ++mt) {
             const int rb = 32 * mt;
@@ -339,7 +445,7 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
                 dP[i] = dl_q;
                 if (!CAUSAL && edge) {   // keys beyond the end: S = -inf, p = exp2(-inf) = 0
                     const int key = kt * TROWS + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
-                    S[i] = key >= len ? -__builtin_inff() : lse_q;
+                    S[i] = key >= klen ? -__builtin_inff() : lse_q;
                 }
             }
 #pragma unroll
@@ -351,8 +457,8 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
                 float p = __builtin_amdgcn_exp2f(c * S[i]);
                 const int key = kt * TROWS + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
                 if constexpr (CAUSAL) {
-                    if (diag) p = key > query ? 0.0f : p;
-                    if (edge) p = (key >= len || query >= len) ? 0.0f : p;
+                    if (diag) p = key > query + shift ? 0.0f : p;
+                    if (edge) p = (key >= klen || query >= len) ? 0.0f : p;
                 }
                 dP[i] = p * dP[i];        // dS^T
             }

@@ -1,10 +1,10 @@
 // fa_bwd_varlen_qk.hip -- the translation unit of the backward over packed sequences with separate Q and K / V lengths: the
-// kernels of fa_bwd_varlen_qk.hpp for both dtypes and both masks, and the enqueue of one backward (three or four launches on
-// one stream).  Shapes and pointers are validated by the caller (fa_bwd_launch_varlen_qk, fa_capi.hip).  The flags of
-// fa_bwd_varlen.hip: same contraction, same bits.
+// kernels of fa_bwd_varlen.hpp in their two-range form (BwdVarlenQKArgs) for both dtypes and both masks, and the enqueue of one
+// backward (three or four launches on one stream).  Shapes and pointers are validated by the caller (fa_bwd_launch_varlen_qk,
+// fa_capi.hip).  The flags of fa_bwd_varlen.hip: same contraction, same bits.
 #include <hip/hip_runtime.h>
 
-#include "fa_bwd_varlen_qk.hpp"
+#include "fa_bwd_varlen.hpp"
 
 namespace fa {
 
@@ -33,17 +33,17 @@ static hipError_t bwd_varlen_qk_enqueue_t(const BwdVarlenQKArgs &a, hipStream_t 
     const int64_t n_kv = a.n_heads / a.group;
     const dim3 block(bwd::THREADS);
     if (a.total_k > 0) {   // (no key rows: nothing to write, and the dQ kernel stores zeros)
-        rc = hipLaunchKernel((const void *)&fa_bwd_dkdv_varlen_qk_kernel<DT, CAUSAL>,
+        rc = hipLaunchKernel((const void *)&fa_bwd_dkdv_varlen_kernel<BwdVarlenQKArgs, DT, CAUSAL>,
                              dim3((unsigned)((int64_t)a.n_seqs * n_kv * a.split * a.n_blocks_k)), block, params, 0, s);
         if (rc != hipSuccess) return rc;
         if (a.split > 1) {
             const int64_t n = n_kv * a.total_k * 2 * (bwd::D / 8);
-            rc = hipLaunchKernel((const void *)&fa_bwd_dkdv_reduce_varlen_qk_kernel<DT>, dim3((unsigned)((n + 255) / 256)), dim3(256), params, 0, s);
+            rc = hipLaunchKernel((const void *)&fa_bwd_dkdv_reduce_varlen_kernel<BwdVarlenQKArgs, DT>, dim3((unsigned)((n + 255) / 256)), dim3(256), params, 0, s);
             if (rc != hipSuccess) return rc;
         }
     }
     if (a.total_tokens == 0) return hipSuccess;
-    return hipLaunchKernel((const void *)&fa_bwd_dq_varlen_qk_kernel<DT, CAUSAL>, dim3((unsigned)((int64_t)a.n_seqs * a.n_heads * a.n_blocks)),
+    return hipLaunchKernel((const void *)&fa_bwd_dq_varlen_kernel<BwdVarlenQKArgs, DT, CAUSAL>, dim3((unsigned)((int64_t)a.n_seqs * a.n_heads * a.n_blocks)),
                            block, params, 0, s);
 }
 

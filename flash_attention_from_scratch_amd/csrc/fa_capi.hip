@@ -19,9 +19,7 @@
 #include "../../include/fa_hip.h"
 #include "fa_bwd_gqa.hpp"
 #include "fa_bwd_varlen.hpp"
-#include "fa_bwd_varlen_qk.hpp"
 #include "fa_decode_kernel.hpp"
-#include "fa_decode_fp8_kernel.hpp"
 #include "fa_kvcache_append_kernel.hpp"
 #include "fa_registry.hpp"
 

@@ -1,5 +1,7 @@
 // fa_decode_kernel.hpp -- KV-cache decode attention for gfx950: a few query rows per sequence against a long K / V cache of
-// a per-sequence length the DEVICE holds.  HBM-bound: K and V are read once, ~2 * rows FLOP per byte.
+// a per-sequence length the DEVICE holds, the cache in Q's 16-bit type or in fp8 (OCP e4m3fn).
+// HBM-bound: K and V are read once, ~2 * rows FLOP per byte.  One text of the split kernel serves both caches: ARGS names
+// the form (DecodeArgs: 16-bit, DecodeFp8Args: fp8) and `if constexpr (FP8)` marks every site where they differ.
 //
 //  * Split kernel, grid batch * n_kv_heads * num_splits, 4 waves.  The rows = seqlen_q * group query rows that share one K / V
 //    head (row r = query position r / group, head kv_head * group + r % group) are the N dimension of
@@ -19,7 +21,26 @@
 //  * Clamping (include/fa_hip.h): len to [0, max_len]; a key at or beyond len is FETCHED from key len - 1 (K and V: a
 //    p = 0 would not silence a NaN in V) and masked in S; block_table entries to [0, num_pages), only those of pages below
 //    ceil(len / page_size) read.  page_size % 64 == 0, so a 32-key unit lies in one page.
+//
+// What fp8 changes (one fp32 descale per (batch entry, K / V head) and tensor; Q, O, the partials and the combine kernel, the
+// grid, the four waves, the row packing, the split of the key tiles, the clamping and the merge of the waves are as above):
+//  * K and V are fetched as fp8, 16 bytes per lane and load, 8 loads per 32-key unit (the 16-bit form: 16):
+//        K   lane (li, g), load (kt, j): key 16 kt + li, d 64 j + 16 g .. + 15 -- 64-byte row segments, as in the 16-bit form.
+//            Bytes 8 h .. 8 h + 7 of the load are the lane's A operand of MFMA k-step s = 2 j + h, so k-step s, lane group g,
+//            element e multiplies d = 64 (s >> 1) + 16 g + 8 (s & 1) + e; Q^T is loaded in the same permutation of d (a dot
+//            product does not mind the order of its terms)
+//        V   lane (r = lane >> 3, c = lane & 7), load i: key 8 i + r, d 16 c .. + 15 -- whole 128-byte rows
+//    K stays fp8 in the prefetch registers and is converted to Q's type (v_cvt_scalef32_pk_{bf16,f16}_fp8, scale 1: every finite
+//    e4m3 value is exact in both) right before its MFMAs; V is converted before it is written to the wave's 16-bit LDS image,
+//    whose layout and transposed reads are unchanged.
+//  * k_descale is folded into the exponent's constant c = k_descale / sqrt(128) * log2(e) (a float product; the 16-bit form
+//    rounds the double product once): S and the running maximum m stay in raw (undescaled) logit units, and
+//    lse = m * k_descale / sqrt(128) + log(l).  (A positive descale keeps the maximum the maximum.)  v_descale is folded into
+//    the final 1 / l.  Both are one scalar per workgroup; no address depends on either.
+//  * A prefetch register set is 32 VGPRs instead of 64, so the 64-row form holds V a unit ahead as the others do.
 #pragma once
+#include <type_traits>
+
 #include "fa_fwd_kernel16.hpp"
 
 namespace fa {
@@ -38,27 +59,63 @@ struct DecodeArgs {
     int32_t max_len, page_size, num_pages, num_splits, causal;
 };
 
+// the 16-bit path's arguments (k, v: the fp8 bytes; kv_*: strides in bytes = elements) and the descales
+struct DecodeFp8Args {
+    DecodeArgs d;
+    const float *k_descale, *v_descale;   // (batch, n_kv_heads), row stride ds_bs; null = 1
+    int64_t ds_bs;
+};
+
 namespace decode {
 constexpr int D = 128, UNIT = 32, TILE = 64, NWAVES = 4, THREADS = NWAVES * 64;
 constexpr int VROW = 288;              // bytes per key of the V image: 256 + 32, so the 8 keys a 32-lane half's transposed read
                                        // covers (32 bytes of each) fall on all 64 banks
 constexpr int VBYTES = UNIT * VROW;    // one wave's image
 constexpr int row_tiles(int rows) { return rows <= 16 ? 1 : rows <= 32 ? 2 : 4; }
+
+// what both forms share of their arguments
+__host__ __device__ inline const DecodeArgs &common(const DecodeArgs &a) { return a; }
+__host__ __device__ inline const DecodeArgs &common(const DecodeFp8Args &a) { return a.d; }
+
+// eight e4m3fn values (two dwords, lowest byte first) as eight values of Q's type
+template <int DT>
+static FA_DEV typename Elem<DT>::vec8 cvt_fp8x8(unsigned w0, unsigned w1) {
+    u32x4 r;
+    if constexpr (DT == 15) {
+        r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false));
+        r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true));
+        r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false));
+        r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true));
+    } else {
+        r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, false));
+        r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, true));
+        r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, false));
+        r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, true));
+    }
+    return __builtin_bit_cast(typename Elem<DT>::vec8, r);
+}
 }  // namespace decode
 
-template <int DT, int NT, bool PAGED>
-__global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const DecodeArgs a) {
+template <class ARGS, int DT, int NT, bool PAGED>
+__global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const ARGS args) {
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
     using namespace decode;
+    constexpr bool FP8 = std::is_same_v<ARGS, DecodeFp8Args>;
     constexpr int KS = D / 32, DT16 = D / 16;
     constexpr int MERGE = NT * DT16 * 64 * 16;   // one wave's accumulators
     constexpr int MAIN = NWAVES * VBYTES > MERGE ? NWAVES * VBYTES : MERGE;
     __shared__ __attribute__((aligned(16))) char smem[MAIN + (NWAVES + 1) * NT * 16 * 4];
+    const DecodeArgs &a = common(args);
+    [[maybe_unused]] const uint8_t *const k8 = (const uint8_t *)a.k, *const v8 = (const uint8_t *)a.v;   // fp8: the cache's bytes
+    // one 32-key unit in the prefetch registers: 16 bytes per lane and load
+    using KRegs = std::conditional_t<FP8, u32x4[2][2], vec8[2][KS]>;
+    using VRegs = std::conditional_t<FP8, u32x4[4], s16x8[8]>;
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int li = lane & 15, g = lane >> 4;
+    [[maybe_unused]] const int vr = lane >> 3, vc = lane & 7;   // fp8: V's load shape
     const int nsp = a.num_splits;
     const int split = blockIdx.x % nsp, kvh = (blockIdx.x / nsp) % a.n_kv_heads, b = blockIdx.x / (nsp * a.n_kv_heads);
 
@@ -68,8 +125,13 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     const int t0 = (int)((int64_t)n_tiles * split / nsp), t1 = (int)((int64_t)n_tiles * (split + 1) / nsp);
     const int n_units = (len + UNIT - 1) / UNIT;
     const int u_end = 2 * t1 < n_units ? 2 * t1 : n_units;
+    float kd = 1.0f, vd = 1.0f;
+    if constexpr (FP8) {
+        kd = args.k_descale ? args.k_descale[(int64_t)b * args.ds_bs + kvh] : 1.0f;
+        vd = args.v_descale ? args.v_descale[(int64_t)b * args.ds_bs + kvh] : 1.0f;
+    }
 
-    // Q^T, resident; lim: the first key a row does not see
+    // Q^T, resident (fp8: in K's permutation of d); lim: the first key a row does not see
     vec8 Qr[NT][KS];
     int lim[NT];
 #pragma unroll
@@ -77,14 +139,20 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
         const int r = nt * 16 + li;
         const bool valid = r < a.rows;
         const int rr = valid ? r : 0, qi = rr / a.group, qh = kvh * a.group + rr % a.group;
-        const uint16_t *qp = a.q + (int64_t)b * a.q_bs + (int64_t)qi * a.q_ss + (int64_t)qh * a.q_hs + g * 8;
+        const uint16_t *qp = a.q + (int64_t)b * a.q_bs + (int64_t)qi * a.q_ss + (int64_t)qh * a.q_hs + g * (FP8 ? 16 : 8);
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) Qr[nt][ks] = *(const vec8 *)(qp + ks * 32);
+        for (int ks = 0; ks < KS; ++ks) Qr[nt][ks] = *(const vec8 *)(qp + (FP8 ? (ks >> 1) * 64 + (ks & 1) * 8 : ks * 32));
         lim[nt] = !valid ? 0 : (a.causal ? len - a.seqlen_q + qi + 1 : len);
     }
 
-    const float scale = 1.0f / __builtin_sqrtf((float)D);
-    const float c = (float)((double)scale * 1.4426950408889634074);
+    float scale, c;   // logits (fp8: raw logits) -> logits, and -> the exponent of exp2
+    if constexpr (FP8) {
+        scale = kd / __builtin_sqrtf((float)D);
+        c = scale * 1.4426950408889634074f;
+    } else {
+        scale = 1.0f / __builtin_sqrtf((float)D);
+        c = (float)((double)scale * 1.4426950408889634074);
+    }
     const float ninf = -__builtin_inff();
 
     f32x4 O[NT][DT16];
@@ -97,18 +165,19 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
         l[nt] = 0.0f;
     }
 
-    // one 32-key unit's K (the A operands of S^T: key 16 kt + li, d 32 ks + 8 g ..) and V (key 4 i + g, d 8 li ..: whole rows
-    // per instruction), 16 bytes per lane and load; keys at or beyond len come from key len - 1.  A unit at or beyond u_end
-    // (the prefetch behind a wave's last unit) is still loaded, every lane from the first row of unit `u_valid`: one cached
-    // row instead of 16 KiB, and the number of loads in flight stays the same on every path, so the waits can be counted
-    auto load_unit = [&](int u, int u_valid, vec8 (&Kr)[2][KS], s16x8 (&Vr)[8], auto want_k, auto want_v) {
+    // one 32-key unit's K (16-bit: the A operands of S^T, key 16 kt + li, d 32 ks + 8 g ..) and V (16-bit: key 4 i + g,
+    // d 8 li ..: whole rows per instruction; fp8: the shapes at the head of this file), 16 bytes per lane and load; keys at or
+    // beyond len come from key len - 1.  A unit at or beyond u_end (the prefetch behind a wave's last unit) is still loaded,
+    // every lane from the first row of unit `u_valid`: one cached row instead of 16 (fp8: 8) KiB, and the number of loads in
+    // flight stays the same on every path, so the waits can be counted
+    auto load_unit = [&](int u, int u_valid, KRegs &Kr, VRegs &Vr, auto want_k, auto want_v) {
         const bool real = u < u_end;
         const int key0 = (real ? u : u_valid) * UNIT;
         int64_t base;
         int row0;
         if constexpr (PAGED) {
             const int page = key0 / a.page_size;
-            // a scalar load (the compiler's own would be a vector load behind the unit's 16: waiting for it would drain them all)
+            // a scalar load (the compiler's own would be a vector load behind the unit's own: waiting for it would drain them all)
             int p;
             asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(p) : "s"(a.block_table + (int64_t)b * a.bt_bs + page) : "memory");
             p = p < 0 ? 0 : (p >= a.num_pages ? a.num_pages - 1 : p);
@@ -119,34 +188,62 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
             row0 = key0;
         }
         const int last = real ? len - 1 - key0 : 0;
+        if constexpr (FP8) {
 #pragma unroll
-        for (int kt = 0; kt < 2 && decltype(want_k)::value; ++kt) {
-            const int ko = kt * 16 + li < last ? kt * 16 + li : last;
-            const uint16_t *kp = a.k + base + (int64_t)(row0 + ko) * a.kv_ss + g * 8;
+            for (int kt = 0; kt < 2 && decltype(want_k)::value; ++kt) {
+                const int ko = kt * 16 + li < last ? kt * 16 + li : last;
+                const uint8_t *kp = k8 + base + (int64_t)(row0 + ko) * a.kv_ss + g * 16;
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) Kr[kt][ks] = *(const vec8 *)(kp + ks * 32);
-        }
+                for (int j = 0; j < 2; ++j) Kr[kt][j] = *(const u32x4 *)(kp + j * 64);
+            }
 #pragma unroll
-        for (int i = 0; i < 8 && decltype(want_v)::value; ++i) {
-            const int ko = i * 4 + g < last ? i * 4 + g : last;
-            Vr[i] = *(const s16x8 *)(a.v + base + (int64_t)(row0 + ko) * a.kv_ss + li * 8);
+            for (int i = 0; i < 4 && decltype(want_v)::value; ++i) {
+                const int ko = i * 8 + vr < last ? i * 8 + vr : last;
+                Vr[i] = *(const u32x4 *)(v8 + base + (int64_t)(row0 + ko) * a.kv_ss + vc * 16);
+            }
+        } else {
+#pragma unroll
+            for (int kt = 0; kt < 2 && decltype(want_k)::value; ++kt) {
+                const int ko = kt * 16 + li < last ? kt * 16 + li : last;
+                const uint16_t *kp = a.k + base + (int64_t)(row0 + ko) * a.kv_ss + g * 8;
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) Kr[kt][ks] = *(const vec8 *)(kp + ks * 32);
+            }
+#pragma unroll
+            for (int i = 0; i < 8 && decltype(want_v)::value; ++i) {
+                const int ko = i * 4 + g < last ? i * 4 + g : last;
+                Vr[i] = *(const s16x8 *)(a.v + base + (int64_t)(row0 + ko) * a.kv_ss + li * 8);
+            }
         }
     };
 
     char *vs = smem + wave * VBYTES;
     const char *vrd = vs + (4 * g + (li >> 2)) * VROW + (li & 3) * 8;   // T10: lane 4q + p of a group: row q, columns 4p ..
-    auto compute_unit = [&](int u, const vec8 (&Kr)[2][KS], const s16x8 (&Vr)[8]) {
+    auto compute_unit = [&](int u, const KRegs &Kr, const VRegs &Vr) {
+        if constexpr (FP8) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) *(s16x8 *)(vs + (i * 4 + g) * VROW + li * 16) = Vr[i];
+            for (int i = 0; i < 4; ++i) {
+                char *wp = vs + (i * 8 + vr) * VROW + vc * 32;
+                *(vec8 *)wp = cvt_fp8x8<DT>(Vr[i][0], Vr[i][1]);
+                *(vec8 *)(wp + 16) = cvt_fp8x8<DT>(Vr[i][2], Vr[i][3]);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) *(s16x8 *)(vs + (i * 4 + g) * VROW + li * 16) = Vr[i];
+        }
         f32x4 S[NT][2];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) S[nt][0] = S[nt][1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
+            for (int kt = 0; kt < 2; ++kt) {
+                vec8 ka;
+                if constexpr (FP8) ka = cvt_fp8x8<DT>(Kr[kt][ks >> 1][2 * (ks & 1)], Kr[kt][ks >> 1][2 * (ks & 1) + 1]);
+                else ka = Kr[kt][ks];
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) S[nt][kt] = E::mfma16(Kr[kt][ks], Qr[nt][ks], S[nt][kt]);
+                for (int nt = 0; nt < NT; ++nt) S[nt][kt] = E::mfma16(ka, Qr[nt][ks], S[nt][kt]);
+            }
         vec8 Pb[NT];
         const int key_g = u * UNIT + 4 * g;
 #pragma unroll
@@ -189,14 +286,14 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
 
     // Two register sets, A and B, taken in turn (the loop is unrolled by two, so no set is ever copied into the other): a
     // unit's loads are issued before the previous unit's work and waited for with the next unit's loads still in flight.
-    // 64 rows: Q^T and O^T take 192 registers, so only K is held a unit ahead; V is requested at the top of its own unit
-    // and arrives under the S^T products and the softmax (with V a unit ahead as well that form spills).
+    // 16-bit cache, 64 rows: Q^T and O^T take 192 registers, so only K is held a unit ahead; V is requested at the top of its
+    // own unit and arrives under the S^T products and the softmax (with V a unit ahead as well that form spills).
     {
-        constexpr bool V_AHEAD = NT < 4;
+        constexpr bool V_AHEAD = FP8 || NT < 4;
         using Ahead = BoolTag<V_AHEAD>;
         using Late = BoolTag<!V_AHEAD>;
-        vec8 Ka[2][KS], Kb[2][KS];
-        s16x8 Va[8], Vb[8];
+        KRegs Ka, Kb;
+        VRegs Va, Vb;
         int u = 2 * t0 + wave;
         if (u < u_end) load_unit(u, u, Ka, Va, BoolTag<true>{}, Ahead{});
         while (u < u_end) {
@@ -258,13 +355,13 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     }
     if (wave != 0) return;
 
-    // lane (li, g) holds row 16 nt + li, d 16 t + 4 g .. + 3
+    // lane (li, g) holds row 16 nt + li, d 16 t + 4 g .. + 3 (fp8: m is a raw logit, l a sum of undescaled V's weights)
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         const int r = nt * 16 + li;
         if (r >= a.rows) continue;
         const bool any = l[nt] > 0.0f;
-        const float inv = any ? 1.0f / l[nt] : 0.0f;
+        const float inv = any ? vd / l[nt] : 0.0f;
         const float lse = any ? m[nt] * scale + __logf(l[nt]) : ninf;
         const int qi = r / a.group, qh = kvh * a.group + r % a.group;
         if (nsp == 1) {
@@ -314,7 +411,37 @@ __global__ void __launch_bounds__(64) fa_decode_combine_kernel(const DecodeArgs 
     if (a.lse && threadIdx.x == 0) a.lse[((int64_t)b * a.n_heads + qh) * a.seqlen_q + qi] = lse;
 }
 
-// the split kernel and, for num_splits > 1, the combine kernel on stream s (fa_decode.hip)
-hipError_t decode_enqueue(const DecodeArgs &a, int dtype, hipStream_t s);
+// The enqueue of one decode in either form: the split kernel and, for num_splits > 1, the combine kernel (the partial format
+// is the same, so the fp8 form launches it on its DecodeArgs part) on stream s.  Instantiated by fa_decode.hip (DecodeArgs) and
+// fa_decode_fp8.hip (DecodeFp8Args), which hold the kernels.
+template <class ARGS, int DT, int NT, bool PAGED>
+static hipError_t decode_enqueue_t(const ARGS &args, hipStream_t s) {
+    const DecodeArgs &a = decode::common(args);
+    void *params[] = {(void *)&args}, *cparams[] = {(void *)&a};
+    const hipError_t rc = hipLaunchKernel((const void *)&fa_decode_split_kernel<ARGS, DT, NT, PAGED>,
+                                          dim3((unsigned)((int64_t)a.batch * a.n_kv_heads * a.num_splits)), dim3(decode::THREADS), params, 0, s);
+    if (rc != hipSuccess || a.num_splits == 1) return rc;
+    return hipLaunchKernel((const void *)&fa_decode_combine_kernel<DT>, dim3((unsigned)((int64_t)a.batch * a.n_kv_heads * a.rows)), dim3(64),
+                           cparams, 0, s);
+}
+
+template <class ARGS>
+static hipError_t decode_enqueue_any(const ARGS &args, int dtype, hipStream_t s) {
+    const DecodeArgs &a = decode::common(args);
+    const bool paged = a.block_table != nullptr, bf16 = dtype == 15;
+    auto go = [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        if (bf16) return paged ? decode_enqueue_t<ARGS, 15, NT, true>(args, s) : decode_enqueue_t<ARGS, 15, NT, false>(args, s);
+        return paged ? decode_enqueue_t<ARGS, 5, NT, true>(args, s) : decode_enqueue_t<ARGS, 5, NT, false>(args, s);
+    };
+    switch (decode::row_tiles(a.rows)) {
+    case 1: return go(IntTag<1>{});
+    case 2: return go(IntTag<2>{});
+    default: return go(IntTag<4>{});
+    }
+}
+
+hipError_t decode_enqueue(const DecodeArgs &a, int dtype, hipStream_t s);          // fa_decode.hip
+hipError_t decode_fp8_enqueue(const DecodeFp8Args &a, int dtype, hipStream_t s);   // fa_decode_fp8.hip
 
 }  // namespace fa

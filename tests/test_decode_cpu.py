@@ -167,13 +167,13 @@ def test_decode_slice_isa():
     assert sizes and all(s == "0" for s in sizes)
     assert all(s == "0" for s in re.findall(r"\.vgpr_spill_count:\s+(\d+)", text))
     names = set(re.findall(r"^\s+\.name:\s+(_Z\w+)$", text, re.M))
-    want = {f"_ZN2fa22fa_decode_split_kernelILi{dt}ELi{nt}ELb{p}EEEvNS_10DecodeArgsE" for dt in (15, 5) for nt in (1, 2, 4) for p in (0, 1)}
+    want = {f"_ZN2fa22fa_decode_split_kernelINS_10DecodeArgsELi{dt}ELi{nt}ELb{p}EEEvT_" for dt in (15, 5) for nt in (1, 2, 4) for p in (0, 1)}
     want |= {f"_ZN2fa24fa_decode_combine_kernelILi{dt}EEEvNS_10DecodeArgsE" for dt in (15, 5)}
     assert names == want, names ^ want
     for name, body in _kernels(text).items():   # each dtype's kernels use that dtype's MFMA only
-        if "split_kernelILi15" in name:
+        if "split_kernelINS_10DecodeArgsELi15E" in name:
             assert "v_mfma_f32_16x16x32_bf16" in body and "v_mfma_f32_16x16x32_f16" not in body
-        if "split_kernelILi5" in name:
+        if "split_kernelINS_10DecodeArgsELi5E" in name:
             assert "v_mfma_f32_16x16x32_f16" in body and "v_mfma_f32_16x16x32_bf16" not in body
 
 

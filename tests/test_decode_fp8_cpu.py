@@ -146,16 +146,16 @@ def test_fp8_slice_isa():
     assert all(s == "0" for s in re.findall(r"\.vgpr_spill_count:\s+(\d+)", text))
     assert all(s == "0" for s in re.findall(r"\.sgpr_spill_count:\s+(\d+)", text))
     names = set(re.findall(r"^\s+\.name:\s+(_Z\w+)$", text, re.M))
-    want = {f"_ZN2fa26fa_decode_fp8_split_kernelILi{dt}ELi{nt}ELb{p}EEEvNS_13DecodeFp8ArgsE" for dt in (15, 5) for nt in (1, 2, 4) for p in (0, 1)}
+    want = {f"_ZN2fa22fa_decode_split_kernelINS_13DecodeFp8ArgsELi{dt}ELi{nt}ELb{p}EEEvT_" for dt in (15, 5) for nt in (1, 2, 4) for p in (0, 1)}
     want |= {f"_ZN2fa24fa_decode_combine_kernelILi{dt}EEEvNS_10DecodeArgsE" for dt in (15, 5)}   # the 16-bit path's, from its header
     assert names == want, names ^ want
     kernels = _kernels(text)
     assert set(kernels) == want
     for name, body in kernels.items():   # each dtype's kernels convert to, and multiply in, that dtype only
-        if "split_kernelILi15" in name:
+        if "split_kernelINS_13DecodeFp8ArgsELi15E" in name:
             assert "v_mfma_f32_16x16x32_bf16" in body and "v_mfma_f32_16x16x32_f16" not in body
             assert "v_cvt_scalef32_pk_bf16_fp8" in body and "v_cvt_scalef32_pk_f16_fp8" not in body
-        if "split_kernelILi5" in name:
+        if "split_kernelINS_13DecodeFp8ArgsELi5E" in name:
             assert "v_mfma_f32_16x16x32_f16" in body and "v_mfma_f32_16x16x32_bf16" not in body
             assert "v_cvt_scalef32_pk_f16_fp8" in body and "v_cvt_scalef32_pk_bf16_fp8" not in body
         if "combine" in name:

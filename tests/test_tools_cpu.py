@@ -358,6 +358,31 @@ def test_visit_histogram_matches_the_committed_digest():
     assert got["second_pass_half_visits"] == want["second_pass_half_visits"], "the half-item visit's histogram moved"
 
 
+def test_folded_kernels_keep_their_recorded_bodies():
+    """The decode split kernel (16-bit and fp8 cache) and the varlen backward (one and two ranges) are one text each,
+    instantiated per form in a slice of its own (fa_decode_kernel.hpp, fa_bwd_varlen.hpp).  tests/golden/folded_kernel_bodies.json
+    holds what the last commit with two texts per family compiled to (tools/isa_bodies.py): per kernel, keyed by slice, family,
+    argument form and template arguments, a SHA-256 of the normalised function body and one of the .amdhsa_* descriptor block.
+    The build must give the same 28 + 22 kernels, hash for hash: a change to the shared text that moves the code of a form it
+    did not mean to touch fails here.  The hashes are one hipcc's; under another the comparison says nothing and is skipped."""
+    import json
+
+    import pytest
+
+    from flash_attention_from_scratch_amd.tools import isa_bodies
+
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "folded_kernel_bodies.json")))
+    got = isa_bodies.bodies()
+    assert got is not None, "the build keeps the ISA of every slice under csrc/build (make -C flash_attention_from_scratch_amd/csrc)"
+    if got["hipcc"] != want["hipcc"]:
+        pytest.skip(f"the record is of another hipcc ({want['hipcc']}); this one: {got['hipcc']}")
+    count = lambda prefixes: sum(k.startswith(prefixes) for k in got["kernels"])  # noqa: E731
+    assert count(("decode/", "decode_fp8/")) == 28 and count(("bwd_varlen/", "bwd_varlen_qk/")) == 22
+    assert set(got["kernels"]) == set(want["kernels"]), set(got["kernels"]) ^ set(want["kernels"])
+    moved = sorted(k for k, v in want["kernels"].items() if got["kernels"][k] != v)
+    assert not moved, moved
+
+
 def test_product_translation_units_cannot_instantiate_timing_only_variants(tmp_path):
     """VERDICT r05 task 8: the persistent kernel's experiment bits (template argument ABL: most of them compute WRONG
     results on purpose, for timing) exist only in tools built with -DFA_TUNE.  The product's slices are compiled without it

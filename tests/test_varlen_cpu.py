@@ -237,8 +237,13 @@ def test_varlen_slices_have_mfma_and_no_scratch():
     assert "ds_read_b64_tr_b16" in text
     assert "scratch_" not in text
     assert re.search(r"private_segment_fixed_size:\s+[1-9]", text) is None
-    for kernel in ("fa_bwd_dkdv_varlen_kernel", "fa_bwd_dq_varlen_kernel", "fa_bwd_delta_varlen_kernel", "fa_bwd_dkdv_reduce_varlen_kernel"):
-        assert kernel in text, kernel
+    # one text per kernel (fa_bwd_varlen.hpp): this slice holds the one-range forms, and none of the two-range ones
+    names = set(re.findall(r"^\s+\.name:\s+(_Z\w+)$", text, re.M))
+    want = {f"_ZN2fa26fa_bwd_delta_varlen_kernelILi{dt}EEEvNS_13BwdVarlenArgsE" for dt in (15, 5)}
+    want |= {f"_ZN2fa32fa_bwd_dkdv_reduce_varlen_kernelINS_13BwdVarlenArgsELi{dt}EEEvT_" for dt in (15, 5)}
+    for kernel in ("25fa_bwd_dkdv_varlen_kernel", "23fa_bwd_dq_varlen_kernel"):
+        want |= {f"_ZN2fa{kernel}INS_13BwdVarlenArgsELi{dt}ELb{c}EEEvT_" for dt in (15, 5) for c in (0, 1)}
+    assert names == want, names ^ want
 
 
 def test_dense_training_entry_points_still_refuse_ragged_lengths():

@@ -305,8 +305,14 @@ def test_varlen_qk_slices_have_mfma_and_no_scratch():
     assert "v_mfma_f32_32x32x16_bf16" in text and "v_mfma_f32_32x32x16_f16" in text
     assert "ds_read_b64_tr_b16" in text
     _no_scratch_no_spills(text)
-    for kernel in ("fa_bwd_dkdv_varlen_qk_kernel", "fa_bwd_dq_varlen_qk_kernel", "fa_bwd_dkdv_reduce_varlen_qk_kernel"):
-        assert re.search(rf"^_ZN2fa\d+{kernel}\w+:", text, flags=re.M), kernel
+    # one text per kernel (fa_bwd_varlen.hpp): this slice holds the two-range forms (delta comes from the one-range slice)
+    names = set(re.findall(r"^\s+\.name:\s+(_Z\w+)$", text, re.M))
+    want = {f"_ZN2fa32fa_bwd_dkdv_reduce_varlen_kernelINS_15BwdVarlenQKArgsELi{dt}EEEvT_" for dt in (15, 5)}
+    for kernel in ("25fa_bwd_dkdv_varlen_kernel", "23fa_bwd_dq_varlen_kernel"):
+        want |= {f"_ZN2fa{kernel}INS_15BwdVarlenQKArgsELi{dt}ELb{c}EEEvT_" for dt in (15, 5) for c in (0, 1)}
+    assert names == want, names ^ want
+    for name in want:
+        assert re.search(rf"^{name}:", text, flags=re.M), name
     assert "atomic" not in text   # no float atomics: a fixed order of sums
 
 
