@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "fa_decode_fp8_supported", "fa_decode_fp8_num_splits", "fa_decode_fp8_workspace_bytes", "fa_decode_fp8_launch",
     "fa_kvcache_append_launch",
     "fa_fwd_varlen_kvcache_supported", "fa_fwd_launch_varlen_kvcache",
+    "fa_fwd_varlen_kvcache_fp8_supported", "fa_fwd_launch_varlen_kvcache_fp8",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -224,6 +225,21 @@ def make_kvcache_layout(**fields):
     return a
 
 
+class FaKvcacheFp8Scales(ctypes.Structure):   # fa_kvcache_fp8_scales (the fp8 side of a prefill against an fp8 cache: encoding and descales)
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("kv_dtype", ctypes.c_int32), ("k_descale", ctypes.c_void_p), ("v_descale", ctypes.c_void_p),
+        ("descale_batch_stride", ctypes.c_int64),
+    ]
+
+
+def make_kvcache_fp8_scales(**fields):
+    """fa_kvcache_fp8_scales with struct_size set; kv_dtype defaults to e4m3fn, everything not given to 0 / null."""
+    a = FaKvcacheFp8Scales(struct_size=ctypes.sizeof(FaKvcacheFp8Scales), kv_dtype=FA_KV_FP8_E4M3FN)
+    for name, value in fields.items():
+        setattr(a, name, value)
+    return a
+
+
 def make_varlen_layout(cu_seqlens_ptr, n_seqs, total_tokens, max_seqlen):
     return FaVarlenLayout(struct_size=ctypes.sizeof(FaVarlenLayout), cu_seqlens=cu_seqlens_ptr, n_seqs=n_seqs,
                           total_tokens=total_tokens, max_seqlen=max_seqlen)
@@ -368,6 +384,12 @@ def load():
     lib.fa_decode_workspace_bytes.argtypes = [ctypes.POINTER(FaDecodeArgs)]
     lib.fa_decode_launch.restype = ctypes.c_int
     lib.fa_decode_launch.argtypes = [ctypes.POINTER(FaDecodeArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    lib.fa_fwd_varlen_kvcache_fp8_supported.restype = ctypes.c_int
+    lib.fa_fwd_varlen_kvcache_fp8_supported.argtypes = [cfg_p, ctypes.POINTER(FaFwdOpts)]
+    lib.fa_fwd_launch_varlen_kvcache_fp8.restype = ctypes.c_int
+    lib.fa_fwd_launch_varlen_kvcache_fp8.argtypes = [args_p, ctypes.POINTER(FaKvLayout), ctypes.POINTER(FaVarlenLayout),
+                                                     ctypes.POINTER(FaKvcacheLayout), ctypes.POINTER(FaKvcacheFp8Scales),
+                                                     ctypes.POINTER(FaFwdOpts), ctypes.c_void_p, ctypes.c_void_p]
     lib.fa_decode_fp8_supported.restype = ctypes.c_int
     lib.fa_decode_fp8_supported.argtypes = [ctypes.POINTER(FaDecodeFp8Args)]
     lib.fa_decode_fp8_num_splits.restype = ctypes.c_int

@@ -48,6 +48,9 @@ int varlen_lds_bytes_dt15();
 // fa_inst_varlen_kvcache.hip: the same forward with its keys taken from a KV cache (the varlen form's LDS)
 kernel_fn_varlen_kvcache varlen_kvcache_kernel_dt15(bool first_block_skip);
 kernel_fn_varlen_kvcache varlen_kvcache_kernel_dt5(bool first_block_skip);
+// fa_inst_varlen_kvcache_fp8.hip: ... from an fp8 (e4m3fn) KV cache (the same LDS)
+kernel_fn_varlen_kvcache_fp8 varlen_kvcache_fp8_kernel_dt15(bool first_block_skip);
+kernel_fn_varlen_kvcache_fp8 varlen_kvcache_fp8_kernel_dt5(bool first_block_skip);
 // fa_bwd_varlen.hip / fa_bwd_varlen_qk.hip: the packed backward, and its form with separate Q and K / V lengths
 hipError_t bwd_varlen_enqueue(const BwdVarlenArgs &a, int dtype, bool causal, hipStream_t s);
 hipError_t bwd_varlen_qk_enqueue(const BwdVarlenQKArgs &a, int dtype, bool causal, hipStream_t s);
@@ -290,6 +293,17 @@ void do_init_body(int dev, DeviceState *st) {
         if (rc != hipSuccess) {
             st->status = FA_ERR_LAUNCH;
             snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, varlen KV-cache form) on device %d: %s",
+                     fa::varlen_lds_bytes_dt15(), dev, hipGetErrorString(rc));
+            return;
+        }
+    }
+    // ... and against an fp8 KV cache (fa_fwd_launch_varlen_kvcache_fp8)
+    for (int i = 0; i < 4; ++i) {
+        const void *fn = (i & 2) ? (const void *)fa::varlen_kvcache_fp8_kernel_dt5((i & 1) != 0) : (const void *)fa::varlen_kvcache_fp8_kernel_dt15((i & 1) != 0);
+        const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, fa::varlen_lds_bytes_dt15());
+        if (rc != hipSuccess) {
+            st->status = FA_ERR_LAUNCH;
+            snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, varlen fp8 KV-cache form) on device %d: %s",
                      fa::varlen_lds_bytes_dt15(), dev, hipGetErrorString(rc));
             return;
         }
@@ -1031,13 +1045,30 @@ int kvcache_validate(const fa_kvcache_layout *kc, const fa_kv_layout *kv, const 
     return FA_OK;
 }
 
+// the fp8 side of fa_fwd_launch_varlen_kvcache_fp8: fa_decode_fp8_launch's rules for the same fields (kv: already validated as a
+// 16-bit cache's, whose rules for sign and size hold for bytes too)
+int kvcache_fp8_validate(const fa_kvcache_fp8_scales *sc, const fa_kv_layout *kv) {
+    if (sc->struct_size < sizeof(fa_kvcache_fp8_scales))
+        return fail(FA_ERR_SHAPE, "fa_kvcache_fp8_scales.struct_size (%u) is smaller than this library's (%zu)", sc->struct_size,
+                    sizeof(fa_kvcache_fp8_scales));
+    if (sc->kv_dtype != FA_KV_FP8_E4M3FN)
+        return fail(FA_ERR_DTYPE, "kv_dtype (%d) is not served: the fp8 cache is e4m3fn (FA_KV_FP8_E4M3FN)", sc->kv_dtype);
+    if ((sc->k_descale || sc->v_descale) && sc->descale_batch_stride < kv->n_kv_heads)
+        return fail(FA_ERR_SHAPE, "descale_batch_stride (%lld) is smaller than n_kv_heads (%lld)", (long long)sc->descale_batch_stride,
+                    (long long)kv->n_kv_heads);
+    // (the strides' multiple of 16 bytes: checked in fwd_launch_varlen, in front of the rules worded in elements)
+    if (((uintptr_t)sc->k_descale | (uintptr_t)sc->v_descale) & 3) return fail(FA_ERR_ALIGN, "k_descale and v_descale must be 4-byte aligned");
+    return FA_OK;
+}
+
 // the forward of `entry` (a public entry point; `total`: its name for the query side's total)
 // `kc` non-null: the key side is a KV cache (fa_fwd_launch_varlen_kvcache), and vk is not used
+// `fp8_side`: ... an fp8 one (fa_fwd_launch_varlen_kvcache_fp8): k, v are bytes, kv's strides count bytes, `sc` holds the descales
 int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
                       const fa_varlen_layout *vk, const fa_fwd_opts *opts, float *lse, void *stream, const fa_kvcache_layout *kc = nullptr,
-                      bool cache_side = false) {
+                      bool cache_side = false, const fa_kvcache_fp8_scales *sc = nullptr, bool fp8_side = false) {
     if (cache_side) vk = vq;   // (one valid layout for the checks both launches share)
-    if (!args || !kv || !vq || !vk || (cache_side && !kc)) return fail(FA_ERR_NULL, "null pointer argument");
+    if (!args || !kv || !vq || !vk || (cache_side && !kc) || (fp8_side && !sc)) return fail(FA_ERR_NULL, "null pointer argument");
     if (!args->q || !args->k || !args->v || !args->o) return fail(FA_ERR_NULL, "null pointer argument");
     if (!lse) return fail(FA_ERR_NULL, "lse is null: %s needs a (n_heads, %s) fp32 buffer", entry, total);
     if (args->cfg.dtype != FA_FP16 && args->cfg.dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
@@ -1055,12 +1086,16 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
         return fail(FA_ERR_SHAPE, "grouped-query attention needs n_kv_heads (%lld) to divide n_heads (%lld)", (long long)kv->n_kv_heads,
                     (long long)args->n_heads);
     if ((rc = check_strides_varlen("q", args->n_heads, args->seq_stride, args->head_stride)) != FA_OK) return rc;
-    if ((rc = check_strides_varlen("kv", kv->n_kv_heads, kv->kv_seq_stride, kv->kv_head_stride)) != FA_OK) return rc;
+    // (an fp8 cache's strides count bytes: its own alignment rule first, so that no message about elements is reached with one)
+    if (fp8_side && ((kv->kv_batch_stride | kv->kv_seq_stride | kv->kv_head_stride) & 15))
+        return fail(FA_ERR_ALIGN, "kv strides of an fp8 cache must be multiples of 16 bytes");
+    if ((rc = check_strides_varlen(fp8_side ? "kv (fp8 cache: bytes for elements)" : "kv", kv->n_kv_heads, kv->kv_seq_stride, kv->kv_head_stride)) != FA_OK) return rc;
     if ((rc = varlen_grid_check(vq, args->n_heads)) != FA_OK) return rc;
     if (((uintptr_t)args->q | (uintptr_t)args->k | (uintptr_t)args->v | (uintptr_t)args->o) & 15)
         return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
     if ((uintptr_t)lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
     if (cache_side && (rc = kvcache_validate(kc, kv, vq)) != FA_OK) return rc;
+    if (fp8_side && (rc = kvcache_fp8_validate(sc, kv)) != FA_OK) return rc;
     if (vq->total_tokens == 0) {   // (no query rows: nothing to write)
         if (o.ms) *o.ms = 0.0f;
         return FA_OK;
@@ -1069,7 +1104,8 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
     if (!dev) return rc;
     const char *why;
     const fa::KernelEntry *e = varlen_entry(&args->cfg, &why);
-    fa::KernelArgsVarlenKVCache ca;
+    fa::KernelArgsVarlenKVCacheFp8 fa8;
+    fa::KernelArgsVarlenKVCache &ca = fa8.c;
     fa::KernelArgsVarlenQK qa;
     fa::KernelArgsVarlen &va = cache_side ? ca.v : qa.v;
     va.base.q = args->q;
@@ -1109,6 +1145,13 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
         ca.max_len = (int32_t)(kc->max_seqlen_k > 0 ? kc->max_seqlen_k : cap);
         fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kvcache_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_kernel_dt5(fbs);
         kernel_args = &ca;
+    }
+    if (fp8_side) {
+        fa8.k_descale = sc->k_descale;
+        fa8.v_descale = sc->v_descale;
+        fa8.ds_bs = sc->descale_batch_stride;
+        fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kvcache_fp8_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_fp8_kernel_dt5(fbs);
+        kernel_args = &fa8;
     }
     const dim3 grid((unsigned)(va.base.n_bh * va.base.n_q_blocks)), block((unsigned)e->threads);
     const hipStream_t s = (hipStream_t)stream;
@@ -1275,6 +1318,13 @@ int fa_fwd_varlen_kvcache_supported(const fa_fwd_config *cfg, const fa_fwd_opts 
 int fa_fwd_launch_varlen_kvcache(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_kvcache_layout *kc,
                                  const fa_fwd_opts *opts, float *lse, void *stream) {
     return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true);
+}
+
+int fa_fwd_varlen_kvcache_fp8_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
+
+int fa_fwd_launch_varlen_kvcache_fp8(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_kvcache_layout *kc,
+                                     const fa_kvcache_fp8_scales *sc, const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache_fp8", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true, sc, true);
 }
 
 int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *a) {

@@ -77,23 +77,7 @@ constexpr int row_tiles(int rows) { return rows <= 16 ? 1 : rows <= 32 ? 2 : 4; 
 __host__ __device__ inline const DecodeArgs &common(const DecodeArgs &a) { return a; }
 __host__ __device__ inline const DecodeArgs &common(const DecodeFp8Args &a) { return a.d; }
 
-// eight e4m3fn values (two dwords, lowest byte first) as eight values of Q's type
-template <int DT>
-static FA_DEV typename Elem<DT>::vec8 cvt_fp8x8(unsigned w0, unsigned w1) {
-    u32x4 r;
-    if constexpr (DT == 15) {
-        r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false));
-        r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true));
-        r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false));
-        r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true));
-    } else {
-        r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, false));
-        r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, true));
-        r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, false));
-        r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, true));
-    }
-    return __builtin_bit_cast(typename Elem<DT>::vec8, r);
-}
+// (eight e4m3fn values as eight values of Q's type: cvt_fp8x8, fa_fwd_kernel.hpp)
 }  // namespace decode
 
 template <class ARGS, int DT, int NT, bool PAGED>

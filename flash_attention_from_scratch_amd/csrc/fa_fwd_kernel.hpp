@@ -62,6 +62,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace fa {
 
@@ -244,6 +245,31 @@ template <> struct Elem<5> {  // fp16
         return r;
     }
 };
+
+// eight e4m3fn values (two dwords, lowest byte first) as eight values of Q's type: exact, every e4m3 value is a bf16 and an fp16
+// (the fp8 caches: fa_decode_kernel.hpp, and fa_fwd_kernel_varlen_kvcache_fp8 below)
+template <int DT>
+static FA_DEV typename Elem<DT>::vec8 cvt_fp8x8(unsigned w0, unsigned w1) {
+    u32x4 r;
+    if constexpr (DT == 15) {
+        r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false));
+        r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true));
+        r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false));
+        r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true));
+    } else {
+        r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, false));
+        r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, true));
+        r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, false));
+        r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, true));
+    }
+    return __builtin_bit_cast(typename Elem<DT>::vec8, r);
+}
+
+// a product that keeps its own rounding: never contracted into an fma with the add that consumes it
+static FA_DEV float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
 
 // Single-instruction VALU forms for the hand-placed schedule: plain C++ lets hipcc SLP-pack adjacent
 // f32 adds into v_pk_add_f32 and canonicalise fmaxf inputs, both slower beside MFMAs.
@@ -451,6 +477,41 @@ struct KernelArgsVarlenKVCache {
     int32_t max_len;               // min(capacity, max_seqlen_k)
 };
 typedef void (*kernel_fn_varlen_kvcache)(const KernelArgsVarlenKVCache);
+// ... against an fp8 (e4m3fn) cache (fa_fwd_launch_varlen_kvcache_fp8): fa_fwd_kernel_varlen_kvcache_fp8 is
+// fa_fwd_kernel_varlen_kvcache with one more way to FETCH a tile.  Only fa_inst_varlen_kvcache_fp8.hip defines
+// FA_KERNEL_VARLEN_KVCACHE_FP8 (beside the other two) and gets that kernel INSTEAD; `if constexpr (FP8)` (or an #ifdef arm where
+// a name exists in one form only) marks every site where the two differ.  k and v hold one byte per element, so the cache's
+// strides count bytes.  The DMA cannot convert, so the tiles take the register-staged transport (DMA == false) with the
+// conversion between the load and the LDS write: the LDS images are byte for byte what the DMA builds from the dequantized
+// cache, and everything behind them is the 16-bit kernel's.  Key j of sequence b, K / V head g stands for
+// float(k8[j]) * k_descale[b][g], likewise V: k_descale goes into the exponent's constant c (S and the running max stay raw
+// logits), v_descale into the final 1 / l.  No address depends on either.
+struct KernelArgsVarlenKVCacheFp8 {
+    KernelArgsVarlenKVCache c;            // k, v: the fp8 bytes; kv_seq_stride, kv_head_stride, page_stride: bytes
+    const float *k_descale, *v_descale;   // (n_seqs, n_kv_heads) fp32 (DEVICE), row stride ds_bs; null = 1
+    int64_t ds_bs;
+};
+typedef void (*kernel_fn_varlen_kvcache_fp8)(const KernelArgsVarlenKVCacheFp8);
+#ifdef FA_KERNEL_VARLEN_KVCACHE_FP8
+#define FA_FP8_CACHE true
+#define FA_K_DESCALED(c0) (fa8.k_descale ? (c0) * fa8.k_descale[(int64_t)b * fa8.ds_bs + h / va.group] : (c0))
+#define FA_ST_SS32 kv_ss   // the K / V seq stride of the register-staged transport: the cache's (bytes) ...
+// m c of the LSE line, rounded before log2 l is added.  With c a compile-time constant (every other form) hipcc moves the
+// product into finite_or_zero's select, which keeps it from contracting with the add; with c a run-time value (c0 k_descale)
+// it would form fma(m, c, log2 l) and lse would differ from the 16-bit cache's in the last bit.
+#define FA_LSE_M_TIMES_C(m, c) mul_rounded(m, c)
+#else
+#define FA_FP8_CACHE false
+#define FA_K_DESCALED(c0) c0
+#define FA_LSE_M_TIMES_C(m, c) m * c
+#define FA_ST_SS32 ss      // ... or the dense kernels', Q's (no other varlen form is built on that transport: the static_assert)
+#endif
+// the register-staged transport's tile: the fp8 cache's is found by the walk (the caller passes its base), a tensor's by its number
+#ifdef FA_KERNEL_VARLEN_KVCACHE_FP8
+#define FA_ST_TILE(tensor, it) (tensor)
+#else
+#define FA_ST_TILE(tensor, it) tensor + (int64_t)(n_kv - 1 - it) * tile_stride
+#endif
 #ifdef FA_KERNEL_VARLEN
 #define FA_KV_SS32 kv_ss
 #define FA_SEQ_LEN v_seq_len
@@ -488,12 +549,17 @@ __global__ void
 #ifdef FA_KERNEL_VARLEN
 // (one workgroup per SIMD set: with m live up to the LSE store the 256-register budget of two waves per SIMD spills)
 __launch_bounds__(NWAVES * 64, 1)
-#ifdef FA_KERNEL_VARLEN_KVCACHE
+#ifdef FA_KERNEL_VARLEN_KVCACHE_FP8
+fa_fwd_kernel_varlen_kvcache_fp8(const KernelArgsVarlenKVCacheFp8 fa8) {
+    const KernelArgsVarlenKVCache &qa = fa8.c;
+#elif defined(FA_KERNEL_VARLEN_KVCACHE)
 fa_fwd_kernel_varlen_kvcache(const KernelArgsVarlenKVCache qa) {
 #else
 fa_fwd_kernel_varlen(const KernelArgsVarlenQK qa) {
 #endif
-    static_assert(MASK && DMA && KSPLIT == 1 && ABL == 0 && QT == 1, "the varlen form is the masked LDS-DMA kernel");
+    // (the fp8 cache's form: the same kernel on the register-staged transport, which can convert)
+    static_assert(MASK && DMA != FA_FP8_CACHE && KSPLIT == 1 && ABL == 0 && QT == 1,
+                  "the varlen form is the masked LDS-DMA kernel; against an fp8 cache, the masked register-staged one");
     const KernelArgsVarlen &va = qa.v;  // (the query side)
     const KernelArgs &args = va.base;   // (seq_len and n_kv_blocks are the sequence's: FA_SEQ_LEN, FA_N_KV_BLOCKS)
 #else
@@ -503,6 +569,8 @@ fa_fwd_kernel(const KernelArgs args) {
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
     using TR = FwdTraits<DT, QT, NWAVES, BC, SWZ, EAGER, OPT, PIPE, DMA, MASK, D, KSPLIT>;
+    enum : bool { FP8 = FA_FP8_CACHE };      // K / V are e4m3fn bytes (fa_fwd_kernel_varlen_kvcache_fp8 only)
+    static_assert(!FP8 || (D == 128 && BC == 64 && NWAVES == 4), "the fp8 transport is built for 64-key tiles of d_head 128, four waves");
     static_assert(KSPLIT == 1 || (KSPLIT == 2 && NWAVES == 4 && QT == 1 && BC == 64 && DMA && !MASK && D == 128),
                   "the key split is built for (B_r 64, B_c 64, 4 waves)");
     constexpr int ROWB = 2 * D;              // bytes per K / V / O row (256, or 128 at d_head 64)
@@ -557,6 +625,7 @@ fa_fwd_kernel(const KernelArgs args) {
     if (MASK && args.causal) qb = nq - 1 - qb;  // longest rows first
     const int b = bh / args.n_heads, h = bh % args.n_heads;
     const int64_t ss = args.seq_stride;
+    typedef std::conditional_t<FA_FP8_CACHE, uint8_t, uint16_t> kv_elem;   // what a K / V stride counts
 #ifdef FA_KERNEL_VARLEN
     // b is the sequence: its first row and length from cu_seqlens, clamped so that every row this workgroup derives is a row
     // of the tensors whatever cu_seqlens holds (first row in [0, total_tokens], length in [0, min(max_seqlen, what is left)])
@@ -593,14 +662,14 @@ fa_fwd_kernel(const KernelArgs args) {
     const int64_t head_off = v_row0 * ss + (int64_t)h * args.head_stride;
     const int64_t kv_head_off = k_row0 * kv_ss + (int64_t)(h / va.group) * va.kv_head_stride;
     const uint16_t *Qg = (const uint16_t *)args.q + head_off;
-    const uint16_t *Kg = (const uint16_t *)args.k + kv_head_off;
-    const uint16_t *Vg = (const uint16_t *)args.v + kv_head_off;
+    const kv_elem *Kg = (const kv_elem *)args.k + kv_head_off;   // (fp8: the strides count bytes)
+    const kv_elem *Vg = (const kv_elem *)args.v + kv_head_off;
     uint16_t *Og = (uint16_t *)args.o + head_off;
 #else
     const int64_t head_off = (int64_t)b * args.batch_stride + (int64_t)h * args.head_stride;
     const uint16_t *Qg = (const uint16_t *)args.q + head_off;
-    const uint16_t *Kg = (const uint16_t *)args.k + head_off;
-    const uint16_t *Vg = (const uint16_t *)args.v + head_off;
+    const kv_elem *Kg = (const kv_elem *)args.k + head_off;
+    const kv_elem *Vg = (const kv_elem *)args.v + head_off;
     uint16_t *Og = (uint16_t *)args.o + head_off;
 #endif
 
@@ -670,6 +739,14 @@ fa_fwd_kernel(const KernelArgs args) {
     // load whose wait the compiler places at the first use -- as a global load between the DMA's inline asm it becomes a vector
     // load that is waited for (vmcnt(0): the K tile just requested) on the spot.  K is requested one tile ahead of V, so V's
     // base is the last K base or the one before it (kc_last, kc_prev).
+    // The register-staged transport (the fp8 cache's) asks in another order -- prologue K0 V0 K1 V1 K2, visit `it` K(it+3) then
+    // V(it+2) -- but K tiles still come in visit order, each once, so kc_offset / kc_step and the table entry's lead (requested
+    // behind one K request, used by the next) stand as they are; only the V rule is derived again.  V0 and V1 are requested
+    // right behind their own K: kc_last.  V(j), j >= 2, is requested in visit j - 2 behind K(j + 1) if that tile exists
+    // (j + 1 < n_kv): the last K request is one tile ahead and V's base is kc_prev; else K(j) was the walk's last request (K(n_kv - 1)
+    // was requested in visit n_kv - 4 or in the prologue, and nothing since): kc_last.  K2, requested between V1 and V2, moves K1's base
+    // out of (kc_last, kc_prev) only after V1 has used it.  One pair of bases serves both orders: the DMA's rule with its
+    // `it > 0` read `it >= 2` (load_v), and no counter of V's own.
     typedef const __attribute__((address_space(4))) int32_t *kc_table_ptr;
     const int kc_tpp = qa.tiles_per_page;
     int kc_page = (n_kv - 1) / kc_tpp;
@@ -703,9 +780,9 @@ fa_fwd_kernel(const KernelArgs args) {
     };
     auto issue_k = [&](int it, int stage) {
 #ifdef FA_KERNEL_VARLEN_KVCACHE
-        const uint16_t *base = Kg + kc_offset();   // (K tiles are requested in visit order, each once)
+        const kv_elem *base = Kg + kc_offset();   // (K tiles are requested in visit order, each once)
 #else
-        const uint16_t *base = Kg + (int64_t)(n_kv - 1 - it) * tile_stride;
+        const kv_elem *base = Kg + (int64_t)(n_kv - 1 - it) * tile_stride;
 #endif
         const unsigned kdst = smem_base + stage * TILE;
         if (ABL & 16) return;
@@ -736,9 +813,9 @@ fa_fwd_kernel(const KernelArgs args) {
     auto issue_v = [&](int it, int stage) {
 #ifdef FA_KERNEL_VARLEN_KVCACHE
         // V(it) follows K(it + 1) except in the prologue and at the last tile: then K(it) was the last K request
-        const uint16_t *base = Vg + ((it > 0 && it + 1 < n_kv) ? kc_prev : kc_last);
+        const kv_elem *base = Vg + ((it > 0 && it + 1 < n_kv) ? kc_prev : kc_last);
 #else
-        const uint16_t *base = Vg + (int64_t)(n_kv - 1 - it) * tile_stride;
+        const kv_elem *base = Vg + (int64_t)(n_kv - 1 - it) * tile_stride;
 #endif
         const unsigned vdst = smem_base + V_BASE + stage * TILE;
         if (ABL & 16) return;
@@ -765,38 +842,79 @@ fa_fwd_kernel(const KernelArgs args) {
     // 16-B chunk (row 4i + L/16, chunk L%16): fully coalesced 256-B rows from global, and a
     // per-lane LDS address builds the same K / V images the DMA path builds by permuting
     // its source.  One set of landing registers per tile kind lives across a whole visit.
-    f32x4 kreg[DMA_PER_WAVE], vreg[DMA_PER_WAVE];
-    const int st_r = lane >> 4, st_c = lane & 15;
-    const unsigned st_goff = (unsigned)((((int64_t)(4 * wave + st_r)) * ss + st_c * 8) * 2);
-    const unsigned st_gstep = (unsigned)(((int64_t)(4 * NWAVES)) * ss * 2);  // bytes between a wave's pieces
-    const int st_krow = 4 * (wave & 3) + st_r;                               // (tile row) & 15
-    const unsigned st_kwr = wave * 1024 + st_r * 256 + ((st_c ^ (SWZ ? st_krow : 0)) << 4);
-    const unsigned st_vwr = (wave >> 1) * 2048 + ((wave & 1) * 4 + st_r) * 64 + (st_c >> 2) * 512 + (st_c & 3) * 16;
-    auto load_tile = [&](const uint16_t *tensor, int it, f32x4 (&reg)[DMA_PER_WAVE]) {
-        const char *tile = (const char *)(tensor + (int64_t)(n_kv - 1 - it) * tile_stride);
-        if (const int valid = ragged_rows(it)) {
+    // fp8 cache: a tile is 64 keys x 128 bytes, two 16-byte loads per lane (piece i = 8 tile rows; lane L fetches bytes
+    // 16 c .. 16 c + 15, c = L % 8, of row 8 i + L / 8: whole 128-byte rows from global), converted behind the barrier into the
+    // two 16-bit chunks 2c, 2c + 1 of the K image's row (XOR key & 15: the second chunk is the first's address ^ 16) or the matching
+    // 32 bytes of the V image's subtile [key / 8][c / 2], row key & 7, half c & 1.
+    // (enumerators, like FP8: the other forms' code does not change by a name)
+    enum : int {
+        ST_PER_WAVE = FP8 ? DMA_PER_WAVE / 2 : DMA_PER_WAVE,   // landing registers (16 bytes per lane) per tile
+        ST_ROWS = FP8 ? 8 : 4,                                 // tile rows per piece
+        ST_ESZ = FP8 ? 1 : 2                                   // bytes per K / V element
+    };
+    f32x4 kreg[ST_PER_WAVE], vreg[ST_PER_WAVE];
+    const int st_r = FP8 ? lane >> 3 : lane >> 4, st_c = FP8 ? lane & 7 : lane & 15;
+    // (FA_ST_SS32 names a local of this kernel: ss, or kv_ss in the fp8 cache's form)
+    const unsigned st_goff = (unsigned)((((int64_t)(ST_ROWS * wave + st_r)) * FA_ST_SS32 + st_c * (16 / ST_ESZ)) * ST_ESZ);
+    const unsigned st_gstep = (unsigned)(((int64_t)(ST_ROWS * NWAVES)) * FA_ST_SS32 * ST_ESZ);  // bytes between a wave's pieces
+    const int st_krow = FP8 ? 8 * (wave & 1) + st_r : 4 * (wave & 3) + st_r;                // (tile row) & 15
+    const unsigned st_kwr = FP8 ? (8 * wave + st_r) * 256 + (((2 * st_c) ^ (SWZ ? st_krow : 0)) << 4)
+                                : wave * 1024 + st_r * 256 + ((st_c ^ (SWZ ? st_krow : 0)) << 4);
+    const unsigned st_vwr = FP8 ? wave * 2048 + (st_c >> 1) * 512 + st_r * 64 + (st_c & 1) * 32
+                                : (wave >> 1) * 2048 + ((wave & 1) * 4 + st_r) * 64 + (st_c >> 2) * 512 + (st_c & 3) * 16;
+    auto load_tile = [&](const kv_elem *tensor, int it, f32x4 (&reg)[ST_PER_WAVE]) {
+        // (FA_ST_TILE uses the locals n_kv and tile_stride, except in the fp8 cache's form, where `tensor` is the tile already)
+        const char *tile = (const char *)(FA_ST_TILE(tensor, it));
+        if (const int valid = ragged_rows(it)) {   // (rows beyond the end come from the last valid row, as the DMA fetches them)
 #pragma unroll
-            for (int j = 0; j < DMA_PER_WAVE; ++j) {
-                int row = 4 * (wave + NWAVES * j) + st_r;
+            for (int j = 0; j < ST_PER_WAVE; ++j) {
+                int row = ST_ROWS * (wave + NWAVES * j) + st_r;
                 row = row < valid ? row : valid - 1;
-                reg[j] = *(const f32x4 *)(tile + ((int64_t)row * ss + st_c * 8) * 2);
+                reg[j] = *(const f32x4 *)(tile + ((int64_t)row * FA_ST_SS32 + st_c * (16 / ST_ESZ)) * ST_ESZ);
             }
             return;
         }
 #pragma unroll
-        for (int j = 0; j < DMA_PER_WAVE; ++j) reg[j] = *(const f32x4 *)(tile + st_goff + j * st_gstep);
+        for (int j = 0; j < ST_PER_WAVE; ++j) reg[j] = *(const f32x4 *)(tile + st_goff + j * st_gstep);
     };
+#ifdef FA_KERNEL_VARLEN_KVCACHE_FP8
+    // (the cache's tiles: the walk's bases, K in visit order and V by the rule derived at kc_offset)
+    auto load_k = [&](int it) {
+        load_tile(Kg + kc_offset(), it, kreg);
+        kc_step();
+    };
+    auto load_v = [&](int it) { load_tile(Vg + ((it >= 2 && it + 1 < n_kv) ? kc_prev : kc_last), it, vreg); };
+#else
     auto load_k = [&](int it) { load_tile(Kg, it, kreg); };
     auto load_v = [&](int it) { load_tile(Vg, it, vreg); };
+#endif
     auto store_k = [&](int stage) {
         char *dst = smem + stage * TILE + st_kwr;
+        if constexpr (FP8) {
 #pragma unroll
-        for (int j = 0; j < DMA_PER_WAVE; ++j) *(f32x4 *)(dst + j * NWAVES * 1024) = kreg[j];
+            for (int j = 0; j < ST_PER_WAVE; ++j) {
+                const u32x4 w = __builtin_bit_cast(u32x4, kreg[j]);
+                *(vec8 *)(dst + j * 8192) = cvt_fp8x8<DT>(w[0], w[1]);
+                *(vec8 *)(smem + stage * TILE + ((st_kwr ^ 16) + j * 8192)) = cvt_fp8x8<DT>(w[2], w[3]);
+            }
+            return;
+        }
+#pragma unroll
+        for (int j = 0; j < ST_PER_WAVE; ++j) *(f32x4 *)(dst + j * NWAVES * 1024) = kreg[j];
     };
     auto store_v = [&](int stage) {
         char *dst = smem + V_BASE + stage * TILE + st_vwr;
+        if constexpr (FP8) {
 #pragma unroll
-        for (int j = 0; j < DMA_PER_WAVE; ++j) *(f32x4 *)(dst + j * (NWAVES / 2) * 2048) = vreg[j];
+            for (int j = 0; j < ST_PER_WAVE; ++j) {
+                const u32x4 w = __builtin_bit_cast(u32x4, vreg[j]);
+                *(vec8 *)(dst + j * 8192) = cvt_fp8x8<DT>(w[0], w[1]);
+                *(vec8 *)(dst + j * 8192 + 16) = cvt_fp8x8<DT>(w[2], w[3]);
+            }
+            return;
+        }
+#pragma unroll
+        for (int j = 0; j < ST_PER_WAVE; ++j) *(f32x4 *)(dst + j * (NWAVES / 2) * 2048) = vreg[j];
     };
     auto dma_wait = [&]() { if (DMA && !(ABL & 8)) dma_wait_all(); };
     auto barrier = [&]() { if (!(ABL & 8)) wg_barrier(); };
@@ -833,7 +951,9 @@ fa_fwd_kernel(const KernelArgs args) {
     }
 
     // forward_kernel.cuh:150-151 (fp32 product of rsqrt(d) and log2 e)
-    const float c = (float)((double)(1.0f / __builtin_sqrtf((float)D)) * 1.4426950408889634074);
+    // (fp8 cache: times k_descale, FA_K_DESCALED, which reads the locals fa8, b, h and va -- one multiply per workgroup; S and the running max stay raw logits, and
+    // exp2(s c - m c), the rescale factors and lse = ln l + m c come out in descaled units: a positive descale keeps the max the max)
+    const float c = FA_K_DESCALED((float)((double)(1.0f / __builtin_sqrtf((float)D)) * 1.4426950408889634074));
 
     f32x16 O[QT][DTILES];
     float m[QT], l[QT];
@@ -1286,6 +1406,7 @@ fa_fwd_kernel(const KernelArgs args) {
     }
 
 #ifdef FA_KERNEL_VARLEN
+    // (FA_LSE_M_TIMES_C: m * c, in the fp8 cache's form with a rounding of its own; it names nothing but its arguments)
     // lse = ln l + m / sqrt d in the kernel's own units (m c is log2): one fp32 per valid row; both lane halves hold it
     // (this (sequence, head)'s rows of lse, found again here rather than kept in registers across the loop)
     int64_t l_row0 = va.cu_seqlens[b];
@@ -1296,7 +1417,7 @@ fa_fwd_kernel(const KernelArgs args) {
         const float l_row = pair_sum(l[qt]);
         const int row = wave_row0 + qt * 32 + r31;
         if (hi == 0 && row < FA_Q_LEN_END)   // (a row without keys: l = 0, m = -inf -> ln 0 + 0 = -inf)
-            lse_rows[row] = (__builtin_amdgcn_logf(l_row) + finite_or_zero(m[qt]) * c) * 0.693147180559945309f;
+            lse_rows[row] = (__builtin_amdgcn_logf(l_row) + FA_LSE_M_TIMES_C(finite_or_zero(m[qt]), c)) * 0.693147180559945309f;
     }
 #endif
     if ((ABL & 32) && args.seq_len < 0) {  // never true: keeps the landing registers allocated
@@ -1350,7 +1471,12 @@ fa_fwd_kernel(const KernelArgs args) {
         for (int qt = 0; qt < QT; ++qt) {
 #ifdef FA_KERNEL_VARLEN
             const float l_all = pair_sum(l[qt]);
+#ifdef FA_KERNEL_VARLEN_KVCACHE_FP8
+            // ... with v_descale folded in (read here, not held across the loop)
+            const float inv = l_all == 0.0f ? 0.0f : (1.0f / l_all) * (fa8.v_descale ? fa8.v_descale[(int64_t)b * fa8.ds_bs + h / va.group] : 1.0f);
+#else
             const float inv = l_all == 0.0f ? 0.0f : 1.0f / l_all;   // a row that saw no key: o = 0, not 0 / 0
+#endif
 #else
             const float inv = 1.0f / pair_sum(l[qt]);
 #endif

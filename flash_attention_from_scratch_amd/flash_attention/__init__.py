@@ -131,8 +131,8 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
 
 
 def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table=None, causal=False,
-                           max_seqlen_k=None, timed=False):
-    """Prefill against a K / V cache (DESIGN.md 10.9; flash-attn's flash_attn_varlen_func(..., block_table=)): chunked prefill
+                           max_seqlen_k=None, timed=False, k_descale=None, v_descale=None):
+    """Prefill against a K / V cache (DESIGN.md 10.9, 10.10; flash-attn's flash_attn_varlen_func(..., block_table=)): chunked prefill
     behind a cached prefix, prompts behind a shared prefix, verification of more rows than forward_kvcache serves.  q
     (total_q, n_heads, 128) holds the query rows of all sequences packed, sequence i's at rows cu_seqlens_q[i] ..
     cu_seqlens_q[i + 1] - 1 (int32, n_seqs + 1 entries ON THE DEVICE), at most max_seqlen_q (a Python int) each.  The keys are
@@ -142,9 +142,16 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
     append_kvcache for one) included.  causal is bottom-right aligned: query r sees keys j <= r + (len_k - len_q); a row that sees
     no key gives o = 0, lse = -inf.  max_seqlen_k (a Python int) bounds every length, None = the capacity.
     -> (o, lse[, ms]) with lse fp32 (n_heads, total_q): bit for bit forward_varlen(cu_seqlens_k=) on the same keys packed.  bf16 /
-    fp16; an fp8 cache is refused.  No device synchronisation unless timed; graph-capturable; the same inputs give the same bits."""
+    fp16.  No device synchronisation unless timed; graph-capturable; the same inputs give the same bits.
+    An fp8 cache (torch.float8_e4m3fn, the cache append_kvcache writes and forward_kvcache decodes against) is served when BOTH
+    k_descale and v_descale are given: fp32 (n_seqs, n_kv_heads) ON THE DEVICE, last dimension contiguous, never read by the host.
+    Key j of sequence b (the sequence index, for a paged cache too), K / V head h stands for float(k8[j]) * k_descale[b, h],
+    likewise V, and the result is the 16-bit call's on those values.  Note the asymmetry with forward_kvcache, where a missing
+    descale means 1: here an fp8 cache with either descale missing is refused -- pass ones for an unscaled cache.  A descale with
+    a 16-bit cache, caches of two dtypes and fp8 encodings other than e4m3fn are refused."""
     return flash_attention_kernels.forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens,
-                                                          block_table=block_table, causal=causal, max_seqlen_k=max_seqlen_k, timed=timed)
+                                                          block_table=block_table, causal=causal, max_seqlen_k=max_seqlen_k, timed=timed,
+                                                          k_descale=k_descale, v_descale=v_descale)
 
 
 def append_kvcache(k_cache, v_cache, k, v, cache_seqlens, block_table=None, q=None, rotary_cos=None, rotary_sin=None,

@@ -683,23 +683,46 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
 
 
 def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table=None, causal=False,
-                           max_seqlen_k=None, timed=False):
+                           max_seqlen_k=None, timed=False, k_descale=None, v_descale=None):
     """Prefill against a K / V cache (fa_fwd_launch_varlen_kvcache): forward_varlen(cu_seqlens_k=) whose keys are read from the
     cache in place.  q (total_q, n_heads, 128) packed, cu_seqlens_q an int32 device tensor of n_seqs + 1 row offsets, max_seqlen_q
     a Python int; k_cache, v_cache (n_seqs, seqlen_cache, n_kv_heads, 128), or with block_table (n_seqs, max_pages_per_seq) int32 on
     the device (num_pages, page_size, n_kv_heads, 128); cache_seqlens (n_seqs,) int32 on the device, the valid keys of each
     sequence, the chunk's own (already appended) included.  causal is bottom-right aligned.  -> (o, lse[, ms]); o contiguous, lse
     fp32 (n_heads, total_q).  The host reads no device array; no device synchronisation unless timed.  The caches pass as they
-    are and are refused if the launch cannot address them; an fp8 cache is refused."""
+    are and are refused if the launch cannot address them.
+    A torch.float8_e4m3fn cache takes fa_fwd_launch_varlen_kvcache_fp8 when BOTH k_descale and v_descale are given: fp32
+    (n_seqs, n_kv_heads) on q's device, last dimension contiguous, never read by the host; key j of sequence b (the sequence, also
+    for a paged cache) and K / V head h stands for float(k8[j]) * k_descale[b, h], likewise V.  Unlike forward_kvcache, where None
+    means 1, an fp8 cache with a descale missing is refused here: pass tensors of ones for an unscaled cache.  A descale with a
+    16-bit cache is refused."""
     tensors = [(q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cu_seqlens_q, "cu_seqlens_q"), (cache_seqlens, "cache_seqlens")]
     if block_table is not None:
         tensors.append((block_table, "block_table"))
     for t, name in tensors:
         if not isinstance(t, torch.Tensor):
             raise RuntimeError(f"{name} must be a tensor")
-    if k_cache.dtype in _FLOAT8_DTYPES or v_cache.dtype in _FLOAT8_DTYPES:
-        raise RuntimeError("forward_varlen_kvcache reads a bf16 / fp16 cache: an fp8 cache is not served here (forward_kvcache "
-                           "decodes against one)")
+    fp8 = k_cache.dtype in _FLOAT8_DTYPES or v_cache.dtype in _FLOAT8_DTYPES
+    if fp8 and k_cache.dtype != v_cache.dtype:
+        raise RuntimeError(f"k_cache and v_cache must have one data type (got {k_cache.dtype} and {v_cache.dtype})")
+    if fp8 and k_cache.dtype != torch.float8_e4m3fn:
+        raise RuntimeError(f"an fp8 cache must be torch.float8_e4m3fn (got {k_cache.dtype})")
+    if fp8 and (k_descale is None or v_descale is None):
+        raise RuntimeError("forward_varlen_kvcache: an fp8 cache is not served without both k_descale and v_descale (fp32 (n_seqs, "
+                           "n_kv_heads) tensors on q's device; pass ones for an unscaled cache -- None does not mean 1 here)")
+    if not fp8 and (k_descale is not None or v_descale is not None):
+        raise RuntimeError("k_descale / v_descale belong to an fp8 (torch.float8_e4m3fn) cache; this cache is 16-bit")
+    if fp8:
+        tensors += [(k_descale, "k_descale"), (v_descale, "v_descale")]
+        for t, name in tensors[-2:]:
+            if not isinstance(t, torch.Tensor):
+                raise RuntimeError(f"{name} must be a tensor")
+        if k_cache.dim() == 4 and cu_seqlens_q.dim() == 1 and cu_seqlens_q.numel() >= 2:   # (what they are is checked before where they are)
+            want = (cu_seqlens_q.numel() - 1, k_cache.shape[2])
+            for t, name in tensors[-2:]:
+                if t.dtype != torch.float32 or tuple(t.shape) != want or t.stride(1) != 1:
+                    raise RuntimeError(f"{name} must be an fp32 (n_seqs, n_kv_heads) = {want} tensor on q's device with a contiguous "
+                                       "last dimension")
     for t, name in tensors:
         if not t.is_cuda:
             raise RuntimeError(f"{name} must be a CUDA tensor")
@@ -707,7 +730,7 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
             raise RuntimeError(f"{name} must be on q's device ({q.device}, got {t.device})")
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise RuntimeError("Only fp16 and bf16 are supported")
-    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+    if not fp8 and (k_cache.dtype != q.dtype or v_cache.dtype != q.dtype):
         raise RuntimeError("Input tensors must have the same data type")
     if q.dim() != 3 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[3] != q.shape[2]:
         raise RuntimeError("q must have shape (total_q, n_heads, d_head), k_cache and v_cache one shape (n_seqs or num_pages, "
@@ -732,10 +755,15 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
         raise RuntimeError("max_seqlen_k must be a Python int (a bound on every length; the device is not asked)")
     if q.stride(2) != 1:
         raise RuntimeError("packed sequences: q needs a contiguous last dimension")
-    if (_decode_needs_copy(k_cache) or _decode_needs_copy(v_cache) or k_cache.stride() != v_cache.stride()):
+    kv_unit = 16 if fp8 else 8   # 16 bytes
+    if (_decode_needs_copy(k_cache) or _decode_needs_copy(v_cache) or k_cache.stride() != v_cache.stride()
+            or any(s % kv_unit for s in k_cache.stride()[:-1])):
         # (a serving cache is gigabytes: copying it on every call would be silently slow)
-        raise RuntimeError("k_cache and v_cache need one stride set, a contiguous last dimension, strides that are multiples of 8 "
+        raise RuntimeError(f"k_cache and v_cache need one stride set, a contiguous last dimension, strides that are multiples of {kv_unit} "
                            "elements and a 16-byte aligned base")
+    if fp8 and (k_descale.stride(0) != v_descale.stride(0) or k_descale.stride(0) < n_kv or k_descale.data_ptr() % 4 or v_descale.data_ptr() % 4):
+        # (the launch has one row stride for both, at least a row long -- an expanded or single row has any: two small copies)
+        k_descale, v_descale = k_descale.contiguous(), v_descale.contiguous()
     paged = block_table is not None
     lib = _capi.load()
     cfg = _capi.make_config(varlen_config(q.dtype))
@@ -757,8 +785,14 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
         ms = ctypes.c_float(0.0)
         opts = _capi.make_opts(causal=causal, ms=ms if timed else None)
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        _capi.check(lib.fa_fwd_launch_varlen_kvcache(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(vq), ctypes.byref(kc),
-                                                     ctypes.byref(opts), ctypes.c_void_p(lse.data_ptr()), stream))
+        if fp8:
+            sc = _capi.make_kvcache_fp8_scales(k_descale=k_descale.data_ptr(), v_descale=v_descale.data_ptr(),
+                                               descale_batch_stride=k_descale.stride(0))
+            _capi.check(lib.fa_fwd_launch_varlen_kvcache_fp8(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(vq), ctypes.byref(kc),
+                                                             ctypes.byref(sc), ctypes.byref(opts), ctypes.c_void_p(lse.data_ptr()), stream))
+        else:
+            _capi.check(lib.fa_fwd_launch_varlen_kvcache(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(vq), ctypes.byref(kc),
+                                                         ctypes.byref(opts), ctypes.c_void_p(lse.data_ptr()), stream))
     return (o, lse, float(ms.value)) if timed else (o, lse)
 
 

@@ -10,7 +10,16 @@ Cases: a chunk of 512 and 2048 query tokens per sequence behind prefixes of 0, 8
 chunk: the chunk's own keys are in the cache), causal (bottom-right), H / Hkv = 32 / 8 and 16 / 16.  Per case: the median over
 the runs of (a) / (c), (b) / (c) and (d) / (c), the median margin, and whether (a) / (c) and (b) / (c) lie inside 1 + margin.
 
-    python flash_attention_from_scratch_amd/tools/prefill_bench.py [--reps N] [--runs N] [--batch N] [--page-size N] [--out FILE]
+--kv-dtype fp8: the same cases with three arms instead, on paged caches of one table, alternating in one process:
+  (a) forward_varlen_kvcache(k_descale=, v_descale=) on the e4m3fn cache (quantize_kvcache_fp8 of the 16-bit one);
+  (b) forward_varlen_kvcache on the 16-bit cache the fp8 one was quantized from -- it runs twice per round, and the spread between
+      its two medians is the margin;
+  (c) what a caller without the fp8 form does once per chunk: dequantize the used pages of the fp8 cache into a 16-bit copy
+      (float(x8) * descale of the page's sequence), then (b) on the copy.
+Per case: fp8 / 16-bit, fp8 / (dequantize + 16-bit), the margin, and the error of (a) against (b) on the dequantized cache (both
+compute in the 16-bit type; with general descales the dequantized values round once more in (b) and (c)).
+
+    python flash_attention_from_scratch_amd/tools/prefill_bench.py [--reps N] [--runs N] [--batch N] [--page-size N] [--kv-dtype {16bit,fp8}] [--out FILE]
 """
 import argparse
 import json
@@ -111,6 +120,75 @@ def case(chunk, prefix, batch, H, Hkv, page_size, dtype, reps, runs):
     return line
 
 
+def case_fp8(chunk, prefix, batch, H, Hkv, page_size, dtype, reps, runs):
+    len_k = prefix + chunk
+    cap = (len_k + page_size - 1) // page_size * page_size
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    q = torch.randn((batch * chunk, H, 128), generator=gen, device="cuda").to(dtype)
+    kc, vc = (torch.randn((batch, cap, Hkv, 128), generator=gen, device="cuda").to(dtype) for _ in range(2))
+    k8c, v8c, kd, vd = flash_attention.quantize_kvcache_fp8(kc, vc)
+    per_seq = cap // page_size
+    perm = torch.randperm(batch * per_seq, generator=torch.Generator().manual_seed(1))
+    table = perm.view(batch, per_seq).to(torch.int32).cuda()
+    shape = (batch * per_seq, page_size, Hkv, 128)
+    kp, vp = (torch.empty(shape, dtype=dtype, device="cuda") for _ in range(2))
+    kp[perm.cuda()] = kc.view(shape)
+    vp[perm.cuda()] = vc.view(shape)
+    k8, v8 = (torch.empty(shape, dtype=torch.uint8, device="cuda") for _ in range(2))
+    k8[perm.cuda()] = k8c.view(torch.uint8).view(shape)
+    v8[perm.cuda()] = v8c.view(torch.uint8).view(shape)
+    k8, v8 = k8.view(torch.float8_e4m3fn), v8.view(torch.float8_e4m3fn)
+    del kc, vc, k8c, v8c
+    lens = torch.full((batch,), len_k, dtype=torch.int32, device="cuda")
+    cuq = _cu([chunk] * batch)
+    used = table.flatten().long()                                   # (every page of the table is in use: cap - len_k < page_size)
+    seq_of_page = torch.arange(batch, device="cuda").repeat_interleave(per_seq)
+
+    def dequantize():
+        kq, vq = (torch.empty(shape, dtype=dtype, device="cuda") for _ in range(2))
+        kq[used] = (k8[used].float() * kd[seq_of_page][:, None, :, None]).to(dtype)
+        vq[used] = (v8[used].float() * vd[seq_of_page][:, None, :, None]).to(dtype)
+        return kq, vq
+
+    fp8 = lambda **kw: flash_attention.forward_varlen_kvcache(q, k8, v8, cuq, chunk, lens, block_table=table, causal=True,   # noqa: E731
+                                                              k_descale=kd, v_descale=vd, **kw)
+    b16 = lambda k, v, **kw: flash_attention.forward_varlen_kvcache(q, k, v, cuq, chunk, lens, block_table=table, causal=True, **kw)   # noqa: E731
+    kq, vq = dequantize()
+    got, want = fp8(), b16(kq, vq)
+    err = (got[0].float() - want[0].float()).abs().max().item()
+    lse_err = (got[1] - want[1]).abs().max().item()
+    del kq, vq, got, want
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    per_run = []
+    for _ in range(runs):
+        t = {name: [] for name in ("fp8", "b16_a", "b16_b", "dequant_b16")}
+        for i in range(reps + 2):
+            *_, b1 = b16(kp, vp, timed=True)
+            *_, a = fp8(timed=True)
+            *_, b2 = b16(kp, vp, timed=True)
+            ev[0].record()
+            kq, vq = dequantize()
+            b16(kq, vq)
+            ev[1].record()
+            torch.cuda.synchronize()
+            d = ev[0].elapsed_time(ev[1])
+            del kq, vq
+            if i > 1:
+                for name, ms in zip(t, (a, b1, b2, d)):
+                    t[name].append(ms)
+        per_run.append({name: _median(x) for name, x in t.items()})
+    b16_ms = [0.5 * (r["b16_a"] + r["b16_b"]) for r in per_run]
+    margin = _median([abs(r["b16_a"] - r["b16_b"]) / p for r, p in zip(per_run, b16_ms)])
+    flop = 4.0 * 128 * H * batch * _pairs(chunk, len_k)
+    fp8_ms = _median([r["fp8"] for r in per_run])
+    return {"chunk": chunk, "prefix": prefix, "batch": batch, "n_heads": H, "n_kv_heads": Hkv, "page_size": page_size, "causal": True,
+            "dtype": str(dtype).replace("torch.", ""), "kv_dtype": "fp8_e4m3fn", "reps": reps, "runs": runs,
+            **{name + "_ms": _median([r[name] for r in per_run]) for name in per_run[0]},
+            "fp8_tflops": flop / fp8_ms * 1e-9, "fp8_over_b16": _median([r["fp8"] / p for r, p in zip(per_run, b16_ms)]),
+            "fp8_over_dequant_b16": _median([r["fp8"] / r["dequant_b16"] for r in per_run]), "margin": margin,
+            "max_abs_o_minus_b16": err, "max_abs_lse_minus_b16": lse_err}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
@@ -118,16 +196,19 @@ def main():
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--page-size", type=int, default=256)
     ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "inference", "prefill_kvcache_bench_bf16.jsonl"))
+    ap.add_argument("--kv-dtype", choices=("16bit", "fp8"), default="16bit", help="fp8: the e4m3fn cache against the 16-bit one")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    fp8 = a.kv_dtype == "fp8"
+    a.out = a.out or os.path.join(ROOT, "profiles", "inference", f"prefill_kvcache_{'fp8_' if fp8 else ''}bench_{a.dtype}.jsonl")
     assert torch.cuda.is_available(), "prefill_bench.py needs the GPU"
     dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float16
-    lines = [{"tool": "prefill_bench.py", "toolchain": _toolchain(), "torch": torch.__version__, "device": torch.cuda.get_device_name(0)}]
+    lines = [{"tool": "prefill_bench.py" + (" --kv-dtype fp8" if fp8 else ""), "toolchain": _toolchain(), "torch": torch.__version__, "device": torch.cuda.get_device_name(0)}]
     print(json.dumps(lines[0]), flush=True)
     for H, Hkv in ((32, 8), (16, 16)):
         for prefix in (0, 8192, 65536):
             for chunk in (512, 2048):
-                lines.append(case(chunk, prefix, a.batch, H, Hkv, a.page_size, dtype, a.reps, a.runs))
+                lines.append((case_fp8 if fp8 else case)(chunk, prefix, a.batch, H, Hkv, a.page_size, dtype, a.reps, a.runs))
                 print(json.dumps(lines[-1]), flush=True)
                 torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

@@ -549,6 +549,34 @@ int fa_fwd_launch_varlen_kvcache(const fa_fwd_args *args, const fa_kv_layout *kv
                                  const fa_kvcache_layout *cache, const fa_fwd_opts *opts, float *lse, void *stream);
 
 /*
+ * The same prefill against an fp8 K / V cache (the cache of fa_decode_fp8_launch and fa_kvcache_append_launch; enum fa_kv_dtype
+ * below).  args->k, ->v hold OCP e4m3fn bytes in the two shapes above, one byte per element, so kv's strides count BYTES; q, o
+ * and lse are fa_fwd_launch_varlen_kvcache's.  fa_kvcache_layout is unchanged; the fp8 side travels in fa_kvcache_fp8_scales:
+ * struct_size = sizeof(fa_kvcache_fp8_scales), kv_dtype = FA_KV_FP8_E4M3FN (anything else is FA_ERR_DTYPE), and k_descale,
+ * v_descale (either may be null, which means 1): fp32 DEVICE arrays (n_seqs, n_kv_heads), row stride descale_batch_stride
+ * elements -- b is the SEQUENCE index for both cache shapes.  Key j of sequence b, K / V head h stands for
+ * float(k8[j]) * k_descale[b][h], likewise V; the result is the 16-bit call's on those values (bit for bit when the descaled
+ * values are exact in q's type and the descales are powers of two).  The host never reads the descales (like the lengths and the
+ * table they may change between graph replays); they must be finite and positive, which is not checked, and no address
+ * depends on them.  An e4m3 NaN in a valid row propagates; at or beyond len_k it is never fetched.
+ * Grid, clamping, causal rule, empty rows, determinism: fa_fwd_launch_varlen_kvcache's.  One launch, no split, no workspace.
+ * Refused before any HIP call: what fa_fwd_launch_varlen_kvcache refuses, and kv_dtype (FA_ERR_DTYPE); kv strides not
+ * multiples of 16 bytes, k / v not 16-byte aligned, descale pointers not 4-byte aligned (FA_ERR_ALIGN); struct_size,
+ * descale_batch_stride < n_kv_heads with a descale given (FA_ERR_SHAPE).  total_q = 0 returns FA_OK without a device.
+ */
+typedef struct fa_kvcache_fp8_scales {
+    uint32_t struct_size;         /* sizeof(fa_kvcache_fp8_scales) */
+    int32_t kv_dtype;             /* fa_kv_dtype: FA_KV_FP8_E4M3FN */
+    const float *k_descale;       /* DEVICE (n_seqs, n_kv_heads) fp32; null = 1 */
+    const float *v_descale;
+    int64_t descale_batch_stride;
+} fa_kvcache_fp8_scales;
+int fa_fwd_varlen_kvcache_fp8_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_kvcache_fp8(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                     const fa_kvcache_layout *cache, const fa_kvcache_fp8_scales *scales, const fa_fwd_opts *opts,
+                                     float *lse, void *stream);
+
+/*
  * KV-cache decode attention (forward only): a few query rows per sequence against a long K / V cache whose valid length per
  * batch entry lies in DEVICE memory.  bf16 / fp16, d_head 128, MHA and GQA / MQA (query head h reads K / V head
  * h / (n_heads / n_kv_heads)), softmax scale 1 / sqrt(128).
