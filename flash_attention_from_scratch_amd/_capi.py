@@ -37,6 +37,9 @@ EXPORTED_SYMBOLS = (
     "fa_kvcache_append_launch",
     "fa_fwd_varlen_kvcache_supported", "fa_fwd_launch_varlen_kvcache",
     "fa_fwd_varlen_kvcache_fp8_supported", "fa_fwd_launch_varlen_kvcache_fp8",
+    "fa_decode_window_supported", "fa_decode_window_num_splits", "fa_decode_window_workspace_bytes", "fa_decode_window_launch",
+    "fa_decode_fp8_window_supported", "fa_decode_fp8_window_num_splits", "fa_decode_fp8_window_workspace_bytes",
+    "fa_decode_fp8_window_launch",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -178,6 +181,14 @@ def make_decode_fp8_args(**fields):
     for name, value in fields.items():
         setattr(a, name, value)
     return a
+
+
+class FaWindow(ctypes.Structure):   # fa_window (sliding-window attention: keys seen below / above a row's position, -1 = unbounded)
+    _fields_ = [("struct_size", ctypes.c_uint32), ("left", ctypes.c_int32), ("right", ctypes.c_int32)]
+
+
+def make_window(left=-1, right=-1):
+    return FaWindow(struct_size=ctypes.sizeof(FaWindow), left=left, right=right)
 
 
 class FaKvcacheAppendArgs(ctypes.Structure):   # fa_kvcache_append_args (the append / rotary / quantize / advance step in front of a decode)
@@ -398,6 +409,13 @@ def load():
     lib.fa_decode_fp8_workspace_bytes.argtypes = [ctypes.POINTER(FaDecodeFp8Args)]
     lib.fa_decode_fp8_launch.restype = ctypes.c_int
     lib.fa_decode_fp8_launch.argtypes = [ctypes.POINTER(FaDecodeFp8Args), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    for name, args_t in (("fa_decode_window", FaDecodeArgs), ("fa_decode_fp8_window", FaDecodeFp8Args)):
+        pair = [ctypes.POINTER(args_t), ctypes.POINTER(FaWindow)]
+        for suffix, restype, more in (("supported", ctypes.c_int, []), ("num_splits", ctypes.c_int, []),
+                                      ("workspace_bytes", ctypes.c_int64, []),
+                                      ("launch", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)])):
+            fn = getattr(lib, f"{name}_{suffix}")
+            fn.restype, fn.argtypes = restype, pair + more
     lib.fa_kvcache_append_launch.restype = ctypes.c_int
     lib.fa_kvcache_append_launch.argtypes = [ctypes.POINTER(FaKvcacheAppendArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p

@@ -1431,17 +1431,25 @@ int decode_validate(const fa_decode_args *a) {
 // The split rule: a pure function of batch, n_kv_heads and the host's key bound.  The smallest power of two that gives
 // the grid one workgroup per CU of an MI355X (256, the count the GQA backward's split uses), while a split keeps at
 // least 256 keys of the bound, at most 128.
-int64_t decode_splits(const fa_decode_args *a) {
+int64_t decode_key_bound(const fa_decode_args *a) { return a->max_seqlen_k > 0 ? a->max_seqlen_k : decode_capacity(a); }
+int64_t decode_splits_for(const fa_decode_args *a, int64_t max_k) {
     if (a->num_splits > 0) return a->num_splits;
-    const int64_t max_k = a->max_seqlen_k > 0 ? a->max_seqlen_k : decode_capacity(a);
     int64_t s = 1;
     while (a->batch * a->n_kv_heads * s < kDecodeWantWgs && s < kDecodeMaxSplits) s *= 2;
     const int64_t by_keys = (max_k + kDecodeKeysPerSplit - 1) / kDecodeKeysPerSplit;
     return s < by_keys ? s : (by_keys < 1 ? 1 : by_keys);
 }
+int64_t decode_splits(const fa_decode_args *a) { return decode_splits_for(a, decode_key_bound(a)); }
 
 int64_t decode_part_o_bytes(const fa_decode_args *a, int64_t splits) {
     return (int64_t)sizeof(float) * splits * a->batch * a->n_kv_heads * (a->seqlen_q * (a->n_heads / a->n_kv_heads)) * 128;
+}
+
+// fa_decode_workspace_bytes for a split count: the fp32 partial o (a multiple of 512 bytes), then the partial lse
+int64_t decode_workspace(const fa_decode_args *a, int64_t splits) {
+    if (splits == 1) return 0;
+    const int64_t po = decode_part_o_bytes(a, splits);
+    return po + ((po / 128 + 15) & ~(int64_t)15);
 }
 
 // the kernels' arguments from validated ones
@@ -1512,10 +1520,7 @@ int fa_decode_num_splits(const fa_decode_args *a) {
 int64_t fa_decode_workspace_bytes(const fa_decode_args *a) {
     const int rc = decode_validate(a);
     if (rc != FA_OK) return rc;
-    const int64_t splits = decode_splits(a);
-    if (splits == 1) return 0;
-    const int64_t po = decode_part_o_bytes(a, splits);   // (a multiple of 512), then the partial lse
-    return po + ((po / 128 + 15) & ~(int64_t)15);
+    return decode_workspace(a, decode_splits(a));
 }
 
 int fa_decode_launch(const fa_decode_args *a, void *stream, float *ms) {
@@ -1588,6 +1593,131 @@ int fa_decode_fp8_launch(const fa_decode_fp8_args *a, void *stream, float *ms) {
     d.ds_bs = a->descale_batch_stride;
     const hipStream_t s = (hipStream_t)stream;
     return bwd_run([&] { return fa::decode_fp8_enqueue(d, a->dtype, s); }, s, ms);
+}
+
+// ---- ... with a sliding window: the two decodes' arguments and rules, and fa_window ---------------------------------------------
+namespace {
+// (called behind decode_validate: `a` is valid)
+int window_validate(const fa_window *w, const fa_decode_args *a) {
+    const int causal = a->causal;
+    if (!w) return fail(FA_ERR_NULL, "fa_window is null: (left, right) is needed (-1 = unbounded; the unwindowed entry point takes none)");
+    if (w->struct_size < sizeof(fa_window))
+        return fail(FA_ERR_SHAPE, "fa_window.struct_size (%u) is smaller than this library's (%zu)", w->struct_size, sizeof(fa_window));
+    if (w->left < -1 || w->right < -1)
+        return fail(FA_ERR_SHAPE, "window (%d, %d): left and right must be -1 (unbounded) or not negative", w->left, w->right);
+    if (causal && w->right > 0)
+        return fail(FA_ERR_SHAPE, "causal means right = 0: a window with right = %d cannot be causal as well (pass right = -1 or 0)", w->right);
+    // (the kernel adds a row's position and its clamped distances in 32 bits: fa_decode_kernel.hpp)
+    if (decode_capacity(a) > (1 << 30) - 128) return fail(FA_ERR_SHAPE, "cache too large for a window: at most 2^30 - 128 keys per entry");
+    return FA_OK;
+}
+int window_right(const fa_window *w, int causal) { return causal ? 0 : w->right; }
+
+// The split rule with a window: the same rule, its key bound the keys a workgroup can visit, left + seqlen_q + right, when
+// both sides are bounded (and that is less)
+int64_t decode_window_splits(const fa_decode_args *a, const fa_window *w) {
+    int64_t max_k = decode_key_bound(a);
+    const int64_t right = window_right(w, a->causal);
+    if (w->left >= 0 && right >= 0) {
+        const int64_t span = (int64_t)w->left + a->seqlen_q + right;
+        max_k = span < max_k ? span : max_k;
+    }
+    return decode_splits_for(a, max_k);
+}
+
+// fa_decode_launch's checks of the pointers' values
+int decode_pointers(const fa_decode_args *a, int64_t splits, const char *ws_query) {
+    if (splits > 1 && !a->workspace) return fail(FA_ERR_NULL, "workspace is null: allocate %s(args, window) bytes of device memory", ws_query);
+    if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) & 15) return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
+    if (((uintptr_t)a->cache_seqlens | (uintptr_t)a->block_table | (uintptr_t)a->lse) & 3)
+        return fail(FA_ERR_ALIGN, "cache_seqlens, block_table and lse must be 4-byte aligned");
+    if (splits > 1 && ((uintptr_t)a->workspace & 15)) return fail(FA_ERR_ALIGN, "workspace must be 16-byte aligned (it holds the splits' fp32 partials)");
+    return FA_OK;
+}
+}  // namespace
+
+int fa_decode_window_supported(const fa_decode_args *a, const fa_window *w) {
+    return decode_validate(a) == FA_OK && window_validate(w, a) == FA_OK ? 1 : 0;
+}
+
+int fa_decode_window_num_splits(const fa_decode_args *a, const fa_window *w) {
+    int rc = decode_validate(a);
+    if (rc != FA_OK || (rc = window_validate(w, a)) != FA_OK) return rc;
+    return (int)decode_window_splits(a, w);
+}
+
+int64_t fa_decode_window_workspace_bytes(const fa_decode_args *a, const fa_window *w) {
+    int rc = decode_validate(a);
+    if (rc != FA_OK || (rc = window_validate(w, a)) != FA_OK) return rc;
+    return decode_workspace(a, decode_window_splits(a, w));
+}
+
+int fa_decode_window_launch(const fa_decode_args *a, const fa_window *w, void *stream, float *ms) {
+    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
+    if (!a->q || !a->k || !a->v || !a->o) return fail(FA_ERR_NULL, "null tensor pointer (q, k, v and o are all needed)");
+    if (!a->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to batch int32 lengths is needed");
+    int rc = decode_validate(a);
+    if (rc != FA_OK || (rc = window_validate(w, a)) != FA_OK) return rc;
+    if (a->batch == 0) {
+        if (ms) *ms = 0.0f;
+        return FA_OK;
+    }
+    const int64_t splits = decode_window_splits(a, w);
+    if ((rc = decode_pointers(a, splits, "fa_decode_window_workspace_bytes")) != FA_OK) return rc;
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    fa::DecodeWindowArgs d;
+    decode_fill(d.d, a, splits);
+    d.left = w->left;
+    d.right = window_right(w, a->causal);
+    const hipStream_t s = (hipStream_t)stream;
+    return bwd_run([&] { return fa::decode_window_enqueue(d, a->dtype, s); }, s, ms);
+}
+
+int fa_decode_fp8_window_supported(const fa_decode_fp8_args *a, const fa_window *w) {
+    fa_decode_args base;
+    return decode_fp8_validate(a, &base) == FA_OK && window_validate(w, &base) == FA_OK ? 1 : 0;
+}
+
+int fa_decode_fp8_window_num_splits(const fa_decode_fp8_args *a, const fa_window *w) {
+    fa_decode_args base;
+    int rc = decode_fp8_validate(a, &base);
+    if (rc != FA_OK || (rc = window_validate(w, &base)) != FA_OK) return rc;
+    return (int)decode_window_splits(&base, w);
+}
+
+int64_t fa_decode_fp8_window_workspace_bytes(const fa_decode_fp8_args *a, const fa_window *w) {
+    fa_decode_args base;
+    int rc = decode_fp8_validate(a, &base);
+    if (rc != FA_OK || (rc = window_validate(w, &base)) != FA_OK) return rc;
+    return decode_workspace(&base, decode_window_splits(&base, w));
+}
+
+int fa_decode_fp8_window_launch(const fa_decode_fp8_args *a, const fa_window *w, void *stream, float *ms) {
+    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
+    if (!a->q || !a->k || !a->v || !a->o) return fail(FA_ERR_NULL, "null tensor pointer (q, k, v and o are all needed)");
+    if (!a->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to batch int32 lengths is needed");
+    fa_decode_args base;
+    int rc = decode_fp8_validate(a, &base);
+    if (rc != FA_OK || (rc = window_validate(w, &base)) != FA_OK) return rc;
+    if (a->batch == 0) {
+        if (ms) *ms = 0.0f;
+        return FA_OK;
+    }
+    const int64_t splits = decode_window_splits(&base, w);
+    if ((rc = decode_pointers(&base, splits, "fa_decode_fp8_window_workspace_bytes")) != FA_OK) return rc;
+    if (((uintptr_t)a->k_descale | (uintptr_t)a->v_descale) & 3) return fail(FA_ERR_ALIGN, "k_descale and v_descale must be 4-byte aligned");
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    fa::DecodeFp8WindowArgs d;
+    decode_fill(d.f.d, &base, splits);
+    d.f.k_descale = a->k_descale;
+    d.f.v_descale = a->v_descale;
+    d.f.ds_bs = a->descale_batch_stride;
+    d.left = w->left;
+    d.right = window_right(w, base.causal);
+    const hipStream_t s = (hipStream_t)stream;
+    return bwd_run([&] { return fa::decode_fp8_window_enqueue(d, a->dtype, s); }, s, ms);
 }
 
 // ---- the KV-cache append in front of a decode --------------------------------------------------------------------------------

@@ -38,6 +38,16 @@
 //    lse = m * k_descale / sqrt(128) + log(l).  (A positive descale keeps the maximum the maximum.)  v_descale is folded into
 //    the final 1 / l.  Both are one scalar per workgroup; no address depends on either.
 //  * A prefetch register set is 32 VGPRs instead of 64, so the 64-row form holds V a unit ahead as the others do.
+//
+// What a sliding window changes (DecodeWindowArgs / DecodeFp8WindowArgs: the forms above and (left, right), -1 = unbounded;
+// `if constexpr (WINDOW)` marks the sites).  Row i at position p = len - seqlen_q + i sees the keys
+// max(0, p - left) .. min(len - 1, p + right); causal arrives as right = 0.  lo_min = max(0, len - seqlen_q - left) is the
+// lowest key any row of the workgroup sees:
+//  * the workgroup's key tiles are [lo_min / 64, ceil(len / 64)), shared by the splits with the same formula, and the first
+//    32-key unit a wave visits is at or above lo_min / 32: no key, page or block_table entry wholly below lo_min is touched;
+//  * a lane whose key lies below lo_min FETCHES key lo_min (as one at or beyond len fetches len - 1) and is masked;
+//  * the mask is lo <= key < hi per row, both derived from the row's position.  The partial format, the combine kernel and the
+//    merge are unchanged.
 #pragma once
 #include <type_traits>
 
@@ -66,6 +76,16 @@ struct DecodeFp8Args {
     int64_t ds_bs;
 };
 
+// ... and a sliding window: left / right keys a row sees below / above its own position, -1 = unbounded (causal: right = 0)
+struct DecodeWindowArgs {
+    DecodeArgs d;
+    int32_t left, right;
+};
+struct DecodeFp8WindowArgs {
+    DecodeFp8Args f;
+    int32_t left, right;
+};
+
 namespace decode {
 constexpr int D = 128, UNIT = 32, TILE = 64, NWAVES = 4, THREADS = NWAVES * 64;
 constexpr int VROW = 288;              // bytes per key of the V image: 256 + 32, so the 8 keys a 32-lane half's transposed read
@@ -76,6 +96,13 @@ constexpr int row_tiles(int rows) { return rows <= 16 ? 1 : rows <= 32 ? 2 : 4; 
 // what both forms share of their arguments
 __host__ __device__ inline const DecodeArgs &common(const DecodeArgs &a) { return a; }
 __host__ __device__ inline const DecodeArgs &common(const DecodeFp8Args &a) { return a.d; }
+__host__ __device__ inline const DecodeArgs &common(const DecodeWindowArgs &a) { return a.d; }
+__host__ __device__ inline const DecodeArgs &common(const DecodeFp8WindowArgs &a) { return a.f.d; }
+// the fp8 forms' descales
+__host__ __device__ inline const DecodeFp8Args &fp8_part(const DecodeFp8Args &a) { return a; }
+__host__ __device__ inline const DecodeFp8Args &fp8_part(const DecodeFp8WindowArgs &a) { return a.f; }
+template <class ARGS> constexpr bool is_fp8 = std::is_same_v<ARGS, DecodeFp8Args> || std::is_same_v<ARGS, DecodeFp8WindowArgs>;
+template <class ARGS> constexpr bool is_window = std::is_same_v<ARGS, DecodeWindowArgs> || std::is_same_v<ARGS, DecodeFp8WindowArgs>;
 
 // (eight e4m3fn values as eight values of Q's type: cvt_fp8x8, fa_fwd_kernel.hpp)
 }  // namespace decode
@@ -85,7 +112,7 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
     using namespace decode;
-    constexpr bool FP8 = std::is_same_v<ARGS, DecodeFp8Args>;
+    constexpr bool FP8 = is_fp8<ARGS>, WINDOW = is_window<ARGS>;
     constexpr int KS = D / 32, DT16 = D / 16;
     constexpr int MERGE = NT * DT16 * 64 * 16;   // one wave's accumulators
     constexpr int MAIN = NWAVES * VBYTES > MERGE ? NWAVES * VBYTES : MERGE;
@@ -106,18 +133,40 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     int len = a.cache_seqlens[b];
     len = len < 0 ? 0 : (len > a.max_len ? a.max_len : len);
     const int n_tiles = (len + TILE - 1) / TILE;
-    const int t0 = (int)((int64_t)n_tiles * split / nsp), t1 = (int)((int64_t)n_tiles * (split + 1) / nsp);
+    [[maybe_unused]] int lo_min = 0;   // window: the lowest key a row of this workgroup sees (<= len - 1 when len > 0)
+    int t0, t1;
+    if constexpr (WINDOW) {
+        if (args.left >= 0) {
+            const int64_t lo = (int64_t)len - a.seqlen_q - args.left;
+            lo_min = lo > 0 ? (int)lo : 0;
+        }
+        const int tl = lo_min / TILE, nt_w = n_tiles - tl;   // (len = 0: lo_min = 0, no tile)
+        t0 = tl + (int)((int64_t)nt_w * split / nsp);
+        t1 = tl + (int)((int64_t)nt_w * (split + 1) / nsp);
+    } else {
+        t0 = (int)((int64_t)n_tiles * split / nsp);
+        t1 = (int)((int64_t)n_tiles * (split + 1) / nsp);
+    }
     const int n_units = (len + UNIT - 1) / UNIT;
     const int u_end = 2 * t1 < n_units ? 2 * t1 : n_units;
     float kd = 1.0f, vd = 1.0f;
     if constexpr (FP8) {
-        kd = args.k_descale ? args.k_descale[(int64_t)b * args.ds_bs + kvh] : 1.0f;
-        vd = args.v_descale ? args.v_descale[(int64_t)b * args.ds_bs + kvh] : 1.0f;
+        const DecodeFp8Args &f = fp8_part(args);
+        kd = f.k_descale ? f.k_descale[(int64_t)b * f.ds_bs + kvh] : 1.0f;
+        vd = f.v_descale ? f.v_descale[(int64_t)b * f.ds_bs + kvh] : 1.0f;
     }
 
-    // Q^T, resident (fp8: in K's permutation of d); lim: the first key a row does not see
+    // Q^T, resident (fp8: in K's permutation of d); lim: the first key a row does not see.  Window: lim holds the row's position
+    // p instead (one register per row tile, as before), and each unit derives the row's bounds p - w_left and
+    // min(len, p + w_right + 1) from it -- neither needs its clamp at 0, keys are not negative
     vec8 Qr[NT][KS];
     int lim[NT];
+    [[maybe_unused]] int w_left = 0, w_right = 0;
+    if constexpr (WINDOW) {   // unbounded, or beyond what any length reaches (the host: len <= 2^30 - 128; p >= -seqlen_q >= -64): all one
+        constexpr int FAR = (1 << 30) + 64;
+        w_left = args.left < 0 || args.left > FAR ? FAR : args.left;
+        w_right = args.right < 0 || args.right > FAR ? FAR : args.right;
+    }
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         const int r = nt * 16 + li;
@@ -126,7 +175,11 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
         const uint16_t *qp = a.q + (int64_t)b * a.q_bs + (int64_t)qi * a.q_ss + (int64_t)qh * a.q_hs + g * (FP8 ? 16 : 8);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) Qr[nt][ks] = *(const vec8 *)(qp + (FP8 ? (ks >> 1) * 64 + (ks & 1) * 8 : ks * 32));
-        lim[nt] = !valid ? 0 : (a.causal ? len - a.seqlen_q + qi + 1 : len);
+        if constexpr (WINDOW) {
+            lim[nt] = !valid ? -(1 << 30) - 66 : len - a.seqlen_q + qi;   // (a padded row: p + w_right + 1 < 0)
+        } else {
+            lim[nt] = !valid ? 0 : (a.causal ? len - a.seqlen_q + qi + 1 : len);
+        }
     }
 
     float scale, c;   // logits (fp8: raw logits) -> logits, and -> the exponent of exp2
@@ -153,7 +206,12 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     // d 8 li ..: whole rows per instruction; fp8: the shapes at the head of this file), 16 bytes per lane and load; keys at or
     // beyond len come from key len - 1.  A unit at or beyond u_end (the prefetch behind a wave's last unit) is still loaded,
     // every lane from the first row of unit `u_valid`: one cached row instead of 16 (fp8: 8) KiB, and the number of loads in
-    // flight stays the same on every path, so the waits can be counted
+    // flight stays the same on every path, so the waits can be counted.  Window: a key below lo_min comes from key lo_min (the
+    // wave's first unit may begin below it), and so does the prefetch behind the last unit when that is unit `u_valid`'s first row
+    auto clamp_key = [](int ko, [[maybe_unused]] int first, int last) {
+        if constexpr (WINDOW) ko = ko < first ? first : ko;
+        return ko < last ? ko : last;
+    };
     auto load_unit = [&](int u, int u_valid, KRegs &Kr, VRegs &Vr, auto want_k, auto want_v) {
         const bool real = u < u_end;
         const int key0 = (real ? u : u_valid) * UNIT;
@@ -171,31 +229,33 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
             base = (int64_t)b * a.kv_bs + (int64_t)kvh * a.kv_hs;
             row0 = key0;
         }
-        const int last = real ? len - 1 - key0 : 0;
+        [[maybe_unused]] int first = 0;
+        if constexpr (WINDOW) first = lo_min > key0 ? lo_min - key0 : 0;
+        const int last = real ? len - 1 - key0 : first;
         if constexpr (FP8) {
 #pragma unroll
             for (int kt = 0; kt < 2 && decltype(want_k)::value; ++kt) {
-                const int ko = kt * 16 + li < last ? kt * 16 + li : last;
+                const int ko = clamp_key(kt * 16 + li, first, last);
                 const uint8_t *kp = k8 + base + (int64_t)(row0 + ko) * a.kv_ss + g * 16;
 #pragma unroll
                 for (int j = 0; j < 2; ++j) Kr[kt][j] = *(const u32x4 *)(kp + j * 64);
             }
 #pragma unroll
             for (int i = 0; i < 4 && decltype(want_v)::value; ++i) {
-                const int ko = i * 8 + vr < last ? i * 8 + vr : last;
+                const int ko = clamp_key(i * 8 + vr, first, last);
                 Vr[i] = *(const u32x4 *)(v8 + base + (int64_t)(row0 + ko) * a.kv_ss + vc * 16);
             }
         } else {
 #pragma unroll
             for (int kt = 0; kt < 2 && decltype(want_k)::value; ++kt) {
-                const int ko = kt * 16 + li < last ? kt * 16 + li : last;
+                const int ko = clamp_key(kt * 16 + li, first, last);
                 const uint16_t *kp = a.k + base + (int64_t)(row0 + ko) * a.kv_ss + g * 8;
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) Kr[kt][ks] = *(const vec8 *)(kp + ks * 32);
             }
 #pragma unroll
             for (int i = 0; i < 8 && decltype(want_v)::value; ++i) {
-                const int ko = i * 4 + g < last ? i * 4 + g : last;
+                const int ko = clamp_key(i * 4 + g, first, last);
                 Vr[i] = *(const s16x8 *)(a.v + base + (int64_t)(row0 + ko) * a.kv_ss + li * 8);
             }
         }
@@ -234,9 +294,20 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
         for (int nt = 0; nt < NT; ++nt) {
             float s[8];
             float mx = ninf;
+            // window: lo <= key < hi as ONE unsigned compare, key - lo < span (two compares per element hold two lane masks each)
+            [[maybe_unused]] unsigned from_lo = 0, span = 0;
+            if constexpr (WINDOW) {
+                const int hi = lim[nt] + w_right + 1 < len ? lim[nt] + w_right + 1 : len;
+                const int lo = (int)((unsigned)lim[nt] - (unsigned)w_left);   // (a padded row may wrap: hi < 0 masks it)
+                span = hi > lo ? (unsigned)hi - (unsigned)lo : 0u;
+                from_lo = (unsigned)key_g - (unsigned)lo;
+            }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {   // element j: key 16 (j >> 2) + 4 g + (j & 3) of the unit
-                s[j] = key_g + 16 * (j >> 2) + (j & 3) < lim[nt] ? S[nt][j >> 2][j & 3] : ninf;
+                bool seen;
+                if constexpr (WINDOW) seen = from_lo + (unsigned)(16 * (j >> 2) + (j & 3)) < span;
+                else seen = key_g + 16 * (j >> 2) + (j & 3) < lim[nt];
+                s[j] = seen ? S[nt][j >> 2][j & 3] : ninf;
                 mx = fmaxf(mx, s[j]);
             }
             const float m_new = fmaxf(m[nt], quad_max(mx));
@@ -279,6 +350,7 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
         KRegs Ka, Kb;
         VRegs Va, Vb;
         int u = 2 * t0 + wave;
+        if constexpr (WINDOW) u = (2 * t0 > lo_min / UNIT ? 2 * t0 : lo_min / UNIT) + wave;   // (only the lowest tile's first unit can lie below)
         if (u < u_end) load_unit(u, u, Ka, Va, BoolTag<true>{}, Ahead{});
         while (u < u_end) {
             if constexpr (!V_AHEAD) load_unit(u, u, Ka, Va, BoolTag<false>{}, Late{});
@@ -295,21 +367,31 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
         }
     }
 
+    // (Window, whose 64-row fp8 form stands at the register file's end: what the lines below need of the lane's coordinates and of
+    // the logits' scale is made again from what the loop keeps -- else the allocator holds r = 16 nt + li, the lane and the scale
+    // in registers of their own across the loop, and spills them; likewise the reciprocal behind r / group.  The same values,
+    // the same operations.)
+    int li_e = li, g_e = g, group_e = a.group;
+    [[maybe_unused]] float kd_e = kd;
+    if constexpr (WINDOW) asm volatile("" : "+v"(li_e), "+v"(g_e), "+s"(kd_e), "+s"(group_e));
+    const int lane_e = WINDOW ? (g_e << 4 | li_e) : lane;
+    const float scale_e = WINDOW && FP8 ? kd_e / __builtin_sqrtf((float)D) : scale;
+
     // the four waves' states into wave 0: one reference per row for all of them, then plain sums in wave order
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) l[nt] = quad_sum(l[nt]);
     float *m_sh = (float *)(smem + MAIN), *l_sh = m_sh + NWAVES * NT * 16, *o_sh = (float *)smem;
     __syncthreads();   // every wave is done with its V image
-    if (g == 0) {
+    if (g_e == 0) {
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) m_sh[(wave * NT + nt) * 16 + li] = m[nt];
+        for (int nt = 0; nt < NT; ++nt) m_sh[(wave * NT + nt) * 16 + li_e] = m[nt];
     }
     __syncthreads();
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         float m_all = ninf;
 #pragma unroll
-        for (int w = 0; w < NWAVES; ++w) m_all = fmaxf(m_all, m_sh[(w * NT + nt) * 16 + li]);
+        for (int w = 0; w < NWAVES; ++w) m_all = fmaxf(m_all, m_sh[(w * NT + nt) * 16 + li_e]);
         const float m_ref = m_all == ninf ? 0.0f : m_all;
         const float alpha = __builtin_amdgcn_exp2f((m[nt] - m_ref) * c);
         m[nt] = m_all;
@@ -322,8 +404,8 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
 #pragma unroll
-                for (int t = 0; t < DT16; ++t) *(f32x4 *)(o_sh + ((nt * DT16 + t) * 64 + lane) * 4) = O[nt][t];
-                if (g == 0) l_sh[nt * 16 + li] = l[nt];
+                for (int t = 0; t < DT16; ++t) *(f32x4 *)(o_sh + ((nt * DT16 + t) * 64 + lane_e) * 4) = O[nt][t];
+                if (g_e == 0) l_sh[nt * 16 + li_e] = l[nt];
             }
         }
         __syncthreads();
@@ -331,8 +413,8 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
 #pragma unroll
-                for (int t = 0; t < DT16; ++t) O[nt][t] += *(const f32x4 *)(o_sh + ((nt * DT16 + t) * 64 + lane) * 4);
-                l[nt] += l_sh[nt * 16 + li];
+                for (int t = 0; t < DT16; ++t) O[nt][t] += *(const f32x4 *)(o_sh + ((nt * DT16 + t) * 64 + lane_e) * 4);
+                l[nt] += l_sh[nt * 16 + li_e];
             }
         }
         __syncthreads();
@@ -342,14 +424,14 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     // lane (li, g) holds row 16 nt + li, d 16 t + 4 g .. + 3 (fp8: m is a raw logit, l a sum of undescaled V's weights)
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-        const int r = nt * 16 + li;
+        const int r = nt * 16 + li_e;
         if (r >= a.rows) continue;
         const bool any = l[nt] > 0.0f;
         const float inv = any ? vd / l[nt] : 0.0f;
-        const float lse = any ? m[nt] * scale + __logf(l[nt]) : ninf;
-        const int qi = r / a.group, qh = kvh * a.group + r % a.group;
+        const float lse = any ? m[nt] * scale_e + __logf(l[nt]) : ninf;
+        const int qi = r / group_e, qh = kvh * group_e + r % group_e;
         if (nsp == 1) {
-            uint16_t *op = a.o + (int64_t)b * a.o_bs + (int64_t)qi * a.o_ss + (int64_t)qh * a.o_hs + 4 * g;
+            uint16_t *op = a.o + (int64_t)b * a.o_bs + (int64_t)qi * a.o_ss + (int64_t)qh * a.o_hs + 4 * g_e;
 #pragma unroll
             for (int t = 0; t < DT16; ++t) {
                 u32x2 w;
@@ -357,13 +439,13 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
                 w[1] = E::pack2(O[nt][t][2] * inv, O[nt][t][3] * inv);
                 *(u32x2 *)(op + 16 * t) = w;
             }
-            if (a.lse && g == 0) a.lse[((int64_t)b * a.n_heads + qh) * a.seqlen_q + qi] = lse;
+            if (a.lse && g_e == 0) a.lse[((int64_t)b * a.n_heads + qh) * a.seqlen_q + qi] = lse;
         } else {
             const int64_t row = (((int64_t)split * a.batch + b) * a.n_kv_heads + kvh) * a.rows + r;
-            float *pp = a.part_o + row * D + 4 * g;
+            float *pp = a.part_o + row * D + 4 * g_e;
 #pragma unroll
             for (int t = 0; t < DT16; ++t) *(f32x4 *)(pp + 16 * t) = O[nt][t] * inv;
-            if (g == 0) a.part_lse[row] = lse;
+            if (g_e == 0) a.part_lse[row] = lse;
         }
     }
 }
@@ -396,8 +478,9 @@ __global__ void __launch_bounds__(64) fa_decode_combine_kernel(const DecodeArgs 
 }
 
 // The enqueue of one decode in either form: the split kernel and, for num_splits > 1, the combine kernel (the partial format
-// is the same, so the fp8 form launches it on its DecodeArgs part) on stream s.  Instantiated by fa_decode.hip (DecodeArgs) and
-// fa_decode_fp8.hip (DecodeFp8Args), which hold the kernels.
+// is the same, so the fp8 form launches it on its DecodeArgs part) on stream s.  Instantiated by fa_decode.hip (DecodeArgs),
+// fa_decode_fp8.hip (DecodeFp8Args), fa_decode_window.hip (DecodeWindowArgs) and fa_decode_fp8_window.hip (DecodeFp8WindowArgs),
+// which hold the kernels.
 template <class ARGS, int DT, int NT, bool PAGED>
 static hipError_t decode_enqueue_t(const ARGS &args, hipStream_t s) {
     const DecodeArgs &a = decode::common(args);
@@ -427,5 +510,7 @@ static hipError_t decode_enqueue_any(const ARGS &args, int dtype, hipStream_t s)
 
 hipError_t decode_enqueue(const DecodeArgs &a, int dtype, hipStream_t s);          // fa_decode.hip
 hipError_t decode_fp8_enqueue(const DecodeFp8Args &a, int dtype, hipStream_t s);   // fa_decode_fp8.hip
+hipError_t decode_window_enqueue(const DecodeWindowArgs &a, int dtype, hipStream_t s);          // fa_decode_window.hip
+hipError_t decode_fp8_window_enqueue(const DecodeFp8WindowArgs &a, int dtype, hipStream_t s);   // fa_decode_fp8_window.hip
 
 }  // namespace fa

@@ -104,8 +104,8 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
 
 
 def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
-                    num_splits=0, timed=False, k_descale=None, v_descale=None, k=None, v=None, rotary_cos=None, rotary_sin=None,
-                    rotary_interleaved=False, advance_seqlens=False):
+                    num_splits=0, timed=False, k_descale=None, v_descale=None, window_size=(-1, -1), k=None, v=None, rotary_cos=None,
+                    rotary_sin=None, rotary_interleaved=False, advance_seqlens=False):
     """Decode attention against a K / V cache: q (batch, seqlen_q, n_heads, 128) against k_cache / v_cache
     (batch, seqlen_cache, n_kv_heads, 128) -- or, with block_table (batch, max_pages_per_seq) int32, pages (num_pages,
     page_size, n_kv_heads, 128) -- of which cache_seqlens (batch,) int32 ON THE DEVICE says how many keys are valid, the newest
@@ -122,12 +122,19 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
     the call (flash-attn's flash_attn_with_kvcache); the new rows are appended in place first (append_kvcache: rotated with
     rotary_cos / rotary_sin (seqlen_ro, rotary_dim / 2) like q, quantized for an fp8 cache) and the attention covers
     cache_seqlens + seqlen_new keys.  advance_seqlens=True also writes the new lengths into cache_seqlens.  max_seqlen_k bounds the
-    lengths after the append.  Rotary without k / v, k without v, and rotary under causal with seqlen_new != seqlen_q are refused."""
+    lengths after the append.  Rotary without k / v, k without v, and rotary under causal with seqlen_new != seqlen_q are refused.
+
+    Sliding-window (local) attention (flash-attn's window_size): window_size=(left, right), two Python ints, -1 =
+    unbounded.  Query row i, at position p = len - seqlen_q + i, sees the keys max(0, p - left) .. min(len - 1, p + right); causal
+    means right = 0 (causal with another bounded right is a ValueError, like values below -1).  (-1, -1) is the call above,
+    unchanged.  The kernel fetches no key below the lowest one a row of the batch entry sees and reads no block_table entry of a
+    page wholly below it: such rows and pages may be stale, freed or reused.  With k / v the window applies to the lengths after
+    the append."""
     return flash_attention_kernels.forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=block_table, causal=causal,
                                                    return_lse=return_lse, max_seqlen_k=max_seqlen_k, num_splits=num_splits, timed=timed,
                                                    k_descale=k_descale, v_descale=v_descale, k=k, v=v, rotary_cos=rotary_cos,
                                                    rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved,
-                                                   advance_seqlens=advance_seqlens)
+                                                   advance_seqlens=advance_seqlens, window_size=window_size)
 
 
 def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table=None, causal=False,

@@ -441,11 +441,33 @@ def _decode_needs_copy(t):
 _FLOAT8_DTYPES = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
 
 
-def kvcache_num_splits(q, k_cache, v_cache, cache_seqlens, block_table=None, max_seqlen_k=None, num_splits=0):
+def _window(window_size, causal):
+    """window_size=(left, right) as forward_kvcache and forward_varlen_kvcache take it -> None for (-1, -1) (the unwindowed entry
+    points), else (left, right).  Bad values are a ValueError before the library is asked."""
+    if (not isinstance(window_size, (tuple, list)) or len(window_size) != 2
+            or any(not isinstance(w, int) or isinstance(w, bool) for w in window_size)):
+        raise ValueError(f"window_size must be a pair of Python ints (left, right), -1 = unbounded (got {window_size!r})")
+    left, right = window_size
+    if left < -1 or right < -1:
+        raise ValueError(f"window_size {(left, right)}: left and right must be -1 (unbounded) or not negative")
+    if not -2 ** 31 <= left < 2 ** 31 or not -2 ** 31 <= right < 2 ** 31:
+        raise ValueError(f"window_size {(left, right)}: left and right are 32-bit (pass -1 for unbounded)")
+    if causal and right not in (-1, 0):
+        raise ValueError(f"causal means right = 0: window_size {(left, right)} cannot be causal as well (pass right = -1 or 0)")
+    return None if (left, right) == (-1, -1) else (left, right)
+
+
+def kvcache_num_splits(q, k_cache, v_cache, cache_seqlens, block_table=None, max_seqlen_k=None, num_splits=0, causal=False,
+                       window_size=(-1, -1)):
     """The split count forward_kvcache uses for these arguments (fa_decode_num_splits, or fa_decode_fp8_num_splits for an fp8
-    cache: the same rule): the same checks, nothing allocated, no launch."""
-    _, args, fp8 = _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, False, max_seqlen_k, num_splits, None, None)
+    cache: the same rule; with a window_size other than (-1, -1) their _window_ forms, whose rule also reads causal): the same
+    checks, nothing allocated, no launch."""
+    window = _window(window_size, causal)
+    _, args, fp8 = _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_seqlen_k, num_splits, None, None)
     lib = _capi.load()
+    if window is not None:
+        w = _capi.make_window(*window)
+        return _capi.check((lib.fa_decode_fp8_window_num_splits if fp8 else lib.fa_decode_window_num_splits)(ctypes.byref(args), ctypes.byref(w)))
     return _capi.check((lib.fa_decode_fp8_num_splits if fp8 else lib.fa_decode_num_splits)(ctypes.byref(args)))
 
 
@@ -630,8 +652,8 @@ def append_kvcache(k_cache, v_cache, k, v, cache_seqlens, block_table=None, q=No
 
 
 def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
-                    num_splits=0, timed=False, k_descale=None, v_descale=None, k=None, v=None, rotary_cos=None, rotary_sin=None,
-                    rotary_interleaved=False, advance_seqlens=False):
+                    num_splits=0, timed=False, k_descale=None, v_descale=None, window_size=(-1, -1), k=None, v=None, rotary_cos=None,
+                    rotary_sin=None, rotary_interleaved=False, advance_seqlens=False):
     """Decode attention against a K / V cache (fa_decode_launch): q (batch, seqlen_q, n_heads, 128); k_cache, v_cache
     (batch, seqlen_cache, n_kv_heads, 128), or with block_table (batch, max_pages_per_seq) int32 on the device
     (num_pages, page_size, n_kv_heads, 128); cache_seqlens (batch,) int32 on the device, the valid keys of each entry (the
@@ -644,7 +666,12 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
     append_kvcache writes the new rows first (rotating them and q with rotary_cos / rotary_sin, quantizing for an fp8 cache), and
     the attention runs over cache_seqlens + seqlen_new keys with the rotated q, on the same stream.  advance_seqlens writes the new
     lengths into cache_seqlens in place (one captured graph is then a whole decode step).  max_seqlen_k bounds the lengths after
-    the append; timed's ms stays the decode's alone."""
+    the append; timed's ms stays the decode's alone.
+    window_size=(left, right), Python ints, -1 = unbounded: query row i, at position p = len - seqlen_q + i, sees the keys
+    max(0, p - left) .. min(len - 1, p + right); causal means right = 0.  (-1, -1) takes the entry points above unchanged, anything
+    else fa_decode_window_launch / fa_decode_fp8_window_launch, which fetch nothing below the lowest key a row sees.  With k / v
+    the window applies to the lengths after the append.  Bad values are a ValueError."""
+    window = _window(window_size, causal)
     if k is not None or v is not None or rotary_cos is not None or rotary_sin is not None or advance_seqlens:
         if k is None or v is None:
             raise RuntimeError("k and v come together; rotary_cos / rotary_sin and advance_seqlens need them (the append is what they act on)")
@@ -666,8 +693,15 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
     lse = torch.empty((batch, n_heads, seqlen_q), dtype=torch.float32, device=q.device) if return_lse else None
     args.o, args.lse = o.data_ptr(), (lse.data_ptr() if return_lse else None)
     lib = _capi.load()
-    workspace_bytes, launch = ((lib.fa_decode_fp8_workspace_bytes, lib.fa_decode_fp8_launch) if fp8 else
-                               (lib.fa_decode_workspace_bytes, lib.fa_decode_launch))
+    if window is None:
+        workspace_bytes, launch = ((lib.fa_decode_fp8_workspace_bytes, lib.fa_decode_fp8_launch) if fp8 else
+                                   (lib.fa_decode_workspace_bytes, lib.fa_decode_launch))
+    else:
+        w = _capi.make_window(*window)
+        sized, run = ((lib.fa_decode_fp8_window_workspace_bytes, lib.fa_decode_fp8_window_launch) if fp8 else
+                      (lib.fa_decode_window_workspace_bytes, lib.fa_decode_window_launch))
+        workspace_bytes = lambda a: sized(a, ctypes.byref(w))                         # noqa: E731
+        launch = lambda a, stream, ms: run(a, ctypes.byref(w), stream, ms)            # noqa: E731
     nbytes = workspace_bytes(ctypes.byref(args))
     _capi.check(nbytes if nbytes < 0 else 0)
     with torch.cuda.device(q.device):

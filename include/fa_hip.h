@@ -711,6 +711,42 @@ int64_t fa_decode_fp8_workspace_bytes(const fa_decode_fp8_args *args); /* bytes,
 int fa_decode_fp8_launch(const fa_decode_fp8_args *args, void *stream, float *ms);
 
 /*
+ * Sliding-window (local) attention for both decodes (flash-attn's window_size=(left, right)).  fa_window: struct_size =
+ * sizeof(fa_window); left, right: how many keys a query row sees below and above its own position, -1 = unbounded.  With
+ * p = len - seqlen_q + i the position of query row i (the bottom-right alignment of `causal`), the row sees key j iff
+ *     max(0, p - left) <= j <= min(len - 1, p + right);
+ * args->causal means right = 0 (causal with right > 0 is refused; right = -1 or 0 may accompany it).  A row that sees no key
+ * gives o = 0 and lse = -inf.  (-1, -1) computes what the unwindowed entry point computes, and with a forced num_splits the
+ * same bits.  Everything else -- shapes, strides, the cache's two addressings, the fp8 descales, the workspace format, the
+ * fixed-order combine, determinism, graph capture -- is fa_decode_launch's and fa_decode_fp8_launch's.
+ *
+ * Clamping, extended downwards.  lo_min = max(0, len - seqlen_q - left) (0 for left = -1) is the lowest key any row of the
+ * batch entry sees.  No key below lo_min is fetched, and no block_table entry of a page that lies wholly below lo_min is read;
+ * a lane whose key would fall below lo_min fetches key lo_min and is masked, as a lane at or beyond len fetches len - 1.  So
+ * stale rows, freed or reused pages and garbage table entries below the window cannot reach a result.  Keys from lo_min up
+ * to a later row's own lower bound are valid keys of the entry and are fetched for all of its rows.
+ *
+ * The split rule (fa_decode_window_num_splits) is fa_decode_num_splits' with its key bound replaced by
+ * min(max_seqlen_k or capacity, left + seqlen_q + right) when both sides are bounded (causal: right = 0), the old bound
+ * otherwise: a window wider than the bound gives the unwindowed count.  The workspace follows the split count.
+ * Refused before any HIP call: what the unwindowed entry point refuses; a null fa_window (FA_ERR_NULL); its struct_size, left or
+ * right below -1, causal with right > 0, a capacity above 2^30 - 128 keys (FA_ERR_SHAPE).
+ */
+typedef struct fa_window {
+    uint32_t struct_size;      /* sizeof(fa_window) */
+    int32_t left;              /* -1 = unbounded */
+    int32_t right;             /* -1 = unbounded */
+} fa_window;
+int fa_decode_window_supported(const fa_decode_args *args, const fa_window *window);
+int fa_decode_window_num_splits(const fa_decode_args *args, const fa_window *window);          /* or a negative fa_status */
+int64_t fa_decode_window_workspace_bytes(const fa_decode_args *args, const fa_window *window); /* bytes, or a negative fa_status */
+int fa_decode_window_launch(const fa_decode_args *args, const fa_window *window, void *stream, float *ms);
+int fa_decode_fp8_window_supported(const fa_decode_fp8_args *args, const fa_window *window);
+int fa_decode_fp8_window_num_splits(const fa_decode_fp8_args *args, const fa_window *window);
+int64_t fa_decode_fp8_window_workspace_bytes(const fa_decode_fp8_args *args, const fa_window *window);
+int fa_decode_fp8_window_launch(const fa_decode_fp8_args *args, const fa_window *window, void *stream, float *ms);
+
+/*
  * The step in front of a decode: append seqlen_new new K / V rows per batch entry to the cache IN PLACE, at the positions the
  * device-side lengths name, optionally rotate the new keys and the query (rotary embedding), quantize for an fp8 cache, and
  * advance the lengths.  One kernel on `stream`; the host reads none of the device arrays, so the launch is asynchronous and
