@@ -21,8 +21,18 @@ tests/test_beacon_cpu.py asserts the outcome: every target's fp32 probability li
 least two keys.  A row that sees no key gets plain noise.  u is drawn for positions up to n_k INCLUSIVE (and further, for a
 cache with capacity behind its length), so the key behind the last one exists and holds the beacon the last rows' queries point at.
 
+Two-sided windows (forward_kvcache(window_size=(left, right))): row r at position p = n_k - n_q + r sees lo_r .. hi_r with
+lo_r = max(0, p - left) (0 for left < 0) and hi_r = min(n_k - 1, p + right) (n_k - 1 for right < 0; causal means right = 0),
+and is live iff hi_r >= lo_r.  The query leaks in both directions, q[r] = b_r (u[t] + LEAK w_hi + LEAK w_lo) + NOISE z with
+w_hi = u[hi_r + 1] and w_lo = u[lo_r - 1] (absent when lo_r = 0), each made orthogonal to u[t], and beta_r is the smaller root of
+beta = L + kappa beta^2 with L = ln(max(hi_r - lo_r, 1)) + NOISE^2 beta_k / (2 sqrt(128)) and kappa = (1 + LEAK^2 n_leaks) / 256,
+n_leaks = 2 when lo_r >= 1, else 1: with lo_r = 0 the one-sided formula above.  window_positions lists what the window moves:
+every row's two edges, lo_min = max(0, n_k - n_q - left) and the key above it, the unit, tile, page and split boundaries counted
+from lo_min's tile; assign_window_targets gives a position only to a row whose window holds it.
+
 Nothing here reads the code under test: the positions come from the sizes the kernels are documented to use (64-key tiles,
-32-key units, 128-row blocks, pages, the split rule 64 floor(n_tiles s / num_splits)).  Plain helper module: no tests, no
+32-key units, 128-row blocks, pages, the split rule 64 floor(n_tiles s / num_splits), under a window
+64 (tl + floor((n_tiles - tl) s / num_splits)) with tl = lo_min / 64).  Plain helper module: no tests, no
 fixtures; runs on the CPU or the GPU with a seed.
 """
 import math
@@ -49,6 +59,14 @@ VARLEN_FAMILIES = {   # name -> ((len_q, len_k) pairs, loose (max_seqlen_q, max_
     "loose": ([(37, 1000), (128, 192), (65, 63)], (1024, 2048)),
 }
 DENSE_CASES = [(1000, True), (1024, True), (4096, False)]   # (seq_len, causal): forward_ex on the default configuration
+# the windowed decode launches of tests/test_window_beacon_gpu.py (the shapes are DECODE_SHAPES): one batch of all lengths.  136 and
+# 143 put lo_min on a tile boundary and on a tile's middle (lo_min % 64 = 0 and 32) at every seqlen_q of DECODE_SHAPES: 136 - 4 - 100
+# = 32, 136 - 8 - 0 = 128 and 136 - 8 - 64 = 64, 143 - 16 - 63 = 64 and 143 - 16 - 31 = 96, beside 1000 - 4 - 100 = 896 and 1000 - 8 - 0 = 992
+WINDOW_LENGTHS = [1, 2, 33, 64, 65, 130, 136, 143, 1000, 4097]
+WINDOW_CACHE_LEN = 4352                          # a multiple of both page sizes, and rows behind the longest entry
+WINDOWS = [(0, -1, True), (1, -1, True), (31, -1, True), (63, 0, False), (64, -1, True), (100, -1, True), (200, 3, False),
+           (3, 2, False), (-1, 3, False), (1000, -1, True), (5000, -1, True)]   # (left, right, causal); causal: right = 0
+WINDOW_SPLITS = [1, 3, 16, 0]                    # 0: the rule's (fa_decode_window_num_splits)
 
 
 # ---- the inputs -------------------------------------------------------------------------------------------------------------
@@ -67,9 +85,10 @@ def beacon_kv(n_k, dtype, n_alloc=None, seed=0, device="cpu"):
     return (sign * (a / math.sqrt(D))).to(dtype), v.to(dtype)
 
 
-def beacon_q(k, n_k, targets, diag, dtype, seed=0):
+def beacon_q(k, n_k, targets, diag, dtype, seed=0, lo=None):
     """Query rows for one K / V head's beacons: k (>= n_k + 1, 128) from beacon_kv; targets and diag int64 (n_q,) on k's
-    device, targets[r] in [0, diag[r]] or -1, diag[r] in [-inf, n_k - 1] (< 0: the row sees no key)."""
+    device, targets[r] in [0, diag[r]] or -1, diag[r] in [-inf, n_k - 1] (< 0: the row sees no key).  lo: int64 (n_q,), the
+    first key each row sees (a two-sided window: targets[r] in [lo[r], diag[r]], and a second leak towards key lo[r] - 1)."""
     device = k.device
     gen = torch.Generator(device=device).manual_seed(seed)
     n_q = targets.numel()
@@ -82,8 +101,16 @@ def beacon_q(k, n_k, targets, diag, dtype, seed=0):
     w = w - (w * ut).sum(-1, keepdim=True) * ut
     z_perp = z - (z * ut).sum(-1, keepdim=True) * ut
     beta_k = _beta_k(n_k)
-    big_l = torch.log(diag.clamp_min(1).double()) + 0.5 * NOISE ** 2 * beta_k / math.sqrt(D)
-    kappa = (1.0 + LEAK ** 2) / (2.0 * D)                      # beta = L + kappa beta^2, the smaller root
+    if lo is None:
+        big_l = torch.log(diag.clamp_min(1).double()) + 0.5 * NOISE ** 2 * beta_k / math.sqrt(D)
+        kappa = (1.0 + LEAK ** 2) / (2.0 * D)                  # beta = L + kappa beta^2, the smaller root
+    else:
+        assert bool((targets[live] >= lo[live]).all()) and bool((lo >= 0).all())
+        below = (lo >= 1)[:, None]
+        w_lo = u[(lo - 1).clamp_min(0)] / math.sqrt(D)
+        w = w + torch.where(below, w_lo - (w_lo * ut).sum(-1, keepdim=True) * ut, torch.zeros_like(w_lo))
+        big_l = torch.log((diag - lo).clamp_min(1).double()) + 0.5 * NOISE ** 2 * beta_k / math.sqrt(D)
+        kappa = (1.0 + LEAK ** 2 * (1 + below[:, 0].double())) / (2.0 * D)
     beta = (1.0 - torch.sqrt(1.0 - 4.0 * kappa * big_l)) / (2.0 * kappa)
     b = (beta * math.sqrt(D) / math.sqrt(beta_k * math.sqrt(D))).float()[:, None]
     q = torch.where(live[:, None], b * (ut + LEAK * w) + NOISE * z_perp, NOISE * z)
@@ -103,6 +130,26 @@ def diagonals(n_q, n_k, causal, device="cpu"):
     if causal:
         return torch.arange(n_q, device=device) + (n_k - n_q)
     return torch.full((n_q,), n_k - 1, dtype=torch.int64, device=device)
+
+
+def window_sides(left, right, causal):
+    """(left, right, causal) as forward_kvcache takes them -> the (left, right) the mask uses: causal means right = 0"""
+    assert not causal or right in (-1, 0)
+    return left, (0 if causal else right)
+
+
+def window_bounds(n_q, n_k, left, right, device="cpu"):
+    """The first and the last key each of n_q rows sees under window (left, right), -1 = unbounded -> lo, hi int64 (n_q,);
+    lo >= 0 always, and a row is live iff hi >= lo (a dead row has hi < 0: its position lies more than `right` below key 0)."""
+    p = torch.arange(n_q, device=device) + (n_k - n_q)
+    lo = torch.zeros_like(p) if left < 0 else (p - left).clamp_min(0)
+    hi = torch.full_like(p, n_k - 1) if right < 0 else (p + right).clamp_max(n_k - 1)
+    return lo, hi
+
+
+def window_lo_min(n, seqlen_q, left):
+    """the lowest key any row of the entry sees"""
+    return 0 if left < 0 else max(0, n - seqlen_q - left)
 
 
 # ---- the positions that matter ------------------------------------------------------------------------------------------------
@@ -153,6 +200,22 @@ def dense_positions(n, diagonals=True):
     return _unique_inside(pos + (list(range(n)) if diagonals else []), n)
 
 
+def window_positions(n, seqlen_q, left, right, num_splits, page_sizes=(64, 256)):
+    """forward_kvcache with window_size, one entry of length n: every live row's first and last key, lo_min and the key above
+    it, n - 2 and n - 1, both sides of the 32-key unit and 64-key tile boundaries in the tile that holds lo_min and in the tile
+    after it, of the first page boundary above lo_min for each page size, and of every windowed split boundary
+    64 (tl + floor((n_tiles - tl) s / num_splits)), tl = lo_min / 64; all inside [lo_min, n)."""
+    lo, hi = window_bounds(seqlen_q, n, left, right)
+    live = hi >= lo
+    lo_min = window_lo_min(n, seqlen_q, left)
+    n_tiles, tl = (n + 63) // 64, lo_min // 64
+    pos = [p for pair in zip(lo[live].tolist(), hi[live].tolist()) for p in pair] + [lo_min, lo_min + 1, n - 2, n - 1]
+    pos += _both_sides(64 * tl + off for off in (32, 64, 96, 128))
+    pos += _both_sides(p * (lo_min // p + 1) for p in page_sizes)
+    pos += _both_sides(64 * (tl + (n_tiles - tl) * s // num_splits) for s in range(1, num_splits))
+    return [p for p in _unique_inside(pos, n) if p >= lo_min]
+
+
 def assign_targets(n_q, n_heads, n_k, listed, causal, phase=0):
     """Spread `listed` over the n_q x n_heads rows of one sequence -> (targets int64 (n_heads, n_q), -1 on rows that see no key;
     n_phases).  Without a mask the first row of head 0 targets the last key (every row's diagonal) and the other rows take the
@@ -199,6 +262,59 @@ def build_sequence(n_q, n_k, n_heads, n_kv_heads, listed, dtype, causal, phase=0
     return dict(q=q, k=k, v=v, targets=targets, diag=diag.cpu(), n_phases=n_phases, n_q=n_q, n_k=n_k, listed=list(listed))
 
 
+def assign_window_targets(n_heads, lo, hi, listed, phase=0):
+    """Spread `listed` over the rows of one windowed entry -> (targets int64 (n_heads, n_q), -1 on rows that see no key;
+    n_phases).  lo, hi: window_bounds.  Head 0 of every live row targets the row's own last key and head 1 its own first key, in
+    every phase; the other heads take the listed positions that are no live row's edge, each given only to a row whose
+    [lo, hi] holds it -- the positions fewest rows can hold first, each to the holding row with most heads left -- and a
+    position that finds no head waits for the next phase.  A head left over targets an edge of its row (even heads the last
+    key, odd heads the first).  An entry with fewer phases than its launch repeats them in turn."""
+    assert n_heads >= 2
+    lo, hi = lo.tolist(), hi.tolist()
+    n_q = len(lo)
+    live = [r for r in range(n_q) if hi[r] >= lo[r]]
+    targets = torch.full((n_heads, n_q), -1, dtype=torch.int64)
+    for r in live:
+        targets[0::2, r], targets[1::2, r] = hi[r], lo[r]
+    edges = {e for r in live for e in (lo[r], hi[r])}
+    holders = {p: [r for r in live if lo[r] <= p <= hi[r]] for p in listed if p not in edges}
+    rest = sorted(holders, key=lambda p: len(holders[p]))          # (stable: the list's order among equals)
+    phases = []
+    while rest:
+        free = {r: list(range(2, n_heads)) for r in live}
+        placed, waiting = {}, []
+        for p in rest:
+            rows = [r for r in holders[p] if free[r]]
+            if rows:
+                r = max(rows, key=lambda r: len(free[r]))
+                placed[free[r].pop(0), r] = p
+            else:
+                waiting.append(p)
+        assert placed, ("no live row sees", rest)
+        phases.append(placed)
+        rest = waiting
+    if phases:
+        for (h, r), p in phases[phase % len(phases)].items():
+            targets[h, r] = p
+    return targets, max(len(phases), 1)
+
+
+def build_window_sequence(n_q, n_k, n_heads, n_kv_heads, listed, dtype, left, right, phase=0, n_alloc=None, seed=0, device="cpu",
+                          kv=None):
+    """build_sequence under window (left, right) (causal: pass right = 0) -> the same dict with lo (n_q,) beside diag, which
+    holds hi; eager, references and target_probabilities read both."""
+    lo, hi = window_bounds(n_q, n_k, left, right)
+    targets, n_phases = assign_window_targets(n_heads, lo, hi, listed, phase)
+    group = n_heads // n_kv_heads
+    if kv is None:
+        pairs = [beacon_kv(n_k, dtype, n_alloc, seed * 1000 + 2 * h, device) for h in range(n_kv_heads)]
+        kv = torch.stack([p[0] for p in pairs], dim=1), torch.stack([p[1] for p in pairs], dim=1)
+    k, v = kv
+    q = torch.stack([beacon_q(k[:, h // group], n_k, targets[h].to(device), hi.to(device), dtype, seed * 1000 + 2 * h + 1 + 7919 * phase,
+                              lo=lo.to(device)) for h in range(n_heads)], dim=1)
+    return dict(q=q, k=k, v=v, targets=targets, diag=hi, lo=lo, n_phases=n_phases, n_q=n_q, n_k=n_k, listed=list(listed))
+
+
 def cpu_cap(n, limit=1100):
     """A length the CPU tests can afford: lengths beyond `limit` keep their remainder by 64 on top of 1024 keys."""
     return n if n <= limit else 1024 + n % 64
@@ -233,14 +349,16 @@ def pack(seqs):
 
 # ---- the reference and the comparison -----------------------------------------------------------------------------------------
 
-def eager(q, k, v, diag, dtype, delta=0, want_p=False):
+def eager(q, k, v, diag, dtype, delta=0, want_p=False, lo=None, delta_lo=0):
     """Eager attention of one sequence in `dtype` arithmetic: q (n_q, H, 128), k / v (n_keys, Hkv, 128), row r sees keys
-    j <= diag[r] + delta (delta != 0: a deliberately wrong mask) -> o (n_q, H, 128) in dtype, lse fp32 (H, n_q)[, p].
-    A row that sees no key: o = 0, lse = -inf."""
+    j <= diag[r] + delta (delta != 0: a deliberately wrong mask) and, with lo (n_q,), j >= lo[r] + delta_lo
+    -> o (n_q, H, 128) in dtype, lse fp32 (H, n_q)[, p].  A row that sees no key: o = 0, lse = -inf."""
     group = q.shape[1] // k.shape[1]
     kk, vv = k.to(dtype).repeat_interleave(group, dim=1), v.to(dtype).repeat_interleave(group, dim=1)
     s = torch.einsum("qhd,khd->hqk", q.to(dtype), kk) * (1.0 / math.sqrt(D))
     hidden = torch.arange(k.shape[0], device=q.device)[None, :] > (diag.to(q.device)[:, None] + delta)
+    if lo is not None:
+        hidden = hidden | (torch.arange(k.shape[0], device=q.device)[None, :] < (lo.to(q.device)[:, None] + delta_lo))
     s = s.masked_fill(hidden[None], NEG_INF)
     dead = hidden.all(dim=1)[None, :, None]
     lse = torch.logsumexp(s.float().masked_fill(dead, 0.0), dim=-1).masked_fill(dead[..., 0], NEG_INF)
@@ -255,19 +373,20 @@ def references(seq):
     if seq["n_q"] == 0 or n_k == 0:
         o = torch.zeros(seq["q"].shape, dtype=torch.float32, device=seq["q"].device)
         return o, torch.full((seq["q"].shape[1], seq["n_q"]), NEG_INF, device=o.device), o.to(dtype)
-    o32, lse32 = eager(seq["q"], seq["k"][:n_k], seq["v"][:n_k], seq["diag"], torch.float32)
-    o16, _ = eager(seq["q"], seq["k"][:n_k], seq["v"][:n_k], seq["diag"], dtype)
+    o32, lse32 = eager(seq["q"], seq["k"][:n_k], seq["v"][:n_k], seq["diag"], torch.float32, lo=seq.get("lo"))
+    o16, _ = eager(seq["q"], seq["k"][:n_k], seq["v"][:n_k], seq["diag"], dtype, lo=seq.get("lo"))
     return o32, lse32, o16
 
 
 def target_probabilities(seq, lse32):
     """fp32 probability of every row's target, exp(q . k[target] / sqrt(128) - lse32) -> (H, n_q) and the mask of the rows
-    the [P_LO, P_HI] condition holds for: live rows that see at least two keys."""
+    the [P_LO, P_HI] condition holds for: live rows that see at least two keys (diag + 1, under a window diag + 1 - lo)."""
     q, k, targets = seq["q"].float(), seq["k"].float(), seq["targets"].to(seq["q"].device)
     group = q.shape[1] // k.shape[1]
     kt = torch.stack([k[targets[h].clamp_min(0), h // group] for h in range(q.shape[1])])          # (H, n_q, 128)
     p = torch.exp((q.transpose(0, 1) * kt).sum(-1) * (1.0 / math.sqrt(D)) - lse32)
-    several = ((targets >= 0) & (seq["diag"].to(p.device) >= 1)[None, :])
+    sees = seq["diag"] + 1 if seq.get("lo") is None else seq["diag"] + 1 - seq["lo"]
+    several = ((targets >= 0) & (sees.to(p.device) >= 2)[None, :])
     return p, several
 
 

@@ -154,6 +154,22 @@ def _paginate8(k8, v8, lens, page_size, poison, seed=3):
     return kp.view(F8), vp.view(F8), table.to(k.device)
 
 
+def _beacon_fp8_cache(first, lens, Hkv, dtype):
+    """The fp8 cache of a batch of beacon entries (`first`: one build_sequence dict per entry of `lens`, keys up to the capacity)
+    -> k8, v8, k_descale, v_descale and the dequantized fp32 k and v the oracle runs on.  K is stored as +- 1 with
+    k_descale[b, :] = a / sqrt(128), exact and different for every batch entry; V goes through quantize_kvcache_fp8.  Shared
+    with tests/test_window_beacon_gpu.py."""
+    B = len(lens)
+    k16, v16 = torch.stack([s["k"] for s in first]), torch.stack([s["v"] for s in first])
+    k8 = torch.sign(k16.float()).to(F8)
+    assert bool((k8.float().abs() == 1).all())
+    kd = torch.tensor([math.sqrt(bi._beta_k(n) * math.sqrt(bi.D)) / math.sqrt(bi.D) for n in lens], device=DEV).float()[:, None].repeat(1, Hkv).contiguous()
+    assert kd[:, 0].unique().numel() >= B - 1   # (lengths 1 and 2 share beta_k)
+    assert bool(((k8.float() * kd[:, None, :, None]).to(dtype) == k16).all())   # the beacons' K, before its rounding to 16 bit
+    _, v8, _, vd = _fa().quantize_kvcache_fp8(k16, v16)
+    return k8, v8, kd, vd, k8.float() * kd[:, None, :, None], v8.float() * vd[:, None, :, None]
+
+
 @pytest.mark.parametrize("dtype", DTYPES, ids=["bf16", "fp16"])
 @pytest.mark.parametrize("causal", [False, True], ids=["plain", "causal"])
 @pytest.mark.parametrize("H,Hkv,Sq", bi.DECODE_SHAPES)
@@ -167,17 +183,9 @@ def test_decode_fp8_on_beacons(dtype, causal, H, Hkv, Sq):
 
     fa = _fa()
     lens, cap = BEACON_LENGTHS, BEACON_CACHE_LEN
-    B = len(lens)
     lens_t = torch.tensor(lens, dtype=torch.int32, device=DEV)
     first = [bi.build_sequence(Sq, n, H, Hkv, [0], dtype, causal, n_alloc=cap, seed=b, device=DEV) for b, n in enumerate(lens)]
-    k16, v16 = torch.stack([s["k"] for s in first]), torch.stack([s["v"] for s in first])
-    k8 = torch.sign(k16.float()).to(F8)
-    assert bool((k8.float().abs() == 1).all())
-    kd = torch.tensor([math.sqrt(bi._beta_k(n) * math.sqrt(bi.D)) / math.sqrt(bi.D) for n in lens], device=DEV).float()[:, None].repeat(1, Hkv).contiguous()
-    assert kd[:, 0].unique().numel() >= B - 1   # (lengths 1 and 2 share beta_k)
-    assert bool(((k8.float() * kd[:, None, :, None]).to(dtype) == k16).all())   # the beacons' K, before its rounding to 16 bit
-    _, v8, _, vd = fa.quantize_kvcache_fp8(k16, v16)
-    kdq, vdq = k8.float() * kd[:, None, :, None], v8.float() * vd[:, None, :, None]
+    k8, v8, kd, vd, kdq, vdq = _beacon_fp8_cache(first, lens, Hkv, dtype)
     paged = [_paginate8(k8, v8, lens, page_size, poison=False) for page_size in (64, 256)]
     q0 = torch.stack([s["q"] for s in first])
     failures, worst_o, worst_lse, p_lo, p_hi = [], 0.0, 0.0, 1.0, 0.0

@@ -4,6 +4,15 @@ The oracle is fp32 eager attention per batch entry with the window mask: query r
 p = n - seqlen_q + i, sees key j iff max(0, p - left) <= j <= min(n - 1, p + right) (-1 = unbounded, causal = right 0).  The
 tolerance rule is tests/test_decode_gpu.py's: max|O - O32| <= max(O_TOL[dtype], 2 * max|O_eager16 - O32|), lse 1e-3 absolute,
 -inf exactly for rows that see no key.
+
+What these inputs can see: they are N(0, 1), so every key weighs about 1 / w in a row that sees w keys, and a key lost, doubled
+or leaked at an edge or a seam moves lse by ln(1 + 1 / w) and o by about |v| / w.  Against lse 1e-3 and O_TOL 2^-6 (bf16) a
+single-key error shows in o up to about 100 keys and in lse up to about 1000: the small windows (left 0, 1, 31) catch a uniform
+off-by-one, test_split_consistency at left 1000 sits on the bar, and (200, 3) is seen by lse alone.  What they cannot see: an
+error that depends on where lo_min falls in a tile, unit, page or split, and anything at the widths models use (1024, 4096).
+The poisoning tests pin what lies BELOW lo_min; the keys between lo_min and a later row's own first key, which are fetched and
+must be masked, and the first key above a bounded right edge are pinned by tests/test_window_beacon_gpu.py, on inputs where
+every such key carries about half of some row's probability.
 """
 import math
 
