@@ -60,7 +60,7 @@ namespace {
 
 thread_local char g_err[512] = "";
 
-int fail(int code, const char *fmt, ...) {
+__attribute__((cold)) int fail(int code, const char *fmt, ...) {   // (cold: the rules around a refusal stay small enough to inline)
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
@@ -813,7 +813,7 @@ int bwd_prepare(const fa_bwd_args *a, fa::BwdArgs *out) {
 
 // enqueue() on s; ms != nullptr: bracketed by events, blocking, the elapsed ms into *ms
 extern "C++" {   // (a template, inside the extern "C" block)
-template <class F> int bwd_run(F enqueue, hipStream_t s, float *ms) {
+template <class F> int enqueue_timed(F enqueue, hipStream_t s, float *ms) {
     if (!ms) {
         const hipError_t hrc = enqueue();
         return hrc == hipSuccess ? FA_OK : fail(FA_ERR_LAUNCH, "hipLaunchKernel (backward): %s", hipGetErrorString(hrc));
@@ -887,7 +887,7 @@ int fa_bwd_launch(const fa_bwd_args *a, void *stream, float *ms) {
     DeviceState *dev = current_device(&rc);
     if (!dev) return rc;
     const hipStream_t s = (hipStream_t)stream;
-    return bwd_run([&] { return fa::bwd_enqueue(ba, a->dtype, a->causal != 0, s); }, s, ms);
+    return enqueue_timed([&] { return fa::bwd_enqueue(ba, a->dtype, a->causal != 0, s); }, s, ms);
 }
 
 int64_t fa_bwd_gqa_workspace_bytes(const fa_bwd_gqa_args *g) {
@@ -919,7 +919,7 @@ int fa_bwd_launch_gqa(const fa_bwd_gqa_args *g, void *stream, float *ms) {
     ga.group = (int32_t)(a->n_heads / g->n_kv_heads);
     ga.split = (int32_t)split;
     const hipStream_t s = (hipStream_t)stream;
-    return bwd_run([&] { return fa::bwd_gqa_enqueue(ga, a->dtype, a->causal != 0, s); }, s, ms);
+    return enqueue_timed([&] { return fa::bwd_gqa_enqueue(ga, a->dtype, a->causal != 0, s); }, s, ms);
 }
 
 int fa_fwd_gqa_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) {
@@ -948,6 +948,117 @@ int fa_fwd_launch_gqa(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_
     if ((uintptr_t)lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
     return launch_ex_impl(args, opts, stream, lse, kv);
 }
+
+// ---- the KV cache, as decode, the append and the cache prefill see it ------------------------------------------------------------
+// One description of a contiguous or paged cache, filled by one constructor per public struct (each in front of its path), and one
+// set of rules over it.  The rules are small functions that every path calls where its own order of checks has them: that order is
+// observable -- an input that breaks two rules reports the first -- and tests/test_host_corpus_cpu.py pins it.
+namespace {
+extern "C++" {   // (inside the file's extern "C" block: internal linkage, so that nothing here is exported; templates need it too)
+struct CacheView {
+    const int32_t *cache_seqlens = nullptr, *block_table = nullptr;   // block_table: null = a contiguous cache
+    int64_t seqlen_cache = 0, num_pages = 0, page_size = 0, max_pages_per_seq = 0, block_table_stride = 0, max_seqlen_k = 0;
+    int64_t entries = 0, n_kv_heads = 0;       // entries: batch, or the prefill's n_seqs
+    int64_t kv_bs = 0, kv_ss = 0, kv_hs = 0;   // elements (an fp8 cache: bytes)
+    bool fp8 = false;
+    const float *k_descale = nullptr, *v_descale = nullptr;
+    int64_t descale_bs = 0;
+    const char *words_4b = "";   // the path's name for the pointers cache_alignment checks
+    bool paged() const { return block_table != nullptr; }
+    int64_t capacity() const { return paged() ? max_pages_per_seq * page_size : seqlen_cache; }   // keys per entry
+    int64_t slots() const { return paged() ? num_pages : entries; }                                // the cache tensors' first size
+};
+
+// one stride set: positive where the size asks for it, multiples of `unit` elements (16 bytes)
+int stride_set(const char *which, int64_t unit, int64_t n0, int64_t n1, int64_t n2, int64_t bs, int64_t ss, int64_t hs) {
+    if (ss <= 0 || bs < 0 || hs < 0 || (n0 > 1 && bs == 0) || (n2 > 1 && hs == 0) || (n1 > 1 && ss == 0))
+        return fail(FA_ERR_SHAPE, "%s strides must be positive (batch %lld, seq %lld, head %lld elements)", which, (long long)bs,
+                    (long long)ss, (long long)hs);
+    if ((bs | ss | hs) & (unit - 1)) return fail(FA_ERR_ALIGN, "%s strides must be multiples of %lld elements (16 bytes)", which, (long long)unit);
+    return FA_OK;
+}
+
+// the page rule (no kernel serves another page size).  The append asks it ahead of its sizes, where page_size may still be bad.
+int cache_page_rule(const CacheView &c) {
+    if (c.paged() && c.page_size > 0 && c.page_size % 64 != 0)
+        return fail(FA_ERR_NO_KERNEL, "paged cache: page_size must be a multiple of 64 (got %lld)", (long long)c.page_size);
+    return FA_OK;
+}
+
+// the sizes of a paged or a contiguous cache
+int cache_sizes(const CacheView &c) {
+    if (!c.paged()) return c.seqlen_cache > 0 ? FA_OK : fail(FA_ERR_SHAPE, "seqlen_cache must be positive (got %lld)", (long long)c.seqlen_cache);
+    if (c.page_size <= 0 || c.num_pages <= 0 || c.max_pages_per_seq <= 0)
+        return fail(FA_ERR_SHAPE, "paged cache: num_pages, page_size and max_pages_per_seq must be positive");
+    if (const int rc = cache_page_rule(c)) return rc;
+    if (c.block_table_stride < c.max_pages_per_seq)
+        return fail(FA_ERR_SHAPE, "block_table_stride (%lld) is smaller than max_pages_per_seq (%lld)", (long long)c.block_table_stride,
+                    (long long)c.max_pages_per_seq);
+    if (c.num_pages > INT32_MAX / 2 || c.page_size > INT32_MAX / 2 || c.max_pages_per_seq > INT32_MAX / 2)
+        return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
+    return FA_OK;
+}
+
+// ... and, behind them, the capacity and the host's bound on the lengths (0 = the capacity; the append has none)
+int cache_bounds(const CacheView &c) {
+    const int64_t cap = c.capacity();
+    if (cap > INT32_MAX / 2) return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
+    if (c.max_seqlen_k < 0 || c.max_seqlen_k > cap)
+        return fail(FA_ERR_SHAPE, "max_seqlen_k (%lld) must lie in [0, %lld] (0 = the cache's capacity)", (long long)c.max_seqlen_k, (long long)cap);
+    return FA_OK;
+}
+
+// the cache's stride set (decode and the append; the prefill's token and head strides take the packed tensors' rules)
+int cache_strides(const CacheView &c, int64_t unit) { return stride_set("kv", unit, c.slots(), c.capacity(), c.n_kv_heads, c.kv_bs, c.kv_ss, c.kv_hs); }
+
+// an fp8 cache's strides count bytes (decode and the prefill; the append words the same rule as stride_set's, unit 16)
+int cache_fp8_strides(const CacheView &c) {
+    if (c.fp8 && ((c.kv_bs | c.kv_ss | c.kv_hs) & 15)) return fail(FA_ERR_ALIGN, "kv strides of an fp8 cache must be multiples of 16 bytes");
+    return FA_OK;
+}
+
+int cache_descale_stride(const CacheView &c) {
+    if ((c.k_descale || c.v_descale) && c.descale_bs < c.n_kv_heads)
+        return fail(FA_ERR_SHAPE, "descale_batch_stride (%lld) is smaller than n_kv_heads (%lld)", (long long)c.descale_bs, (long long)c.n_kv_heads);
+    return FA_OK;
+}
+
+// the 4-byte pointers: the lengths, the block table and what else the path names with them in words_4b
+int cache_alignment(const CacheView &c, uintptr_t others = 0) {
+    if (((uintptr_t)c.cache_seqlens | (uintptr_t)c.block_table | others) & 3) return fail(FA_ERR_ALIGN, "%s must be 4-byte aligned", c.words_4b);
+    return FA_OK;
+}
+int cache_descale_alignment(const CacheView &c) {
+    if (((uintptr_t)c.k_descale | (uintptr_t)c.v_descale) & 3) return fail(FA_ERR_ALIGN, "k_descale and v_descale must be 4-byte aligned");
+    return FA_OK;
+}
+
+// the geometry, from any struct with these members (a public struct, or the prefill's layout)
+template <class A> void cache_geometry(CacheView &c, const A &a) {
+    c.cache_seqlens = a.cache_seqlens;
+    c.block_table = a.block_table;
+    c.seqlen_cache = a.seqlen_cache;
+    c.num_pages = a.num_pages;
+    c.page_size = a.page_size;
+    c.max_pages_per_seq = a.max_pages_per_seq;
+    c.block_table_stride = a.block_table_stride;
+}
+// ... and the stride set and the heads of a struct that carries them itself (decode and the append)
+template <class A> void cache_tensors(CacheView &c, const A &a) {
+    cache_geometry(c, a);
+    c.entries = a.batch;
+    c.n_kv_heads = a.n_kv_heads;
+    c.kv_bs = a.kv_batch_stride;
+    c.kv_ss = a.kv_seq_stride;
+    c.kv_hs = a.kv_head_stride;
+}
+template <class A> void cache_descales(CacheView &c, const A &a) {
+    c.k_descale = a.k_descale;
+    c.v_descale = a.v_descale;
+    c.descale_bs = a.descale_batch_stride;
+}
+}
+}  // namespace
 
 // ---- packed variable-length sequences: one range for Q and K / V (fa_*_varlen) or one each (fa_*_varlen_qk) ------------------
 // One host path, of two ranges; the entry points with one fa_varlen_layout pass it for both sides.  Each entry point keeps its
@@ -1007,58 +1118,39 @@ const fa::KernelEntry *varlen_entry(const fa_fwd_config *cfg, const char **why) 
 const char *kNoVarlen = "packed variable-length sequences are served by the (B_r 128, B_c 64, 4 warps) + buffer configuration at d_head "
                         "128 only, plain or causal, without speculative, prescaled_q and stats";
 
-// the cache side of fa_fwd_launch_varlen_kvcache: fa_decode_launch's rules for the same fields (kv and vq: already validated)
-int64_t kvcache_capacity(const fa_kvcache_layout *kc) { return kc->block_table ? kc->max_pages_per_seq * kc->page_size : kc->seqlen_cache; }
-int kvcache_validate(const fa_kvcache_layout *kc, const fa_kv_layout *kv, const fa_varlen_layout *vq) {
+// the cache side of fa_fwd_launch_varlen_kvcache and its fp8 form (`sc`): `c` already holds kv's strides and heads and vq's n_seqs,
+// all validated; each struct is read once its own struct_size has passed
+int kvcache_validate(CacheView &c, const fa_kvcache_layout *kc, const fa_kvcache_fp8_scales *sc) {
     if (kc->struct_size < sizeof(fa_kvcache_layout))
         return fail(FA_ERR_SHAPE, "fa_kvcache_layout.struct_size (%u) is smaller than this library's (%zu)", kc->struct_size,
                     sizeof(fa_kvcache_layout));
-    if (!kc->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to n_seqs int32 lengths is needed");
-    if (kc->block_table) {
-        if (kc->page_size <= 0 || kc->num_pages <= 0 || kc->max_pages_per_seq <= 0)
-            return fail(FA_ERR_SHAPE, "paged cache: num_pages, page_size and max_pages_per_seq must be positive");
-        if (kc->page_size % 64 != 0)
-            return fail(FA_ERR_NO_KERNEL, "paged cache: page_size must be a multiple of 64 (got %lld)", (long long)kc->page_size);
-        if (kc->block_table_stride < kc->max_pages_per_seq)
-            return fail(FA_ERR_SHAPE, "block_table_stride (%lld) is smaller than max_pages_per_seq (%lld)", (long long)kc->block_table_stride,
-                        (long long)kc->max_pages_per_seq);
-        if (kc->num_pages > INT32_MAX / 2 || kc->page_size > INT32_MAX / 2 || kc->max_pages_per_seq > INT32_MAX / 2 ||
-            kc->block_table_stride > INT32_MAX / 2)
-            return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
-    } else if (kc->seqlen_cache <= 0) {
-        return fail(FA_ERR_SHAPE, "seqlen_cache must be positive (got %lld)", (long long)kc->seqlen_cache);
-    } else if (kc->batch != vq->n_seqs) {
+    cache_geometry(c, *kc);
+    c.max_seqlen_k = kc->max_seqlen_k;
+    c.words_4b = "cache_seqlens and block_table";
+    if (!c.cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to n_seqs int32 lengths is needed");
+    int rc = cache_sizes(c);
+    if (rc != FA_OK) return rc;
+    // (the two rules only this path has, where it has always asked them: its kernel keeps the table's stride in 32 bits, and its
+    // contiguous cache has a batch size of its own to compare)
+    if (c.paged() && c.block_table_stride > INT32_MAX / 2) return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
+    if (!c.paged() && kc->batch != c.entries)
         return fail(FA_ERR_SHAPE, "a contiguous cache needs one batch entry per sequence: batch (%lld) must equal n_seqs (%lld)",
-                    (long long)kc->batch, (long long)vq->n_seqs);
-    }
-    const int64_t cap = kvcache_capacity(kc);
-    if (cap > INT32_MAX / 2) return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
-    if (kc->max_seqlen_k < 0 || kc->max_seqlen_k > cap)
-        return fail(FA_ERR_SHAPE, "max_seqlen_k (%lld) must lie in [0, %lld] (0 = the cache's capacity)", (long long)kc->max_seqlen_k, (long long)cap);
-    const int64_t entries = kc->block_table ? kc->num_pages : vq->n_seqs;
-    if (kv->kv_batch_stride < 0 || (entries > 1 && kv->kv_batch_stride == 0))
-        return fail(FA_ERR_SHAPE, "kv strides must be positive (the cache's %s stride is %lld elements)", kc->block_table ? "page" : "batch",
-                    (long long)kv->kv_batch_stride);
-    if (kv->kv_batch_stride & 7) return fail(FA_ERR_ALIGN, "kv strides must be multiples of 8 elements (16 bytes)");
-    if (((uintptr_t)kc->cache_seqlens | (uintptr_t)kc->block_table) & 3)
-        return fail(FA_ERR_ALIGN, "cache_seqlens and block_table must be 4-byte aligned");
-    return FA_OK;
-}
-
-// the fp8 side of fa_fwd_launch_varlen_kvcache_fp8: fa_decode_fp8_launch's rules for the same fields (kv: already validated as a
-// 16-bit cache's, whose rules for sign and size hold for bytes too)
-int kvcache_fp8_validate(const fa_kvcache_fp8_scales *sc, const fa_kv_layout *kv) {
+                    (long long)kc->batch, (long long)c.entries);
+    if ((rc = cache_bounds(c)) != FA_OK) return rc;
+    // (the token and head strides passed the packed tensors' rules in fwd_launch_varlen: what is left is the first stride)
+    if (c.kv_bs < 0 || (c.slots() > 1 && c.kv_bs == 0))
+        return fail(FA_ERR_SHAPE, "kv strides must be positive (the cache's %s stride is %lld elements)", c.paged() ? "page" : "batch",
+                    (long long)c.kv_bs);
+    if (c.kv_bs & 7) return fail(FA_ERR_ALIGN, "kv strides must be multiples of 8 elements (16 bytes)");
+    if ((rc = cache_alignment(c)) != FA_OK || !sc) return rc;
     if (sc->struct_size < sizeof(fa_kvcache_fp8_scales))
         return fail(FA_ERR_SHAPE, "fa_kvcache_fp8_scales.struct_size (%u) is smaller than this library's (%zu)", sc->struct_size,
                     sizeof(fa_kvcache_fp8_scales));
     if (sc->kv_dtype != FA_KV_FP8_E4M3FN)
         return fail(FA_ERR_DTYPE, "kv_dtype (%d) is not served: the fp8 cache is e4m3fn (FA_KV_FP8_E4M3FN)", sc->kv_dtype);
-    if ((sc->k_descale || sc->v_descale) && sc->descale_batch_stride < kv->n_kv_heads)
-        return fail(FA_ERR_SHAPE, "descale_batch_stride (%lld) is smaller than n_kv_heads (%lld)", (long long)sc->descale_batch_stride,
-                    (long long)kv->n_kv_heads);
-    // (the strides' multiple of 16 bytes: checked in fwd_launch_varlen, in front of the rules worded in elements)
-    if (((uintptr_t)sc->k_descale | (uintptr_t)sc->v_descale) & 3) return fail(FA_ERR_ALIGN, "k_descale and v_descale must be 4-byte aligned");
-    return FA_OK;
+    cache_descales(c, *sc);
+    if ((rc = cache_descale_stride(c)) != FA_OK) return rc;
+    return cache_descale_alignment(c);
 }
 
 // the forward of `entry` (a public entry point; `total`: its name for the query side's total)
@@ -1087,15 +1179,20 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
                     (long long)args->n_heads);
     if ((rc = check_strides_varlen("q", args->n_heads, args->seq_stride, args->head_stride)) != FA_OK) return rc;
     // (an fp8 cache's strides count bytes: its own alignment rule first, so that no message about elements is reached with one)
-    if (fp8_side && ((kv->kv_batch_stride | kv->kv_seq_stride | kv->kv_head_stride) & 15))
-        return fail(FA_ERR_ALIGN, "kv strides of an fp8 cache must be multiples of 16 bytes");
+    CacheView cache;   // (kv's and vq's part now; the layout's and the scales' in kvcache_validate, behind their struct_size)
+    cache.entries = vq->n_seqs;
+    cache.n_kv_heads = kv->n_kv_heads;
+    cache.kv_bs = kv->kv_batch_stride;
+    cache.kv_ss = kv->kv_seq_stride;
+    cache.kv_hs = kv->kv_head_stride;
+    cache.fp8 = fp8_side;
+    if ((rc = cache_fp8_strides(cache)) != FA_OK) return rc;
     if ((rc = check_strides_varlen(fp8_side ? "kv (fp8 cache: bytes for elements)" : "kv", kv->n_kv_heads, kv->kv_seq_stride, kv->kv_head_stride)) != FA_OK) return rc;
     if ((rc = varlen_grid_check(vq, args->n_heads)) != FA_OK) return rc;
     if (((uintptr_t)args->q | (uintptr_t)args->k | (uintptr_t)args->v | (uintptr_t)args->o) & 15)
         return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
     if ((uintptr_t)lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
-    if (cache_side && (rc = kvcache_validate(kc, kv, vq)) != FA_OK) return rc;
-    if (fp8_side && (rc = kvcache_fp8_validate(sc, kv)) != FA_OK) return rc;
+    if (cache_side && (rc = kvcache_validate(cache, kc, fp8_side ? sc : nullptr)) != FA_OK) return rc;
     if (vq->total_tokens == 0) {   // (no query rows: nothing to write)
         if (o.ms) *o.ms = 0.0f;
         return FA_OK;
@@ -1135,27 +1232,27 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
     const void *fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kernel_dt15(fbs) : (const void *)fa::varlen_kernel_dt5(fbs);
     void *kernel_args = &qa;
     if (cache_side) {
-        const int64_t cap = kvcache_capacity(kc);
-        ca.cache_seqlens = kc->cache_seqlens;
-        ca.block_table = kc->block_table;
+        const int64_t cap = cache.capacity();
+        ca.cache_seqlens = cache.cache_seqlens;
+        ca.block_table = cache.block_table;
         ca.page_stride = kv->kv_batch_stride;
-        ca.bt_stride = kc->block_table ? (int32_t)kc->block_table_stride : 0;
-        ca.num_pages = kc->block_table ? (int32_t)kc->num_pages : (int32_t)vq->n_seqs;
-        ca.tiles_per_page = (int32_t)(kc->block_table ? kc->page_size / 64 : (cap + 63) / 64);   // (contiguous: one "page" per entry)
-        ca.max_len = (int32_t)(kc->max_seqlen_k > 0 ? kc->max_seqlen_k : cap);
+        ca.bt_stride = cache.paged() ? (int32_t)cache.block_table_stride : 0;
+        ca.num_pages = (int32_t)cache.slots();
+        ca.tiles_per_page = (int32_t)(cache.paged() ? cache.page_size / 64 : (cap + 63) / 64);   // (contiguous: one "page" per entry)
+        ca.max_len = (int32_t)(cache.max_seqlen_k > 0 ? cache.max_seqlen_k : cap);
         fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kvcache_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_kernel_dt5(fbs);
         kernel_args = &ca;
     }
     if (fp8_side) {
-        fa8.k_descale = sc->k_descale;
-        fa8.v_descale = sc->v_descale;
-        fa8.ds_bs = sc->descale_batch_stride;
+        fa8.k_descale = cache.k_descale;
+        fa8.v_descale = cache.v_descale;
+        fa8.ds_bs = cache.descale_bs;
         fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kvcache_fp8_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_fp8_kernel_dt5(fbs);
         kernel_args = &fa8;
     }
     const dim3 grid((unsigned)(va.base.n_bh * va.base.n_q_blocks)), block((unsigned)e->threads);
     const hipStream_t s = (hipStream_t)stream;
-    return bwd_run([&] {
+    return enqueue_timed([&] {
         void *params[] = {kernel_args};
         return hipLaunchKernel(fn, grid, block, params, (size_t)e->lds_bytes, s);
     }, s, o.ms);
@@ -1349,7 +1446,7 @@ int fa_bwd_launch_varlen(const fa_bwd_varlen_args *args, void *stream, float *ms
     bwd_varlen_fill(both, a);
     const fa::BwdVarlenArgs va = one_range(both);
     const hipStream_t s = (hipStream_t)stream;
-    return bwd_run([&] { return fa::bwd_varlen_enqueue(va, a->dtype, a->causal != 0, s); }, s, ms);
+    return enqueue_timed([&] { return fa::bwd_varlen_enqueue(va, a->dtype, a->causal != 0, s); }, s, ms);
 }
 
 int fa_bwd_launch_varlen_qk(const fa_bwd_varlen_qk_args *a, void *stream, float *ms) {
@@ -1364,29 +1461,61 @@ int fa_bwd_launch_varlen_qk(const fa_bwd_varlen_qk_args *a, void *stream, float 
     fa::BwdVarlenQKArgs va;
     bwd_varlen_fill(va, a);
     const hipStream_t s = (hipStream_t)stream;
-    return bwd_run([&] { return fa::bwd_varlen_qk_enqueue(va, a->dtype, a->causal != 0, s); }, s, ms);
+    return enqueue_timed([&] { return fa::bwd_varlen_qk_enqueue(va, a->dtype, a->causal != 0, s); }, s, ms);
 }
 
 // ---- KV-cache decode ------------------------------------------------------------------------------------------------------
+// fa_decode_args and fa_decode_fp8_args carry the same members under the same names (the fp8 struct adds its encoding and
+// descales), so one text over either struct serves the sixteen entry points: a planner (validate, then the split count) for the
+// twelve queries and one launch body for the four launches.  What only one struct has sits in the two decode_struct_rules.
 namespace {
+extern "C++" {   // (as for the cache's rules above; the two overloads need it as well)
 constexpr int64_t kDecodeMaxRows = 64, kDecodeWantWgs = 256, kDecodeKeysPerSplit = 256, kDecodeMaxSplits = 128, kDecodeMaxForced = 1024;
 
-int64_t decode_capacity(const fa_decode_args *a) { return a->block_table ? a->max_pages_per_seq * a->page_size : a->seqlen_cache; }
-
-// one stride set of the decode path: positive multiples of 8 elements (the kernels form 64-bit offsets)
-int decode_strides(const char *which, int64_t n0, int64_t n1, int64_t n2, int64_t bs, int64_t ss, int64_t hs) {
-    if (ss <= 0 || bs < 0 || hs < 0 || (n0 > 1 && bs == 0) || (n2 > 1 && hs == 0) || (n1 > 1 && ss == 0))
-        return fail(FA_ERR_SHAPE, "%s strides must be positive (batch %lld, seq %lld, head %lld elements)", which, (long long)bs,
-                    (long long)ss, (long long)hs);
-    if ((bs | ss | hs) & 7) return fail(FA_ERR_ALIGN, "%s strides must be multiples of 8 elements (16 bytes)", which);
+int decode_struct_rules(const fa_decode_args *a, CacheView &) {
+    if (a->struct_size < sizeof(fa_decode_args))
+        return fail(FA_ERR_SHAPE, "fa_decode_args.struct_size (%u) is smaller than this library's (%zu)", a->struct_size, sizeof(fa_decode_args));
+    return FA_OK;
+}
+int decode_struct_rules(const fa_decode_fp8_args *a, CacheView &c) {
+    if (a->struct_size < sizeof(fa_decode_fp8_args))
+        return fail(FA_ERR_SHAPE, "fa_decode_fp8_args.struct_size (%u) is smaller than this library's (%zu)", a->struct_size,
+                    sizeof(fa_decode_fp8_args));
+    if (a->kv_dtype != FA_KV_FP8_E4M3FN)
+        return fail(FA_ERR_DTYPE, "kv_dtype (%d) is not served: the fp8 cache is e4m3fn (FA_KV_FP8_E4M3FN)", a->kv_dtype);
+    c.fp8 = true;
+    cache_descales(c, *a);
     return FA_OK;
 }
 
-// everything but the pointers' values: dtype, kernel, sizes, strides -- in the order of the statuses' numbers
-int decode_validate(const fa_decode_args *a) {
+int window_right(const fa_window *w, int causal) { return causal ? 0 : w->right; }
+
+// (called behind decode_validate: the cache is valid)
+int window_validate(const fa_window *w, int causal, const CacheView &c) {
+    if (!w) return fail(FA_ERR_NULL, "fa_window is null: (left, right) is needed (-1 = unbounded; the unwindowed entry point takes none)");
+    if (w->struct_size < sizeof(fa_window))
+        return fail(FA_ERR_SHAPE, "fa_window.struct_size (%u) is smaller than this library's (%zu)", w->struct_size, sizeof(fa_window));
+    if (w->left < -1 || w->right < -1)
+        return fail(FA_ERR_SHAPE, "window (%d, %d): left and right must be -1 (unbounded) or not negative", w->left, w->right);
+    if (causal && w->right > 0)
+        return fail(FA_ERR_SHAPE, "causal means right = 0: a window with right = %d cannot be causal as well (pass right = -1 or 0)", w->right);
+    // (the kernel adds a row's position and its clamped distances in 32 bits: fa_decode_kernel.hpp)
+    if (c.capacity() > (1 << 30) - 128) return fail(FA_ERR_SHAPE, "cache too large for a window: at most 2^30 - 128 keys per entry");
+    return FA_OK;
+}
+
+struct DecodePlan {
+    int status = FA_OK;
+    int64_t splits = 0;
+    CacheView cache;
+};
+int plan_splits(const DecodePlan &p) { return p.status != FA_OK ? p.status : (int)p.splits; }
+
+// everything but the pointers' values: dtype, kernel, sizes, strides -- in the order of the statuses' numbers; fills `c`
+template <class A> int decode_validate(const A *a, CacheView &c) {
     if (!a) return fail(FA_ERR_NULL, "null pointer argument");
-    if (a->struct_size < sizeof(fa_decode_args))
-        return fail(FA_ERR_SHAPE, "fa_decode_args.struct_size (%u) is smaller than this library's (%zu)", a->struct_size, sizeof(fa_decode_args));
+    int rc = decode_struct_rules(a, c);
+    if (rc != FA_OK) return rc;
     if (a->dtype != FA_FP16 && a->dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
     if (a->d_head != 128) return fail(FA_ERR_SHAPE, "decode supports d_head = 128 only (got %lld)", (long long)a->d_head);
     if (a->batch < 0 || a->seqlen_q <= 0 || a->n_heads <= 0) return fail(FA_ERR_SHAPE, "batch must not be negative, seqlen_q and n_heads must be positive");
@@ -1398,69 +1527,69 @@ int decode_validate(const fa_decode_args *a) {
     if (a->seqlen_q > kDecodeMaxRows || a->seqlen_q * group > kDecodeMaxRows)
         return fail(FA_ERR_NO_KERNEL, "decode serves seqlen_q * (n_heads / n_kv_heads) <= 64 packed query rows (got %lld * %lld): use the "
                                       "forward entry points for longer queries", (long long)a->seqlen_q, (long long)group);
-    if (a->block_table) {
-        if (a->page_size <= 0 || a->num_pages <= 0 || a->max_pages_per_seq <= 0)
-            return fail(FA_ERR_SHAPE, "paged cache: num_pages, page_size and max_pages_per_seq must be positive");
-        if (a->page_size % 64 != 0)
-            return fail(FA_ERR_NO_KERNEL, "paged cache: page_size must be a multiple of 64 (got %lld)", (long long)a->page_size);
-        if (a->block_table_stride < a->max_pages_per_seq)
-            return fail(FA_ERR_SHAPE, "block_table_stride (%lld) is smaller than max_pages_per_seq (%lld)", (long long)a->block_table_stride,
-                        (long long)a->max_pages_per_seq);
-        if (a->num_pages > INT32_MAX / 2 || a->page_size > INT32_MAX / 2 || a->max_pages_per_seq > INT32_MAX / 2)
-            return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
-    } else if (a->seqlen_cache <= 0) {
-        return fail(FA_ERR_SHAPE, "seqlen_cache must be positive (got %lld)", (long long)a->seqlen_cache);
-    }
-    const int64_t cap = decode_capacity(a);
-    if (cap > INT32_MAX / 2) return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
-    if (a->max_seqlen_k < 0 || a->max_seqlen_k > cap)
-        return fail(FA_ERR_SHAPE, "max_seqlen_k (%lld) must lie in [0, %lld] (0 = the cache's capacity)", (long long)a->max_seqlen_k, (long long)cap);
+    cache_tensors(c, *a);
+    c.max_seqlen_k = a->max_seqlen_k;
+    c.words_4b = "cache_seqlens, block_table and lse";
+    if ((rc = cache_sizes(c)) != FA_OK || (rc = cache_bounds(c)) != FA_OK) return rc;
     if (a->num_splits < 0 || a->num_splits > kDecodeMaxForced)
         return fail(FA_ERR_SHAPE, "num_splits (%d) must lie in [0, %lld] (0 = the split rule)", a->num_splits, (long long)kDecodeMaxForced);
-    int rc = decode_strides("q", a->batch, a->seqlen_q, a->n_heads, a->q_batch_stride, a->q_seq_stride, a->q_head_stride);
-    if (rc != FA_OK) return rc;
-    if ((rc = decode_strides("o", a->batch, a->seqlen_q, a->n_heads, a->o_batch_stride, a->o_seq_stride, a->o_head_stride)) != FA_OK) return rc;
-    if ((rc = decode_strides("kv", a->block_table ? a->num_pages : a->batch, cap, a->n_kv_heads, a->kv_batch_stride, a->kv_seq_stride,
-                             a->kv_head_stride)) != FA_OK)
-        return rc;
+    if ((rc = stride_set("q", 8, a->batch, a->seqlen_q, a->n_heads, a->q_batch_stride, a->q_seq_stride, a->q_head_stride)) != FA_OK) return rc;
+    if ((rc = stride_set("o", 8, a->batch, a->seqlen_q, a->n_heads, a->o_batch_stride, a->o_seq_stride, a->o_head_stride)) != FA_OK) return rc;
+    if ((rc = cache_strides(c, 8)) != FA_OK) return rc;
     if (a->batch * a->n_kv_heads * kDecodeMaxForced > INT32_MAX || a->batch * a->n_heads * a->seqlen_q > INT32_MAX)
         return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
-    return FA_OK;
+    if ((rc = cache_descale_stride(c)) != FA_OK) return rc;   // (the fp8 side's two: nothing to refuse in a 16-bit cache)
+    return cache_fp8_strides(c);
 }
 
 // The split rule: a pure function of batch, n_kv_heads and the host's key bound.  The smallest power of two that gives
 // the grid one workgroup per CU of an MI355X (256, the count the GQA backward's split uses), while a split keeps at
-// least 256 keys of the bound, at most 128.
-int64_t decode_key_bound(const fa_decode_args *a) { return a->max_seqlen_k > 0 ? a->max_seqlen_k : decode_capacity(a); }
-int64_t decode_splits_for(const fa_decode_args *a, int64_t max_k) {
+// least 256 keys of the bound, at most 128.  With a window the bound is the keys a workgroup can visit, left + seqlen_q +
+// right, when both sides are bounded (and that is less).
+template <class A> int64_t decode_splits(const A *a, const CacheView &c, const fa_window *w) {
     if (a->num_splits > 0) return a->num_splits;
+    int64_t max_k = c.max_seqlen_k > 0 ? c.max_seqlen_k : c.capacity();
+    if (w && w->left >= 0 && window_right(w, a->causal) >= 0) {
+        const int64_t span = (int64_t)w->left + a->seqlen_q + window_right(w, a->causal);
+        max_k = span < max_k ? span : max_k;
+    }
     int64_t s = 1;
     while (a->batch * a->n_kv_heads * s < kDecodeWantWgs && s < kDecodeMaxSplits) s *= 2;
     const int64_t by_keys = (max_k + kDecodeKeysPerSplit - 1) / kDecodeKeysPerSplit;
     return s < by_keys ? s : (by_keys < 1 ? 1 : by_keys);
 }
-int64_t decode_splits(const fa_decode_args *a) { return decode_splits_for(a, decode_key_bound(a)); }
 
-int64_t decode_part_o_bytes(const fa_decode_args *a, int64_t splits) {
+// The planner of every decode entry point: the arguments (either struct) and, for a window form, its fa_window (null is refused
+// there) -> status, split count and the cache as validated.
+template <class A> DecodePlan decode_plan(const A *a, bool windowed, const fa_window *w) {
+    DecodePlan p;
+    p.status = decode_validate(a, p.cache);
+    if (p.status == FA_OK && windowed) p.status = window_validate(w, a->causal, p.cache);
+    if (p.status == FA_OK) p.splits = decode_splits(a, p.cache, windowed ? w : nullptr);
+    return p;
+}
+
+template <class A> int64_t decode_part_o_bytes(const A *a, int64_t splits) {
     return (int64_t)sizeof(float) * splits * a->batch * a->n_kv_heads * (a->seqlen_q * (a->n_heads / a->n_kv_heads)) * 128;
 }
 
-// fa_decode_workspace_bytes for a split count: the fp32 partial o (a multiple of 512 bytes), then the partial lse
-int64_t decode_workspace(const fa_decode_args *a, int64_t splits) {
-    if (splits == 1) return 0;
-    const int64_t po = decode_part_o_bytes(a, splits);
+// the workspace of a plan: the fp32 partial o (a multiple of 512 bytes), then the partial lse; none for one split
+template <class A> int64_t plan_workspace(const A *a, const DecodePlan &p) {
+    if (p.status != FA_OK) return p.status;
+    if (p.splits == 1) return 0;
+    const int64_t po = decode_part_o_bytes(a, p.splits);
     return po + ((po / 128 + 15) & ~(int64_t)15);
 }
 
 // the kernels' arguments from validated ones
-void decode_fill(fa::DecodeArgs &d, const fa_decode_args *a, int64_t splits) {
+template <class A> void decode_fill(fa::DecodeArgs &d, const A *a, const CacheView &c, int64_t splits) {
     d.q = (const uint16_t *)a->q;
     d.k = (const uint16_t *)a->k;
     d.v = (const uint16_t *)a->v;
     d.o = (uint16_t *)a->o;
     d.lse = a->lse;
-    d.cache_seqlens = a->cache_seqlens;
-    d.block_table = a->block_table;
+    d.cache_seqlens = c.cache_seqlens;
+    d.block_table = c.block_table;
     d.part_o = splits > 1 ? (float *)a->workspace : nullptr;
     d.part_lse = splits > 1 ? (float *)((char *)a->workspace + decode_part_o_bytes(a, splits)) : nullptr;
     d.q_bs = a->q_batch_stride;
@@ -1469,274 +1598,100 @@ void decode_fill(fa::DecodeArgs &d, const fa_decode_args *a, int64_t splits) {
     d.o_bs = a->o_batch_stride;
     d.o_ss = a->o_seq_stride;
     d.o_hs = a->o_head_stride;
-    d.kv_bs = a->kv_batch_stride;
-    d.kv_ss = a->kv_seq_stride;
-    d.kv_hs = a->kv_head_stride;
-    d.bt_bs = a->block_table ? a->block_table_stride : 0;
+    d.kv_bs = c.kv_bs;
+    d.kv_ss = c.kv_ss;
+    d.kv_hs = c.kv_hs;
+    d.bt_bs = c.paged() ? c.block_table_stride : 0;
     d.batch = (int32_t)a->batch;
     d.seqlen_q = (int32_t)a->seqlen_q;
     d.n_heads = (int32_t)a->n_heads;
     d.n_kv_heads = (int32_t)a->n_kv_heads;
     d.group = (int32_t)(a->n_heads / a->n_kv_heads);
     d.rows = d.seqlen_q * d.group;
-    d.max_len = (int32_t)decode_capacity(a);
-    d.page_size = a->block_table ? (int32_t)a->page_size : 0;
-    d.num_pages = a->block_table ? (int32_t)a->num_pages : 0;
+    d.max_len = (int32_t)c.capacity();
+    d.page_size = c.paged() ? (int32_t)c.page_size : 0;
+    d.num_pages = c.paged() ? (int32_t)c.num_pages : 0;
     d.num_splits = (int32_t)splits;
     d.causal = a->causal != 0;
 }
 
-// ---- ... against an fp8 cache: fa_decode_args' leading fields, validated as such, and the fp8 rules ------------------------
-static_assert(offsetof(fa_decode_fp8_args, kv_head_stride) == offsetof(fa_decode_args, kv_head_stride) &&
-              offsetof(fa_decode_fp8_args, k_descale) == sizeof(fa_decode_args), "fa_decode_fp8_args begins with fa_decode_args' fields");
-
-int decode_fp8_validate(const fa_decode_fp8_args *a, fa_decode_args *base) {
+// The launch of all four forms; `ws_query`: the entry point's workspace query, for its message.
+template <class A> int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_query, void *stream, float *ms) {
     if (!a) return fail(FA_ERR_NULL, "null pointer argument");
-    if (a->struct_size < sizeof(fa_decode_fp8_args))
-        return fail(FA_ERR_SHAPE, "fa_decode_fp8_args.struct_size (%u) is smaller than this library's (%zu)", a->struct_size,
-                    sizeof(fa_decode_fp8_args));
-    if (a->kv_dtype != FA_KV_FP8_E4M3FN)
-        return fail(FA_ERR_DTYPE, "kv_dtype (%d) is not served: the fp8 cache is e4m3fn (FA_KV_FP8_E4M3FN)", a->kv_dtype);
-    memcpy(base, a, sizeof(fa_decode_args));
-    base->struct_size = sizeof(fa_decode_args);
-    const int rc = decode_validate(base);
+    if (!a->q || !a->k || !a->v || !a->o) return fail(FA_ERR_NULL, "null tensor pointer (q, k, v and o are all needed)");
+    if (!a->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to batch int32 lengths is needed");
+    const DecodePlan p = decode_plan(a, windowed, w);
+    if (p.status != FA_OK) return p.status;
+    if (a->batch == 0) {
+        if (ms) *ms = 0.0f;
+        return FA_OK;
+    }
+    const CacheView &c = p.cache;
+    if (p.splits > 1 && !a->workspace)
+        return fail(FA_ERR_NULL, "workspace is null: allocate %s(%s) bytes of device memory", ws_query, windowed ? "args, window" : "args");
+    if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) & 15) return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
+    int rc = cache_alignment(c, (uintptr_t)a->lse);
     if (rc != FA_OK) return rc;
-    if ((a->k_descale || a->v_descale) && a->descale_batch_stride < a->n_kv_heads)
-        return fail(FA_ERR_SHAPE, "descale_batch_stride (%lld) is smaller than n_kv_heads (%lld)", (long long)a->descale_batch_stride,
-                    (long long)a->n_kv_heads);
-    if ((a->kv_batch_stride | a->kv_seq_stride | a->kv_head_stride) & 15)
-        return fail(FA_ERR_ALIGN, "kv strides of an fp8 cache must be multiples of 16 bytes");
-    return FA_OK;
+    // (fa_decode_fp8_launch asks the descales' alignment in front of the workspace's, its window form behind it: both orders kept)
+    if (!windowed && (rc = cache_descale_alignment(c)) != FA_OK) return rc;
+    if (p.splits > 1 && ((uintptr_t)a->workspace & 15)) return fail(FA_ERR_ALIGN, "workspace must be 16-byte aligned (it holds the splits' fp32 partials)");
+    if (windowed && (rc = cache_descale_alignment(c)) != FA_OK) return rc;
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    fa::DecodeFp8WindowArgs k;   // (the widest form: the other three's arguments are its members)
+    decode_fill(k.f.d, a, c, p.splits);
+    k.f.k_descale = c.k_descale;
+    k.f.v_descale = c.v_descale;
+    k.f.ds_bs = c.descale_bs;
+    k.left = windowed ? w->left : -1;
+    k.right = windowed ? window_right(w, a->causal) : -1;
+    const fa::DecodeWindowArgs kw = {k.f.d, k.left, k.right};
+    const hipStream_t s = (hipStream_t)stream;
+    return enqueue_timed([&] {
+        if (c.fp8) return windowed ? fa::decode_fp8_window_enqueue(k, a->dtype, s) : fa::decode_fp8_enqueue(k.f, a->dtype, s);
+        return windowed ? fa::decode_window_enqueue(kw, a->dtype, s) : fa::decode_enqueue(k.f.d, a->dtype, s);
+    }, s, ms);
+}
 }
 }  // namespace
 
-int fa_decode_supported(const fa_decode_args *a) { return decode_validate(a) == FA_OK ? 1 : 0; }
-
-int fa_decode_num_splits(const fa_decode_args *a) {
-    const int rc = decode_validate(a);
-    return rc != FA_OK ? rc : (int)decode_splits(a);
-}
-
-int64_t fa_decode_workspace_bytes(const fa_decode_args *a) {
-    const int rc = decode_validate(a);
-    if (rc != FA_OK) return rc;
-    return decode_workspace(a, decode_splits(a));
-}
-
+int fa_decode_supported(const fa_decode_args *a) { return decode_plan(a, false, nullptr).status == FA_OK; }
+int fa_decode_num_splits(const fa_decode_args *a) { return plan_splits(decode_plan(a, false, nullptr)); }
+int64_t fa_decode_workspace_bytes(const fa_decode_args *a) { return plan_workspace(a, decode_plan(a, false, nullptr)); }
 int fa_decode_launch(const fa_decode_args *a, void *stream, float *ms) {
-    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
-    if (!a->q || !a->k || !a->v || !a->o) return fail(FA_ERR_NULL, "null tensor pointer (q, k, v and o are all needed)");
-    if (!a->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to batch int32 lengths is needed");
-    int rc = decode_validate(a);
-    if (rc != FA_OK) return rc;
-    if (a->batch == 0) {
-        if (ms) *ms = 0.0f;
-        return FA_OK;
-    }
-    const int64_t splits = decode_splits(a);
-    if (splits > 1 && !a->workspace)
-        return fail(FA_ERR_NULL, "workspace is null: allocate fa_decode_workspace_bytes(args) bytes of device memory");
-    if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) & 15) return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
-    if (((uintptr_t)a->cache_seqlens | (uintptr_t)a->block_table | (uintptr_t)a->lse) & 3)
-        return fail(FA_ERR_ALIGN, "cache_seqlens, block_table and lse must be 4-byte aligned");
-    if (splits > 1 && ((uintptr_t)a->workspace & 15)) return fail(FA_ERR_ALIGN, "workspace must be 16-byte aligned (it holds the splits' fp32 partials)");
-    DeviceState *dev = current_device(&rc);
-    if (!dev) return rc;
-    fa::DecodeArgs d;
-    decode_fill(d, a, splits);
-    const hipStream_t s = (hipStream_t)stream;
-    return bwd_run([&] { return fa::decode_enqueue(d, a->dtype, s); }, s, ms);
+    return decode_launch(a, false, nullptr, "fa_decode_workspace_bytes", stream, ms);
 }
 
-int fa_decode_fp8_supported(const fa_decode_fp8_args *a) {
-    fa_decode_args base;
-    return decode_fp8_validate(a, &base) == FA_OK ? 1 : 0;
-}
-
-int fa_decode_fp8_num_splits(const fa_decode_fp8_args *a) {
-    fa_decode_args base;
-    const int rc = decode_fp8_validate(a, &base);
-    return rc != FA_OK ? rc : (int)decode_splits(&base);
-}
-
-int64_t fa_decode_fp8_workspace_bytes(const fa_decode_fp8_args *a) {
-    fa_decode_args base;
-    const int rc = decode_fp8_validate(a, &base);
-    return rc != FA_OK ? rc : fa_decode_workspace_bytes(&base);
-}
-
+int fa_decode_fp8_supported(const fa_decode_fp8_args *a) { return decode_plan(a, false, nullptr).status == FA_OK; }
+int fa_decode_fp8_num_splits(const fa_decode_fp8_args *a) { return plan_splits(decode_plan(a, false, nullptr)); }
+int64_t fa_decode_fp8_workspace_bytes(const fa_decode_fp8_args *a) { return plan_workspace(a, decode_plan(a, false, nullptr)); }
 int fa_decode_fp8_launch(const fa_decode_fp8_args *a, void *stream, float *ms) {
-    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
-    if (!a->q || !a->k || !a->v || !a->o) return fail(FA_ERR_NULL, "null tensor pointer (q, k, v and o are all needed)");
-    if (!a->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to batch int32 lengths is needed");
-    fa_decode_args base;
-    int rc = decode_fp8_validate(a, &base);
-    if (rc != FA_OK) return rc;
-    if (a->batch == 0) {
-        if (ms) *ms = 0.0f;
-        return FA_OK;
-    }
-    const int64_t splits = decode_splits(&base);
-    if (splits > 1 && !a->workspace)
-        return fail(FA_ERR_NULL, "workspace is null: allocate fa_decode_fp8_workspace_bytes(args) bytes of device memory");
-    if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) & 15) return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
-    if (((uintptr_t)a->cache_seqlens | (uintptr_t)a->block_table | (uintptr_t)a->lse) & 3)
-        return fail(FA_ERR_ALIGN, "cache_seqlens, block_table and lse must be 4-byte aligned");
-    if (((uintptr_t)a->k_descale | (uintptr_t)a->v_descale) & 3) return fail(FA_ERR_ALIGN, "k_descale and v_descale must be 4-byte aligned");
-    if (splits > 1 && ((uintptr_t)a->workspace & 15)) return fail(FA_ERR_ALIGN, "workspace must be 16-byte aligned (it holds the splits' fp32 partials)");
-    DeviceState *dev = current_device(&rc);
-    if (!dev) return rc;
-    fa::DecodeFp8Args d;
-    decode_fill(d.d, &base, splits);
-    d.k_descale = a->k_descale;
-    d.v_descale = a->v_descale;
-    d.ds_bs = a->descale_batch_stride;
-    const hipStream_t s = (hipStream_t)stream;
-    return bwd_run([&] { return fa::decode_fp8_enqueue(d, a->dtype, s); }, s, ms);
+    return decode_launch(a, false, nullptr, "fa_decode_fp8_workspace_bytes", stream, ms);
 }
 
-// ---- ... with a sliding window: the two decodes' arguments and rules, and fa_window ---------------------------------------------
-namespace {
-// (called behind decode_validate: `a` is valid)
-int window_validate(const fa_window *w, const fa_decode_args *a) {
-    const int causal = a->causal;
-    if (!w) return fail(FA_ERR_NULL, "fa_window is null: (left, right) is needed (-1 = unbounded; the unwindowed entry point takes none)");
-    if (w->struct_size < sizeof(fa_window))
-        return fail(FA_ERR_SHAPE, "fa_window.struct_size (%u) is smaller than this library's (%zu)", w->struct_size, sizeof(fa_window));
-    if (w->left < -1 || w->right < -1)
-        return fail(FA_ERR_SHAPE, "window (%d, %d): left and right must be -1 (unbounded) or not negative", w->left, w->right);
-    if (causal && w->right > 0)
-        return fail(FA_ERR_SHAPE, "causal means right = 0: a window with right = %d cannot be causal as well (pass right = -1 or 0)", w->right);
-    // (the kernel adds a row's position and its clamped distances in 32 bits: fa_decode_kernel.hpp)
-    if (decode_capacity(a) > (1 << 30) - 128) return fail(FA_ERR_SHAPE, "cache too large for a window: at most 2^30 - 128 keys per entry");
-    return FA_OK;
-}
-int window_right(const fa_window *w, int causal) { return causal ? 0 : w->right; }
-
-// The split rule with a window: the same rule, its key bound the keys a workgroup can visit, left + seqlen_q + right, when
-// both sides are bounded (and that is less)
-int64_t decode_window_splits(const fa_decode_args *a, const fa_window *w) {
-    int64_t max_k = decode_key_bound(a);
-    const int64_t right = window_right(w, a->causal);
-    if (w->left >= 0 && right >= 0) {
-        const int64_t span = (int64_t)w->left + a->seqlen_q + right;
-        max_k = span < max_k ? span : max_k;
-    }
-    return decode_splits_for(a, max_k);
-}
-
-// fa_decode_launch's checks of the pointers' values
-int decode_pointers(const fa_decode_args *a, int64_t splits, const char *ws_query) {
-    if (splits > 1 && !a->workspace) return fail(FA_ERR_NULL, "workspace is null: allocate %s(args, window) bytes of device memory", ws_query);
-    if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) & 15) return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
-    if (((uintptr_t)a->cache_seqlens | (uintptr_t)a->block_table | (uintptr_t)a->lse) & 3)
-        return fail(FA_ERR_ALIGN, "cache_seqlens, block_table and lse must be 4-byte aligned");
-    if (splits > 1 && ((uintptr_t)a->workspace & 15)) return fail(FA_ERR_ALIGN, "workspace must be 16-byte aligned (it holds the splits' fp32 partials)");
-    return FA_OK;
-}
-}  // namespace
-
-int fa_decode_window_supported(const fa_decode_args *a, const fa_window *w) {
-    return decode_validate(a) == FA_OK && window_validate(w, a) == FA_OK ? 1 : 0;
-}
-
-int fa_decode_window_num_splits(const fa_decode_args *a, const fa_window *w) {
-    int rc = decode_validate(a);
-    if (rc != FA_OK || (rc = window_validate(w, a)) != FA_OK) return rc;
-    return (int)decode_window_splits(a, w);
-}
-
-int64_t fa_decode_window_workspace_bytes(const fa_decode_args *a, const fa_window *w) {
-    int rc = decode_validate(a);
-    if (rc != FA_OK || (rc = window_validate(w, a)) != FA_OK) return rc;
-    return decode_workspace(a, decode_window_splits(a, w));
-}
-
+int fa_decode_window_supported(const fa_decode_args *a, const fa_window *w) { return decode_plan(a, true, w).status == FA_OK; }
+int fa_decode_window_num_splits(const fa_decode_args *a, const fa_window *w) { return plan_splits(decode_plan(a, true, w)); }
+int64_t fa_decode_window_workspace_bytes(const fa_decode_args *a, const fa_window *w) { return plan_workspace(a, decode_plan(a, true, w)); }
 int fa_decode_window_launch(const fa_decode_args *a, const fa_window *w, void *stream, float *ms) {
-    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
-    if (!a->q || !a->k || !a->v || !a->o) return fail(FA_ERR_NULL, "null tensor pointer (q, k, v and o are all needed)");
-    if (!a->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to batch int32 lengths is needed");
-    int rc = decode_validate(a);
-    if (rc != FA_OK || (rc = window_validate(w, a)) != FA_OK) return rc;
-    if (a->batch == 0) {
-        if (ms) *ms = 0.0f;
-        return FA_OK;
-    }
-    const int64_t splits = decode_window_splits(a, w);
-    if ((rc = decode_pointers(a, splits, "fa_decode_window_workspace_bytes")) != FA_OK) return rc;
-    DeviceState *dev = current_device(&rc);
-    if (!dev) return rc;
-    fa::DecodeWindowArgs d;
-    decode_fill(d.d, a, splits);
-    d.left = w->left;
-    d.right = window_right(w, a->causal);
-    const hipStream_t s = (hipStream_t)stream;
-    return bwd_run([&] { return fa::decode_window_enqueue(d, a->dtype, s); }, s, ms);
+    return decode_launch(a, true, w, "fa_decode_window_workspace_bytes", stream, ms);
 }
 
-int fa_decode_fp8_window_supported(const fa_decode_fp8_args *a, const fa_window *w) {
-    fa_decode_args base;
-    return decode_fp8_validate(a, &base) == FA_OK && window_validate(w, &base) == FA_OK ? 1 : 0;
-}
-
-int fa_decode_fp8_window_num_splits(const fa_decode_fp8_args *a, const fa_window *w) {
-    fa_decode_args base;
-    int rc = decode_fp8_validate(a, &base);
-    if (rc != FA_OK || (rc = window_validate(w, &base)) != FA_OK) return rc;
-    return (int)decode_window_splits(&base, w);
-}
-
-int64_t fa_decode_fp8_window_workspace_bytes(const fa_decode_fp8_args *a, const fa_window *w) {
-    fa_decode_args base;
-    int rc = decode_fp8_validate(a, &base);
-    if (rc != FA_OK || (rc = window_validate(w, &base)) != FA_OK) return rc;
-    return decode_workspace(&base, decode_window_splits(&base, w));
-}
-
+int fa_decode_fp8_window_supported(const fa_decode_fp8_args *a, const fa_window *w) { return decode_plan(a, true, w).status == FA_OK; }
+int fa_decode_fp8_window_num_splits(const fa_decode_fp8_args *a, const fa_window *w) { return plan_splits(decode_plan(a, true, w)); }
+int64_t fa_decode_fp8_window_workspace_bytes(const fa_decode_fp8_args *a, const fa_window *w) { return plan_workspace(a, decode_plan(a, true, w)); }
 int fa_decode_fp8_window_launch(const fa_decode_fp8_args *a, const fa_window *w, void *stream, float *ms) {
-    if (!a) return fail(FA_ERR_NULL, "null pointer argument");
-    if (!a->q || !a->k || !a->v || !a->o) return fail(FA_ERR_NULL, "null tensor pointer (q, k, v and o are all needed)");
-    if (!a->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to batch int32 lengths is needed");
-    fa_decode_args base;
-    int rc = decode_fp8_validate(a, &base);
-    if (rc != FA_OK || (rc = window_validate(w, &base)) != FA_OK) return rc;
-    if (a->batch == 0) {
-        if (ms) *ms = 0.0f;
-        return FA_OK;
-    }
-    const int64_t splits = decode_window_splits(&base, w);
-    if ((rc = decode_pointers(&base, splits, "fa_decode_fp8_window_workspace_bytes")) != FA_OK) return rc;
-    if (((uintptr_t)a->k_descale | (uintptr_t)a->v_descale) & 3) return fail(FA_ERR_ALIGN, "k_descale and v_descale must be 4-byte aligned");
-    DeviceState *dev = current_device(&rc);
-    if (!dev) return rc;
-    fa::DecodeFp8WindowArgs d;
-    decode_fill(d.f.d, &base, splits);
-    d.f.k_descale = a->k_descale;
-    d.f.v_descale = a->v_descale;
-    d.f.ds_bs = a->descale_batch_stride;
-    d.left = w->left;
-    d.right = window_right(w, base.causal);
-    const hipStream_t s = (hipStream_t)stream;
-    return bwd_run([&] { return fa::decode_fp8_window_enqueue(d, a->dtype, s); }, s, ms);
+    return decode_launch(a, true, w, "fa_decode_fp8_window_workspace_bytes", stream, ms);
 }
 
 // ---- the KV-cache append in front of a decode --------------------------------------------------------------------------------
 namespace {
-// one stride set of the append: positive where the size asks for it, multiples of `unit` elements (16 bytes)
-int append_strides(const char *which, int64_t unit, int64_t n0, int64_t n1, int64_t n2, int64_t bs, int64_t ss, int64_t hs) {
-    if (ss <= 0 || bs < 0 || hs < 0 || (n0 > 1 && bs == 0) || (n2 > 1 && hs == 0) || (n1 > 1 && ss == 0))
-        return fail(FA_ERR_SHAPE, "%s strides must be positive (batch %lld, seq %lld, head %lld elements)", which, (long long)bs,
-                    (long long)ss, (long long)hs);
-    if ((bs | ss | hs) & (unit - 1)) return fail(FA_ERR_ALIGN, "%s strides must be multiples of %lld elements (16 bytes)", which, (long long)unit);
-    return FA_OK;
-}
-
 // the bytes [p, p + extent) a (n0, n1, n2, 128) tensor of 16-bit elements spans
 int64_t append_extent(int64_t n0, int64_t n1, int64_t n2, int64_t bs, int64_t ss, int64_t hs) {
     return 2 * ((n0 - 1) * bs + (n1 - 1) * ss + (n2 - 1) * hs + 128);
 }
 
-int append_validate(const fa_kvcache_append_args *a) {
+// fills `c` once the struct's size has passed
+int append_validate(const fa_kvcache_append_args *a, CacheView &c) {
     if (!a) return fail(FA_ERR_NULL, "null pointer argument");
     if (a->struct_size < sizeof(fa_kvcache_append_args))
         return fail(FA_ERR_SHAPE, "fa_kvcache_append_args.struct_size (%u) is smaller than this library's (%zu)", a->struct_size,
@@ -1749,29 +1704,18 @@ int append_validate(const fa_kvcache_append_args *a) {
     if (a->dtype != FA_FP16 && a->dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
     if (a->kv_dtype != 0 && a->kv_dtype != FA_KV_FP8_E4M3FN)
         return fail(FA_ERR_DTYPE, "kv_dtype (%d) is not served: 0 (the cache has dtype) or FA_KV_FP8_E4M3FN", a->kv_dtype);
-    const bool fp8 = a->kv_dtype == FA_KV_FP8_E4M3FN;
-    if (a->block_table && a->page_size > 0 && a->page_size % 64 != 0)
-        return fail(FA_ERR_NO_KERNEL, "paged cache: page_size must be a multiple of 64 (got %lld)", (long long)a->page_size);
+    cache_tensors(c, *a);
+    cache_descales(c, *a);
+    c.fp8 = a->kv_dtype == FA_KV_FP8_E4M3FN;
+    c.words_4b = "cache_seqlens, seqlens_out, block_table, k_descale and v_descale";
+    int rc = cache_page_rule(c);   // (this path reports the page size in front of its other sizes)
+    if (rc != FA_OK) return rc;
     if (a->d_head != 128) return fail(FA_ERR_SHAPE, "the append supports d_head = 128 only (got %lld)", (long long)a->d_head);
     if (a->batch < 0 || a->seqlen_new < 0 || a->n_kv_heads <= 0)
         return fail(FA_ERR_SHAPE, "batch and seqlen_new must not be negative, n_kv_heads must be positive");
     if (a->batch > INT32_MAX / 2 || a->seqlen_new > INT32_MAX / 2 || a->n_kv_heads > INT32_MAX / 2 || a->seqlen_new * a->n_kv_heads > INT32_MAX / 64)
         return fail(FA_ERR_SHAPE, "problem too large: the append's item counts are 32-bit");
-    int64_t cap;
-    if (a->block_table) {
-        if (a->page_size <= 0 || a->num_pages <= 0 || a->max_pages_per_seq <= 0)
-            return fail(FA_ERR_SHAPE, "paged cache: num_pages, page_size and max_pages_per_seq must be positive");
-        if (a->block_table_stride < a->max_pages_per_seq)
-            return fail(FA_ERR_SHAPE, "block_table_stride (%lld) is smaller than max_pages_per_seq (%lld)", (long long)a->block_table_stride,
-                        (long long)a->max_pages_per_seq);
-        if (a->num_pages > INT32_MAX / 2 || a->page_size > INT32_MAX / 2 || a->max_pages_per_seq > INT32_MAX / 2)
-            return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
-        cap = a->max_pages_per_seq * a->page_size;
-    } else {
-        if (a->seqlen_cache <= 0) return fail(FA_ERR_SHAPE, "seqlen_cache must be positive (got %lld)", (long long)a->seqlen_cache);
-        cap = a->seqlen_cache;
-    }
-    if (cap > INT32_MAX / 2) return fail(FA_ERR_SHAPE, "cache too large: lengths are 32-bit");
+    if ((rc = cache_sizes(c)) != FA_OK || (rc = cache_bounds(c)) != FA_OK) return rc;
     const bool rotary = a->rotary_cos || a->rotary_sin;
     if (rotary) {
         if (!a->rotary_cos || !a->rotary_sin) return fail(FA_ERR_SHAPE, "rotary_cos and rotary_sin come together (one of them is null)");
@@ -1788,21 +1732,16 @@ int append_validate(const fa_kvcache_append_args *a) {
         if (a->seqlen_q > INT32_MAX / 2 || a->n_heads > INT32_MAX / 2 || a->seqlen_q * a->n_heads > INT32_MAX / 64)
             return fail(FA_ERR_SHAPE, "problem too large: the append's item counts are 32-bit");
     }
-    if (!fp8 && (a->k_descale || a->v_descale))
+    if (!c.fp8 && (a->k_descale || a->v_descale))
         return fail(FA_ERR_SHAPE, "k_descale / v_descale belong to an fp8 cache (kv_dtype FA_KV_FP8_E4M3FN); this cache is 16-bit");
-    if (fp8 && (a->k_descale || a->v_descale) && a->descale_batch_stride < a->n_kv_heads)
-        return fail(FA_ERR_SHAPE, "descale_batch_stride (%lld) is smaller than n_kv_heads (%lld)", (long long)a->descale_batch_stride,
-                    (long long)a->n_kv_heads);
-    int rc;
+    if ((rc = cache_descale_stride(c)) != FA_OK) return rc;
     if (a->seqlen_new > 0 &&
-        (rc = append_strides("new", 8, a->batch, a->seqlen_new, a->n_kv_heads, a->new_batch_stride, a->new_seq_stride, a->new_head_stride)) != FA_OK)
+        (rc = stride_set("new", 8, a->batch, a->seqlen_new, a->n_kv_heads, a->new_batch_stride, a->new_seq_stride, a->new_head_stride)) != FA_OK)
         return rc;
-    if ((rc = append_strides("kv", fp8 ? 16 : 8, a->block_table ? a->num_pages : a->batch, cap, a->n_kv_heads, a->kv_batch_stride, a->kv_seq_stride,
-                             a->kv_head_stride)) != FA_OK)
-        return rc;
+    if ((rc = cache_strides(c, c.fp8 ? 16 : 8)) != FA_OK) return rc;   // (an fp8 cache's 16 bytes, in this path's own words)
     if (a->q) {
-        if ((rc = append_strides("q", 8, a->batch, a->seqlen_q, a->n_heads, a->q_batch_stride, a->q_seq_stride, a->q_head_stride)) != FA_OK) return rc;
-        if ((rc = append_strides("q_out", 8, a->batch, a->seqlen_q, a->n_heads, a->qo_batch_stride, a->qo_seq_stride, a->qo_head_stride)) != FA_OK)
+        if ((rc = stride_set("q", 8, a->batch, a->seqlen_q, a->n_heads, a->q_batch_stride, a->q_seq_stride, a->q_head_stride)) != FA_OK) return rc;
+        if ((rc = stride_set("q_out", 8, a->batch, a->seqlen_q, a->n_heads, a->qo_batch_stride, a->qo_seq_stride, a->qo_head_stride)) != FA_OK)
             return rc;
         if (a->batch > 0) {
             const uintptr_t q0 = (uintptr_t)a->q, o0 = (uintptr_t)a->q_out;
@@ -1815,14 +1754,13 @@ int append_validate(const fa_kvcache_append_args *a) {
     if (((uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->k_new | (uintptr_t)a->v_new | (uintptr_t)a->q | (uintptr_t)a->q_out |
          (uintptr_t)a->rotary_cos | (uintptr_t)a->rotary_sin) & 15)
         return fail(FA_ERR_ALIGN, "k, v, k_new, v_new, q, q_out, rotary_cos and rotary_sin must be 16-byte aligned");
-    if (((uintptr_t)a->cache_seqlens | (uintptr_t)a->seqlens_out | (uintptr_t)a->block_table | (uintptr_t)a->k_descale | (uintptr_t)a->v_descale) & 3)
-        return fail(FA_ERR_ALIGN, "cache_seqlens, seqlens_out, block_table, k_descale and v_descale must be 4-byte aligned");
-    return FA_OK;
+    return cache_alignment(c, (uintptr_t)a->seqlens_out | (uintptr_t)a->k_descale | (uintptr_t)a->v_descale);
 }
 }  // namespace
 
 int fa_kvcache_append_launch(const fa_kvcache_append_args *a, void *stream, float *ms) {
-    int rc = append_validate(a);
+    CacheView c;
+    int rc = append_validate(a, c);
     if (rc != FA_OK) return rc;
     if (a->batch == 0) {
         if (ms) *ms = 0.0f;
@@ -1830,7 +1768,7 @@ int fa_kvcache_append_launch(const fa_kvcache_append_args *a, void *stream, floa
     }
     DeviceState *dev = current_device(&rc);
     if (!dev) return rc;
-    const bool rotary = a->rotary_cos != nullptr, fp8 = a->kv_dtype == FA_KV_FP8_E4M3FN, with_q = rotary && a->q;
+    const bool rotary = a->rotary_cos != nullptr, fp8 = c.fp8, with_q = rotary && a->q;
     fa::AppendArgs d;
     d.k_new = (const uint16_t *)a->k_new;
     d.v_new = (const uint16_t *)a->v_new;
@@ -1840,11 +1778,11 @@ int fa_kvcache_append_launch(const fa_kvcache_append_args *a, void *stream, floa
     d.q_out = with_q ? (uint16_t *)a->q_out : nullptr;
     d.cos = (const uint16_t *)a->rotary_cos;
     d.sin = (const uint16_t *)a->rotary_sin;
-    d.cache_seqlens = a->cache_seqlens;
+    d.cache_seqlens = c.cache_seqlens;
     d.seqlens_out = a->seqlens_out;
-    d.block_table = a->block_table;
-    d.k_descale = fp8 ? a->k_descale : nullptr;
-    d.v_descale = fp8 ? a->v_descale : nullptr;
+    d.block_table = c.block_table;
+    d.k_descale = c.k_descale;   // (null for a 16-bit cache: validated)
+    d.v_descale = c.v_descale;
     d.new_bs = a->new_batch_stride;
     d.new_ss = a->new_seq_stride;
     d.new_hs = a->new_head_stride;
@@ -1854,26 +1792,26 @@ int fa_kvcache_append_launch(const fa_kvcache_append_args *a, void *stream, floa
     d.qo_bs = a->qo_batch_stride;
     d.qo_ss = a->qo_seq_stride;
     d.qo_hs = a->qo_head_stride;
-    d.kv_bs = a->kv_batch_stride;
-    d.kv_ss = a->kv_seq_stride;
-    d.kv_hs = a->kv_head_stride;
-    d.bt_bs = a->block_table ? a->block_table_stride : 0;
-    d.ds_bs = a->descale_batch_stride;
+    d.kv_bs = c.kv_bs;
+    d.kv_ss = c.kv_ss;
+    d.kv_hs = c.kv_hs;
+    d.bt_bs = c.paged() ? c.block_table_stride : 0;
+    d.ds_bs = c.descale_bs;
     d.ro_ss = rotary ? a->rotary_seq_stride : 0;
     d.seqlen_new = (int32_t)a->seqlen_new;
     d.seqlen_q = with_q ? (int32_t)a->seqlen_q : 0;
     d.n_heads = with_q ? (int32_t)a->n_heads : 0;
     d.n_kv_heads = (int32_t)a->n_kv_heads;
-    d.max_len = (int32_t)(a->block_table ? a->max_pages_per_seq * a->page_size : a->seqlen_cache);
-    d.page_size = a->block_table ? (int32_t)a->page_size : 0;
-    d.num_pages = a->block_table ? (int32_t)a->num_pages : 0;
+    d.max_len = (int32_t)c.capacity();
+    d.page_size = c.paged() ? (int32_t)c.page_size : 0;
+    d.num_pages = c.paged() ? (int32_t)c.num_pages : 0;
     d.rotary_dim = rotary ? (int32_t)a->rotary_dim : 0;
     d.seqlen_ro = rotary ? (int32_t)a->seqlen_ro : 0;
     d.interleaved = a->rotary_interleaved != 0;
     d.causal = a->causal != 0;
     const hipStream_t s = (hipStream_t)stream;
     const int batch = (int)a->batch;
-    return bwd_run([&] { return fa::kvcache_append_enqueue(d, batch, a->dtype, fp8, s); }, s, ms);
+    return enqueue_timed([&] { return fa::kvcache_append_enqueue(d, batch, a->dtype, fp8, s); }, s, ms);
 }
 
 static void add_slot(const AdaptiveState &ad, int idx, fa_adaptive_info *out) {

@@ -457,6 +457,95 @@ def _window(window_size, causal):
     return None if (left, right) == (-1, -1) else (left, right)
 
 
+def _need_tensors(named):
+    for t, name in named:
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{name} must be a tensor")
+
+
+def _need_device(named, anchor, whose):
+    """Every (tensor, name) is a CUDA tensor on anchor's device, which the message calls `whose` device."""
+    for t, name in named:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+        if t.device != anchor.device:
+            raise RuntimeError(f"{name} must be on {whose} device ({anchor.device}, got {t.device})")
+
+
+class _CacheSide:
+    """The cache side of forward_kvcache, append_kvcache and forward_varlen_kvcache -- k_cache, v_cache, cache_seqlens, block_table
+    and the descales -- with the checks the three share, one definition each.  A caller runs the stages where its own checks sit
+    (a call that breaks two rules reports the first; tests/test_wrapper_refusals_*.py pin that); `entries` ("batch" / "n_seqs") and
+    `whose` ("q's" / "the cache's" device) are the words their messages differ by.  dtypes() sets .fp8; .paged is set at once."""
+
+    def __init__(self, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, entries, whose):
+        self.k_cache, self.v_cache, self.cache_seqlens, self.block_table = k_cache, v_cache, cache_seqlens, block_table
+        self.k_descale, self.v_descale, self.entries, self.whose = k_descale, v_descale, entries, whose
+        self.paged = block_table is not None
+
+    def _descales(self):
+        return ((self.k_descale, "k_descale"), (self.v_descale, "v_descale"))
+
+    def dtypes(self, like, fp8_needs_descales=None):
+        """The cache's data type: fp8 (then e4m3fn, both) or `like`'s (None: the caller compares); descales only with fp8, and
+        with `fp8_needs_descales` (a message) both of them."""
+        k_cache, v_cache = self.k_cache, self.v_cache
+        self.fp8 = fp8 = k_cache.dtype in _FLOAT8_DTYPES or v_cache.dtype in _FLOAT8_DTYPES
+        given = [t for t, _ in self._descales() if t is not None]
+        if fp8 and k_cache.dtype != v_cache.dtype:
+            raise RuntimeError(f"k_cache and v_cache must have one data type (got {k_cache.dtype} and {v_cache.dtype})")
+        if fp8 and k_cache.dtype != torch.float8_e4m3fn:
+            raise RuntimeError(f"an fp8 cache must be torch.float8_e4m3fn (got {k_cache.dtype})")
+        if fp8 and fp8_needs_descales and len(given) < 2:
+            raise RuntimeError(fp8_needs_descales)
+        if not fp8 and like is not None and k_cache.dtype != like.dtype:
+            raise RuntimeError("Input tensors must have the same data type")
+        if not fp8 and given:
+            raise RuntimeError("k_descale / v_descale belong to an fp8 (torch.float8_e4m3fn) cache; this cache is 16-bit")
+        return fp8
+
+    def lengths(self, n, contiguous_needs):
+        """A contiguous cache has n entries (`contiguous_needs`: the caller's words for that); cache_seqlens is n int32."""
+        if not self.paged and self.k_cache.shape[0] != n:
+            raise RuntimeError(f"a contiguous cache needs {contiguous_needs} (pass block_table for a paged cache)")
+        t = self.cache_seqlens
+        if t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise RuntimeError(f"cache_seqlens must be a contiguous int32 tensor of {self.entries} entries on {self.whose} device")
+
+    def table(self, n, max_seqlen_k=None):
+        """block_table is (n, max_pages_per_seq) int32; max_seqlen_k, where the caller has one, a Python int."""
+        t = self.block_table
+        if t is not None and (t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != n or t.stride(1) != 1):
+            raise RuntimeError(f"block_table must be an int32 ({self.entries}, max_pages_per_seq) tensor on {self.whose} device with a "
+                               "contiguous last dimension")
+        if max_seqlen_k is not None and (not isinstance(max_seqlen_k, int) or isinstance(max_seqlen_k, bool)):
+            raise RuntimeError("max_seqlen_k must be a Python int (a bound on every length; the device is not asked)")
+
+    def descales(self, n):
+        """The descales decode and the append take: contiguous fp32 (n, n_kv_heads), or None."""
+        n_kv = self.k_cache.shape[2]
+        for t, name in self._descales():
+            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (n, n_kv) or not t.is_contiguous()):
+                raise RuntimeError(f"{name} must be a contiguous fp32 (batch, n_kv_heads) = ({n}, {n_kv}) tensor on {self.whose} device")
+
+    def strides(self):
+        """The caches pass as they are, so the launch must be able to address them: one stride set, 16-byte units and base."""
+        k_cache, v_cache = self.k_cache, self.v_cache
+        kv_unit = 16 if self.fp8 else 8   # 16 bytes
+        if (_decode_needs_copy(k_cache) or _decode_needs_copy(v_cache) or k_cache.stride() != v_cache.stride()
+                or any(s % kv_unit for s in k_cache.stride()[:-1])):
+            # (a serving cache is gigabytes: copying it on every call would be silently slow)
+            raise RuntimeError(f"k_cache and v_cache need one stride set, a contiguous last dimension, strides that are multiples of {kv_unit} "
+                               "elements and a 16-byte aligned base")
+
+    def geometry(self):
+        """The fields every cache struct has: the two device arrays and the sizes of a paged or a contiguous cache."""
+        k_cache, bt = self.k_cache, self.block_table
+        sizes = ((0, k_cache.shape[0], k_cache.shape[1], bt.shape[1], bt.stride(0)) if self.paged else (k_cache.shape[1], 0, 0, 0, 0))
+        return dict(zip(("seqlen_cache", "num_pages", "page_size", "max_pages_per_seq", "block_table_stride"), sizes),
+                    cache_seqlens=self.cache_seqlens.data_ptr(), block_table=bt.data_ptr() if self.paged else None)
+
+
 def kvcache_num_splits(q, k_cache, v_cache, cache_seqlens, block_table=None, max_seqlen_k=None, num_splits=0, causal=False,
                        window_size=(-1, -1)):
     """The split count forward_kvcache uses for these arguments (fa_decode_num_splits, or fa_decode_fp8_num_splits for an fp8
@@ -474,63 +563,31 @@ def kvcache_num_splits(q, k_cache, v_cache, cache_seqlens, block_table=None, max
 def _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_seqlen_k, num_splits, k_descale, v_descale):
     """forward_kvcache's checks -> (q as the launch takes it, fa_decode_args or fa_decode_fp8_args still without o, lse and
     workspace, whether the cache is fp8)."""
-    tensors = [(q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cache_seqlens, "cache_seqlens")]
-    if block_table is not None:
-        tensors.append((block_table, "block_table"))
-    tensors += [(t, name) for t, name in ((k_descale, "k_descale"), (v_descale, "v_descale")) if t is not None]
-    for t, name in tensors:
-        if not t.is_cuda:
-            raise RuntimeError(f"{name} must be a CUDA tensor")
-        if t.device != q.device:
-            raise RuntimeError(f"{name} must be on q's device ({q.device}, got {t.device})")
+    optional = ((block_table, "block_table"), (k_descale, "k_descale"), (v_descale, "v_descale"))
+    _need_device([(q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cache_seqlens, "cache_seqlens")]
+                 + [(t, name) for t, name in optional if t is not None], q, "q's")
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise RuntimeError("Only fp16 and bf16 are supported")
-    fp8 = k_cache.dtype in _FLOAT8_DTYPES or v_cache.dtype in _FLOAT8_DTYPES
-    if fp8 and k_cache.dtype != v_cache.dtype:
-        raise RuntimeError(f"k_cache and v_cache must have one data type (got {k_cache.dtype} and {v_cache.dtype})")
-    if fp8 and k_cache.dtype != torch.float8_e4m3fn:
-        raise RuntimeError(f"an fp8 cache must be torch.float8_e4m3fn (got {k_cache.dtype})")
-    if not fp8 and k_cache.dtype != q.dtype:
-        raise RuntimeError("Input tensors must have the same data type")
-    if not fp8 and (k_descale is not None or v_descale is not None):
-        raise RuntimeError("k_descale / v_descale belong to an fp8 (torch.float8_e4m3fn) cache; this cache is 16-bit")
+    cache = _CacheSide(k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, "batch", "q's")
+    fp8 = cache.dtypes(like=q)
     if q.dim() != 4 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[3] != q.shape[3]:
         raise RuntimeError("q must have shape (batch, seqlen_q, n_heads, d_head), k_cache and v_cache one shape (batch or "
                            "num_pages, seqlen_cache or page_size, n_kv_heads, d_head)")
     batch, seqlen_q, n_heads, d_head = q.shape
-    if block_table is None and k_cache.shape[0] != batch:
-        raise RuntimeError("a contiguous cache needs q's batch size (pass block_table for a paged cache)")
-    if cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (batch,) or not cache_seqlens.is_contiguous():
-        raise RuntimeError("cache_seqlens must be a contiguous int32 tensor of batch entries on q's device")
-    if block_table is not None and (block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != batch
-                                    or block_table.stride(1) != 1):
-        raise RuntimeError("block_table must be an int32 (batch, max_pages_per_seq) tensor on q's device with a contiguous last dimension")
-    if max_seqlen_k is not None and (not isinstance(max_seqlen_k, int) or isinstance(max_seqlen_k, bool)):
-        raise RuntimeError("max_seqlen_k must be a Python int (a bound on every length; the device is not asked)")
-    for t, name in ((k_descale, "k_descale"), (v_descale, "v_descale")):
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (batch, k_cache.shape[2]) or not t.is_contiguous()):
-            raise RuntimeError(f"{name} must be a contiguous fp32 (batch, n_kv_heads) = ({batch}, {k_cache.shape[2]}) tensor on q's device")
+    cache.lengths(batch, "q's batch size")
+    cache.table(batch, max_seqlen_k)
+    cache.descales(batch)
     if _decode_needs_copy(q):
         q = q.contiguous()
-    kv_unit = 16 if fp8 else 8   # 16 bytes
-    if (_decode_needs_copy(k_cache) or _decode_needs_copy(v_cache) or k_cache.stride() != v_cache.stride()
-            or any(s % kv_unit for s in k_cache.stride()[:-1])):
-        # (a serving cache is gigabytes: copying it on every call would be silently slow)
-        raise RuntimeError(f"k_cache and v_cache need one stride set, a contiguous last dimension, strides that are multiples of {kv_unit} "
-                           "elements and a 16-byte aligned base")
+    cache.strides()
     fields = dict(
         dtype=15 if q.dtype == torch.bfloat16 else 5, causal=1 if causal else 0, num_splits=int(num_splits),
         q=q.data_ptr(), k=k_cache.data_ptr(), v=v_cache.data_ptr(),
-        cache_seqlens=cache_seqlens.data_ptr(), block_table=block_table.data_ptr() if block_table is not None else None,
         batch=batch, seqlen_q=seqlen_q, n_heads=n_heads, n_kv_heads=k_cache.shape[2], d_head=d_head,
-        seqlen_cache=k_cache.shape[1] if block_table is None else 0,
-        num_pages=k_cache.shape[0] if block_table is not None else 0, page_size=k_cache.shape[1] if block_table is not None else 0,
-        max_pages_per_seq=block_table.shape[1] if block_table is not None else 0,
-        block_table_stride=block_table.stride(0) if block_table is not None else 0,
         max_seqlen_k=0 if max_seqlen_k is None else max_seqlen_k,
         q_batch_stride=q.stride(0), q_seq_stride=q.stride(1), q_head_stride=q.stride(2),
         o_batch_stride=seqlen_q * n_heads * d_head, o_seq_stride=n_heads * d_head, o_head_stride=d_head,   # (o: contiguous)
-        kv_batch_stride=k_cache.stride(0), kv_seq_stride=k_cache.stride(1), kv_head_stride=k_cache.stride(2),
+        kv_batch_stride=k_cache.stride(0), kv_seq_stride=k_cache.stride(1), kv_head_stride=k_cache.stride(2), **cache.geometry(),
     )
     if not fp8:
         return q, _capi.make_decode_args(**fields), False
@@ -550,9 +607,7 @@ def append_kvcache(k_cache, v_cache, k, v, cache_seqlens, block_table=None, q=No
     write min(cache_seqlens + seqlen_new, capacity) to seqlens_out (None: a new tensor; cache_seqlens itself: in place).
     q row i is rotated at position cache_seqlens[b] + i with causal, else at cache_seqlens[b].  -> (seqlens_out, q_rot or None).
     One kernel on the current stream; the host reads no device array; graph-capturable."""
-    for t, name in ((k_cache, "k_cache"), (v_cache, "v_cache"), (k, "k"), (v, "v"), (cache_seqlens, "cache_seqlens")):
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{name} must be a tensor")
+    _need_tensors(((k_cache, "k_cache"), (v_cache, "v_cache"), (k, "k"), (v, "v"), (cache_seqlens, "cache_seqlens")))
     rotary = rotary_cos is not None or rotary_sin is not None
     if rotary and (rotary_cos is None or rotary_sin is None):
         raise RuntimeError("rotary_cos and rotary_sin come together")
@@ -562,42 +617,24 @@ def append_kvcache(k_cache, v_cache, k, v, cache_seqlens, block_table=None, q=No
     named = [(k_cache, "k_cache"), (v_cache, "v_cache"), (k, "k"), (v, "v"), (cache_seqlens, "cache_seqlens"), (block_table, "block_table"),
              (q, "q"), (rotary_cos, "rotary_cos"), (rotary_sin, "rotary_sin"), (k_descale, "k_descale"), (v_descale, "v_descale"),
              (seqlens_out, "seqlens_out")]
-    for t, name in named:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError(f"{name} must be a CUDA tensor")
-        if t.device != dev:
-            raise RuntimeError(f"{name} must be on k_cache's device ({dev}, got {t.device})")
+    _need_device([(t, name) for t, name in named if t is not None], k_cache, "k_cache's")
     if k.dtype not in (torch.float16, torch.bfloat16):
         raise RuntimeError("Only fp16 and bf16 are supported")
     if v.dtype != k.dtype or any(t is not None and t.dtype != k.dtype for t in (q, rotary_cos, rotary_sin)):
         raise RuntimeError("Input tensors must have the same data type (k, v, q, rotary_cos, rotary_sin)")
-    fp8 = k_cache.dtype in _FLOAT8_DTYPES or v_cache.dtype in _FLOAT8_DTYPES
-    if k_cache.dtype != v_cache.dtype:
+    if k_cache.dtype != v_cache.dtype:   # (this path also compares two 16-bit caches)
         raise RuntimeError(f"k_cache and v_cache must have one data type (got {k_cache.dtype} and {v_cache.dtype})")
-    if fp8 and k_cache.dtype != torch.float8_e4m3fn:
-        raise RuntimeError(f"an fp8 cache must be torch.float8_e4m3fn (got {k_cache.dtype})")
-    if not fp8 and k_cache.dtype != k.dtype:
-        raise RuntimeError("Input tensors must have the same data type")
-    if not fp8 and (k_descale is not None or v_descale is not None):
-        raise RuntimeError("k_descale / v_descale belong to an fp8 (torch.float8_e4m3fn) cache; this cache is 16-bit")
+    cache = _CacheSide(k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, "batch", "the cache's")
+    fp8 = cache.dtypes(like=k)
     if k.dim() != 4 or k.shape != v.shape or k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[2:] != k.shape[2:]:
         raise RuntimeError("k and v must have one shape (batch, seqlen_new, n_kv_heads, d_head), k_cache and v_cache one shape (batch or "
                            "num_pages, seqlen_cache or page_size, n_kv_heads, d_head)")
     batch, seqlen_new, n_kv_heads, d_head = k.shape
-    if block_table is None and k_cache.shape[0] != batch:
-        raise RuntimeError("a contiguous cache needs k's batch size (pass block_table for a paged cache)")
-    if cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (batch,) or not cache_seqlens.is_contiguous():
-        raise RuntimeError("cache_seqlens must be a contiguous int32 tensor of batch entries on the cache's device")
+    cache.lengths(batch, "k's batch size")
     if seqlens_out is not None and (seqlens_out.dtype != torch.int32 or tuple(seqlens_out.shape) != (batch,) or not seqlens_out.is_contiguous()):
         raise RuntimeError("seqlens_out must be a contiguous int32 tensor of batch entries on the cache's device (or cache_seqlens itself)")
-    if block_table is not None and (block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != batch
-                                    or block_table.stride(1) != 1):
-        raise RuntimeError("block_table must be an int32 (batch, max_pages_per_seq) tensor on the cache's device with a contiguous last dimension")
-    for t, name in ((k_descale, "k_descale"), (v_descale, "v_descale")):
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (batch, n_kv_heads) or not t.is_contiguous()):
-            raise RuntimeError(f"{name} must be a contiguous fp32 (batch, n_kv_heads) = ({batch}, {n_kv_heads}) tensor on the cache's device")
+    cache.table(batch)
+    cache.descales(batch)
     if rotary:
         if rotary_cos.dim() != 2 or rotary_cos.shape != rotary_sin.shape or rotary_cos.shape[0] < 1:
             raise RuntimeError("rotary_cos and rotary_sin must have one shape (seqlen_ro, rotary_dim / 2)")
@@ -613,35 +650,27 @@ def append_kvcache(k_cache, v_cache, k, v, cache_seqlens, block_table=None, q=No
             q = q.contiguous()
     if _decode_needs_copy(k) or _decode_needs_copy(v) or k.stride() != v.stride():
         k, v = k.contiguous(), v.contiguous()
-    kv_unit = 16 if fp8 else 8   # 16 bytes
-    if (_decode_needs_copy(k_cache) or _decode_needs_copy(v_cache) or k_cache.stride() != v_cache.stride()
-            or any(s % kv_unit for s in k_cache.stride()[:-1])):
-        raise RuntimeError(f"k_cache and v_cache need one stride set, a contiguous last dimension, strides that are multiples of {kv_unit} "
-                           "elements and a 16-byte aligned base")
+    cache.strides()
     with torch.cuda.device(dev):
         if seqlens_out is None:
             seqlens_out = torch.empty_like(cache_seqlens)
         q_out = torch.empty(q.shape, dtype=q.dtype, device=dev) if q is not None else None
-        paged = block_table is not None
         args = _capi.make_kvcache_append_args(
             dtype=15 if k.dtype == torch.bfloat16 else 5, kv_dtype=_capi.FA_KV_FP8_E4M3FN if fp8 else 0, causal=1 if causal else 0,
             rotary_interleaved=1 if rotary_interleaved else 0,
             k_new=k.data_ptr(), v_new=v.data_ptr(), k=k_cache.data_ptr(), v=v_cache.data_ptr(),
             q=q.data_ptr() if q is not None else None, q_out=q_out.data_ptr() if q is not None else None,
             rotary_cos=rotary_cos.data_ptr() if rotary else None, rotary_sin=rotary_sin.data_ptr() if rotary else None,
-            cache_seqlens=cache_seqlens.data_ptr(), seqlens_out=seqlens_out.data_ptr(),
-            block_table=block_table.data_ptr() if paged else None,
+            seqlens_out=seqlens_out.data_ptr(),
             k_descale=k_descale.data_ptr() if k_descale is not None else None,
             v_descale=v_descale.data_ptr() if v_descale is not None else None,
             batch=batch, seqlen_new=seqlen_new, seqlen_q=q.shape[1] if q is not None else 0, n_heads=q.shape[2] if q is not None else 0,
-            n_kv_heads=n_kv_heads, d_head=d_head, seqlen_cache=0 if paged else k_cache.shape[1],
-            num_pages=k_cache.shape[0] if paged else 0, page_size=k_cache.shape[1] if paged else 0,
-            max_pages_per_seq=block_table.shape[1] if paged else 0, block_table_stride=block_table.stride(0) if paged else 0,
+            n_kv_heads=n_kv_heads, d_head=d_head,
             rotary_dim=rotary_dim if rotary else 0, seqlen_ro=rotary_cos.shape[0] if rotary else 0,
             rotary_seq_stride=rotary_cos.stride(0) if rotary else 0,
             new_batch_stride=k.stride(0), new_seq_stride=k.stride(1), new_head_stride=k.stride(2),
             kv_batch_stride=k_cache.stride(0), kv_seq_stride=k_cache.stride(1), kv_head_stride=k_cache.stride(2),
-            descale_batch_stride=n_kv_heads,
+            descale_batch_stride=n_kv_heads, **cache.geometry(),
         )
         if q is not None:
             args.q_batch_stride, args.q_seq_stride, args.q_head_stride = q.stride(0), q.stride(1), q.stride(2)
@@ -733,35 +762,21 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
     tensors = [(q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cu_seqlens_q, "cu_seqlens_q"), (cache_seqlens, "cache_seqlens")]
     if block_table is not None:
         tensors.append((block_table, "block_table"))
-    for t, name in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{name} must be a tensor")
-    fp8 = k_cache.dtype in _FLOAT8_DTYPES or v_cache.dtype in _FLOAT8_DTYPES
-    if fp8 and k_cache.dtype != v_cache.dtype:
-        raise RuntimeError(f"k_cache and v_cache must have one data type (got {k_cache.dtype} and {v_cache.dtype})")
-    if fp8 and k_cache.dtype != torch.float8_e4m3fn:
-        raise RuntimeError(f"an fp8 cache must be torch.float8_e4m3fn (got {k_cache.dtype})")
-    if fp8 and (k_descale is None or v_descale is None):
-        raise RuntimeError("forward_varlen_kvcache: an fp8 cache is not served without both k_descale and v_descale (fp32 (n_seqs, "
-                           "n_kv_heads) tensors on q's device; pass ones for an unscaled cache -- None does not mean 1 here)")
-    if not fp8 and (k_descale is not None or v_descale is not None):
-        raise RuntimeError("k_descale / v_descale belong to an fp8 (torch.float8_e4m3fn) cache; this cache is 16-bit")
+    _need_tensors(tensors)
+    cache = _CacheSide(k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, "n_seqs", "q's")
+    fp8 = cache.dtypes(like=None, fp8_needs_descales=(
+        "forward_varlen_kvcache: an fp8 cache is not served without both k_descale and v_descale (fp32 (n_seqs, "
+        "n_kv_heads) tensors on q's device; pass ones for an unscaled cache -- None does not mean 1 here)"))
     if fp8:
         tensors += [(k_descale, "k_descale"), (v_descale, "v_descale")]
-        for t, name in tensors[-2:]:
-            if not isinstance(t, torch.Tensor):
-                raise RuntimeError(f"{name} must be a tensor")
+        _need_tensors(tensors[-2:])
         if k_cache.dim() == 4 and cu_seqlens_q.dim() == 1 and cu_seqlens_q.numel() >= 2:   # (what they are is checked before where they are)
             want = (cu_seqlens_q.numel() - 1, k_cache.shape[2])
             for t, name in tensors[-2:]:
                 if t.dtype != torch.float32 or tuple(t.shape) != want or t.stride(1) != 1:
                     raise RuntimeError(f"{name} must be an fp32 (n_seqs, n_kv_heads) = {want} tensor on q's device with a contiguous "
                                        "last dimension")
-    for t, name in tensors:
-        if not t.is_cuda:
-            raise RuntimeError(f"{name} must be a CUDA tensor")
-        if t.device != q.device:
-            raise RuntimeError(f"{name} must be on q's device ({q.device}, got {t.device})")
+    _need_device(tensors, q, "q's")
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise RuntimeError("Only fp16 and bf16 are supported")
     if not fp8 and (k_cache.dtype != q.dtype or v_cache.dtype != q.dtype):
@@ -778,27 +793,14 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
     n_seqs = cu_seqlens_q.numel() - 1
     if not isinstance(max_seqlen_q, int) or isinstance(max_seqlen_q, bool):
         raise RuntimeError("max_seqlen_q must be a Python int (a bound on every sequence's query rows; the device is not asked)")
-    if block_table is None and k_cache.shape[0] != n_seqs:
-        raise RuntimeError("a contiguous cache needs one batch entry per sequence (pass block_table for a paged cache)")
-    if cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (n_seqs,) or not cache_seqlens.is_contiguous():
-        raise RuntimeError("cache_seqlens must be a contiguous int32 tensor of n_seqs entries on q's device")
-    if block_table is not None and (block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != n_seqs
-                                    or block_table.stride(1) != 1):
-        raise RuntimeError("block_table must be an int32 (n_seqs, max_pages_per_seq) tensor on q's device with a contiguous last dimension")
-    if max_seqlen_k is not None and (not isinstance(max_seqlen_k, int) or isinstance(max_seqlen_k, bool)):
-        raise RuntimeError("max_seqlen_k must be a Python int (a bound on every length; the device is not asked)")
+    cache.lengths(n_seqs, "one batch entry per sequence")
+    cache.table(n_seqs, max_seqlen_k)
     if q.stride(2) != 1:
         raise RuntimeError("packed sequences: q needs a contiguous last dimension")
-    kv_unit = 16 if fp8 else 8   # 16 bytes
-    if (_decode_needs_copy(k_cache) or _decode_needs_copy(v_cache) or k_cache.stride() != v_cache.stride()
-            or any(s % kv_unit for s in k_cache.stride()[:-1])):
-        # (a serving cache is gigabytes: copying it on every call would be silently slow)
-        raise RuntimeError(f"k_cache and v_cache need one stride set, a contiguous last dimension, strides that are multiples of {kv_unit} "
-                           "elements and a 16-byte aligned base")
+    cache.strides()
     if fp8 and (k_descale.stride(0) != v_descale.stride(0) or k_descale.stride(0) < n_kv or k_descale.data_ptr() % 4 or v_descale.data_ptr() % 4):
         # (the launch has one row stride for both, at least a row long -- an expanded or single row has any: two small copies)
         k_descale, v_descale = k_descale.contiguous(), v_descale.contiguous()
-    paged = block_table is not None
     lib = _capi.load()
     cfg = _capi.make_config(varlen_config(q.dtype))
     with torch.cuda.device(q.device):
@@ -810,12 +812,8 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
                                n_heads=n_heads, d_head=d_head, batch_stride=0, seq_stride=q.stride(0), head_stride=q.stride(1), cfg=cfg)
         kv = _capi.make_kv_layout(n_kv, k_cache.stride(0), k_cache.stride(1), k_cache.stride(2))
         vq = _capi.make_varlen_layout(cu_seqlens_q.data_ptr(), n_seqs, total, max(max_seqlen_q, 1))   # (a bound of 0: nothing but empties)
-        kc = _capi.make_kvcache_layout(
-            cache_seqlens=cache_seqlens.data_ptr(), block_table=block_table.data_ptr() if paged else None,
-            seqlen_cache=0 if paged else k_cache.shape[1], batch=0 if paged else k_cache.shape[0],
-            num_pages=k_cache.shape[0] if paged else 0, page_size=k_cache.shape[1] if paged else 0,
-            max_pages_per_seq=block_table.shape[1] if paged else 0, block_table_stride=block_table.stride(0) if paged else 0,
-            max_seqlen_k=0 if max_seqlen_k is None else max_seqlen_k)
+        kc = _capi.make_kvcache_layout(batch=0 if cache.paged else k_cache.shape[0], max_seqlen_k=0 if max_seqlen_k is None else max_seqlen_k,
+                                       **cache.geometry())
         ms = ctypes.c_float(0.0)
         opts = _capi.make_opts(causal=causal, ms=ms if timed else None)
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
