@@ -40,6 +40,9 @@ EXPORTED_SYMBOLS = (
     "fa_decode_window_supported", "fa_decode_window_num_splits", "fa_decode_window_workspace_bytes", "fa_decode_window_launch",
     "fa_decode_fp8_window_supported", "fa_decode_fp8_window_num_splits", "fa_decode_fp8_window_workspace_bytes",
     "fa_decode_fp8_window_launch",
+    "fa_fwd_varlen_qk_window_supported", "fa_fwd_launch_varlen_qk_window",
+    "fa_fwd_varlen_kvcache_window_supported", "fa_fwd_launch_varlen_kvcache_window",
+    "fa_fwd_varlen_kvcache_fp8_window_supported", "fa_fwd_launch_varlen_kvcache_fp8_window",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -416,6 +419,13 @@ def load():
                                       ("launch", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)])):
             fn = getattr(lib, f"{name}_{suffix}")
             fn.restype, fn.argtypes = restype, pair + more
+    # the sliding-window forms of the packed forward and the prefills: the sibling's arguments with an fa_window in front of opts
+    for name, sibling in (("varlen_qk_window", "varlen_qk"), ("varlen_kvcache_window", "varlen_kvcache"),
+                          ("varlen_kvcache_fp8_window", "varlen_kvcache_fp8")):
+        fn = getattr(lib, f"fa_fwd_{name}_supported")
+        fn.restype, fn.argtypes = ctypes.c_int, [cfg_p, ctypes.POINTER(FaFwdOpts)]
+        fn, argtypes = getattr(lib, f"fa_fwd_launch_{name}"), list(getattr(lib, f"fa_fwd_launch_{sibling}").argtypes)
+        fn.restype, fn.argtypes = ctypes.c_int, argtypes[:-3] + [ctypes.POINTER(FaWindow)] + argtypes[-3:]
     lib.fa_kvcache_append_launch.restype = ctypes.c_int
     lib.fa_kvcache_append_launch.argtypes = [ctypes.POINTER(FaKvcacheAppendArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p

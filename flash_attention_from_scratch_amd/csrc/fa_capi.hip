@@ -51,6 +51,13 @@ kernel_fn_varlen_kvcache varlen_kvcache_kernel_dt5(bool first_block_skip);
 // fa_inst_varlen_kvcache_fp8.hip: ... from an fp8 (e4m3fn) KV cache (the same LDS)
 kernel_fn_varlen_kvcache_fp8 varlen_kvcache_fp8_kernel_dt15(bool first_block_skip);
 kernel_fn_varlen_kvcache_fp8 varlen_kvcache_fp8_kernel_dt5(bool first_block_skip);
+// fa_inst_varlen_window.hip, fa_inst_varlen_kvcache_window.hip, fa_inst_varlen_kvcache_fp8_window.hip: the three under a sliding window
+kernel_fn_varlen_window varlen_window_kernel_dt15(bool first_block_skip);
+kernel_fn_varlen_window varlen_window_kernel_dt5(bool first_block_skip);
+kernel_fn_varlen_kvcache_window varlen_kvcache_window_kernel_dt15(bool first_block_skip);
+kernel_fn_varlen_kvcache_window varlen_kvcache_window_kernel_dt5(bool first_block_skip);
+kernel_fn_varlen_kvcache_fp8_window varlen_kvcache_fp8_window_kernel_dt15(bool first_block_skip);
+kernel_fn_varlen_kvcache_fp8_window varlen_kvcache_fp8_window_kernel_dt5(bool first_block_skip);
 // fa_bwd_varlen.hip / fa_bwd_varlen_qk.hip: the packed backward, and its form with separate Q and K / V lengths
 hipError_t bwd_varlen_enqueue(const BwdVarlenArgs &a, int dtype, bool causal, hipStream_t s);
 hipError_t bwd_varlen_qk_enqueue(const BwdVarlenQKArgs &a, int dtype, bool causal, hipStream_t s);
@@ -305,6 +312,20 @@ void do_init_body(int dev, DeviceState *st) {
             st->status = FA_ERR_LAUNCH;
             snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, varlen fp8 KV-cache form) on device %d: %s",
                      fa::varlen_lds_bytes_dt15(), dev, hipGetErrorString(rc));
+            return;
+        }
+    }
+    // ... and the sliding-window forms of the three (fa_fwd_launch_varlen_qk_window, _kvcache_window, _kvcache_fp8_window)
+    for (int i = 0; i < 12; ++i) {
+        const bool fbs = (i & 1) != 0, dt5 = (i & 2) != 0;
+        const void *fn = i < 4 ? (dt5 ? (const void *)fa::varlen_window_kernel_dt5(fbs) : (const void *)fa::varlen_window_kernel_dt15(fbs))
+                       : i < 8 ? (dt5 ? (const void *)fa::varlen_kvcache_window_kernel_dt5(fbs) : (const void *)fa::varlen_kvcache_window_kernel_dt15(fbs))
+                               : (dt5 ? (const void *)fa::varlen_kvcache_fp8_window_kernel_dt5(fbs) : (const void *)fa::varlen_kvcache_fp8_window_kernel_dt15(fbs));
+        const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, fa::varlen_lds_bytes_dt15());
+        if (rc != hipSuccess) {
+            st->status = FA_ERR_LAUNCH;
+            snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, varlen sliding-window form %d) on device %d: %s",
+                     fa::varlen_lds_bytes_dt15(), i, dev, hipGetErrorString(rc));
             return;
         }
     }
@@ -1060,6 +1081,25 @@ template <class A> void cache_descales(CacheView &c, const A &a) {
 }
 }  // namespace
 
+// ---- fa_window: the rules every windowed entry point shares (decode, the packed forward, the prefills) ----------------------
+namespace {
+constexpr int64_t kWindowMaxLen = (1 << 30) - 128;   // the kernels add a row's position and its clamped distances in 32 bits
+int window_right(const fa_window *w, int causal) { return causal ? 0 : w->right; }
+
+// (called behind the unwindowed entry's own rules: the cache is valid)
+int window_validate(const fa_window *w, int causal, int64_t capacity) {
+    if (!w) return fail(FA_ERR_NULL, "fa_window is null: (left, right) is needed (-1 = unbounded; the unwindowed entry point takes none)");
+    if (w->struct_size < sizeof(fa_window))
+        return fail(FA_ERR_SHAPE, "fa_window.struct_size (%u) is smaller than this library's (%zu)", w->struct_size, sizeof(fa_window));
+    if (w->left < -1 || w->right < -1)
+        return fail(FA_ERR_SHAPE, "window (%d, %d): left and right must be -1 (unbounded) or not negative", w->left, w->right);
+    if (causal && w->right > 0)
+        return fail(FA_ERR_SHAPE, "causal means right = 0: a window with right = %d cannot be causal as well (pass right = -1 or 0)", w->right);
+    if (capacity > kWindowMaxLen) return fail(FA_ERR_SHAPE, "cache too large for a window: at most 2^30 - 128 keys per entry");
+    return FA_OK;
+}
+}  // namespace
+
 // ---- packed variable-length sequences: one range for Q and K / V (fa_*_varlen) or one each (fa_*_varlen_qk) ------------------
 // One host path, of two ranges; the entry points with one fa_varlen_layout pass it for both sides.  Each entry point keeps its
 // own name, and its name for the query side's total, in its messages.  The forward has one kernel; the backward keeps the
@@ -1156,9 +1196,11 @@ int kvcache_validate(CacheView &c, const fa_kvcache_layout *kc, const fa_kvcache
 // the forward of `entry` (a public entry point; `total`: its name for the query side's total)
 // `kc` non-null: the key side is a KV cache (fa_fwd_launch_varlen_kvcache), and vk is not used
 // `fp8_side`: ... an fp8 one (fa_fwd_launch_varlen_kvcache_fp8): k, v are bytes, kv's strides count bytes, `sc` holds the descales
+// `windowed`: the entry's sliding-window form, with its fa_window `w` (null is refused, behind everything the entry itself refuses)
 int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
                       const fa_varlen_layout *vk, const fa_fwd_opts *opts, float *lse, void *stream, const fa_kvcache_layout *kc = nullptr,
-                      bool cache_side = false, const fa_kvcache_fp8_scales *sc = nullptr, bool fp8_side = false) {
+                      bool cache_side = false, const fa_kvcache_fp8_scales *sc = nullptr, bool fp8_side = false, bool windowed = false,
+                      const fa_window *w = nullptr) {
     if (cache_side) vk = vq;   // (one valid layout for the checks both launches share)
     if (!args || !kv || !vq || !vk || (cache_side && !kc) || (fp8_side && !sc)) return fail(FA_ERR_NULL, "null pointer argument");
     if (!args->q || !args->k || !args->v || !args->o) return fail(FA_ERR_NULL, "null pointer argument");
@@ -1193,6 +1235,13 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
         return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
     if ((uintptr_t)lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
     if (cache_side && (rc = kvcache_validate(cache, kc, fp8_side ? sc : nullptr)) != FA_OK) return rc;
+    if (windowed) {   // (the key bound: the cache's capacity, or the packed key side's max_seqlen; then the query side's)
+        if ((rc = window_validate(w, o.causal, cache_side ? cache.capacity() : 0)) != FA_OK) return rc;
+        if (!cache_side && vk->max_seqlen > kWindowMaxLen)
+            return fail(FA_ERR_SHAPE, "max_seqlen_k too large for a window: at most 2^30 - 128 keys per sequence");
+        if (vq->max_seqlen > kWindowMaxLen)
+            return fail(FA_ERR_SHAPE, "max_seqlen_q too large for a window: at most 2^30 - 128 query rows per sequence");
+    }
     if (vq->total_tokens == 0) {   // (no query rows: nothing to write)
         if (o.ms) *o.ms = 0.0f;
         return FA_OK;
@@ -1201,7 +1250,8 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
     if (!dev) return rc;
     const char *why;
     const fa::KernelEntry *e = varlen_entry(&args->cfg, &why);
-    fa::KernelArgsVarlenKVCacheFp8 fa8;
+    fa::KernelArgsVarlenKVCacheFp8Window wf8;   // (the widest form: the cache forms' arguments are its members)
+    fa::KernelArgsVarlenKVCacheFp8 &fa8 = wf8.a;
     fa::KernelArgsVarlenKVCache &ca = fa8.c;
     fa::KernelArgsVarlenQK qa;
     fa::KernelArgsVarlen &va = cache_side ? ca.v : qa.v;
@@ -1249,6 +1299,26 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
         fa8.ds_bs = cache.descale_bs;
         fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kvcache_fp8_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_fp8_kernel_dt5(fbs);
         kernel_args = &fa8;
+    }
+    // the sliding-window forms: the same arguments and (left, right), causal as right = 0 (the kernel's one rule for both)
+    fa::KernelArgsVarlenWindow wqa;
+    fa::KernelArgsVarlenKVCacheWindow wca;
+    if (windowed) {
+        const bool bf16 = args->cfg.dtype == FA_BF16;
+        wf8.left = w->left;
+        wf8.right = window_right(w, o.causal);
+        if (fp8_side) {
+            fn = bf16 ? (const void *)fa::varlen_kvcache_fp8_window_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_fp8_window_kernel_dt5(fbs);
+            kernel_args = &wf8;
+        } else if (cache_side) {
+            wca = {ca, wf8.left, wf8.right};
+            fn = bf16 ? (const void *)fa::varlen_kvcache_window_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_window_kernel_dt5(fbs);
+            kernel_args = &wca;
+        } else {
+            wqa = {qa, wf8.left, wf8.right};
+            fn = bf16 ? (const void *)fa::varlen_window_kernel_dt15(fbs) : (const void *)fa::varlen_window_kernel_dt5(fbs);
+            kernel_args = &wqa;
+        }
     }
     const dim3 grid((unsigned)(va.base.n_bh * va.base.n_q_blocks)), block((unsigned)e->threads);
     const hipStream_t s = (hipStream_t)stream;
@@ -1424,6 +1494,26 @@ int fa_fwd_launch_varlen_kvcache_fp8(const fa_fwd_args *args, const fa_kv_layout
     return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache_fp8", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true, sc, true);
 }
 
+// the sliding-window forms of the three: the same body with an fa_window (served: what the sibling serves)
+int fa_fwd_varlen_qk_window_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
+int fa_fwd_launch_varlen_qk_window(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_varlen_layout *vk,
+                                   const fa_window *w, const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen("fa_fwd_launch_varlen_qk_window", "total_q", args, kv, vq, vk, opts, lse, stream, nullptr, false, nullptr, false, true, w);
+}
+int fa_fwd_varlen_kvcache_window_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
+int fa_fwd_launch_varlen_kvcache_window(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
+                                        const fa_kvcache_layout *kc, const fa_window *w, const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache_window", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true, nullptr, false,
+                             true, w);
+}
+int fa_fwd_varlen_kvcache_fp8_window_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
+int fa_fwd_launch_varlen_kvcache_fp8_window(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
+                                            const fa_kvcache_layout *kc, const fa_kvcache_fp8_scales *sc, const fa_window *w,
+                                            const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache_fp8_window", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true, sc, true,
+                             true, w);
+}
+
 int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *a) {
     if (!a) return fail(FA_ERR_NULL, "null pointer argument");
     const fa_bwd_varlen_qk_args b = both_sides(a);
@@ -1488,22 +1578,6 @@ int decode_struct_rules(const fa_decode_fp8_args *a, CacheView &c) {
     return FA_OK;
 }
 
-int window_right(const fa_window *w, int causal) { return causal ? 0 : w->right; }
-
-// (called behind decode_validate: the cache is valid)
-int window_validate(const fa_window *w, int causal, const CacheView &c) {
-    if (!w) return fail(FA_ERR_NULL, "fa_window is null: (left, right) is needed (-1 = unbounded; the unwindowed entry point takes none)");
-    if (w->struct_size < sizeof(fa_window))
-        return fail(FA_ERR_SHAPE, "fa_window.struct_size (%u) is smaller than this library's (%zu)", w->struct_size, sizeof(fa_window));
-    if (w->left < -1 || w->right < -1)
-        return fail(FA_ERR_SHAPE, "window (%d, %d): left and right must be -1 (unbounded) or not negative", w->left, w->right);
-    if (causal && w->right > 0)
-        return fail(FA_ERR_SHAPE, "causal means right = 0: a window with right = %d cannot be causal as well (pass right = -1 or 0)", w->right);
-    // (the kernel adds a row's position and its clamped distances in 32 bits: fa_decode_kernel.hpp)
-    if (c.capacity() > (1 << 30) - 128) return fail(FA_ERR_SHAPE, "cache too large for a window: at most 2^30 - 128 keys per entry");
-    return FA_OK;
-}
-
 struct DecodePlan {
     int status = FA_OK;
     int64_t splits = 0;
@@ -1564,7 +1638,7 @@ template <class A> int64_t decode_splits(const A *a, const CacheView &c, const f
 template <class A> DecodePlan decode_plan(const A *a, bool windowed, const fa_window *w) {
     DecodePlan p;
     p.status = decode_validate(a, p.cache);
-    if (p.status == FA_OK && windowed) p.status = window_validate(w, a->causal, p.cache);
+    if (p.status == FA_OK && windowed) p.status = window_validate(w, a->causal, p.cache.capacity());
     if (p.status == FA_OK) p.splits = decode_splits(a, p.cache, windowed ? w : nullptr);
     return p;
 }

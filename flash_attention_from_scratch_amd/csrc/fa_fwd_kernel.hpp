@@ -492,6 +492,34 @@ struct KernelArgsVarlenKVCacheFp8 {
     int64_t ds_bs;
 };
 typedef void (*kernel_fn_varlen_kvcache_fp8)(const KernelArgsVarlenKVCacheFp8);
+// A sliding window on any of the three (fa_fwd_launch_varlen_qk_window, fa_fwd_launch_varlen_kvcache_window,
+// fa_fwd_launch_varlen_kvcache_fp8_window): the form's arguments and (left, right), -1 = unbounded, causal arriving as right = 0
+// (args.causal then only orders the Q blocks).  fa_inst_varlen*_window.hip define FA_KERNEL_VARLEN_WINDOW beside their sibling's
+// macros and get fa_fwd_kernel_varlen*_window INSTEAD; `if constexpr (WIN)` or an #ifdef arm marks every site that differs
+// (DESIGN.md 10.13).  Query row r of sequence b sits at position p = r + (len_k - len_q) and sees the keys
+// lo_r = max(0, p - left) .. hi_r = min(len_k - 1, p + right); a row with hi_r < lo_r (p + right < 0) gives o = 0, lse = -inf.
+// Both bounds grow with r, so a workgroup owning rows r0 .. r1 visits the tiles hi_r1 / 64 down to lo_r0 / 64 and nothing else:
+// n_kv stays "top tile + 1" (the tile arithmetic: kv0, ragged_rows, FA_ST_TILE), FA_N_VISITS is the visit count every
+// comparison against `it` uses (n_kv itself in the other forms).  No key below the workgroup's floor lo_r0 is fetched: in
+// the floor tile a lane whose row lies below it fetches row lo_r0 (the same tile, the same page) and is masked, as rows at or
+// beyond len_k fetch row len_k - 1; no table entry of a page wholly below the floor is read.
+template <class A> struct Windowed {
+    A a;
+    int32_t left, right;
+};
+typedef Windowed<KernelArgsVarlenQK> KernelArgsVarlenWindow;
+typedef Windowed<KernelArgsVarlenKVCache> KernelArgsVarlenKVCacheWindow;
+typedef Windowed<KernelArgsVarlenKVCacheFp8> KernelArgsVarlenKVCacheFp8Window;
+typedef void (*kernel_fn_varlen_window)(const KernelArgsVarlenWindow);
+typedef void (*kernel_fn_varlen_kvcache_window)(const KernelArgsVarlenKVCacheWindow);
+typedef void (*kernel_fn_varlen_kvcache_fp8_window)(const KernelArgsVarlenKVCacheFp8Window);
+#ifdef FA_KERNEL_VARLEN_WINDOW
+#define FA_VARLEN_WINDOW true
+#define FA_N_VISITS n_vis
+#else
+#define FA_VARLEN_WINDOW false
+#define FA_N_VISITS n_kv
+#endif
 #ifdef FA_KERNEL_VARLEN_KVCACHE_FP8
 #define FA_FP8_CACHE true
 #define FA_K_DESCALED(c0) (fa8.k_descale ? (c0) * fa8.k_descale[(int64_t)b * fa8.ds_bs + h / va.group] : (c0))
@@ -549,11 +577,21 @@ __global__ void
 #ifdef FA_KERNEL_VARLEN
 // (one workgroup per SIMD set: with m live up to the LSE store the 256-register budget of two waves per SIMD spills)
 __launch_bounds__(NWAVES * 64, 1)
-#ifdef FA_KERNEL_VARLEN_KVCACHE_FP8
+#if defined(FA_KERNEL_VARLEN_KVCACHE_FP8) && defined(FA_KERNEL_VARLEN_WINDOW)
+fa_fwd_kernel_varlen_kvcache_fp8_window(const KernelArgsVarlenKVCacheFp8Window wa) {
+    const KernelArgsVarlenKVCacheFp8 &fa8 = wa.a;
+    const KernelArgsVarlenKVCache &qa = fa8.c;
+#elif defined(FA_KERNEL_VARLEN_KVCACHE_FP8)
 fa_fwd_kernel_varlen_kvcache_fp8(const KernelArgsVarlenKVCacheFp8 fa8) {
     const KernelArgsVarlenKVCache &qa = fa8.c;
+#elif defined(FA_KERNEL_VARLEN_KVCACHE) && defined(FA_KERNEL_VARLEN_WINDOW)
+fa_fwd_kernel_varlen_kvcache_window(const KernelArgsVarlenKVCacheWindow wa) {
+    const KernelArgsVarlenKVCache &qa = wa.a;
 #elif defined(FA_KERNEL_VARLEN_KVCACHE)
 fa_fwd_kernel_varlen_kvcache(const KernelArgsVarlenKVCache qa) {
+#elif defined(FA_KERNEL_VARLEN_WINDOW)
+fa_fwd_kernel_varlen_window(const KernelArgsVarlenWindow wa) {
+    const KernelArgsVarlenQK &qa = wa.a;
 #else
 fa_fwd_kernel_varlen(const KernelArgsVarlenQK qa) {
 #endif
@@ -570,6 +608,7 @@ fa_fwd_kernel(const KernelArgs args) {
     using vec8 = typename E::vec8;
     using TR = FwdTraits<DT, QT, NWAVES, BC, SWZ, EAGER, OPT, PIPE, DMA, MASK, D, KSPLIT>;
     enum : bool { FP8 = FA_FP8_CACHE };      // K / V are e4m3fn bytes (fa_fwd_kernel_varlen_kvcache_fp8 only)
+    enum : bool { WIN = FA_VARLEN_WINDOW };  // a sliding window (the fa_fwd_kernel_varlen*_window forms only)
     static_assert(!FP8 || (D == 128 && BC == 64 && NWAVES == 4), "the fp8 transport is built for 64-key tiles of d_head 128, four waves");
     static_assert(KSPLIT == 1 || (KSPLIT == 2 && NWAVES == 4 && QT == 1 && BC == 64 && DMA && !MASK && D == 128),
                   "the key split is built for (B_r 64, B_c 64, 4 waves)");
@@ -693,7 +732,22 @@ fa_fwd_kernel(const KernelArgs args) {
     const int S_len = FA_SEQ_LEN;
     const int wg_row0 = qb * TR::kBr;
     int n_kv_ = FA_N_KV_BLOCKS;
-    if (MASK && args.causal) {
+#ifdef FA_KERNEL_VARLEN_WINDOW
+    // the window's distances: unbounded, or beyond what any position reaches, is FAR (the host: lengths <= 2^30 - 128, so a
+    // position lies in (-2^30, 2^30) and position -+ distance stays inside 32 bits)
+    constexpr int FAR = 1 << 30;
+    const int w_left = wa.left < 0 || wa.left > FAR ? FAR : wa.left;
+    const int w_right = wa.right < 0 || wa.right > FAR ? FAR : wa.right;
+    // the workgroup's key range: from its first row's floor to its last row's ceiling (both bounds grow with the row)
+    const int wg_last_row = (wg_row0 + TR::kBr < q_len ? wg_row0 + TR::kBr : q_len) - 1;
+    const int wg_hi = FA_SHIFTED(wg_last_row) + w_right < S_len - 1 ? FA_SHIFTED(wg_last_row) + w_right : S_len - 1;   // (< 0: no key at all)
+    const int wg_lo = FA_SHIFTED(wg_row0) - w_left > 0 ? FA_SHIFTED(wg_row0) - w_left : 0;   // (<= wg_hi wherever wg_hi >= 0)
+    n_kv_ = wg_hi < 0 ? 0 : (int)((unsigned)wg_hi / BC) + 1;
+    const int n_vis = n_kv_ - (int)((unsigned)wg_lo / BC);   // tiles wg_hi / 64 down to wg_lo / 64
+#else
+    constexpr int wg_lo = 0;   // (no floor: floor_row)
+#endif
+    if (!WIN && MASK && args.causal) {
         const int last_row = (wg_row0 + TR::kBr < FA_Q_LEN ? wg_row0 + TR::kBr : FA_Q_LEN) - 1;
 #ifdef FA_KERNEL_VARLEN
         const int need = FA_SHIFTED(last_row) < 0 ? 0 : FA_SHIFTED(last_row) / BC + 1;   // (no key at all: len_q - len_k rows or more above)
@@ -743,10 +797,12 @@ fa_fwd_kernel(const KernelArgs args) {
     // V(it+2) -- but K tiles still come in visit order, each once, so kc_offset / kc_step and the table entry's lead (requested
     // behind one K request, used by the next) stand as they are; only the V rule is derived again.  V0 and V1 are requested
     // right behind their own K: kc_last.  V(j), j >= 2, is requested in visit j - 2 behind K(j + 1) if that tile exists
-    // (j + 1 < n_kv): the last K request is one tile ahead and V's base is kc_prev; else K(j) was the walk's last request (K(n_kv - 1)
-    // was requested in visit n_kv - 4 or in the prologue, and nothing since): kc_last.  K2, requested between V1 and V2, moves K1's base
+    // (j + 1 < n): the last K request is one tile ahead and V's base is kc_prev; else K(j) was the walk's last request (K(n - 1)
+    // was requested in visit n - 4 or in the prologue, and nothing since): kc_last.  K2, requested between V1 and V2, moves K1's base
     // out of (kc_last, kc_prev) only after V1 has used it.  One pair of bases serves both orders: the DMA's rule with its
-    // `it > 0` read `it >= 2` (load_v), and no counter of V's own.
+    // `it > 0` read `it >= 2` (load_v), and no counter of V's own.  (n: the visit count, FA_N_VISITS.)
+    // WIN: the walk starts at the top tile as ever and ends at the floor tile; kc_step's look-ahead stops at that tile's page
+    // (kc_page_lo), so the entry of a page wholly below the workgroup's floor is never read.
     typedef const __attribute__((address_space(4))) int32_t *kc_table_ptr;
     const int kc_tpp = qa.tiles_per_page;
     int kc_page = (n_kv - 1) / kc_tpp;
@@ -754,6 +810,11 @@ fa_fwd_kernel(const KernelArgs args) {
     const bool kc_paged = qa.block_table != nullptr;
     const kc_table_ptr kc_row = (kc_table_ptr)(unsigned long long)(qa.block_table + (int64_t)b * qa.bt_stride);
     int kc_cur = kc_paged ? kc_row[kc_page] : b;   // (contiguous cache: the "page" is the batch entry)
+#ifdef FA_KERNEL_VARLEN_WINDOW
+    const int kc_page_lo = (int)((unsigned)wg_lo / BC) / kc_tpp;   // the floor tile's page: no entry below it is read
+#else
+    constexpr int kc_page_lo = 0;
+#endif
     int64_t kc_last = 0, kc_prev = 0;
     auto kc_offset = [&]() {   // the next K tile's offset (elements): the entry clamped to a page of the cache
         const int p = kc_cur < 0 ? 0 : (kc_cur >= qa.num_pages ? qa.num_pages - 1 : kc_cur);
@@ -768,15 +829,24 @@ fa_fwd_kernel(const KernelArgs args) {
         }
         kc_tip = kc_tpp - 1;
         --kc_page;
-        if (kc_paged && kc_page >= 0) kc_cur = kc_row[kc_page];
+        if (kc_paged && kc_page >= kc_page_lo) kc_cur = kc_row[kc_page];
     };
 #endif
     f32x4 abl_dummy[2 * DMA_PER_WAVE];  // ABL & 32 only: landing registers of plain loads
     // MASK: rows of the last sequence block that lie beyond seq_len are fetched from the last
     // valid row instead (their logits are masked, their P is exactly 0).
+    // WIN: the floor tile is ragged from below -- its rows below the workgroup's floor are fetched from the floor's row
+    // (floor_row), and it takes the ragged path even when all 64 rows are valid.  A tile may be clamped at both ends.
     auto ragged_rows = [&](int it) -> int {  // valid rows of visit it's tile if it is ragged, else 0
         const int kv0 = (n_kv - 1 - it) * BC;
+        if constexpr (WIN) {
+            if (kv0 < wg_lo) return kv0 + BC > S_len ? S_len - kv0 : BC;
+        }
         return (MASK && kv0 + BC > S_len) ? S_len - kv0 : 0;
+    };
+    auto floor_row = [&](int it) -> int {  // first fetched row of visit it's tile (WIN; < valid: wg_lo <= wg_hi < S_len)
+        const int kv0 = (n_kv - 1 - it) * BC;
+        return wg_lo > kv0 ? wg_lo - kv0 : 0;
     };
     auto issue_k = [&](int it, int stage) {
 #ifdef FA_KERNEL_VARLEN_KVCACHE
@@ -791,6 +861,7 @@ fa_fwd_kernel(const KernelArgs args) {
             for (int j = 0; j < DMA_PER_WAVE; ++j) {
                 int row = RPP * (wave + NWAVES * j) + k_row_in_piece;
                 row = row < valid ? row : valid - 1;
+                if constexpr (WIN) row = row < floor_row(it) ? floor_row(it) : row;
                 const unsigned off = (unsigned)(((int64_t)row * FA_KV_SS32 + (((lane & (CPR - 1)) ^ k_swz) << 3)) * 2);
                 glds16_sv(base, off, kdst + (wave + NWAVES * j) * 1024);
             }
@@ -813,7 +884,7 @@ fa_fwd_kernel(const KernelArgs args) {
     auto issue_v = [&](int it, int stage) {
 #ifdef FA_KERNEL_VARLEN_KVCACHE
         // V(it) follows K(it + 1) except in the prologue and at the last tile: then K(it) was the last K request
-        const kv_elem *base = Vg + ((it > 0 && it + 1 < n_kv) ? kc_prev : kc_last);
+        const kv_elem *base = Vg + ((it > 0 && it + 1 < FA_N_VISITS) ? kc_prev : kc_last);
 #else
         const kv_elem *base = Vg + (int64_t)(n_kv - 1 - it) * tile_stride;
 #endif
@@ -825,6 +896,7 @@ fa_fwd_kernel(const KernelArgs args) {
                 const int sub = 2 * (wave + NWAVES * j) + v_sub_in_piece;
                 int row = 8 * (sub / DSUB) + (int)v_lane_row;
                 row = row < valid ? row : valid - 1;
+                if constexpr (WIN) row = row < floor_row(it) ? floor_row(it) : row;
                 const unsigned off = (unsigned)(((int64_t)row * FA_KV_SS32 + (sub % DSUB) * 32 + v_lane_d) * 2);
                 glds16_sv(base, off, vdst + (wave + NWAVES * j) * 1024);
             }
@@ -870,6 +942,7 @@ fa_fwd_kernel(const KernelArgs args) {
             for (int j = 0; j < ST_PER_WAVE; ++j) {
                 int row = ST_ROWS * (wave + NWAVES * j) + st_r;
                 row = row < valid ? row : valid - 1;
+                if constexpr (WIN) row = row < floor_row(it) ? floor_row(it) : row;
                 reg[j] = *(const f32x4 *)(tile + ((int64_t)row * FA_ST_SS32 + st_c * (16 / ST_ESZ)) * ST_ESZ);
             }
             return;
@@ -883,7 +956,7 @@ fa_fwd_kernel(const KernelArgs args) {
         load_tile(Kg + kc_offset(), it, kreg);
         kc_step();
     };
-    auto load_v = [&](int it) { load_tile(Vg + ((it >= 2 && it + 1 < n_kv) ? kc_prev : kc_last), it, vreg); };
+    auto load_v = [&](int it) { load_tile(Vg + ((it >= 2 && it + 1 < FA_N_VISITS) ? kc_prev : kc_last), it, vreg); };
 #else
     auto load_k = [&](int it) { load_tile(Kg, it, kreg); };
     auto load_v = [&](int it) { load_tile(Vg, it, vreg); };
@@ -980,6 +1053,33 @@ fa_fwd_kernel(const KernelArgs args) {
 
     // ---- MASK: logits of keys >= seq_len, or above the causal diagonal, become -inf ---------
     const int wave_row0 = wg_row0 + wave_r * TR::kRowsPerWave;
+#ifdef FA_KERNEL_VARLEN_WINDOW
+    // WIN: a tile needs the mask if it reaches above the ceiling of the wave's first row (the lowest ceiling: this covers the
+    // keys >= len_k too) or below the floor of its last row (the highest floor); a tile inside every row's window does not.
+    // mask_S finds each row's two bounds again from the row (nothing more is carried across the loop).
+    auto tile_needs_mask = [&](int it) -> bool {  // wave-uniform
+        const int kv0 = (n_kv - 1 - it) * BC;
+        const int p0 = FA_SHIFTED(wave_row0);
+        const int hi_first = p0 + w_right < S_len - 1 ? p0 + w_right : S_len - 1;
+        return kv0 + BC - 1 > hi_first || kv0 < p0 + (TR::kRowsPerWave - 1) - w_left;
+    };
+    auto mask_S = [&](f32x16 (&S)[QT][NTW], int it) {
+        const int kv0 = (n_kv - 1 - it) * BC;
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt) {
+            const int p = FA_SHIFTED(wave_row0 + qt * 32 + r31);
+            const int hi_r = p + w_right < S_len - 1 ? p + w_right : S_len - 1;   // last live key (< lo_r: a row that sees none)
+            const int lo_r = p - w_left;                                          // first live key (keys are not negative: no clamp at 0)
+#pragma unroll
+            for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int key = kv0 + 32 * (NT0 + nt) + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    S[qt][nt][r] = (key < lo_r || key > hi_r) ? -__builtin_inff() : S[qt][nt][r];
+                }
+        }
+    };
+#else
     auto tile_needs_mask = [&](int it) -> bool {  // wave-uniform
         const int kv0 = (n_kv - 1 - it) * BC;
         return MASK && (kv0 + BC > S_len || (args.causal && kv0 + BC - 1 > FA_SHIFTED(wave_row0)));
@@ -999,6 +1099,7 @@ fa_fwd_kernel(const KernelArgs args) {
                 }
         }
     };
+#endif
     // a row whose keys were all masked so far has m = -inf: exponentiate against 0 instead
     auto finite_or_zero = [&](float mval) { return (MASK && mval == -__builtin_inff()) ? 0.0f : mval; };
 
@@ -1179,15 +1280,15 @@ fa_fwd_kernel(const KernelArgs args) {
             wait_and_barrier();
             FA_STAMP(it, 1);
             if (DMA) {
-                if (it + 2 < n_kv) issue_k(it + 2, it & 1);
-                if (it + 1 < n_kv) issue_v(it + 1, (it + 1) & 1);
+                if (it + 2 < FA_N_VISITS) issue_k(it + 2, it & 1);
+                if (it + 1 < FA_N_VISITS) issue_v(it + 1, (it + 1) & 1);
             } else {
                 // registers hold K(it+2), V(it+1) (loaded during the previous visit); their
                 // LDS stages were freed by the barrier above.  Then start K(it+3), V(it+2).
-                if (it + 2 < n_kv) store_k(it & 1);
-                if (it + 1 < n_kv) store_v((it + 1) & 1);
-                if (it + 3 < n_kv) load_k(it + 3);
-                if (it + 2 < n_kv) load_v(it + 2);
+                if (it + 2 < FA_N_VISITS) store_k(it & 1);
+                if (it + 1 < FA_N_VISITS) store_v((it + 1) & 1);
+                if (it + 3 < FA_N_VISITS) load_k(it + 3);
+                if (it + 2 < FA_N_VISITS) load_v(it + 2);
             }
             // scale_l_O (softmax.cuh:36-49) with the new running max
             float neg_msc[QT], rowsum[QT];
@@ -1260,7 +1361,7 @@ fa_fwd_kernel(const KernelArgs args) {
         };
         if (DMA) {
             wait_and_barrier();  // K(0), V(0) landed
-            if (n_kv > 1) issue_k(1, 1);
+            if (FA_N_VISITS > 1) issue_k(1, 1);
             qk(0, Sa);
             if (MASK && tile_needs_mask(0)) mask_S(Sa, 0);
             row_max(Sa);
@@ -1274,7 +1375,7 @@ fa_fwd_kernel(const KernelArgs args) {
             // (published by that visit's barrier), registers hold K(it+2), V(it+1).
             store_k(0);
             store_v(0);
-            if (n_kv > 1) { load_k(1); load_v(1); }
+            if (FA_N_VISITS > 1) { load_k(1); load_v(1); }
             barrier();
             qk(0, Sa);
             if (MASK && tile_needs_mask(0)) mask_S(Sa, 0);
@@ -1283,15 +1384,15 @@ fa_fwd_kernel(const KernelArgs args) {
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) m[qt] = mx[qt];
             }
-            if (n_kv > 1) store_k(1);
-            if (n_kv > 2) load_k(2);
+            if (FA_N_VISITS > 1) store_k(1);
+            if (FA_N_VISITS > 2) load_k(2);
         }
         int it = 0;
-        for (; it + 2 < n_kv; it += 2) {
+        for (; it + 2 < FA_N_VISITS; it += 2) {
             visit(it, Sa, Sb, FalseTag{});
             visit(it + 1, Sb, Sa, FalseTag{});
         }
-        if (it + 2 == n_kv) {
+        if (it + 2 == FA_N_VISITS) {
             visit(it, Sa, Sb, FalseTag{});
             visit(it + 1, Sb, Sa, TrueTag{});
         } else {
@@ -1305,14 +1406,14 @@ fa_fwd_kernel(const KernelArgs args) {
             wait_and_barrier();  // tile `it` landed for every wave; stage^1 free again
             FA_STAMP(it, 1);
             if (DMA) {
-                if (it + 1 < n_kv) {
+                if (it + 1 < FA_N_VISITS) {
                     issue_k(it + 1, stage ^ 1);
                     issue_v(it + 1, stage ^ 1);
                 }
             } else {
                 // registers hold tile it+1 (loaded during the previous visit)
-                if (it + 1 < n_kv) { store_k(stage ^ 1); store_v(stage ^ 1); }
-                if (it + 2 < n_kv) { load_k(it + 2); load_v(it + 2); }
+                if (it + 1 < FA_N_VISITS) { store_k(stage ^ 1); store_v(stage ^ 1); }
+                if (it + 2 < FA_N_VISITS) { load_k(it + 2); load_v(it + 2); }
             }
             f32x16 S[QT][NTW];
             vec8 P[QT][NTW][2];
@@ -1333,12 +1434,12 @@ fa_fwd_kernel(const KernelArgs args) {
         if (!DMA) {
             store_k(0);
             store_v(0);
-            if (n_kv > 1) { load_k(1); load_v(1); }
+            if (FA_N_VISITS > 1) { load_k(1); load_v(1); }
         }
         if (OPT) visit(0, TrueTag{}); else visit(0, FalseTag{});
-        for (int it = 1; it < n_kv; ++it) visit(it, FalseTag{});
+        for (int it = 1; it < FA_N_VISITS; ++it) visit(it, FalseTag{});
     } else {
-        for (int it = 0; it < n_kv; ++it) {
+        for (int it = 0; it < FA_N_VISITS; ++it) {
             if (it > 0) barrier();  // everyone done reading the single stage
             issue_k(it, 0);
             issue_v(it, 0);

@@ -1,0 +1,25 @@
+// fa_inst_varlen_window.hip -- the forward over packed variable-length sequences under a sliding window
+// (fa_fwd_kernel_varlen_window; fa_fwd_launch_varlen_qk_window), one translation unit per dtype (-DFA_INST_DT=<5|15>).
+// FA_KERNEL_VARLEN_WINDOW beside FA_KERNEL_VARLEN makes fa_fwd_kernel.hpp define that kernel from the text of
+// fa_fwd_kernel_varlen (which this unit then does not have): the same two forms, with and without the first-block skip,
+// compiled with the varlen slices' flags.  A slice of its own: the unwindowed slice keeps its two kernels and its code.  The
+// varlen form's LDS (varlen_lds_bytes_dt15).  Not in the registry.
+#define FA_KERNEL_VARLEN
+#define FA_KERNEL_VARLEN_WINDOW
+#include "fa_fwd_kernel.hpp"
+
+#ifndef FA_INST_DT
+#error "define FA_INST_DT (5 = fp16, 15 = bf16)"
+#endif
+
+namespace fa {
+
+#define FA_CAT2(a, b) a##b
+#define FA_CAT(a, b) FA_CAT2(a, b)
+kernel_fn_varlen_window FA_CAT(varlen_window_kernel_dt, FA_INST_DT)(bool first_block_skip) {
+    //                                                         DT          QT NW BC  SWZ   EAGER OPT   PIPE  DMA   MASK  D
+    if (first_block_skip) return &fa_fwd_kernel_varlen_window<FA_INST_DT, 1, 4, 64, true, true, true, true, true, true, 128>;
+    return &fa_fwd_kernel_varlen_window<FA_INST_DT, 1, 4, 64, true, true, false, true, true, true, 128>;
+}
+
+}  // namespace fa

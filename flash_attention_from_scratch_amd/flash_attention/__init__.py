@@ -90,7 +90,8 @@ def attention(q, k, v, causal=False):
     return _Attention.apply(q, k, v, causal)
 
 
-def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None):
+def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None, *,
+                   window_size=(-1, -1)):
     """Packed variable-length sequences: q (total_tokens, n_heads, 128), k / v (total_tokens, n_kv_heads, 128), cu_seqlens an
     int32 device tensor of n_seqs + 1 row offsets, max_seqlen a Python int (no device sync) -> (o, lse[, ms]) with lse fp32
     (n_heads, total_tokens).  A query attends to the keys of its own sequence (causal: at or before its position in it).
@@ -98,9 +99,14 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
     With cu_seqlens_k and max_seqlen_k (both or neither: one alone is a ValueError) Q and K / V have lengths of their own:
     cu_seqlens / max_seqlen are Q's, k / v are (total_k, n_kv_heads, 128) with sequence i's keys at rows cu_seqlens_k[i] ..
     cu_seqlens_k[i + 1] - 1, any lengths >= 0 on either side.  causal is then bottom-right aligned (forward_kvcache's and
-    flash-attn's rule): query r sees keys j <= r + (len_k - len_q); a row that sees no key gives o = 0, lse = -inf."""
+    flash-attn's rule): query r sees keys j <= r + (len_k - len_q); a row that sees no key gives o = 0, lse = -inf.
+
+    Sliding-window (local) attention: window_size=(left, right), keyword only, two Python ints, -1 = unbounded.
+    Query row r, at position p = r + (len_k - len_q), sees the keys max(0, p - left) .. min(len_k - 1, p + right); causal means
+    right = 0; bad values are a ValueError.  (-1, -1) is the call above, unchanged.  FORWARD ONLY: backward_varlen and
+    attention_varlen take no window (open) -- do not feed them a windowed forward's o and lse."""
     return flash_attention_kernels.forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=causal, timed=timed,
-                                                  cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
+                                                  cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k, window_size=window_size)
 
 
 def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
@@ -138,7 +144,7 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
 
 
 def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table=None, causal=False,
-                           max_seqlen_k=None, timed=False, k_descale=None, v_descale=None):
+                           max_seqlen_k=None, timed=False, k_descale=None, v_descale=None, *, window_size=(-1, -1)):
     """Prefill against a K / V cache (flash-attn's flash_attn_varlen_func(..., block_table=)): chunked prefill
     behind a cached prefix, prompts behind a shared prefix, verification of more rows than forward_kvcache serves.  q
     (total_q, n_heads, 128) holds the query rows of all sequences packed, sequence i's at rows cu_seqlens_q[i] ..
@@ -155,10 +161,18 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
     Key j of sequence b (the sequence index, for a paged cache too), K / V head h stands for float(k8[j]) * k_descale[b, h],
     likewise V, and the result is the 16-bit call's on those values.  Note the asymmetry with forward_kvcache, where a missing
     descale means 1: here an fp8 cache with either descale missing is refused -- pass ones for an unscaled cache.  A descale with
-    a 16-bit cache, caches of two dtypes and fp8 encodings other than e4m3fn are refused."""
+    a 16-bit cache, caches of two dtypes and fp8 encodings other than e4m3fn are refused.
+
+    Sliding-window (local) attention (forward_kvcache's window_size, so a model with local layers prefills and
+    decodes by one rule): window_size=(left, right), keyword only, two Python ints, -1 = unbounded.  Query row r of sequence b, at
+    position p = r + (len_k - len_q), sees the keys max(0, p - left) .. min(len_k - 1, p + right); causal means right = 0 (causal
+    with another bounded right is a ValueError, like values below -1).  (-1, -1) is the call above, unchanged.  Each block of 128
+    query rows visits only the key tiles of its rows' windows; no cache row, page or block_table entry wholly below
+    max(0, len_k - len_q - left) is read, so such rows and pages may be stale, freed or reused.  Both cache types, paged and
+    contiguous; bit for bit forward_varlen(cu_seqlens_k=, window_size=) on the same keys packed."""
     return flash_attention_kernels.forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens,
                                                           block_table=block_table, causal=causal, max_seqlen_k=max_seqlen_k, timed=timed,
-                                                          k_descale=k_descale, v_descale=v_descale)
+                                                          k_descale=k_descale, v_descale=v_descale, window_size=window_size)
 
 
 def append_kvcache(k_cache, v_cache, k, v, cache_seqlens, block_table=None, q=None, rotary_cos=None, rotary_sin=None,

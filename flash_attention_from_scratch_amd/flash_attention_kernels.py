@@ -345,7 +345,8 @@ def _varlen_layouts(q, k, cu_seqlens, max_seqlen, cu_seqlens_k, max_seqlen_k):
             _capi.make_varlen_layout(cu_seqlens_k.data_ptr(), n_seqs, k.shape[0], max(max_seqlen_k, 1)))
 
 
-def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None):
+def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None, *,
+                   window_size=(-1, -1)):
     """Attention over packed sequences with the row log-sum-exp (fa_fwd_launch_varlen): q (total_tokens, n_heads, 128), k and v
     (total_tokens, n_kv_heads, 128), cu_seqlens an int32 device tensor of n_seqs + 1 row offsets, max_seqlen a Python int.
     Strided views (a packed QKV buffer) pass as they are.  -> (o, lse[, ms]); o contiguous, lse fp32 (n_heads, total_tokens).
@@ -356,7 +357,14 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
     with sequence i's keys at rows cu_seqlens_k[i] .. cu_seqlens_k[i + 1] - 1.  Any lengths >= 0 on either side.  causal is then
     BOTTOM-RIGHT aligned, as in forward_kvcache and flash-attn: query r of a sequence sees keys j <= r + (len_k - len_q).  A row
     that sees no key (len_k = 0; causal rows r < len_q - len_k) gives o = 0 and lse = -inf.  Left at None: k and v share
-    cu_seqlens and max_seqlen (the same kernel with one range for both sides)."""
+    cu_seqlens and max_seqlen (the same kernel with one range for both sides).
+
+    window_size=(left, right), keyword only, Python ints, -1 = unbounded (flash-attn's): query row r of a sequence, at position
+    p = r + (len_k - len_q), sees the keys max(0, p - left) .. min(len_k - 1, p + right); causal means right = 0.  (-1, -1) takes
+    the entry points above unchanged, anything else fa_fwd_launch_varlen_qk_window (one range given: on both sides), which visits
+    no key tile outside a Q block's window and fetches no key row below it.  Bad values are a ValueError.  FORWARD ONLY:
+    backward_varlen and attention_varlen take no window, and the gradients of a windowed forward are not theirs."""
+    window = _window(window_size, causal)
     qk = _qk_sides(cu_seqlens_k, max_seqlen_k)
     _check_varlen(q, k, v, cu_seqlens, max_seqlen, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
     total, n_heads, d_head = q.shape
@@ -374,6 +382,11 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
     opts = _capi.make_opts(causal=causal, ms=ms if timed else None)
     with torch.cuda.device(q.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        if window is not None:
+            w = _capi.make_window(*window)
+            _capi.check(lib.fa_fwd_launch_varlen_qk_window(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(sides[0]), ctypes.byref(sides[-1]),
+                                                           ctypes.byref(w), ctypes.byref(opts), ctypes.c_void_p(lse.data_ptr()), stream))
+            return (o, lse, float(ms.value)) if timed else (o, lse)
         launch = lib.fa_fwd_launch_varlen_qk if qk else lib.fa_fwd_launch_varlen
         _capi.check(launch(ctypes.byref(args), ctypes.byref(kv), *(ctypes.byref(s) for s in sides), ctypes.byref(opts),
                            ctypes.c_void_p(lse.data_ptr()), stream))
@@ -746,7 +759,7 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
 
 
 def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table=None, causal=False,
-                           max_seqlen_k=None, timed=False, k_descale=None, v_descale=None):
+                           max_seqlen_k=None, timed=False, k_descale=None, v_descale=None, *, window_size=(-1, -1)):
     """Prefill against a K / V cache (fa_fwd_launch_varlen_kvcache): forward_varlen(cu_seqlens_k=) whose keys are read from the
     cache in place.  q (total_q, n_heads, 128) packed, cu_seqlens_q an int32 device tensor of n_seqs + 1 row offsets, max_seqlen_q
     a Python int; k_cache, v_cache (n_seqs, seqlen_cache, n_kv_heads, 128), or with block_table (n_seqs, max_pages_per_seq) int32 on
@@ -758,7 +771,14 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
     (n_seqs, n_kv_heads) on q's device, last dimension contiguous, never read by the host; key j of sequence b (the sequence, also
     for a paged cache) and K / V head h stands for float(k8[j]) * k_descale[b, h], likewise V.  Unlike forward_kvcache, where None
     means 1, an fp8 cache with a descale missing is refused here: pass tensors of ones for an unscaled cache.  A descale with a
-    16-bit cache is refused."""
+    16-bit cache is refused.
+    window_size=(left, right), keyword only, Python ints, -1 = unbounded: forward_kvcache's rule with len_q for seqlen_q -- query
+    row r of sequence b, at position p = r + (len_k - len_q), sees the keys max(0, p - left) .. min(len_k - 1, p + right); causal
+    means right = 0.  (-1, -1) takes the entry points above unchanged, anything else fa_fwd_launch_varlen_kvcache_window /
+    fa_fwd_launch_varlen_kvcache_fp8_window: a Q block visits only the key tiles of its rows' windows, and no cache row, page
+    or block_table entry wholly below the sequence's lowest visible key max(0, len_k - len_q - left) is read.  Bad values are a
+    ValueError, before any tensor is looked at."""
+    window = _window(window_size, causal)
     tensors = [(q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cu_seqlens_q, "cu_seqlens_q"), (cache_seqlens, "cache_seqlens")]
     if block_table is not None:
         tensors.append((block_table, "block_table"))
@@ -817,14 +837,17 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
         ms = ctypes.c_float(0.0)
         opts = _capi.make_opts(causal=causal, ms=ms if timed else None)
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        # (a window goes in front of opts, and picks the entry point's _window form)
+        w = [ctypes.byref(_capi.make_window(*window))] if window is not None else []
+        tail = w + [ctypes.byref(opts), ctypes.c_void_p(lse.data_ptr()), stream]
         if fp8:
             sc = _capi.make_kvcache_fp8_scales(k_descale=k_descale.data_ptr(), v_descale=v_descale.data_ptr(),
                                                descale_batch_stride=k_descale.stride(0))
-            _capi.check(lib.fa_fwd_launch_varlen_kvcache_fp8(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(vq), ctypes.byref(kc),
-                                                             ctypes.byref(sc), ctypes.byref(opts), ctypes.c_void_p(lse.data_ptr()), stream))
+            launch = lib.fa_fwd_launch_varlen_kvcache_fp8_window if w else lib.fa_fwd_launch_varlen_kvcache_fp8
+            _capi.check(launch(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(vq), ctypes.byref(kc), ctypes.byref(sc), *tail))
         else:
-            _capi.check(lib.fa_fwd_launch_varlen_kvcache(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(vq), ctypes.byref(kc),
-                                                         ctypes.byref(opts), ctypes.c_void_p(lse.data_ptr()), stream))
+            launch = lib.fa_fwd_launch_varlen_kvcache_window if w else lib.fa_fwd_launch_varlen_kvcache
+            _capi.check(launch(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(vq), ctypes.byref(kc), *tail))
     return (o, lse, float(ms.value)) if timed else (o, lse)
 
 

@@ -747,6 +747,43 @@ int64_t fa_decode_fp8_window_workspace_bytes(const fa_decode_fp8_args *args, con
 int fa_decode_fp8_window_launch(const fa_decode_fp8_args *args, const fa_window *window, void *stream, float *ms);
 
 /*
+ * The same window for the step before decode: the packed forward with separate Q and K / V lengths and both prefills against a
+ * cache.  Each entry takes its unwindowed sibling's arguments (fa_fwd_launch_varlen_qk, fa_fwd_launch_varlen_kvcache,
+ * fa_fwd_launch_varlen_kvcache_fp8) and an fa_window in front of opts.  For sequence b, len_q and len_k are clamped as the
+ * sibling clamps them; query row r sits at position p = r + (len_k - len_q) and sees key j iff
+ *     max(0, p - left) <= j <= min(len_k - 1, p + right);
+ * opts->causal means right = 0 (causal with right > 0 is refused; right = -1 or 0 may accompany it).  A row that sees no key
+ * (p + right < 0) gives o = 0 and lse = -inf.  (-1, -1), or any window that reaches every key, gives the unwindowed entry's
+ * bits; the three entries give one another's bits on the same keys, as their siblings do.  Grid, strides, descales, lse,
+ * determinism, graph capture: the sibling's.  One launch, no split, no workspace.  Forward only: the backward entry points take
+ * no window.
+ *
+ * Clamping, extended downwards.  A workgroup owns 128 query rows r0 .. r1 of one (sequence, head) and visits only the 64-key
+ * tiles from its last row's upper bound down to its first row's lower bound lo_r0 = max(0, r0 + len_k - len_q - left), which
+ * is at least the sequence's lo_b = max(0, len_k - len_q - left) (0 for left = -1).  No key below lo_r0 is fetched, and no
+ * block_table entry of a page that lies wholly below it is read; a lane whose key would fall below lo_r0 fetches key lo_r0
+ * (the same tile, the same page) and is masked, as a lane at or beyond len_k fetches len_k - 1.  So stale rows, freed or
+ * reused pages and garbage table entries below lo_b cannot reach a result, nor can packed key rows of the sequence below it.
+ *
+ * Served (fa_fwd_varlen_*_window_supported): what the sibling serves.  Refused before any HIP call: what the sibling refuses,
+ * first and with its message; then a null fa_window (FA_ERR_NULL); its struct_size, left or right below -1, causal with right >
+ * 0, and a key bound (the cache's capacity; packed: the key side's max_seqlen) or the query side's max_seqlen above
+ * 2^30 - 128 (FA_ERR_SHAPE: the kernel adds positions and distances in 32 bits).  total_q = 0 returns FA_OK without a device.
+ */
+int fa_fwd_varlen_qk_window_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_qk_window(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                   const fa_varlen_layout *varlen_k, const fa_window *window, const fa_fwd_opts *opts, float *lse,
+                                   void *stream);
+int fa_fwd_varlen_kvcache_window_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_kvcache_window(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                        const fa_kvcache_layout *cache, const fa_window *window, const fa_fwd_opts *opts, float *lse,
+                                        void *stream);
+int fa_fwd_varlen_kvcache_fp8_window_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_kvcache_fp8_window(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                            const fa_kvcache_layout *cache, const fa_kvcache_fp8_scales *scales,
+                                            const fa_window *window, const fa_fwd_opts *opts, float *lse, void *stream);
+
+/*
  * The step in front of a decode: append seqlen_new new K / V rows per batch entry to the cache IN PLACE, at the positions the
  * device-side lengths name, optionally rotate the new keys and the query (rotary embedding), quantize for an fp8 cache, and
  * advance the lengths.  One kernel on `stream`; the host reads none of the device arrays, so the launch is asynchronous and
