@@ -30,6 +30,13 @@ n_leaks = 2 when lo_r >= 1, else 1: with lo_r = 0 the one-sided formula above.  
 every row's two edges, lo_min = max(0, n_k - n_q - left) and the key above it, the unit, tile, page and split boundaries counted
 from lo_min's tile; assign_window_targets gives a position only to a row whose window holds it.
 
+The backward's inputs (the section "the backward's cells" at the end; tests/test_backward_beacon_gpu.py): the backward works in
+(row range x key range) pairs, so assign_cell_targets puts a target into every live (32-row band, 32-key cell) pair under the
+shifted diagonal (backward_cells), neighbouring rows' target scores lie BETA_STEP above and below the balanced beta_r, so that a
+row's lse differs from its neighbour's, and beacon_dout adds to seeded noise a component along v[t_r] - o32_r, so that
+|dS32[r, t_r]| >= DS_FLOOR on every targeted row (target_ds).  reference_backward is the explicit fp32 backward with hooks for
+the CPU proof's mutants, and grad_rule the gradient rule of tests/test_backward_gpu.py for one sequence.
+
 Nothing here reads the code under test: the positions come from the sizes the kernels are documented to use (64-key tiles,
 32-key units, 128-row blocks, pages, the split rule 64 floor(n_tiles s / num_splits), under a window
 64 (tl + floor((n_tiles - tl) s / num_splits)) with tl = lo_min / 64).  Plain helper module: no tests, no
@@ -85,10 +92,11 @@ def beacon_kv(n_k, dtype, n_alloc=None, seed=0, device="cpu"):
     return (sign * (a / math.sqrt(D))).to(dtype), v.to(dtype)
 
 
-def beacon_q(k, n_k, targets, diag, dtype, seed=0, lo=None):
+def beacon_q(k, n_k, targets, diag, dtype, seed=0, lo=None, beta_shift=None):
     """Query rows for one K / V head's beacons: k (>= n_k + 1, 128) from beacon_kv; targets and diag int64 (n_q,) on k's
     device, targets[r] in [0, diag[r]] or -1, diag[r] in [-inf, n_k - 1] (< 0: the row sees no key).  lo: int64 (n_q,), the
-    first key each row sees (a two-sided window: targets[r] in [lo[r], diag[r]], and a second leak towards key lo[r] - 1)."""
+    first key each row sees (a two-sided window: targets[r] in [lo[r], diag[r]], and a second leak towards key lo[r] - 1).
+    beta_shift: (n_q,), added to the balanced beta_r (the backward's inputs: neighbouring rows with different lse)."""
     device = k.device
     gen = torch.Generator(device=device).manual_seed(seed)
     n_q = targets.numel()
@@ -112,6 +120,8 @@ def beacon_q(k, n_k, targets, diag, dtype, seed=0, lo=None):
         big_l = torch.log((diag - lo).clamp_min(1).double()) + 0.5 * NOISE ** 2 * beta_k / math.sqrt(D)
         kappa = (1.0 + LEAK ** 2 * (1 + below[:, 0].double())) / (2.0 * D)
     beta = (1.0 - torch.sqrt(1.0 - 4.0 * kappa * big_l)) / (2.0 * kappa)
+    if beta_shift is not None:
+        beta = beta + beta_shift.to(device).double()
     b = (beta * math.sqrt(D) / math.sqrt(beta_k * math.sqrt(D))).float()[:, None]
     q = torch.where(live[:, None], b * (ut + LEAK * w) + NOISE * z_perp, NOISE * z)
     return q.to(dtype)
@@ -406,3 +416,248 @@ def compare(o, lse, o32, lse32, o16, dtype):
             lse_err = (lse[~inf] - lse32[~inf]).abs().max().item()
     ok = finite and err <= bound and inf_ok and lse_err <= LSE_TOL
     return dict(ok=ok, err=err, bound=bound, lse_err=lse_err, inf_ok=inf_ok)
+
+
+# ---- the backward's cells ("Backward cells") ---------------------------------------------------------------------
+#
+# The backward kernels work in (row range x key range) pairs: a dK / dV workgroup owns a 128-key block, 32 keys per wave, and
+# sweeps 64-row Q / dO tiles in two 32-row halves; a dQ workgroup owns 128 rows, 32 per wave, and sweeps 64-key tiles in 32-key
+# halves.  A 32 x 32 product left out of one accumulator, a diagonal flag wrong for one tile, a delta or lse row
+# read from its neighbour touch only the rows and keys of that cell, so the targets below cover every live (32-row band,
+# 32-key cell) pair, and dout is constructed so that every targeted row carries |dS| >= DS_FLOOR on its target.
+
+CELL = 32                     # rows per wave (dQ) and keys per wave (dK / dV): the accumulator a product can be missing from
+BWD_TILE = 64                 # rows per Q / dO tile of a dK / dV sweep, keys per tile of a dQ sweep
+BWD_BLOCK = 128               # keys per dK / dV workgroup, rows per dQ workgroup
+BETA_STEP = 0.4               # even rows' target scores lie BETA_STEP above the balanced beta_r, odd rows' below: lse differs by about it
+DOUT_ALONG = 0.25             # dout's component along v[t_r] - o32_r, in units of the noise's standard deviation
+DS_FLOOR = 0.375              # |dS32[r, t_r]| of every targeted row that sees two keys or more
+BACKWARD_HEADS = [(4, 4), (8, 2)]
+BACKWARD_VARLEN_PAIRS = [(512, 512), (300, 300), (129, 300), (64, 1)]
+
+
+def backward_cells(n_q, n_k, causal):
+    """The live 32-row x 32-key cells of one sequence under the shifted diagonal -> [(row band i, key cell j, on_diagonal)]:
+    band i holds rows 32 i .. 32 i + 31 (clipped to n_q), cell j keys 32 j .. 32 j + 31 (clipped to n_k); a cell is live when
+    some row of the band sees some key of the cell, and on a diagonal when it holds some live row's last key (without a mask
+    that is key n_k - 1 for every row: the last key cell of every band)."""
+    diag = diagonals(n_q, n_k, causal).tolist()
+    cells = []
+    for i in range((n_q + CELL - 1) // CELL):
+        last = [d for d in diag[CELL * i:CELL * (i + 1)] if d >= 0]
+        if last and n_k:
+            on = {d // CELL for d in last}
+            cells += [(i, j, j in on) for j in range(max(last) // CELL + 1)]
+    return cells
+
+
+def assign_cell_targets(n_q, n_heads, n_k, causal, phase=0):
+    """Targets that cover every live cell -> (targets int64 (n_heads, n_q), -1 on rows that see no key; n_phases).  Under the
+    causal mask head 0 of every live row targets its own diagonal, so every diagonal cell is hit and every key that is some
+    row's diagonal is a target; the (row, head) slots of the other heads are dealt in turn over the key cells of their row band
+    (a slot dealt a cell its row does not see whole -- the band's upper diagonal cell -- takes what it sees of it, or keeps the
+    diagonal).  Without a mask every row's last key is n_k - 1: one slot per band takes it and all heads are dealt.  Inside its
+    cell a slot takes a key still NEEDED -- the keys of the diagonal cells that are no row's diagonal, and keys 0, n_k - 2,
+    n_k - 1 -- if it sees one, else a key that moves with the row and the head.  A band with fewer slots than key cells (a ragged
+    last band) needs several phases: the caller repeats the sequence, one phase each, as for assign_targets.  A causal sequence
+    whose diagonals reach no key of some 128-key block gets one phase more, in which head 1 holds the diagonal and head 0 is dealt,
+    so that every head has targets in every block it sees (a head lost from that block's dK / dV sum shows)."""
+    diag = diagonals(n_q, n_k, causal).tolist()
+    base = [[d if d >= 0 else -1 for d in diag] for _ in range(n_heads)]
+    cells = backward_cells(n_q, n_k, causal)
+    if not cells:
+        return torch.tensor(base, dtype=torch.int64).reshape(n_heads, n_q), 1
+    given = {d for d in diag if d >= 0} if causal else set()
+    needed = _unique_inside([0, n_k - 2, n_k - 1] + [p for _, j, on in cells if on for p in range(CELL * j, CELL * (j + 1))], n_k)
+    needed = [p for p in needed if p not in given]
+    bands = {}
+    for i, j, _ in cells:
+        bands.setdefault(i, []).append(j)
+
+    def head_blocks(t, h):
+        return {x // BWD_BLOCK for x in t[h] if x >= 0}
+
+    seen_blocks = {j * CELL // BWD_BLOCK for _, j, _ in cells}
+    phases, p, n_more, extra = [], 0, 1, False
+    while True:
+        # the diagonal's head: head 0; in the one extra phase a causal sequence gets when head 0's diagonals reach no key of some
+        # 128-key block (n_k - n_q >= 128), head 1, so that head 0 is dealt there
+        own = (1 if extra else 0) if causal else None
+        dealt = [h for h in range(n_heads) if h != own]
+        t = [row[:] for row in base]
+        for i, js in bands.items():
+            rows = [r for r in range(CELL * i, min(CELL * (i + 1), n_q)) if diag[r] >= 0]
+            n_slots = len(rows) * len(dealt)
+            if not n_slots:
+                continue
+            n_more = max(n_more, (len(js) + n_slots - 1) // n_slots)
+            band_needed = [] if causal else [n_k - 1]
+            for s in range(n_slots):          # row after row, the heads' order turning with the row and the band
+                r = rows[s // len(dealt)]
+                h = dealt[(s + s // len(dealt) + i) % len(dealt)]
+                j = js[(s + p * n_slots) % len(js)]
+                lo, hi = CELL * j, min(CELL * j + CELL - 1, diag[r])
+                if hi < lo:
+                    continue
+                pick = None
+                for pool in (band_needed, needed):
+                    pick = next((x for x in pool if lo <= x <= hi), None)
+                    if pick is not None:
+                        pool.remove(pick)
+                        break
+                t[h][r] = pick if pick is not None else lo + (r + 5 * h) % (hi - lo + 1)
+        phases.append(t)
+        p += 1
+        if extra or p >= 64:
+            break
+        if p >= n_more and not needed:
+            if causal and n_heads > 1 and not seen_blocks <= set().union(*(head_blocks(ph, 0) for ph in phases)):
+                extra = True
+                continue
+            break
+    return torch.tensor(phases[phase % len(phases)], dtype=torch.int64).reshape(n_heads, n_q), len(phases)
+
+
+def build_cell_sequence(n_q, n_k, n_heads, n_kv_heads, dtype, causal, phase=0, seed=0, device="cpu", kv=None):
+    """build_sequence with the cell-covering targets -> the same dict, with `cells` (backward_cells) in place of `listed`"""
+    targets, n_phases = assign_cell_targets(n_q, n_heads, n_k, causal, phase)
+    group = n_heads // n_kv_heads
+    if kv is None:
+        pairs = [beacon_kv(n_k, dtype, None, seed * 1000 + 2 * h, device) for h in range(n_kv_heads)]
+        kv = torch.stack([p[0] for p in pairs], dim=1), torch.stack([p[1] for p in pairs], dim=1)
+    k, v = kv
+    diag = diagonals(n_q, n_k, causal, device)
+    step = BETA_STEP * (1.0 - 2.0 * (torch.arange(n_q, device=device) % 2))
+    q = torch.stack([beacon_q(k[:, h // group], n_k, targets[h].to(device), diag, dtype, seed * 1000 + 2 * h + 1 + 7919 * phase,
+                              beta_shift=step) for h in range(n_heads)], dim=1) if n_q else torch.zeros((0, n_heads, D), dtype=dtype, device=device)
+    return dict(q=q, k=k, v=v, targets=targets, diag=diag.cpu(), n_phases=n_phases, n_q=n_q, n_k=n_k, listed=[], causal=causal,
+                cells=backward_cells(n_q, n_k, causal))
+
+
+def cell_coverage(seqs):
+    """The phases of ONE (n_q, n_k, causal) -> (live cells no (row, head) target lies in, needed keys no row targets,
+    (head, 128-key block) pairs in which the head has no target although some row of the sequence sees the block)"""
+    first = seqs[0]
+    n_k, heads = first["n_k"], first["q"].shape[1]
+    hit, keys, blocks = set(), set(), set()
+    for s in seqs:
+        for h in range(heads):
+            for r, t in enumerate(s["targets"][h].tolist()):
+                if t >= 0:
+                    hit.add((r // CELL, t // CELL))
+                    keys.add(t)
+                    blocks.add((h, t // BWD_BLOCK))
+    cells = first["cells"]
+    needed = _unique_inside([0, n_k - 2, n_k - 1] + [p for _, j, on in cells if on for p in range(CELL * j, CELL * (j + 1))], n_k)
+    seen_blocks = {j * CELL // BWD_BLOCK for _, j, _ in cells}
+    return ([c[:2] for c in cells if c[:2] not in hit], [p for p in needed if p not in keys],
+            [(h, b) for h in range(heads) for b in sorted(seen_blocks) if (h, b) not in blocks])
+
+
+def _target_values(seq):
+    """v[t_r] of every (row, head) -> (n_q, H, 128) fp32 (rows without a target: key 0's, unused)"""
+    v, targets = seq["v"].float(), seq["targets"].to(seq["q"].device)
+    group = seq["q"].shape[1] // v.shape[1]
+    return torch.stack([v[targets[h].clamp_min(0), h // group] for h in range(targets.shape[0])], dim=1)
+
+
+def beacon_dout(seq, o32, seed=0, along=None):
+    """dout (n_q, H, 128) in the sequence's dtype: seeded N(0, 1) noise z plus the component `along` (default DOUT_ALONG) along
+    e_r = (v[t_r] - o32_r) / |v[t_r] - o32_r|, with the sign of z . e_r, so that dP - delta = dout_r . (v[t_r] - o32_r) on the
+    target has size |v[t_r] - o32_r| (|z . e_r| + along) and is never small by chance.  A row whose o32 IS its target's value
+    (it sees one key) and a row without a target get the noise alone.  o32: the fp32 reference forward's (references)."""
+    along = DOUT_ALONG if along is None else along
+    device = seq["q"].device
+    z = torch.randn(seq["q"].shape, generator=torch.Generator(device=device).manual_seed(seed), device=device)
+    e = _target_values(seq) - o32
+    w = e.norm(dim=-1, keepdim=True)
+    e = torch.where(w > 1e-6, e / w.clamp_min(1e-6), torch.zeros_like(e))
+    e = e * (seq["targets"].to(device).t() >= 0)[..., None]
+    ze = (z * e).sum(-1, keepdim=True)
+    return (z + torch.where(ze >= 0, 1.0, -1.0) * along * e).to(seq["q"].dtype)
+
+
+def target_ds(seq, dout, o32, lse32):
+    """fp32 dS of every row's target, P[r, t_r] (dout_r . (v[t_r] - o32_r)) -> (H, n_q), and target_probabilities' mask of the
+    rows the DS_FLOOR condition holds for (live rows that see two keys or more)"""
+    p, several = target_probabilities(seq, lse32)
+    return p * ((_target_values(seq) - o32) * dout.float()).sum(-1).t(), several
+
+
+def reference_backward(seq, dout, hook=None, want_parts=False):
+    """The explicit fp32 backward of one sequence: P = exp(S - lse32) on the keys the row sees, delta = sum dO o O, dP = dO V^T,
+    dS = P o (dP - delta), dV = P^T dO, dK = dS^T Q / sqrt(d), dQ = dS K / sqrt(d), dK and dV summed over the group
+    -> dq (n_q, H, 128), dk, dv (n_k, Hkv, 128)[, parts].  The dK / dV pass and the dQ pass each form P and dS of their own, as
+    the kernels do, from a state dict the hook may change first: hook(name, state), name "dkdv" or "dq", state = lse (H, n_q),
+    delta (H, n_q), visible (H, n_q, n_k) bool, weight (H, n_q, n_k) -- multiplies P and dS: 0 drops a product, 2 counts it
+    twice -- and, for "dkdv", head_weight (H, n_k): the weight of a query head's dK / dV rows in the group's sum.  A key made
+    visible takes its probability from the state's lse, as a kernel would."""
+    n_q, n_k = seq["n_q"], seq["n_k"]
+    q, k, v, do = seq["q"].float(), seq["k"][:n_k].float(), seq["v"][:n_k].float(), dout.float()
+    heads, kv_heads = q.shape[1], k.shape[1]
+    group = heads // kv_heads
+    kk, vv = k.repeat_interleave(group, dim=1), v.repeat_interleave(group, dim=1)
+    s = torch.einsum("qhd,khd->hqk", q, kk) * (1.0 / math.sqrt(D))
+    visible = torch.arange(n_k, device=q.device)[None, :] <= seq["diag"].to(q.device)[:, None]
+    dead = ~visible.any(dim=1)
+    lse = torch.logsumexp(s.masked_fill(~visible[None], NEG_INF).masked_fill(dead[None, :, None], 0.0), dim=-1)
+    lse = lse.masked_fill(dead[None], NEG_INF)
+    p_true = torch.where(visible[None] & ~dead[None, :, None], torch.exp(s - lse[..., None]), torch.zeros_like(s))
+    o = torch.einsum("hqk,khd->qhd", p_true, vv)
+    delta = (do * o).sum(-1).t().contiguous()
+    dp = torch.einsum("qhd,khd->hqk", do, vv)
+    parts = dict(s=s, lse=lse, delta=delta, dp=dp, o=o, q=q, kk=kk, vv=vv, do=do, visible=visible)
+    for name in ("dkdv", "dq"):
+        state = dict(lse=lse.clone(), delta=delta.clone(), visible=visible[None].expand(heads, -1, -1).clone(), weight=torch.ones_like(s))
+        if name == "dkdv":
+            state["head_weight"] = torch.ones((heads, n_k), device=q.device)
+        if hook is not None:
+            hook(name, state)
+        alive = state["visible"] & torch.isfinite(state["lse"])[..., None]
+        p = torch.where(alive, torch.exp(s - state["lse"].masked_fill(~torch.isfinite(state["lse"]), 0.0)[..., None]), torch.zeros_like(s))
+        p = p * state["weight"]
+        ds = p * (dp - state["delta"][..., None])
+        if name == "dkdv":
+            hw = state["head_weight"].t()[..., None]
+            dv_h = torch.einsum("hqk,qhd->khd", p, do) * hw
+            dk_h = torch.einsum("hqk,qhd->khd", ds, q) * (hw / math.sqrt(D))
+            dv, dk = (x.reshape(n_k, kv_heads, group, D).sum(2) for x in (dv_h, dk_h))
+            parts.update(p=p, ds=ds, dk_h=dk_h, dv_h=dv_h)
+        else:
+            dq = torch.einsum("hqk,khd->qhd", ds, kk) * (1.0 / math.sqrt(D))
+    return (dq, dk, dv, parts) if want_parts else (dq, dk, dv)
+
+
+def eager_backward(seq, dout, dtype):
+    """autograd through eager() in `dtype` arithmetic -> [dq, dk, dv] as fp32: the gradient rule's two references"""
+    n_k = seq["n_k"]
+    leaves = [t.detach().to(dtype).requires_grad_(True) for t in (seq["q"], seq["k"][:n_k], seq["v"][:n_k])]
+    eager(*leaves, seq["diag"], dtype)[0].backward(dout.to(dtype))
+    return [t.grad.float() for t in leaves]
+
+
+def grad_bounds(r32, r16):
+    """The gradient rule's two bounds for one gradient of one sequence (tests/test_varlen_qk_gpu.py's _check_grad, flash-attn's
+    rule): max|g - g32| <= 2 max|g16 - g32| + 1e-4 and ||g - g32|| / ||g32|| <= 2 ||g16 - g32|| / ||g32|| + 1e-3
+    -> dict(bound, rel_bound, norm); a gradient that is zero throughout has no relative part (norm 0)"""
+    norm = r32.norm().item()
+    rel16 = ((r16 - r32).norm().item() / norm) if norm > 0 else 0.0
+    return dict(bound=2 * (r16 - r32).abs().max().item() + 1e-4, rel_bound=2 * rel16 + 1e-3, norm=norm)
+
+
+def grad_rule_stats(err, err_norm, bounds, finite=True):
+    """The rule on the two figures of g - g32, its largest entry and its L2 norm (a difference that is zero outside a few rows
+    has those rows' figures) -> dict(ok, err, bound, rel, rel_bound, ratio): ratio > 1 means rejected"""
+    rel = err_norm / bounds["norm"] if bounds["norm"] > 0 else 0.0
+    ok = finite and err <= bounds["bound"] and rel <= bounds["rel_bound"]
+    return dict(ok=ok, err=err, bound=bounds["bound"], rel=rel, rel_bound=bounds["rel_bound"],
+                ratio=max(err / bounds["bound"], rel / bounds["rel_bound"]) if finite else float("inf"))
+
+
+def grad_rule(g, r32, r16, bounds=None):
+    """The gradient rule for ONE gradient of one sequence or batch entry: g from the code under test, r32 / r16 fp32 and 16-bit
+    eager autograd (eager_backward) -> grad_rule_stats' dict"""
+    g = g.float()
+    diff = g - r32
+    finite = bool(torch.isfinite(g).all()) and g.shape == r32.shape
+    return grad_rule_stats(diff.abs().max().item() if diff.numel() else 0.0, diff.norm().item(), bounds or grad_bounds(r32, r16), finite)
