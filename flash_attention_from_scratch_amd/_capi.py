@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_varlen_qk_window_supported", "fa_fwd_launch_varlen_qk_window",
     "fa_fwd_varlen_kvcache_window_supported", "fa_fwd_launch_varlen_kvcache_window",
     "fa_fwd_varlen_kvcache_fp8_window_supported", "fa_fwd_launch_varlen_kvcache_fp8_window",
+    "fa_bwd_launch_varlen_qk_window",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -426,6 +427,10 @@ def load():
         fn.restype, fn.argtypes = ctypes.c_int, [cfg_p, ctypes.POINTER(FaFwdOpts)]
         fn, argtypes = getattr(lib, f"fa_fwd_launch_{name}"), list(getattr(lib, f"fa_fwd_launch_{sibling}").argtypes)
         fn.restype, fn.argtypes = ctypes.c_int, argtypes[:-3] + [ctypes.POINTER(FaWindow)] + argtypes[-3:]
+    # ... and of the packed backward: the sibling's arguments with an fa_window behind them
+    lib.fa_bwd_launch_varlen_qk_window.restype = ctypes.c_int
+    lib.fa_bwd_launch_varlen_qk_window.argtypes = [ctypes.POINTER(FaBwdVarlenQKArgs), ctypes.POINTER(FaWindow), ctypes.c_void_p,
+                                                   ctypes.POINTER(ctypes.c_float)]
     lib.fa_kvcache_append_launch.restype = ctypes.c_int
     lib.fa_kvcache_append_launch.argtypes = [ctypes.POINTER(FaKvcacheAppendArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p

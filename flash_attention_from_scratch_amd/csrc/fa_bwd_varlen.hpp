@@ -1,8 +1,9 @@
 // fa_bwd_varlen.hpp -- the backward over packed variable-length sequences, with one range per sequence (fa_bwd_launch_varlen,
-// BwdVarlenArgs) or with separate Q and K / V ranges (fa_bwd_launch_varlen_qk, BwdVarlenQKArgs).  One text of each kernel
-// serves both: ARGS names the form, `if constexpr (QK)` marks every site where they differ, and each form is instantiated in
-// a translation unit of its own (fa_bwd_varlen.hip, fa_bwd_varlen_qk.hip), so the one-range kernels carry none of the second
-// range's code.
+// BwdVarlenArgs), with separate Q and K / V ranges (fa_bwd_launch_varlen_qk, BwdVarlenQKArgs), or with two ranges under a sliding
+// window (fa_bwd_launch_varlen_qk_window, BwdVarlenWindowArgs).  One text of each kernel serves all three: ARGS names the form,
+// `if constexpr (QK)` / `if constexpr (WIN)` mark every site where they differ, and each form is instantiated in a translation
+// unit of its own (fa_bwd_varlen.hip, fa_bwd_varlen_qk.hip, fa_bwd_varlen_window.hip), so the one-range kernels carry none of the
+// second range's code and neither carries the window's.
 //
 // One range: Q, dO, dQ, O are (total_tokens, n_heads, 128), K, V, dK, dV (total_tokens, n_kv_heads, 128), and sequence i owns
 // token rows cu_seqlens[i] .. cu_seqlens[i + 1] - 1 (cu_seqlens on the DEVICE: the host never reads it, the launch stays
@@ -36,6 +37,19 @@
 //    dk = dv = 0, written.
 //  * Rows beyond either range's end are fetched from THAT range's last row; both ranges are clamped by seq_range's rule, each
 //    against its own total and max_seqlen.
+//
+// What the window adds (fa_bwd_launch_varlen_qk_window, BwdVarlenWindowArgs, fa_bwd_varlen_window.hip): the
+// third form of the same text, selected by the argument type (`if constexpr (WIN)`; QK now reads "not the one-range form"), so
+// the other two forms keep their names and their instructions.  The forward's rule: query r at p = r + shift sees the keys
+// max(0, p - left) .. min(len_k - 1, p + right), unbounded = 2^30, causal = (right = 0): no CAUSAL instantiation.
+//  * dQ: a block with rows r0 .. r1 visits the key tiles of max(0, r0 + shift - left) .. min(len_k - 1, r1 + shift + right), the
+//    first prefetch being the first VISITED tile; dK / dV: a block with keys k0 .. k1 sweeps the row tiles of
+//    max(0, k0 - shift - right) .. min(len_q - 1, k1 - shift + left).  An empty range sweeps nothing and stores zeros: rows that
+//    see no key, and keys no row sees (below every floor, above every ceiling), are WRITTEN as zeros.
+//  * The mask is a select on p (key < lo_r, key > hi_r, key >= len_k, query >= len_q) behind the workgroup-uniform `outside`:
+//    only a tile that reaches outside some row's window or past either end pays for it, as under `diag` / `edge`.
+//  * Positions fit 32 bits: the host refuses max_seqlen on either side above 2^30 - 128.
+// Split, partials, reduce, grids and the workspace are the two-range form's.
 #pragma once
 #include <type_traits>
 
@@ -79,6 +93,12 @@ struct BwdVarlenQKArgs {
     int32_t n_blocks, n_blocks_k;     // ceil(max_seqlen / 128), ceil(max_seqlen_k / 128): blocks of the grids
 };
 
+// ... under a sliding window (fa_bwd_launch_varlen_qk_window): the two ranges' fields and (left, right), the keys a row sees
+// below and above its position; unbounded arrives as 2^30, causal as right = 0 (the kernels are instantiated without CAUSAL)
+struct BwdVarlenWindowArgs : BwdVarlenQKArgs {
+    int32_t left, right;
+};
+
 namespace bwd {
 
 // sequence -> first row and length, clamped so that every row0 + i, 0 <= i < len, is a row of the tensors
@@ -115,6 +135,14 @@ __host__ __device__ inline int32_t total_k(const BwdVarlenArgs &a) { return a.to
 __host__ __device__ inline int32_t total_k(const BwdVarlenQKArgs &a) { return a.total_k; }
 __host__ __device__ inline int32_t n_blocks_k(const BwdVarlenArgs &a) { return a.n_blocks; }
 __host__ __device__ inline int32_t n_blocks_k(const BwdVarlenQKArgs &a) { return a.n_blocks_k; }
+
+// the 64-row tiles [first, end) that hold rows (or keys) lo .. hi of 0 .. n - 1; none of them: first = end = 0
+FA_DEV void window_tiles(int lo, int hi, int n, int &first, int &end) {
+    lo = lo > 0 ? lo : 0;
+    hi = hi < n - 1 ? hi : n - 1;
+    first = hi < lo ? 0 : lo / TROWS;
+    end = hi < lo ? 0 : hi / TROWS + 1;
+}
 
 // tile_load with the tile's rows clamped to the sequence: row first + r comes from row min(first + r, last)
 FA_DEV void tile_load_clamped(TileRegs &t, const uint16_t *seq_rows, int64_t ss, int first, int last, int tid) {
@@ -158,7 +186,9 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
     using namespace bwd;
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
-    constexpr bool QK = std::is_same_v<ARGS, BwdVarlenQKArgs>;
+    constexpr bool WIN = std::is_same_v<ARGS, BwdVarlenWindowArgs>;
+    constexpr bool QK = !std::is_same_v<ARGS, BwdVarlenArgs>;
+    static_assert(!(WIN && CAUSAL), "the window carries the causal mask as right = 0");
     __shared__ __attribute__((aligned(16))) char img_q[TBYTES];
     __shared__ __attribute__((aligned(16))) char img_do[TBYTES];
     __shared__ __attribute__((aligned(16))) float lse_s[TROWS];   // -lse sqrt(d) of the tile's rows
@@ -205,12 +235,17 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
         dV[t] = f32x16{};
         dK[t] = f32x16{};
     }
-    const int n_it = (len + TROWS - 1) / TROWS;
+    // window: key j is seen by rows j - shift - right .. j - shift + left, so the block's keys (up to the sequence's last) by the
+    // tiles win_it0 .. win_end - 1
+    [[maybe_unused]] int win_it0 = 0, win_end = 0;
+    if constexpr (WIN) window_tiles(kb * KB - shift - a.right, (kb * KB + KB - 1 < klast ? kb * KB + KB - 1 : klast) - shift + a.left, len, win_it0, win_end);
+    const int n_it = WIN ? win_end : (len + TROWS - 1) / TROWS;
     // causal: the Q tiles from the diagonal on (one range: it0 * 64 = kb * 128 < len), that is from the first one that can see
     // the block (two ranges; it0 >= n_it: no query sees it)
     int it0 = 0;
     if constexpr (CAUSAL && QK) it0 = (kb * KB - shift > 0 ? kb * KB - shift : 0) / TROWS;
     else if constexpr (CAUSAL) it0 = kb * (KB / TROWS);
+    else if constexpr (WIN) it0 = win_it0;
     const float *lse_h = a.lse + (int64_t)hq * a.total_tokens + row0;
     const float *dl_h = a.delta + (int64_t)hq * a.total_tokens + row0;
     TileRegs tq, tdo;
@@ -257,6 +292,10 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
             }
             const bool diag = CAUSAL && it * TROWS + shift < kb * KB + KB;   // a tile that holds queries before some key of the block
             const bool edge = key_edge || it * TROWS + TROWS > len;  // ... or rows / keys beyond the sequence
+            // window: ... or a tile that reaches outside some row's window: its last row's floor above the block's first key, or its
+            // first row's ceiling below the block's last
+            [[maybe_unused]] bool outside = false;
+            if constexpr (WIN) outside = edge || it * TROWS + TROWS - 1 + shift - a.left > kb * KB || it * TROWS + shift + a.right < kb * KB + KB - 1;
 #pragma unroll
             for (int mt = 0; mt < TROWS / 32; ++mt) {
                 const int rb = 32 * mt;
@@ -283,6 +322,9 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
                     if constexpr (CAUSAL) {   // (plain: rows beyond the end have S = -inf, see load())
                         if (diag) p = key > query + shift ? 0.0f : p;
                         if (edge) p = (key >= klen || query >= len) ? 0.0f : p;
+                    }
+                    if constexpr (WIN) {
+                        if (outside) p = (key < query + shift - a.left || key > query + shift + a.right || key >= klen || query >= len) ? 0.0f : p;
                     }
                     S[i] = p;                 // P
                     dP[i] = p * dP[i];        // dS = P (dP - delta)
@@ -364,7 +406,9 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
     using namespace bwd;
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
-    constexpr bool QK = std::is_same_v<ARGS, BwdVarlenQKArgs>;
+    constexpr bool WIN = std::is_same_v<ARGS, BwdVarlenWindowArgs>;
+    constexpr bool QK = !std::is_same_v<ARGS, BwdVarlenArgs>;
+    static_assert(!(WIN && CAUSAL), "the window carries the causal mask as right = 0");
     __shared__ __attribute__((aligned(16))) char img_k[TBYTES];
     __shared__ __attribute__((aligned(16))) char img_v[TBYTES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
@@ -419,15 +463,19 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
     // causal: cut at the block's last row's diagonal, (qb + 1) * 128 - 1 + shift; two ranges: no tile when that lies before key 0
     int n_diag = (qb + 1) * (KB / TROWS);
     if constexpr (QK) n_diag = (qb + 1) * KB + shift > 0 ? ((qb + 1) * KB + shift + TROWS - 1) / TROWS : 0;
-    const int n_kt = CAUSAL && n_diag < n_all ? n_diag : n_all;
+    // window: the block's rows (up to the sequence's last) see the keys from its first row's floor to its last row's ceiling: the
+    // tiles kt0 .. win_end - 1
+    [[maybe_unused]] int kt0 = 0, win_end = 0;
+    if constexpr (WIN) window_tiles(qb * KB + shift - a.left, (qb * KB + KB - 1 < last ? qb * KB + KB - 1 : last) + shift + a.right, klen, kt0, win_end);
+    const int n_kt = WIN ? win_end : (CAUSAL && n_diag < n_all ? n_diag : n_all);
     TileRegs tk, tv;
     auto load = [&](int kt) {
         tile_load_clamped(tk, k_seq, a.kv_ss, kt * TROWS, klast, tid);
         tile_load_clamped(tv, v_seq, a.kv_ss, kt * TROWS, klast, tid);
     };
-    if (!QK || n_kt > 0) load(0);   // (two ranges: len_k = 0 has no row to fetch)
+    if (!QK || n_kt > 0) load(kt0);   // (two ranges: len_k = 0 has no row to fetch; window: the first VISITED tile)
     const bool query_edge = qb * KB + KB > len;   // a block that holds rows beyond the sequence
-    for (int kt = 0; kt < n_kt; ++kt) {
+    for (int kt = kt0; kt < n_kt; ++kt) {
         __syncthreads();
         tile_store(img_k, tk, tid);
         tile_store(img_v, tv, tid);
@@ -435,6 +483,10 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
         if (kt + 1 < n_kt) load(kt + 1);
         const bool diag = CAUSAL && kt * TROWS + TROWS > qb * KB + shift;   // a tile that holds keys after some query of the block
         const bool edge = query_edge || kt * TROWS + TROWS > klen;   // ... or rows / keys beyond the sequence
+        // window: ... or a tile that reaches outside some row's window: its first key below the block's last row's floor, or its
+        // last key above the block's first row's ceiling
+        [[maybe_unused]] bool outside = false;
+        if constexpr (WIN) outside = edge || kt * TROWS < qb * KB + KB - 1 + shift - a.left || kt * TROWS + TROWS - 1 > qb * KB + shift + a.right;
 #pragma unroll
         for (int mt = 0; mt < TROWS / 32; ++mt) {
             const int rb = 32 * mt;
@@ -443,7 +495,7 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
             for (int i = 0; i < 16; ++i) {
                 S[i] = lse_q;
                 dP[i] = dl_q;
-                if (!CAUSAL && edge) {   // keys beyond the end: S = -inf, p = exp2(-inf) = 0
+                if (!CAUSAL && !WIN && edge) {   // keys beyond the end: S = -inf, p = exp2(-inf) = 0
                     const int key = kt * TROWS + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
                     S[i] = key >= klen ? -__builtin_inff() : lse_q;
                 }
@@ -459,6 +511,9 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
                 if constexpr (CAUSAL) {
                     if (diag) p = key > query + shift ? 0.0f : p;
                     if (edge) p = (key >= klen || query >= len) ? 0.0f : p;
+                }
+                if constexpr (WIN) {
+                    if (outside) p = (key < query + shift - a.left || key > query + shift + a.right || key >= klen || query >= len) ? 0.0f : p;
                 }
                 dP[i] = p * dP[i];        // dS^T
             }

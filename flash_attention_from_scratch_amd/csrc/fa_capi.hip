@@ -61,6 +61,8 @@ kernel_fn_varlen_kvcache_fp8_window varlen_kvcache_fp8_window_kernel_dt5(bool fi
 // fa_bwd_varlen.hip / fa_bwd_varlen_qk.hip: the packed backward, and its form with separate Q and K / V lengths
 hipError_t bwd_varlen_enqueue(const BwdVarlenArgs &a, int dtype, bool causal, hipStream_t s);
 hipError_t bwd_varlen_qk_enqueue(const BwdVarlenQKArgs &a, int dtype, bool causal, hipStream_t s);
+// fa_bwd_varlen_window.hip: ... under a sliding window (causal arrives as right = 0)
+hipError_t bwd_varlen_window_enqueue(const BwdVarlenWindowArgs &a, int dtype, hipStream_t s);
 }  // namespace fa
 
 namespace {
@@ -1081,7 +1083,7 @@ template <class A> void cache_descales(CacheView &c, const A &a) {
 }
 }  // namespace
 
-// ---- fa_window: the rules every windowed entry point shares (decode, the packed forward, the prefills) ----------------------
+// ---- fa_window: the rules every windowed entry point shares (decode, the packed forward and backward, the prefills) ---------
 namespace {
 constexpr int64_t kWindowMaxLen = (1 << 30) - 128;   // the kernels add a row's position and its clamped distances in 32 bits
 int window_right(const fa_window *w, int causal) { return causal ? 0 : w->right; }
@@ -1552,6 +1554,32 @@ int fa_bwd_launch_varlen_qk(const fa_bwd_varlen_qk_args *a, void *stream, float 
     bwd_varlen_fill(va, a);
     const hipStream_t s = (hipStream_t)stream;
     return enqueue_timed([&] { return fa::bwd_varlen_qk_enqueue(va, a->dtype, a->causal != 0, s); }, s, ms);
+}
+
+// the sliding-window form: the sibling's checks, then the window's (the forward's: fwd_launch_varlen); split, workspace and the
+// argument fill are the sibling's, the kernels take (left, right) with -1 as 2^30 and causal as right = 0
+int fa_bwd_launch_varlen_qk_window(const fa_bwd_varlen_qk_args *a, const fa_window *w, void *stream, float *ms) {
+    int rc = bwd_varlen_checks(a, true, "total_q", "fa_bwd_varlen_qk_workspace_bytes");
+    if (rc != FA_OK) return rc;
+    if ((rc = window_validate(w, a->causal, 0)) != FA_OK) return rc;
+    if (a->varlen_k.max_seqlen > kWindowMaxLen)
+        return fail(FA_ERR_SHAPE, "max_seqlen_k too large for a window: at most 2^30 - 128 keys per sequence");
+    if (a->varlen.max_seqlen > kWindowMaxLen)
+        return fail(FA_ERR_SHAPE, "max_seqlen_q too large for a window: at most 2^30 - 128 query rows per sequence");
+    if (a->varlen.total_tokens == 0 && a->varlen_k.total_tokens == 0) {
+        if (ms) *ms = 0.0f;
+        return FA_OK;
+    }
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    fa::BwdVarlenWindowArgs va;
+    bwd_varlen_fill(va, a);
+    constexpr int32_t kFar = 1 << 30;   // unbounded: beyond every position (kWindowMaxLen), and p - kFar, p + kFar fit 32 bits
+    const int32_t right = window_right(w, a->causal);
+    va.left = w->left < 0 || w->left > kFar ? kFar : w->left;
+    va.right = right < 0 || right > kFar ? kFar : right;
+    const hipStream_t s = (hipStream_t)stream;
+    return enqueue_timed([&] { return fa::bwd_varlen_window_enqueue(va, a->dtype, s); }, s, ms);
 }
 
 // ---- KV-cache decode ------------------------------------------------------------------------------------------------------

@@ -103,8 +103,9 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
 
     Sliding-window (local) attention: window_size=(left, right), keyword only, two Python ints, -1 = unbounded.
     Query row r, at position p = r + (len_k - len_q), sees the keys max(0, p - left) .. min(len_k - 1, p + right); causal means
-    right = 0; bad values are a ValueError.  (-1, -1) is the call above, unchanged.  FORWARD ONLY: backward_varlen and
-    attention_varlen take no window (open) -- do not feed them a windowed forward's o and lse."""
+    right = 0; bad values are a ValueError.  (-1, -1) is the call above, unchanged.  The gradients of a windowed forward are
+    backward_varlen_window's, and attention_varlen(window_size=) pairs the two; backward_varlen takes no window --
+    do not feed it a windowed forward's o and lse."""
     return flash_attention_kernels.forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=causal, timed=timed,
                                                   cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k, window_size=window_size)
 
@@ -205,43 +206,60 @@ def backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=False,
                                                    cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
 
 
+def backward_varlen_window(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, window_size, causal=False, timed=False, cu_seqlens_k=None,
+                           max_seqlen_k=None):
+    """backward_varlen for forward_varlen(window_size=)'s o and lse, under the same window: row r at position
+    p = r + (len_k - len_q) sees the keys max(0, p - left) .. min(len_k - 1, p + right), causal means right = 0.  (-1, -1) is
+    backward_varlen, unchanged; bad values are a ValueError.  A row that sees no key gets dq = 0; a key no row sees -- below
+    every row's floor or above every row's ceiling -- gets dk = dv = 0, written.  Deterministic."""
+    return flash_attention_kernels.backward_varlen_window(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, window_size, causal=causal,
+                                                          timed=timed, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
+
+
 def _varlen_needs_copy(t):
     return t.stride(2) != 1 or t.stride(0) % 8 != 0 or t.stride(1) % 8 != 0 or t.data_ptr() % 16 != 0
 
 
 class _AttentionVarlen(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k):
+    def forward(ctx, q, k, v, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k, window_size=(-1, -1)):
         if _varlen_needs_copy(q):
             q = q.contiguous()
         if _varlen_needs_copy(k) or _varlen_needs_copy(v) or v.stride() != k.stride():
             k, v = k.contiguous(), v.contiguous()
-        o, lse = forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=causal, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
+        o, lse = forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=causal, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k,
+                                window_size=window_size)
         ctx.qk = cu_seqlens_k is not None
         if ctx.qk:
             ctx.save_for_backward(q, k, v, o, lse, cu_seqlens, cu_seqlens_k)
         else:
             ctx.save_for_backward(q, k, v, o, lse, cu_seqlens)
-        ctx.max_seqlen, ctx.max_seqlen_k, ctx.causal = max_seqlen, max_seqlen_k, causal
+        ctx.max_seqlen, ctx.max_seqlen_k, ctx.causal, ctx.window_size = max_seqlen, max_seqlen_k, causal, tuple(window_size)
         return o
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, o, lse, cu_seqlens = ctx.saved_tensors[:6]
         cu_seqlens_k = ctx.saved_tensors[6] if ctx.qk else None
-        dq, dk, dv = backward_varlen(q, k, v, o, lse, dout.contiguous(), cu_seqlens, ctx.max_seqlen, causal=ctx.causal,
-                                     cu_seqlens_k=cu_seqlens_k, max_seqlen_k=ctx.max_seqlen_k)
-        return dq, dk, dv, None, None, None, None, None
+        # ((-1, -1): backward_varlen itself)
+        dq, dk, dv = backward_varlen_window(q, k, v, o, lse, dout.contiguous(), cu_seqlens, ctx.max_seqlen, ctx.window_size,
+                                            causal=ctx.causal, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=ctx.max_seqlen_k)
+        return dq, dk, dv, None, None, None, None, None, None
 
 
-def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, cu_seqlens_k=None, max_seqlen_k=None):
+def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, cu_seqlens_k=None, max_seqlen_k=None, *, window_size=(-1, -1)):
     """softmax(q k^T / sqrt d) v over packed sequences, with gradients (flash-attn's flash_attn_varlen_func): the varlen forward
     with the row log-sum-exp and the varlen HIP backward.  k and v may have n_kv_heads heads.
 
     cu_seqlens_k / max_seqlen_k (both or neither: one alone is a ValueError) give K / V lengths of their own -- cross-attention,
     chunked prefill behind a prefix: cu_seqlens / max_seqlen are then Q's, k / v are (total_k, n_kv_heads, 128), and causal is
     bottom-right aligned: query r of a sequence sees keys j <= r + (len_k - len_q).  A row that sees no key gives o = 0 and
-    dq = 0; a key no query sees gets dk = dv = 0.  Both offset arrays are saved for the backward."""
+    dq = 0; a key no query sees gets dk = dv = 0.  Both offset arrays are saved for the backward.
+
+    window_size=(left, right), keyword only: forward_varlen's sliding window, carried to both passes (the windowed forward and
+    backward_varlen_window), so a model with local layers trains by the rule it is served by.  Bad values are a ValueError before
+    any tensor is looked at; (-1, -1) is the call above, bit for bit."""
+    flash_attention_kernels._window(window_size, causal)
     if (cu_seqlens_k is None) != (max_seqlen_k is None):
         raise ValueError("cu_seqlens_k and max_seqlen_k go together: give both (separate Q and K / V lengths) or neither")
-    return _AttentionVarlen.apply(q, k, v, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k)
+    return _AttentionVarlen.apply(q, k, v, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k, tuple(window_size))

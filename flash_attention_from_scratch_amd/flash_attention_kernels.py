@@ -362,8 +362,8 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
     window_size=(left, right), keyword only, Python ints, -1 = unbounded (flash-attn's): query row r of a sequence, at position
     p = r + (len_k - len_q), sees the keys max(0, p - left) .. min(len_k - 1, p + right); causal means right = 0.  (-1, -1) takes
     the entry points above unchanged, anything else fa_fwd_launch_varlen_qk_window (one range given: on both sides), which visits
-    no key tile outside a Q block's window and fetches no key row below it.  Bad values are a ValueError.  FORWARD ONLY:
-    backward_varlen and attention_varlen take no window, and the gradients of a windowed forward are not theirs."""
+    no key tile outside a Q block's window and fetches no key row below it.  Bad values are a ValueError.  The gradients of a
+    windowed forward are backward_varlen_window's (attention_varlen(window_size=) pairs the two); backward_varlen takes no window."""
     window = _window(window_size, causal)
     qk = _qk_sides(cu_seqlens_k, max_seqlen_k)
     _check_varlen(q, k, v, cu_seqlens, max_seqlen, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
@@ -400,7 +400,25 @@ def backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=False,
 
     cu_seqlens_k / max_seqlen_k (both or neither, else ValueError): separate K / V lengths as in forward_varlen
     (fa_bwd_launch_varlen_qk), causal bottom-right aligned.  A row that saw no key (lse = -inf) gets dq = 0; a key no query
-    sees (len_q = 0: under the bottom-right mask the last row sees every key) gets dk = dv = 0, written."""
+    sees (len_q = 0: under the bottom-right mask the last row sees every key) gets dk = dv = 0, written.
+
+    No window: the gradients of forward_varlen(window_size=) are backward_varlen_window's."""
+    return _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, None)
+
+
+def backward_varlen_window(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, window_size, causal=False, timed=False, cu_seqlens_k=None,
+                           max_seqlen_k=None):
+    """backward_varlen under forward_varlen's window_size=(left, right): dQ, dK, dV from the WINDOWED forward's o and lse, by the
+    forward's rule (row r at p = r + (len_k - len_q) sees the keys max(0, p - left) .. min(len_k - 1, p + right); causal means
+    right = 0).  (-1, -1) is backward_varlen, unchanged; anything else fa_bwd_launch_varlen_qk_window (one range given: on both
+    sides), whose kernels visit no tile outside a block's window.  A row that sees no key (lse = -inf) gets dq = 0; a key no row
+    sees gets dk = dv = 0, written.  Bad window_size values are a ValueError before any tensor is looked at."""
+    window = _window(window_size, causal)
+    return _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window)
+
+
+def _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window):
+    """backward_varlen (window None) and backward_varlen_window (window (left, right): the two-range arguments, given or not)"""
     qk = _qk_sides(cu_seqlens_k, max_seqlen_k)
     _check_varlen(q, k, v, cu_seqlens, max_seqlen, others=((o, "o"), (dout, "dout"), (lse, "lse")),
                   cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
@@ -426,9 +444,12 @@ def backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal=False,
         kv_seq_stride=k.stride(0), kv_head_stride=k.stride(1), dkv_seq_stride=dk.stride(0), dkv_head_stride=dk.stride(1),
         dtype=15 if q.dtype == torch.bfloat16 else 5, causal=1 if causal else 0, varlen=sides[0],
     )
-    if qk:
-        args = _capi.FaBwdVarlenQKArgs(struct_size=ctypes.sizeof(_capi.FaBwdVarlenQKArgs), varlen_k=sides[1], **fields)
+    if qk or window is not None:
+        args = _capi.FaBwdVarlenQKArgs(struct_size=ctypes.sizeof(_capi.FaBwdVarlenQKArgs), varlen_k=sides[-1], **fields)
         workspace_bytes, launch = lib.fa_bwd_varlen_qk_workspace_bytes, lib.fa_bwd_launch_varlen_qk
+        if window is not None:
+            w = _capi.make_window(*window)
+            launch = lambda a, stream, ms: lib.fa_bwd_launch_varlen_qk_window(a, ctypes.byref(w), stream, ms)   # noqa: E731
     else:
         args = _capi.FaBwdVarlenArgs(**fields)
         workspace_bytes, launch = lib.fa_bwd_varlen_workspace_bytes, lib.fa_bwd_launch_varlen

@@ -755,8 +755,9 @@ int fa_decode_fp8_window_launch(const fa_decode_fp8_args *args, const fa_window 
  * opts->causal means right = 0 (causal with right > 0 is refused; right = -1 or 0 may accompany it).  A row that sees no key
  * (p + right < 0) gives o = 0 and lse = -inf.  (-1, -1), or any window that reaches every key, gives the unwindowed entry's
  * bits; the three entries give one another's bits on the same keys, as their siblings do.  Grid, strides, descales, lse,
- * determinism, graph capture: the sibling's.  One launch, no split, no workspace.  Forward only: the backward entry points take
- * no window.
+ * determinism, graph capture: the sibling's.  One launch, no split, no workspace.  The backward of the packed form is
+ * fa_bwd_launch_varlen_qk_window (below); fa_bwd_launch_varlen and fa_bwd_launch_varlen_qk take no window, and the o and lse of
+ * a windowed forward are not theirs.
  *
  * Clamping, extended downwards.  A workgroup owns 128 query rows r0 .. r1 of one (sequence, head) and visits only the 64-key
  * tiles from its last row's upper bound down to its first row's lower bound lo_r0 = max(0, r0 + len_k - len_q - left), which
@@ -782,6 +783,24 @@ int fa_fwd_varlen_kvcache_fp8_window_supported(const fa_fwd_config *cfg, const f
 int fa_fwd_launch_varlen_kvcache_fp8_window(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
                                             const fa_kvcache_layout *cache, const fa_kvcache_fp8_scales *scales,
                                             const fa_window *window, const fa_fwd_opts *opts, float *lse, void *stream);
+
+/*
+ * The backward of fa_fwd_launch_varlen_qk_window: dQ, dK, dV from the windowed forward's o and lse under the same rule (the
+ * arguments of fa_bwd_launch_varlen_qk and the forward's fa_window; args->causal means right = 0).  Kernels of their own (the
+ * windowed form of fa_bwd_launch_varlen_qk's): a dQ workgroup, owning rows r0 .. r1 = min(r0 + 127, len_q - 1), visits the 64-key
+ * tiles from max(0, r0 + shift - left) / 64 to min(len_k - 1, r1 + shift + right) / 64, shift = len_k - len_q; a dK / dV
+ * workgroup, owning keys k0 .. k1 = min(k0 + 127, len_k - 1), sweeps the 64-row Q tiles from max(0, k0 - shift - right) / 64 to
+ * min(len_q - 1, k1 - shift + left) / 64; an empty range sweeps nothing and stores zeros.  A row that sees no key
+ * (lse = -inf) gets dq = 0; a key no row sees -- below every row's floor, above every row's ceiling, or len_q = 0 -- gets
+ * dk = dv = 0, written.  Grids, the dK / dV split, the workspace and its layout are fa_bwd_launch_varlen_qk's:
+ * fa_bwd_varlen_qk_workspace_bytes(args) sizes this call too.  Deterministic, no atomics, graph-capturable.  A window that reaches
+ * every key gives fa_bwd_launch_varlen_qk's gradients within rounding, not its bits in the plain form.
+ *
+ * Refused before any HIP call: what fa_bwd_launch_varlen_qk refuses, first and with its message; then a null fa_window
+ * (FA_ERR_NULL); its struct_size, left or right below -1, causal with right > 0, and max_seqlen of either side above
+ * 2^30 - 128 (FA_ERR_SHAPE).  total_q = total_k = 0 returns FA_OK without a device.
+ */
+int fa_bwd_launch_varlen_qk_window(const fa_bwd_varlen_qk_args *args, const fa_window *window, void *stream, float *ms);
 
 /*
  * The step in front of a decode: append seqlen_new new K / V rows per batch entry to the cache IN PLACE, at the positions the
