@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_varlen_kvcache_window_supported", "fa_fwd_launch_varlen_kvcache_window",
     "fa_fwd_varlen_kvcache_fp8_window_supported", "fa_fwd_launch_varlen_kvcache_fp8_window",
     "fa_bwd_launch_varlen_qk_window",
+    "fa_fwd_varlen_qk_softcap_supported", "fa_fwd_launch_varlen_qk_softcap", "fa_bwd_launch_varlen_qk_softcap",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -193,6 +194,14 @@ class FaWindow(ctypes.Structure):   # fa_window (sliding-window attention: keys 
 
 def make_window(left=-1, right=-1):
     return FaWindow(struct_size=ctypes.sizeof(FaWindow), left=left, right=right)
+
+
+class FaSoftcap(ctypes.Structure):   # fa_softcap (logit soft-capping: softcap * tanh(s / softcap), softcap > 0 and finite)
+    _fields_ = [("struct_size", ctypes.c_uint32), ("softcap", ctypes.c_float)]
+
+
+def make_softcap(softcap):
+    return FaSoftcap(struct_size=ctypes.sizeof(FaSoftcap), softcap=softcap)
 
 
 class FaKvcacheAppendArgs(ctypes.Structure):   # fa_kvcache_append_args (the append / rotary / quantize / advance step in front of a decode)
@@ -431,6 +440,15 @@ def load():
     lib.fa_bwd_launch_varlen_qk_window.restype = ctypes.c_int
     lib.fa_bwd_launch_varlen_qk_window.argtypes = [ctypes.POINTER(FaBwdVarlenQKArgs), ctypes.POINTER(FaWindow), ctypes.c_void_p,
                                                    ctypes.POINTER(ctypes.c_float)]
+    # the soft-capped forms of the two: the windowed sibling's arguments with an fa_softcap behind the fa_window
+    lib.fa_fwd_varlen_qk_softcap_supported.restype = ctypes.c_int
+    lib.fa_fwd_varlen_qk_softcap_supported.argtypes = [cfg_p, ctypes.POINTER(FaFwdOpts)]
+    argtypes = list(lib.fa_fwd_launch_varlen_qk_window.argtypes)
+    lib.fa_fwd_launch_varlen_qk_softcap.restype = ctypes.c_int
+    lib.fa_fwd_launch_varlen_qk_softcap.argtypes = argtypes[:-3] + [ctypes.POINTER(FaSoftcap)] + argtypes[-3:]
+    argtypes = list(lib.fa_bwd_launch_varlen_qk_window.argtypes)
+    lib.fa_bwd_launch_varlen_qk_softcap.restype = ctypes.c_int
+    lib.fa_bwd_launch_varlen_qk_softcap.argtypes = argtypes[:2] + [ctypes.POINTER(FaSoftcap)] + argtypes[2:]
     lib.fa_kvcache_append_launch.restype = ctypes.c_int
     lib.fa_kvcache_append_launch.argtypes = [ctypes.POINTER(FaKvcacheAppendArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p

@@ -50,6 +50,13 @@
 //    only a tile that reaches outside some row's window or past either end pays for it, as under `diag` / `edge`.
 //  * Positions fit 32 bits: the host refuses max_seqlen on either side above 2^30 - 128.
 // Split, partials, reduce, grids and the workspace are the two-range form's.
+//
+// What soft-capping adds (fa_bwd_launch_varlen_qk_softcap, BwdVarlenSoftcapArgs, fa_bwd_varlen_softcap.hip): the
+// fourth form, the window form (`WIN` reads "has a window": a softcap without one arrives with left = right = 2^30) plus
+// `if constexpr (CAP)`.  The forward's logit of a seen key is softcap tanh(s / softcap), s = q . k / sqrt(d).  The other forms start
+// the S accumulator at -lse sqrt(d) so that exp2(c S) is P at once; a tanh in between forbids that, so here S starts at 0,
+// t = tanh(S / A) with A = softcap sqrt(d), p = exp2(c A t - lse log2(e)) (a dead row's -inf gives p = 0, never inf - inf), and
+// dS = p (dP - delta) (1 - t^2).  t lives in S's registers until p replaces it; the masks behind are the window form's.
 #pragma once
 #include <type_traits>
 
@@ -99,6 +106,12 @@ struct BwdVarlenWindowArgs : BwdVarlenQKArgs {
     int32_t left, right;
 };
 
+// ... with logit soft-capping (fa_bwd_launch_varlen_qk_softcap): the window's fields (none: left = right = 2^30) and
+// A = softcap sqrt(d), 1 / A, which the host computes in double and rounds once
+struct BwdVarlenSoftcapArgs : BwdVarlenWindowArgs {
+    float cap_a, cap_inv_a;
+};
+
 namespace bwd {
 
 // sequence -> first row and length, clamped so that every row0 + i, 0 <= i < len, is a row of the tensors
@@ -144,6 +157,13 @@ FA_DEV void window_tiles(int lo, int hi, int n, int &first, int &end) {
     end = hi < lo ? 0 : hi / TROWS + 1;
 }
 
+// soft-capping: tanh(S / A) of a raw logit S = q . k, as 1 - 2 / (exp2(S k) + 1) with k = 2 log2(e) / A (one v_exp_f32, one
+// v_rcp_f32).  exp2 overflowing to +inf gives 1, underflowing to 0 gives -1: no NaN at either end.
+FA_DEV float cap_tanh(float s, float k) {
+    const float e = __builtin_amdgcn_exp2f(s * k);
+    return __builtin_fmaf(__builtin_amdgcn_rcpf(e + 1.0f), -2.0f, 1.0f);
+}
+
 // tile_load with the tile's rows clamped to the sequence: row first + r comes from row min(first + r, last)
 FA_DEV void tile_load_clamped(TileRegs &t, const uint16_t *seq_rows, int64_t ss, int first, int last, int tid) {
 #pragma unroll
@@ -186,12 +206,13 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
     using namespace bwd;
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
-    constexpr bool WIN = std::is_same_v<ARGS, BwdVarlenWindowArgs>;
+    constexpr bool WIN = std::is_base_of_v<BwdVarlenWindowArgs, ARGS>;
+    constexpr bool CAP = std::is_same_v<ARGS, BwdVarlenSoftcapArgs>;
     constexpr bool QK = !std::is_same_v<ARGS, BwdVarlenArgs>;
     static_assert(!(WIN && CAUSAL), "the window carries the causal mask as right = 0");
     __shared__ __attribute__((aligned(16))) char img_q[TBYTES];
     __shared__ __attribute__((aligned(16))) char img_do[TBYTES];
-    __shared__ __attribute__((aligned(16))) float lse_s[TROWS];   // -lse sqrt(d) of the tile's rows
+    __shared__ __attribute__((aligned(16))) float lse_s[TROWS];   // -lse sqrt(d) of the tile's rows (CAP: -lse log2(e))
     __shared__ __attribute__((aligned(16))) float dl_s[TROWS];    // -delta
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     int wg, kb;   // wg = (sequence * n_kv_heads + K / V head) * split + part
@@ -228,7 +249,13 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
         }
     }
     const float c = (float)((double)(1.0f / __builtin_sqrtf((float)D)) * 1.4426950408889634074);
-    const float lse_scale = -log2e_over_c();
+    const float lse_scale = CAP ? -1.4426950408889634f : -log2e_over_c();
+    // soft-capping: S starts at 0 and p = exp2(c (A t + lse_s)), t = tanh(S / A) -- the constants of cap_tanh and of that fma
+    [[maybe_unused]] float cap_k = 0.0f, cap_ca = 0.0f;
+    if constexpr (CAP) {
+        cap_k = a.cap_inv_a * 2.8853900817779268f;
+        cap_ca = c * a.cap_a;
+    }
     f32x16 dV[4], dK[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -307,7 +334,7 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
                     const f32x4 d4 = *(const f32x4 *)(dl_s + rb + 8 * gg + 4 * h);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        S[4 * gg + e] = l4[e];
+                        S[4 * gg + e] = CAP ? 0.0f : l4[e];   // (CAP: the row's term joins behind the tanh)
                         dP[4 * gg + e] = d4[e];
                     }
                 }
@@ -317,7 +344,15 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
                 for (int ks = 0; ks < 8; ++ks) dP = E::mfma(row_read<vec8>(img_do, rb, ks, lane), Vb[ks], dP);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    float p = __builtin_amdgcn_exp2f(c * S[i]);
+                    float p;
+                    [[maybe_unused]] float dt = 1.0f;   // CAP: d tanh = 1 - t^2
+                    if constexpr (CAP) {   // (a dead row's lse_s = -inf: p = exp2(-inf) = 0, no inf - inf)
+                        const float t = cap_tanh(S[i], cap_k);
+                        p = __builtin_amdgcn_exp2f(__builtin_fmaf(t, cap_ca, lse_s[rb + (i & 3) + 8 * (i >> 2) + 4 * h]));
+                        dt = __builtin_fmaf(-t, t, 1.0f);
+                    } else {
+                        p = __builtin_amdgcn_exp2f(c * S[i]);
+                    }
                     const int query = it * TROWS + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
                     if constexpr (CAUSAL) {   // (plain: rows beyond the end have S = -inf, see load())
                         if (diag) p = key > query + shift ? 0.0f : p;
@@ -328,6 +363,7 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dkdv_varlen_kernel(con
                     }
                     S[i] = p;                 // P
                     dP[i] = p * dP[i];        // dS = P (dP - delta)
+                    if constexpr (CAP) dP[i] *= dt;   // ... (1 - t^2)
                 }
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
@@ -406,7 +442,8 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
     using namespace bwd;
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
-    constexpr bool WIN = std::is_same_v<ARGS, BwdVarlenWindowArgs>;
+    constexpr bool WIN = std::is_base_of_v<BwdVarlenWindowArgs, ARGS>;
+    constexpr bool CAP = std::is_same_v<ARGS, BwdVarlenSoftcapArgs>;
     constexpr bool QK = !std::is_same_v<ARGS, BwdVarlenArgs>;
     static_assert(!(WIN && CAUSAL), "the window carries the causal mask as right = 0");
     __shared__ __attribute__((aligned(16))) char img_k[TBYTES];
@@ -450,11 +487,16 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
         // (a row that saw no key has lse = -inf: its S starts at -inf, p = exp2(-inf) = 0, rather than at lse * scale = +inf)
         const float lse_v = a.lse[stat];
         const bool dead = lse_v == -__builtin_inff();
-        lse_q = query < len ? (dead ? -__builtin_inff() : lse_v * -log2e_over_c()) : 0.0f;
+        lse_q = query < len ? (dead ? -__builtin_inff() : lse_v * (CAP ? -1.4426950408889634f : -log2e_over_c())) : 0.0f;
         dl_q = query < len && !dead ? -a.delta[stat] : 0.0f;
     } else {
         lse_q = query < len ? a.lse[stat] * -log2e_over_c() : 0.0f;
         dl_q = query < len ? -a.delta[stat] : 0.0f;
+    }
+    [[maybe_unused]] float cap_k = 0.0f, cap_ca = 0.0f;   // soft-capping: as in the dK / dV kernel
+    if constexpr (CAP) {
+        cap_k = a.cap_inv_a * 2.8853900817779268f;
+        cap_ca = c * a.cap_a;
     }
     f32x16 dQ[4];
 #pragma unroll
@@ -493,7 +535,7 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
             f32x16 S, dP;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                S[i] = lse_q;
+                S[i] = CAP ? 0.0f : lse_q;
                 dP[i] = dl_q;
                 if (!CAUSAL && !WIN && edge) {   // keys beyond the end: S = -inf, p = exp2(-inf) = 0
                     const int key = kt * TROWS + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
@@ -506,7 +548,15 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
             for (int ks = 0; ks < 8; ++ks) dP = E::mfma(row_read<vec8>(img_v, rb, ks, lane), Ob[ks], dP);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                float p = __builtin_amdgcn_exp2f(c * S[i]);
+                float p;
+                [[maybe_unused]] float dt = 1.0f;   // CAP: d tanh = 1 - t^2
+                if constexpr (CAP) {   // (a dead row's lse_q = -inf: p = exp2(-inf) = 0, no inf - inf)
+                    const float t = cap_tanh(S[i], cap_k);
+                    p = __builtin_amdgcn_exp2f(__builtin_fmaf(t, cap_ca, lse_q));
+                    dt = __builtin_fmaf(-t, t, 1.0f);
+                } else {
+                    p = __builtin_amdgcn_exp2f(c * S[i]);
+                }
                 const int key = kt * TROWS + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
                 if constexpr (CAUSAL) {
                     if (diag) p = key > query + shift ? 0.0f : p;
@@ -516,6 +566,7 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
                     if (outside) p = (key < query + shift - a.left || key > query + shift + a.right || key >= klen || query >= len) ? 0.0f : p;
                 }
                 dP[i] = p * dP[i];        // dS^T
+                if constexpr (CAP) dP[i] *= dt;   // ... (1 - t^2)
             }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {

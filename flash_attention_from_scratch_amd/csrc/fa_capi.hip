@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <cmath>
 #include <mutex>
 #include <vector>
 
@@ -63,6 +64,10 @@ hipError_t bwd_varlen_enqueue(const BwdVarlenArgs &a, int dtype, bool causal, hi
 hipError_t bwd_varlen_qk_enqueue(const BwdVarlenQKArgs &a, int dtype, bool causal, hipStream_t s);
 // fa_bwd_varlen_window.hip: ... under a sliding window (causal arrives as right = 0)
 hipError_t bwd_varlen_window_enqueue(const BwdVarlenWindowArgs &a, int dtype, hipStream_t s);
+// fa_inst_varlen_softcap.hip, fa_bwd_varlen_softcap.hip: the packed windowed forward and backward with logit soft-capping
+kernel_fn_varlen_softcap varlen_softcap_kernel_dt15(bool first_block_skip);
+kernel_fn_varlen_softcap varlen_softcap_kernel_dt5(bool first_block_skip);
+hipError_t bwd_varlen_softcap_enqueue(const BwdVarlenSoftcapArgs &a, int dtype, hipStream_t s);
 }  // namespace fa
 
 namespace {
@@ -328,6 +333,17 @@ void do_init_body(int dev, DeviceState *st) {
             st->status = FA_ERR_LAUNCH;
             snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, varlen sliding-window form %d) on device %d: %s",
                      fa::varlen_lds_bytes_dt15(), i, dev, hipGetErrorString(rc));
+            return;
+        }
+    }
+    // ... and the soft-capped form of the packed one (fa_fwd_launch_varlen_qk_softcap)
+    for (int i = 0; i < 4; ++i) {
+        const void *fn = (i & 2) ? (const void *)fa::varlen_softcap_kernel_dt5((i & 1) != 0) : (const void *)fa::varlen_softcap_kernel_dt15((i & 1) != 0);
+        const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, fa::varlen_lds_bytes_dt15());
+        if (rc != hipSuccess) {
+            st->status = FA_ERR_LAUNCH;
+            snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, varlen soft-capped form) on device %d: %s", fa::varlen_lds_bytes_dt15(),
+                     dev, hipGetErrorString(rc));
             return;
         }
     }
@@ -1195,14 +1211,32 @@ int kvcache_validate(CacheView &c, const fa_kvcache_layout *kc, const fa_kvcache
     return cache_descale_alignment(c);
 }
 
+// ---- fa_softcap: the rules of the two soft-capped entry points (called behind the windowed sibling's own rules) -------------
+int softcap_validate(const fa_softcap *c) {
+    if (!c) return fail(FA_ERR_NULL, "fa_softcap is null: a softcap > 0 is needed (without a cap, call the windowed entry point: this level has no \"off\")");
+    if (c->struct_size < sizeof(fa_softcap))
+        return fail(FA_ERR_SHAPE, "fa_softcap.struct_size (%u) is smaller than this library's (%zu)", c->struct_size, sizeof(fa_softcap));
+    if (!(c->softcap > 0.0f) || !std::isfinite(c->softcap))
+        return fail(FA_ERR_SHAPE, "softcap (%g) must be finite and > 0 (0 = no cap is the windowed entry point's job: this level has no \"off\")",
+                    (double)c->softcap);
+    return FA_OK;
+}
+// what the kernels take: A = softcap sqrt(d_head) and 1 / A, computed in double and rounded once (d_head = 128)
+void softcap_constants(const fa_softcap *c, float *a, float *inv_a) {
+    const double A = (double)c->softcap * std::sqrt(128.0);
+    *a = (float)A;
+    *inv_a = (float)(1.0 / A);
+}
+
 // the forward of `entry` (a public entry point; `total`: its name for the query side's total)
 // `kc` non-null: the key side is a KV cache (fa_fwd_launch_varlen_kvcache), and vk is not used
 // `fp8_side`: ... an fp8 one (fa_fwd_launch_varlen_kvcache_fp8): k, v are bytes, kv's strides count bytes, `sc` holds the descales
 // `windowed`: the entry's sliding-window form, with its fa_window `w` (null is refused, behind everything the entry itself refuses)
+// `capped`: ... of the packed windowed form with logit soft-capping, its fa_softcap `cap` refused behind the window's rules
 int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
                       const fa_varlen_layout *vk, const fa_fwd_opts *opts, float *lse, void *stream, const fa_kvcache_layout *kc = nullptr,
                       bool cache_side = false, const fa_kvcache_fp8_scales *sc = nullptr, bool fp8_side = false, bool windowed = false,
-                      const fa_window *w = nullptr) {
+                      const fa_window *w = nullptr, bool capped = false, const fa_softcap *cap = nullptr) {
     if (cache_side) vk = vq;   // (one valid layout for the checks both launches share)
     if (!args || !kv || !vq || !vk || (cache_side && !kc) || (fp8_side && !sc)) return fail(FA_ERR_NULL, "null pointer argument");
     if (!args->q || !args->k || !args->v || !args->o) return fail(FA_ERR_NULL, "null pointer argument");
@@ -1244,6 +1278,7 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
         if (vq->max_seqlen > kWindowMaxLen)
             return fail(FA_ERR_SHAPE, "max_seqlen_q too large for a window: at most 2^30 - 128 query rows per sequence");
     }
+    if (capped && (rc = softcap_validate(cap)) != FA_OK) return rc;
     if (vq->total_tokens == 0) {   // (no query rows: nothing to write)
         if (o.ms) *o.ms = 0.0f;
         return FA_OK;
@@ -1305,6 +1340,7 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
     // the sliding-window forms: the same arguments and (left, right), causal as right = 0 (the kernel's one rule for both)
     fa::KernelArgsVarlenWindow wqa;
     fa::KernelArgsVarlenKVCacheWindow wca;
+    fa::KernelArgsVarlenSoftcap sqa;
     if (windowed) {
         const bool bf16 = args->cfg.dtype == FA_BF16;
         wf8.left = w->left;
@@ -1320,6 +1356,12 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
             wqa = {qa, wf8.left, wf8.right};
             fn = bf16 ? (const void *)fa::varlen_window_kernel_dt15(fbs) : (const void *)fa::varlen_window_kernel_dt5(fbs);
             kernel_args = &wqa;
+            if (capped) {   // (the packed form only)
+                sqa.w = wqa;
+                softcap_constants(cap, &sqa.cap_a, &sqa.cap_inv_a);
+                fn = bf16 ? (const void *)fa::varlen_softcap_kernel_dt15(fbs) : (const void *)fa::varlen_softcap_kernel_dt5(fbs);
+                kernel_args = &sqa;
+            }
         }
     }
     const dim3 grid((unsigned)(va.base.n_bh * va.base.n_q_blocks)), block((unsigned)e->threads);
@@ -1502,6 +1544,13 @@ int fa_fwd_launch_varlen_qk_window(const fa_fwd_args *args, const fa_kv_layout *
                                    const fa_window *w, const fa_fwd_opts *opts, float *lse, void *stream) {
     return fwd_launch_varlen("fa_fwd_launch_varlen_qk_window", "total_q", args, kv, vq, vk, opts, lse, stream, nullptr, false, nullptr, false, true, w);
 }
+// ... with logit soft-capping: the windowed packed body with an fa_softcap behind the window (served: what the sibling serves)
+int fa_fwd_varlen_qk_softcap_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
+int fa_fwd_launch_varlen_qk_softcap(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_varlen_layout *vk,
+                                    const fa_window *w, const fa_softcap *cap, const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen("fa_fwd_launch_varlen_qk_softcap", "total_q", args, kv, vq, vk, opts, lse, stream, nullptr, false, nullptr, false, true, w,
+                             true, cap);
+}
 int fa_fwd_varlen_kvcache_window_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
 int fa_fwd_launch_varlen_kvcache_window(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
                                         const fa_kvcache_layout *kc, const fa_window *w, const fa_fwd_opts *opts, float *lse, void *stream) {
@@ -1558,7 +1607,9 @@ int fa_bwd_launch_varlen_qk(const fa_bwd_varlen_qk_args *a, void *stream, float 
 
 // the sliding-window form: the sibling's checks, then the window's (the forward's: fwd_launch_varlen); split, workspace and the
 // argument fill are the sibling's, the kernels take (left, right) with -1 as 2^30 and causal as right = 0
-int fa_bwd_launch_varlen_qk_window(const fa_bwd_varlen_qk_args *a, const fa_window *w, void *stream, float *ms) {
+// `capped`: fa_bwd_launch_varlen_qk_softcap -- its fa_softcap `cap` refused behind the window's rules, and the soft-capped kernels
+static int bwd_launch_varlen_window(const fa_bwd_varlen_qk_args *a, const fa_window *w, bool capped, const fa_softcap *cap, void *stream,
+                                    float *ms) {
     int rc = bwd_varlen_checks(a, true, "total_q", "fa_bwd_varlen_qk_workspace_bytes");
     if (rc != FA_OK) return rc;
     if ((rc = window_validate(w, a->causal, 0)) != FA_OK) return rc;
@@ -1566,20 +1617,33 @@ int fa_bwd_launch_varlen_qk_window(const fa_bwd_varlen_qk_args *a, const fa_wind
         return fail(FA_ERR_SHAPE, "max_seqlen_k too large for a window: at most 2^30 - 128 keys per sequence");
     if (a->varlen.max_seqlen > kWindowMaxLen)
         return fail(FA_ERR_SHAPE, "max_seqlen_q too large for a window: at most 2^30 - 128 query rows per sequence");
+    if (capped && (rc = softcap_validate(cap)) != FA_OK) return rc;
     if (a->varlen.total_tokens == 0 && a->varlen_k.total_tokens == 0) {
         if (ms) *ms = 0.0f;
         return FA_OK;
     }
     DeviceState *dev = current_device(&rc);
     if (!dev) return rc;
-    fa::BwdVarlenWindowArgs va;
+    fa::BwdVarlenSoftcapArgs ca;   // (the wider form: the window form's arguments are its base)
+    fa::BwdVarlenWindowArgs &va = ca;
     bwd_varlen_fill(va, a);
     constexpr int32_t kFar = 1 << 30;   // unbounded: beyond every position (kWindowMaxLen), and p - kFar, p + kFar fit 32 bits
     const int32_t right = window_right(w, a->causal);
     va.left = w->left < 0 || w->left > kFar ? kFar : w->left;
     va.right = right < 0 || right > kFar ? kFar : right;
     const hipStream_t s = (hipStream_t)stream;
+    if (capped) {
+        softcap_constants(cap, &ca.cap_a, &ca.cap_inv_a);
+        return enqueue_timed([&] { return fa::bwd_varlen_softcap_enqueue(ca, a->dtype, s); }, s, ms);
+    }
     return enqueue_timed([&] { return fa::bwd_varlen_window_enqueue(va, a->dtype, s); }, s, ms);
+}
+int fa_bwd_launch_varlen_qk_window(const fa_bwd_varlen_qk_args *a, const fa_window *w, void *stream, float *ms) {
+    return bwd_launch_varlen_window(a, w, false, nullptr, stream, ms);
+}
+// ... with logit soft-capping: the sibling's checks and the window's, then the cap's
+int fa_bwd_launch_varlen_qk_softcap(const fa_bwd_varlen_qk_args *a, const fa_window *w, const fa_softcap *cap, void *stream, float *ms) {
+    return bwd_launch_varlen_window(a, w, true, cap, stream, ms);
 }
 
 // ---- KV-cache decode ------------------------------------------------------------------------------------------------------

@@ -513,6 +513,25 @@ typedef Windowed<KernelArgsVarlenKVCacheFp8> KernelArgsVarlenKVCacheFp8Window;
 typedef void (*kernel_fn_varlen_window)(const KernelArgsVarlenWindow);
 typedef void (*kernel_fn_varlen_kvcache_window)(const KernelArgsVarlenKVCacheWindow);
 typedef void (*kernel_fn_varlen_kvcache_fp8_window)(const KernelArgsVarlenKVCacheFp8Window);
+// Logit soft-capping on the packed forward (fa_fwd_launch_varlen_qk_softcap): the logit of a key a row sees is
+// softcap tanh(s / softcap), s = q . k / sqrt(d).  fa_inst_varlen_softcap.hip defines FA_KERNEL_VARLEN_SOFTCAP beside the windowed
+// slice's two macros and gets fa_fwd_kernel_varlen_softcap INSTEAD of fa_fwd_kernel_varlen_window: the windowed text (a window of
+// (-1, -1) runs through it) with one more step, FA_CAP_S, on every S tile right behind qk() and in front of the masks -- a masked
+// key stays -inf (tanh(-inf) = -1 would bring it back to life).  The step replaces the raw S = q . k by A tanh(S / A),
+// A = softcap sqrt(d), so c, the running max, alpha and the lse line behind it stand as they are.  The host passes A and 1 / A.
+struct KernelArgsVarlenSoftcap {
+    KernelArgsVarlenWindow w;
+    float cap_a, cap_inv_a;
+};
+typedef void (*kernel_fn_varlen_softcap)(const KernelArgsVarlenSoftcap);
+#ifdef FA_KERNEL_VARLEN_SOFTCAP
+#if !defined(FA_KERNEL_VARLEN_WINDOW) || defined(FA_KERNEL_VARLEN_KVCACHE)
+#error "the soft-capped form is built on the packed windowed form"
+#endif
+#define FA_CAP_S(S) cap_S(S)
+#else
+#define FA_CAP_S(S)
+#endif
 #ifdef FA_KERNEL_VARLEN_WINDOW
 #define FA_VARLEN_WINDOW true
 #define FA_N_VISITS n_vis
@@ -589,6 +608,10 @@ fa_fwd_kernel_varlen_kvcache_window(const KernelArgsVarlenKVCacheWindow wa) {
     const KernelArgsVarlenKVCache &qa = wa.a;
 #elif defined(FA_KERNEL_VARLEN_KVCACHE)
 fa_fwd_kernel_varlen_kvcache(const KernelArgsVarlenKVCache qa) {
+#elif defined(FA_KERNEL_VARLEN_SOFTCAP)
+fa_fwd_kernel_varlen_softcap(const KernelArgsVarlenSoftcap sa) {
+    const KernelArgsVarlenWindow &wa = sa.w;
+    const KernelArgsVarlenQK &qa = wa.a;
 #elif defined(FA_KERNEL_VARLEN_WINDOW)
 fa_fwd_kernel_varlen_window(const KernelArgsVarlenWindow wa) {
     const KernelArgsVarlenQK &qa = wa.a;
@@ -1100,6 +1123,22 @@ fa_fwd_kernel(const KernelArgs args) {
         }
     };
 #endif
+#ifdef FA_KERNEL_VARLEN_SOFTCAP
+    // FA_CAP_S: S -> A tanh(S / A) with tanh(x) = 1 - 2 / (exp2(2 x log2 e) + 1), one v_exp_f32 and one v_rcp_f32 per element.
+    // exp2 overflowing to +inf gives 1 - 2 / inf = 1 and underflowing to 0 gives 1 - 2 = -1: no NaN at either end.
+    const float cap_a = sa.cap_a, cap_m2a = -2.0f * sa.cap_a, cap_k = sa.cap_inv_a * 2.8853900817779268f;   // 2 log2(e) / A
+    auto cap_S = [&](f32x16 (&S)[QT][NTW]) {
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt)
+#pragma unroll
+            for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float e = __builtin_amdgcn_exp2f(S[qt][nt][r] * cap_k);
+                    S[qt][nt][r] = __builtin_fmaf(__builtin_amdgcn_rcpf(e + 1.0f), cap_m2a, cap_a);
+                }
+    };
+#endif
     // a row whose keys were all masked so far has m = -inf: exponentiate against 0 instead
     auto finite_or_zero = [&](float mval) { return (MASK && mval == -__builtin_inff()) ? 0.0f : mval; };
 
@@ -1316,6 +1355,7 @@ fa_fwd_kernel(const KernelArgs args) {
             // ---- matrix stream 1: S_nxt = K(it+1) Q^T ---------------------------------
             if (!LAST) {
                 qk((it + 1) & 1, S_nxt);
+                FA_CAP_S(S_nxt);
                 if (MASK && tile_needs_mask(it + 1)) mask_S(S_nxt, it + 1);
             }
             // ---- vector stream: P = exp2(S_cur c - m c) (softmax.cuh:51-83) -------------
@@ -1363,6 +1403,7 @@ fa_fwd_kernel(const KernelArgs args) {
             wait_and_barrier();  // K(0), V(0) landed
             if (FA_N_VISITS > 1) issue_k(1, 1);
             qk(0, Sa);
+            FA_CAP_S(Sa);
             if (MASK && tile_needs_mask(0)) mask_S(Sa, 0);
             row_max(Sa);
             if constexpr (FAST) {
@@ -1378,6 +1419,7 @@ fa_fwd_kernel(const KernelArgs args) {
             if (FA_N_VISITS > 1) { load_k(1); load_v(1); }
             barrier();
             qk(0, Sa);
+            FA_CAP_S(Sa);
             if (MASK && tile_needs_mask(0)) mask_S(Sa, 0);
             row_max(Sa);
             if constexpr (FAST) {
@@ -1421,6 +1463,7 @@ fa_fwd_kernel(const KernelArgs args) {
             if (ABL & 64) __builtin_amdgcn_s_setprio(1);
             qk(stage, S);
             if (ABL & 64) __builtin_amdgcn_s_setprio(0);
+            FA_CAP_S(S);
             if (MASK && tile_needs_mask(it)) mask_S(S, it);
             FA_STAMP(it, 2);
             softmax(S, P, alpha, first_tag, fast_tag);
@@ -1448,6 +1491,7 @@ fa_fwd_kernel(const KernelArgs args) {
             vec8 P[QT][NTW][2];
             float alpha[QT];
             qk(0, S);
+            FA_CAP_S(S);
             if (MASK && tile_needs_mask(it)) mask_S(S, it);
             if (OPT && it == 0) {
                 softmax(S, P, alpha, TrueTag{}, FalseTag{});

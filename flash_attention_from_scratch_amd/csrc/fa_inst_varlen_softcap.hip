@@ -1,0 +1,26 @@
+// fa_inst_varlen_softcap.hip -- the forward over packed variable-length sequences with logit soft-capping
+// (fa_fwd_kernel_varlen_softcap; fa_fwd_launch_varlen_qk_softcap), one translation unit per dtype (-DFA_INST_DT=<5|15>).
+// FA_KERNEL_VARLEN_SOFTCAP beside the windowed slice's two macros makes fa_fwd_kernel.hpp define that kernel from the text of
+// fa_fwd_kernel_varlen_window (which this unit then does not have): the same two forms, with and without the first-block skip,
+// compiled with the varlen slices' flags.  The windowed text only: a window of (-1, -1) runs through it.  A slice of its own:
+// the other varlen slices keep their kernels and their code.  The varlen form's LDS (varlen_lds_bytes_dt15).  Not in the registry.
+#define FA_KERNEL_VARLEN
+#define FA_KERNEL_VARLEN_WINDOW
+#define FA_KERNEL_VARLEN_SOFTCAP
+#include "fa_fwd_kernel.hpp"
+
+#ifndef FA_INST_DT
+#error "define FA_INST_DT (5 = fp16, 15 = bf16)"
+#endif
+
+namespace fa {
+
+#define FA_CAT2(a, b) a##b
+#define FA_CAT(a, b) FA_CAT2(a, b)
+kernel_fn_varlen_softcap FA_CAT(varlen_softcap_kernel_dt, FA_INST_DT)(bool first_block_skip) {
+    //                                                          DT          QT NW BC  SWZ   EAGER OPT   PIPE  DMA   MASK  D
+    if (first_block_skip) return &fa_fwd_kernel_varlen_softcap<FA_INST_DT, 1, 4, 64, true, true, true, true, true, true, 128>;
+    return &fa_fwd_kernel_varlen_softcap<FA_INST_DT, 1, 4, 64, true, true, false, true, true, true, 128>;
+}
+
+}  // namespace fa

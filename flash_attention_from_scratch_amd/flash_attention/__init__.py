@@ -91,7 +91,7 @@ def attention(q, k, v, causal=False):
 
 
 def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None, *,
-                   window_size=(-1, -1)):
+                   window_size=(-1, -1), softcap=0.0):
     """Packed variable-length sequences: q (total_tokens, n_heads, 128), k / v (total_tokens, n_kv_heads, 128), cu_seqlens an
     int32 device tensor of n_seqs + 1 row offsets, max_seqlen a Python int (no device sync) -> (o, lse[, ms]) with lse fp32
     (n_heads, total_tokens).  A query attends to the keys of its own sequence (causal: at or before its position in it).
@@ -105,9 +105,16 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
     Query row r, at position p = r + (len_k - len_q), sees the keys max(0, p - left) .. min(len_k - 1, p + right); causal means
     right = 0; bad values are a ValueError.  (-1, -1) is the call above, unchanged.  The gradients of a windowed forward are
     backward_varlen_window's, and attention_varlen(window_size=) pairs the two; backward_varlen takes no window --
-    do not feed it a windowed forward's o and lse."""
+    do not feed it a windowed forward's o and lse.
+
+    Logit soft-capping (flash-attn's softcap): softcap, keyword only, a Python float or int, finite and >= 0.  The
+    logit of a key the row sees becomes softcap * tanh(s / softcap), s = q . k / sqrt(128); the cap comes before every mask, so a
+    key the row does not see stays -inf; lse is the log-sum-exp of the capped logits.  0 is off: the call above, unchanged.  Bad
+    values are a ValueError.  The gradients of a soft-capped forward are backward_varlen_softcap's, and attention_varlen(softcap=)
+    pairs the two."""
     return flash_attention_kernels.forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=causal, timed=timed,
-                                                  cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k, window_size=window_size)
+                                                  cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k, window_size=window_size,
+                                                  softcap=softcap)
 
 
 def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
@@ -216,38 +223,51 @@ def backward_varlen_window(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, window
                                                           timed=timed, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
 
 
+def backward_varlen_softcap(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, softcap, window_size=(-1, -1), causal=False, timed=False,
+                            cu_seqlens_k=None, max_seqlen_k=None):
+    """The backward of forward_varlen(softcap=[, window_size=]): dQ, dK, dV from that forward's o and lse under the same softcap and
+    window.  With t = tanh(s / softcap): dS = P (dP - delta) (1 - t^2).  softcap == 0 is backward_varlen_window
+    with the same arguments, unchanged; bad values are a ValueError.  A row that sees no key gets dq = 0; a key no row sees gets
+    dk = dv = 0, written.  Deterministic."""
+    return flash_attention_kernels.backward_varlen_softcap(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, softcap, window_size,
+                                                           causal=causal, timed=timed, cu_seqlens_k=cu_seqlens_k,
+                                                           max_seqlen_k=max_seqlen_k)
+
+
 def _varlen_needs_copy(t):
     return t.stride(2) != 1 or t.stride(0) % 8 != 0 or t.stride(1) % 8 != 0 or t.data_ptr() % 16 != 0
 
 
 class _AttentionVarlen(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k, window_size=(-1, -1)):
+    def forward(ctx, q, k, v, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k, window_size=(-1, -1), softcap=0.0):
         if _varlen_needs_copy(q):
             q = q.contiguous()
         if _varlen_needs_copy(k) or _varlen_needs_copy(v) or v.stride() != k.stride():
             k, v = k.contiguous(), v.contiguous()
         o, lse = forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=causal, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k,
-                                window_size=window_size)
+                                window_size=window_size, softcap=softcap)
         ctx.qk = cu_seqlens_k is not None
         if ctx.qk:
             ctx.save_for_backward(q, k, v, o, lse, cu_seqlens, cu_seqlens_k)
         else:
             ctx.save_for_backward(q, k, v, o, lse, cu_seqlens)
         ctx.max_seqlen, ctx.max_seqlen_k, ctx.causal, ctx.window_size = max_seqlen, max_seqlen_k, causal, tuple(window_size)
+        ctx.softcap = softcap
         return o
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, o, lse, cu_seqlens = ctx.saved_tensors[:6]
         cu_seqlens_k = ctx.saved_tensors[6] if ctx.qk else None
-        # ((-1, -1): backward_varlen itself)
-        dq, dk, dv = backward_varlen_window(q, k, v, o, lse, dout.contiguous(), cu_seqlens, ctx.max_seqlen, ctx.window_size,
-                                            causal=ctx.causal, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=ctx.max_seqlen_k)
-        return dq, dk, dv, None, None, None, None, None, None
+        # (softcap 0: backward_varlen_window itself; (-1, -1) as well: backward_varlen itself)
+        dq, dk, dv = backward_varlen_softcap(q, k, v, o, lse, dout.contiguous(), cu_seqlens, ctx.max_seqlen, ctx.softcap, ctx.window_size,
+                                             causal=ctx.causal, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=ctx.max_seqlen_k)
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
-def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, cu_seqlens_k=None, max_seqlen_k=None, *, window_size=(-1, -1)):
+def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, cu_seqlens_k=None, max_seqlen_k=None, *, window_size=(-1, -1),
+                     softcap=0.0):
     """softmax(q k^T / sqrt d) v over packed sequences, with gradients (flash-attn's flash_attn_varlen_func): the varlen forward
     with the row log-sum-exp and the varlen HIP backward.  k and v may have n_kv_heads heads.
 
@@ -258,8 +278,13 @@ def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, cu_seqlens_k
 
     window_size=(left, right), keyword only: forward_varlen's sliding window, carried to both passes (the windowed forward and
     backward_varlen_window), so a model with local layers trains by the rule it is served by.  Bad values are a ValueError before
-    any tensor is looked at; (-1, -1) is the call above, bit for bit."""
+    any tensor is looked at; (-1, -1) is the call above, bit for bit.
+
+    softcap, keyword only: forward_varlen's logit soft-capping, carried to both passes (the soft-capped forward and
+    backward_varlen_softcap), with or without a window.  Bad values are a ValueError before any tensor is looked at (a bad window
+    first); 0 is the call above, bit for bit."""
     flash_attention_kernels._window(window_size, causal)
+    flash_attention_kernels._softcap(softcap)
     if (cu_seqlens_k is None) != (max_seqlen_k is None):
         raise ValueError("cu_seqlens_k and max_seqlen_k go together: give both (separate Q and K / V lengths) or neither")
-    return _AttentionVarlen.apply(q, k, v, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k, tuple(window_size))
+    return _AttentionVarlen.apply(q, k, v, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k, tuple(window_size), softcap)

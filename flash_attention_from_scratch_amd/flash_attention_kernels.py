@@ -19,6 +19,7 @@ FA_ALLOW_SPECULATIVE=1 (the round-2 mapping, kept for sweeps).
 """
 
 import ctypes
+import math
 import os
 
 import torch
@@ -346,7 +347,7 @@ def _varlen_layouts(q, k, cu_seqlens, max_seqlen, cu_seqlens_k, max_seqlen_k):
 
 
 def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None, *,
-                   window_size=(-1, -1)):
+                   window_size=(-1, -1), softcap=0.0):
     """Attention over packed sequences with the row log-sum-exp (fa_fwd_launch_varlen): q (total_tokens, n_heads, 128), k and v
     (total_tokens, n_kv_heads, 128), cu_seqlens an int32 device tensor of n_seqs + 1 row offsets, max_seqlen a Python int.
     Strided views (a packed QKV buffer) pass as they are.  -> (o, lse[, ms]); o contiguous, lse fp32 (n_heads, total_tokens).
@@ -363,8 +364,15 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
     p = r + (len_k - len_q), sees the keys max(0, p - left) .. min(len_k - 1, p + right); causal means right = 0.  (-1, -1) takes
     the entry points above unchanged, anything else fa_fwd_launch_varlen_qk_window (one range given: on both sides), which visits
     no key tile outside a Q block's window and fetches no key row below it.  Bad values are a ValueError.  The gradients of a
-    windowed forward are backward_varlen_window's (attention_varlen(window_size=) pairs the two); backward_varlen takes no window."""
+    windowed forward are backward_varlen_window's (attention_varlen(window_size=) pairs the two); backward_varlen takes no window.
+
+    softcap, keyword only, a Python float or int, finite and >= 0 (flash-attn's): the logit of a key the row sees becomes
+    softcap * tanh(s / softcap), s = q . k / sqrt(128); masked keys stay -inf, lse is the log-sum-exp of the capped logits.  0 is
+    off: the call above, the same entry points and bits.  Anything else goes through fa_fwd_launch_varlen_qk_softcap with the window
+    ((-1, -1) included; one range given: on both sides).  Bad values are a ValueError.  The gradients are backward_varlen_softcap's
+    (attention_varlen(softcap=) pairs the two)."""
     window = _window(window_size, causal)
+    cap = _softcap(softcap)
     qk = _qk_sides(cu_seqlens_k, max_seqlen_k)
     _check_varlen(q, k, v, cu_seqlens, max_seqlen, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
     total, n_heads, d_head = q.shape
@@ -382,6 +390,12 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
     opts = _capi.make_opts(causal=causal, ms=ms if timed else None)
     with torch.cuda.device(q.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        if cap is not None:
+            w, sc = _capi.make_window(*(window or (-1, -1))), _capi.make_softcap(cap)
+            _capi.check(lib.fa_fwd_launch_varlen_qk_softcap(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(sides[0]), ctypes.byref(sides[-1]),
+                                                            ctypes.byref(w), ctypes.byref(sc), ctypes.byref(opts),
+                                                            ctypes.c_void_p(lse.data_ptr()), stream))
+            return (o, lse, float(ms.value)) if timed else (o, lse)
         if window is not None:
             w = _capi.make_window(*window)
             _capi.check(lib.fa_fwd_launch_varlen_qk_window(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(sides[0]), ctypes.byref(sides[-1]),
@@ -417,8 +431,21 @@ def backward_varlen_window(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, window
     return _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window)
 
 
-def _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window):
-    """backward_varlen (window None) and backward_varlen_window (window (left, right): the two-range arguments, given or not)"""
+def backward_varlen_softcap(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, softcap, window_size=(-1, -1), causal=False, timed=False,
+                            cu_seqlens_k=None, max_seqlen_k=None):
+    """The backward of a soft-capped (and possibly windowed) forward_varlen: dQ, dK, dV from ITS o and lse under the same softcap
+    and window_size.  With t = tanh(s / softcap), s = q . k / sqrt(128): dS = P (dP - delta) (1 - t^2), dQ = dS K / sqrt(128),
+    dK = dS^T Q / sqrt(128), dV = P^T dO (fa_bwd_launch_varlen_qk_softcap; one range given: on both sides).  softcap == 0 is
+    backward_varlen_window with the same arguments, unchanged.  A row that sees no key gets dq = 0; a key no row sees gets
+    dk = dv = 0, written.  Bad window_size or softcap values are a ValueError before any tensor is looked at."""
+    window = _window(window_size, causal)
+    cap = _softcap(softcap)
+    return _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, cap)
+
+
+def _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, cap=None):
+    """backward_varlen (window None), backward_varlen_window (window (left, right): the two-range arguments, given or not) and
+    backward_varlen_softcap (cap a float: the two-range arguments and a window, (-1, -1) where none is given)"""
     qk = _qk_sides(cu_seqlens_k, max_seqlen_k)
     _check_varlen(q, k, v, cu_seqlens, max_seqlen, others=((o, "o"), (dout, "dout"), (lse, "lse")),
                   cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
@@ -444,10 +471,13 @@ def _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, time
         kv_seq_stride=k.stride(0), kv_head_stride=k.stride(1), dkv_seq_stride=dk.stride(0), dkv_head_stride=dk.stride(1),
         dtype=15 if q.dtype == torch.bfloat16 else 5, causal=1 if causal else 0, varlen=sides[0],
     )
-    if qk or window is not None:
+    if qk or window is not None or cap is not None:
         args = _capi.FaBwdVarlenQKArgs(struct_size=ctypes.sizeof(_capi.FaBwdVarlenQKArgs), varlen_k=sides[-1], **fields)
         workspace_bytes, launch = lib.fa_bwd_varlen_qk_workspace_bytes, lib.fa_bwd_launch_varlen_qk
-        if window is not None:
+        if cap is not None:
+            w, sc = _capi.make_window(*(window or (-1, -1))), _capi.make_softcap(cap)
+            launch = lambda a, stream, ms: lib.fa_bwd_launch_varlen_qk_softcap(a, ctypes.byref(w), ctypes.byref(sc), stream, ms)   # noqa: E731
+        elif window is not None:
             w = _capi.make_window(*window)
             launch = lambda a, stream, ms: lib.fa_bwd_launch_varlen_qk_window(a, ctypes.byref(w), stream, ms)   # noqa: E731
     else:
@@ -489,6 +519,21 @@ def _window(window_size, causal):
     if causal and right not in (-1, 0):
         raise ValueError(f"causal means right = 0: window_size {(left, right)} cannot be causal as well (pass right = -1 or 0)")
     return None if (left, right) == (-1, -1) else (left, right)
+
+
+def _softcap(softcap):
+    """softcap as forward_varlen, attention_varlen and backward_varlen_softcap take it -> None for 0 (no cap: the entry points
+    without one), else the float.  A Python float or int (no bool, no tensor), finite and >= 0; anything else is a ValueError before
+    the library is asked."""
+    if isinstance(softcap, bool) or not isinstance(softcap, (int, float)):
+        raise ValueError(f"softcap must be a Python float or int, finite and >= 0, 0 = off (got {softcap!r})")
+    try:
+        value = float(softcap)
+    except OverflowError:   # (an int beyond the floats)
+        value = float("inf")
+    if not math.isfinite(value) or value < 0:
+        raise ValueError(f"softcap {softcap!r}: must be finite and >= 0 (0 = off)")
+    return None if value == 0 else value
 
 
 def _need_tensors(named):

@@ -803,6 +803,35 @@ int fa_fwd_launch_varlen_kvcache_fp8_window(const fa_fwd_args *args, const fa_kv
 int fa_bwd_launch_varlen_qk_window(const fa_bwd_varlen_qk_args *args, const fa_window *window, void *stream, float *ms);
 
 /*
+ * Logit soft-capping on the packed training path (flash-attn's softcap=).  With s = q . k / sqrt(128), the logit
+ * of a key a row sees is softcap * tanh(s / softcap); a key the row does not see (mask, window, beyond the lengths) stays -inf --
+ * the cap is applied before any mask.  lse is the log-sum-exp of the capped logits (natural units), o = softmax(capped) v; a row
+ * that sees no key still gives o = 0, lse = -inf, dq = 0, and a key no row sees dk = dv = 0, written.  The backward, with
+ * t = tanh(s / softcap): dS = P (dP - delta) (1 - t^2), dQ = dS K / sqrt(128), dK = dS^T Q / sqrt(128), dV = P^T dO; delta is
+ * unchanged.  fa_softcap: struct_size = sizeof(fa_softcap); softcap finite and > 0.  This level has no "off": without a cap, call
+ * fa_fwd_launch_varlen_qk_window / fa_bwd_launch_varlen_qk_window (or their unwindowed siblings).
+ *
+ * Both launches take the arguments of their windowed sibling, a window included: (-1, -1) is legal there and means none (a caller
+ * with one range passes its layout on both sides).  Kernels of their own (the windowed text plus the cap; the sibling's tile
+ * ranges, grids, dK / dV split and workspace: fa_bwd_varlen_qk_workspace_bytes(args) sizes the backward).  tanh is
+ * 1 - 2 / (exp2(2 x log2 e) + 1) on the hardware's exp2 and reciprocal: absolute error a few 1e-7, times softcap on the logit;
+ * it saturates to +-1 without a NaN.  Deterministic, no atomics, graph-capturable.
+ *
+ * Refused before any HIP call, in this order: what the windowed sibling refuses, with its status and message; then a null
+ * fa_softcap (FA_ERR_NULL); then its struct_size, or a softcap that is NaN, infinite or <= 0 (FA_ERR_SHAPE).
+ */
+typedef struct fa_softcap {
+    uint32_t struct_size;      /* sizeof(fa_softcap) */
+    float softcap;             /* > 0, finite */
+} fa_softcap;
+int fa_fwd_varlen_qk_softcap_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_qk_softcap(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                    const fa_varlen_layout *varlen_k, const fa_window *window, const fa_softcap *softcap,
+                                    const fa_fwd_opts *opts, float *lse, void *stream);
+int fa_bwd_launch_varlen_qk_softcap(const fa_bwd_varlen_qk_args *args, const fa_window *window, const fa_softcap *softcap,
+                                    void *stream, float *ms);
+
+/*
  * The step in front of a decode: append seqlen_new new K / V rows per batch entry to the cache IN PLACE, at the positions the
  * device-side lengths name, optionally rotate the new keys and the query (rotary embedding), quantize for an fp8 cache, and
  * advance the lengths.  One kernel on `stream`; the host reads none of the device arrays, so the launch is asynchronous and
