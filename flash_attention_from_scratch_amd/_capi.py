@@ -45,6 +45,10 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_varlen_kvcache_fp8_window_supported", "fa_fwd_launch_varlen_kvcache_fp8_window",
     "fa_bwd_launch_varlen_qk_window",
     "fa_fwd_varlen_qk_softcap_supported", "fa_fwd_launch_varlen_qk_softcap", "fa_bwd_launch_varlen_qk_softcap",
+    "fa_fwd_varlen_kvcache_softcap_supported", "fa_fwd_launch_varlen_kvcache_softcap",
+    "fa_fwd_varlen_kvcache_fp8_softcap_supported", "fa_fwd_launch_varlen_kvcache_fp8_softcap",
+    "fa_decode_softcap_supported", "fa_decode_softcap_num_splits", "fa_decode_softcap_launch",
+    "fa_decode_fp8_softcap_supported", "fa_decode_fp8_softcap_num_splits", "fa_decode_fp8_softcap_launch",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -449,6 +453,16 @@ def load():
     argtypes = list(lib.fa_bwd_launch_varlen_qk_window.argtypes)
     lib.fa_bwd_launch_varlen_qk_softcap.restype = ctypes.c_int
     lib.fa_bwd_launch_varlen_qk_softcap.argtypes = argtypes[:2] + [ctypes.POINTER(FaSoftcap)] + argtypes[2:]
+    # ... and of both cache prefills and both decodes: again the windowed sibling's arguments with an fa_softcap behind the fa_window
+    for name in ("varlen_kvcache", "varlen_kvcache_fp8"):
+        fn = getattr(lib, f"fa_fwd_{name}_softcap_supported")
+        fn.restype, fn.argtypes = ctypes.c_int, [cfg_p, ctypes.POINTER(FaFwdOpts)]
+        fn, argtypes = getattr(lib, f"fa_fwd_launch_{name}_softcap"), list(getattr(lib, f"fa_fwd_launch_{name}_window").argtypes)
+        fn.restype, fn.argtypes = ctypes.c_int, argtypes[:-3] + [ctypes.POINTER(FaSoftcap)] + argtypes[-3:]
+    for name in ("fa_decode", "fa_decode_fp8"):
+        for suffix in ("supported", "num_splits", "launch"):   # (sized by the windowed sibling's workspace query)
+            fn, sibling = getattr(lib, f"{name}_softcap_{suffix}"), getattr(lib, f"{name}_window_{suffix}")
+            fn.restype, fn.argtypes = sibling.restype, sibling.argtypes[:2] + [ctypes.POINTER(FaSoftcap)] + sibling.argtypes[2:]
     lib.fa_kvcache_append_launch.restype = ctypes.c_int
     lib.fa_kvcache_append_launch.argtypes = [ctypes.POINTER(FaKvcacheAppendArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p

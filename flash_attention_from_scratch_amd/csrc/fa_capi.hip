@@ -68,6 +68,11 @@ hipError_t bwd_varlen_window_enqueue(const BwdVarlenWindowArgs &a, int dtype, hi
 kernel_fn_varlen_softcap varlen_softcap_kernel_dt15(bool first_block_skip);
 kernel_fn_varlen_softcap varlen_softcap_kernel_dt5(bool first_block_skip);
 hipError_t bwd_varlen_softcap_enqueue(const BwdVarlenSoftcapArgs &a, int dtype, hipStream_t s);
+// fa_inst_varlen_kvcache_softcap.hip, fa_inst_varlen_kvcache_fp8_softcap.hip: both windowed cache prefills with logit soft-capping
+kernel_fn_varlen_kvcache_softcap varlen_kvcache_softcap_kernel_dt15(bool first_block_skip);
+kernel_fn_varlen_kvcache_softcap varlen_kvcache_softcap_kernel_dt5(bool first_block_skip);
+kernel_fn_varlen_kvcache_fp8_softcap varlen_kvcache_fp8_softcap_kernel_dt15(bool first_block_skip);
+kernel_fn_varlen_kvcache_fp8_softcap varlen_kvcache_fp8_softcap_kernel_dt5(bool first_block_skip);
 }  // namespace fa
 
 namespace {
@@ -1211,7 +1216,7 @@ int kvcache_validate(CacheView &c, const fa_kvcache_layout *kc, const fa_kvcache
     return cache_descale_alignment(c);
 }
 
-// ---- fa_softcap: the rules of the two soft-capped entry points (called behind the windowed sibling's own rules) -------------
+// ---- fa_softcap: the rules of the soft-capped entry points (called behind the windowed sibling's own rules) -----------------
 int softcap_validate(const fa_softcap *c) {
     if (!c) return fail(FA_ERR_NULL, "fa_softcap is null: a softcap > 0 is needed (without a cap, call the windowed entry point: this level has no \"off\")");
     if (c->struct_size < sizeof(fa_softcap))
@@ -1232,7 +1237,7 @@ void softcap_constants(const fa_softcap *c, float *a, float *inv_a) {
 // `kc` non-null: the key side is a KV cache (fa_fwd_launch_varlen_kvcache), and vk is not used
 // `fp8_side`: ... an fp8 one (fa_fwd_launch_varlen_kvcache_fp8): k, v are bytes, kv's strides count bytes, `sc` holds the descales
 // `windowed`: the entry's sliding-window form, with its fa_window `w` (null is refused, behind everything the entry itself refuses)
-// `capped`: ... of the packed windowed form with logit soft-capping, its fa_softcap `cap` refused behind the window's rules
+// `capped`: ... of a windowed form (packed or either cache) with logit soft-capping, its fa_softcap `cap` refused behind the window's rules
 int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
                       const fa_varlen_layout *vk, const fa_fwd_opts *opts, float *lse, void *stream, const fa_kvcache_layout *kc = nullptr,
                       bool cache_side = false, const fa_kvcache_fp8_scales *sc = nullptr, bool fp8_side = false, bool windowed = false,
@@ -1341,6 +1346,8 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
     fa::KernelArgsVarlenWindow wqa;
     fa::KernelArgsVarlenKVCacheWindow wca;
     fa::KernelArgsVarlenSoftcap sqa;
+    fa::KernelArgsVarlenKVCacheSoftcap sca;
+    fa::KernelArgsVarlenKVCacheFp8Softcap sf8;
     if (windowed) {
         const bool bf16 = args->cfg.dtype == FA_BF16;
         wf8.left = w->left;
@@ -1348,15 +1355,27 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
         if (fp8_side) {
             fn = bf16 ? (const void *)fa::varlen_kvcache_fp8_window_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_fp8_window_kernel_dt5(fbs);
             kernel_args = &wf8;
+            if (capped) {
+                sf8.w = wf8;
+                softcap_constants(cap, &sf8.cap_a, &sf8.cap_inv_a);
+                fn = bf16 ? (const void *)fa::varlen_kvcache_fp8_softcap_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_fp8_softcap_kernel_dt5(fbs);
+                kernel_args = &sf8;
+            }
         } else if (cache_side) {
             wca = {ca, wf8.left, wf8.right};
             fn = bf16 ? (const void *)fa::varlen_kvcache_window_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_window_kernel_dt5(fbs);
             kernel_args = &wca;
+            if (capped) {
+                sca.w = wca;
+                softcap_constants(cap, &sca.cap_a, &sca.cap_inv_a);
+                fn = bf16 ? (const void *)fa::varlen_kvcache_softcap_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_softcap_kernel_dt5(fbs);
+                kernel_args = &sca;
+            }
         } else {
             wqa = {qa, wf8.left, wf8.right};
             fn = bf16 ? (const void *)fa::varlen_window_kernel_dt15(fbs) : (const void *)fa::varlen_window_kernel_dt5(fbs);
             kernel_args = &wqa;
-            if (capped) {   // (the packed form only)
+            if (capped) {
                 sqa.w = wqa;
                 softcap_constants(cap, &sqa.cap_a, &sqa.cap_inv_a);
                 fn = bf16 ? (const void *)fa::varlen_softcap_kernel_dt15(fbs) : (const void *)fa::varlen_softcap_kernel_dt5(fbs);
@@ -1564,6 +1583,21 @@ int fa_fwd_launch_varlen_kvcache_fp8_window(const fa_fwd_args *args, const fa_kv
     return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache_fp8_window", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true, sc, true,
                              true, w);
 }
+// ... and both windowed cache prefills with logit soft-capping: an fa_softcap behind the window (served: what the sibling serves)
+int fa_fwd_varlen_kvcache_softcap_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
+int fa_fwd_launch_varlen_kvcache_softcap(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
+                                         const fa_kvcache_layout *kc, const fa_window *w, const fa_softcap *cap, const fa_fwd_opts *opts,
+                                         float *lse, void *stream) {
+    return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache_softcap", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true, nullptr, false,
+                             true, w, true, cap);
+}
+int fa_fwd_varlen_kvcache_fp8_softcap_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
+int fa_fwd_launch_varlen_kvcache_fp8_softcap(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
+                                             const fa_kvcache_layout *kc, const fa_kvcache_fp8_scales *sc, const fa_window *w,
+                                             const fa_softcap *cap, const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache_fp8_softcap", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true, sc, true,
+                             true, w, true, cap);
+}
 
 int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *a) {
     if (!a) return fail(FA_ERR_NULL, "null pointer argument");
@@ -1648,8 +1682,8 @@ int fa_bwd_launch_varlen_qk_softcap(const fa_bwd_varlen_qk_args *a, const fa_win
 
 // ---- KV-cache decode ------------------------------------------------------------------------------------------------------
 // fa_decode_args and fa_decode_fp8_args carry the same members under the same names (the fp8 struct adds its encoding and
-// descales), so one text over either struct serves the sixteen entry points: a planner (validate, then the split count) for the
-// twelve queries and one launch body for the four launches.  What only one struct has sits in the two decode_struct_rules.
+// descales), so one text over either struct serves the twenty-two entry points: a planner (validate, then the split count) for the
+// sixteen queries and one launch body for the six launches (the soft-capped forms: four queries, two launches).  What only one struct has sits in the two decode_struct_rules.
 namespace {
 extern "C++" {   // (as for the cache's rules above; the two overloads need it as well)
 constexpr int64_t kDecodeMaxRows = 64, kDecodeWantWgs = 256, kDecodeKeysPerSplit = 256, kDecodeMaxSplits = 128, kDecodeMaxForced = 1024;
@@ -1726,11 +1760,13 @@ template <class A> int64_t decode_splits(const A *a, const CacheView &c, const f
 }
 
 // The planner of every decode entry point: the arguments (either struct) and, for a window form, its fa_window (null is refused
-// there) -> status, split count and the cache as validated.
-template <class A> DecodePlan decode_plan(const A *a, bool windowed, const fa_window *w) {
+// there) -> status, split count and the cache as validated.  `capped`: a soft-capped form, its fa_softcap refused behind the
+// window's rules; the cap does not enter the split rule.
+template <class A> DecodePlan decode_plan(const A *a, bool windowed, const fa_window *w, bool capped = false, const fa_softcap *cap = nullptr) {
     DecodePlan p;
     p.status = decode_validate(a, p.cache);
     if (p.status == FA_OK && windowed) p.status = window_validate(w, a->causal, p.cache.capacity());
+    if (p.status == FA_OK && capped) p.status = softcap_validate(cap);
     if (p.status == FA_OK) p.splits = decode_splits(a, p.cache, windowed ? w : nullptr);
     return p;
 }
@@ -1781,14 +1817,18 @@ template <class A> void decode_fill(fa::DecodeArgs &d, const A *a, const CacheVi
     d.causal = a->causal != 0;
 }
 
-// The launch of all four forms; `ws_query`: the entry point's workspace query, for its message.
-template <class A> int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_query, void *stream, float *ms) {
+// The launch of all six forms; `ws_query`: the entry point's workspace query (a capped form: its windowed sibling's), for its message.  `capped`: a soft-capped form (always
+// windowed), its fa_softcap refused behind everything the windowed sibling refuses.
+template <class A>
+int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_query, void *stream, float *ms, bool capped = false,
+                  const fa_softcap *cap = nullptr) {
     if (!a) return fail(FA_ERR_NULL, "null pointer argument");
     if (!a->q || !a->k || !a->v || !a->o) return fail(FA_ERR_NULL, "null tensor pointer (q, k, v and o are all needed)");
     if (!a->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to batch int32 lengths is needed");
     const DecodePlan p = decode_plan(a, windowed, w);
     if (p.status != FA_OK) return p.status;
-    if (a->batch == 0) {
+    if (a->batch == 0) {   // (nothing to do -- behind the cap's own rules, as in the packed form)
+        if (capped && softcap_validate(cap) != FA_OK) return softcap_validate(cap);
         if (ms) *ms = 0.0f;
         return FA_OK;
     }
@@ -1802,6 +1842,7 @@ template <class A> int decode_launch(const A *a, bool windowed, const fa_window 
     if (!windowed && (rc = cache_descale_alignment(c)) != FA_OK) return rc;
     if (p.splits > 1 && ((uintptr_t)a->workspace & 15)) return fail(FA_ERR_ALIGN, "workspace must be 16-byte aligned (it holds the splits' fp32 partials)");
     if (windowed && (rc = cache_descale_alignment(c)) != FA_OK) return rc;
+    if (capped && (rc = softcap_validate(cap)) != FA_OK) return rc;
     DeviceState *dev = current_device(&rc);
     if (!dev) return rc;
     fa::DecodeFp8WindowArgs k;   // (the widest form: the other three's arguments are its members)
@@ -1812,8 +1853,16 @@ template <class A> int decode_launch(const A *a, bool windowed, const fa_window 
     k.left = windowed ? w->left : -1;
     k.right = windowed ? window_right(w, a->causal) : -1;
     const fa::DecodeWindowArgs kw = {k.f.d, k.left, k.right};
+    fa::DecodeSoftcapArgs ks = {kw, 0.0f, 0.0f};
+    fa::DecodeFp8SoftcapArgs ks8 = {k, 0.0f, 0.0f};
+    if (capped) {
+        softcap_constants(cap, &ks.cap_a, &ks.cap_inv_a);
+        ks8.cap_a = ks.cap_a;
+        ks8.cap_inv_a = ks.cap_inv_a;
+    }
     const hipStream_t s = (hipStream_t)stream;
     return enqueue_timed([&] {
+        if (capped) return c.fp8 ? fa::decode_fp8_softcap_enqueue(ks8, a->dtype, s) : fa::decode_softcap_enqueue(ks, a->dtype, s);
         if (c.fp8) return windowed ? fa::decode_fp8_window_enqueue(k, a->dtype, s) : fa::decode_fp8_enqueue(k.f, a->dtype, s);
         return windowed ? fa::decode_window_enqueue(kw, a->dtype, s) : fa::decode_enqueue(k.f.d, a->dtype, s);
     }, s, ms);
@@ -1847,6 +1896,29 @@ int fa_decode_fp8_window_num_splits(const fa_decode_fp8_args *a, const fa_window
 int64_t fa_decode_fp8_window_workspace_bytes(const fa_decode_fp8_args *a, const fa_window *w) { return plan_workspace(a, decode_plan(a, true, w)); }
 int fa_decode_fp8_window_launch(const fa_decode_fp8_args *a, const fa_window *w, void *stream, float *ms) {
     return decode_launch(a, true, w, "fa_decode_fp8_window_workspace_bytes", stream, ms);
+}
+
+// ... with logit soft-capping: the windowed forms with an fa_softcap behind the window.  The split count is the windowed entry's for
+// the same arguments, and so is the workspace: no workspace query of their own (as the soft-capped backward has none), the launch is
+// sized by fa_decode_window_workspace_bytes / fa_decode_fp8_window_workspace_bytes.
+int fa_decode_softcap_supported(const fa_decode_args *a, const fa_window *w, const fa_softcap *cap) {
+    return decode_plan(a, true, w, true, cap).status == FA_OK;
+}
+int fa_decode_softcap_num_splits(const fa_decode_args *a, const fa_window *w, const fa_softcap *cap) {
+    return plan_splits(decode_plan(a, true, w, true, cap));
+}
+int fa_decode_softcap_launch(const fa_decode_args *a, const fa_window *w, const fa_softcap *cap, void *stream, float *ms) {
+    return decode_launch(a, true, w, "fa_decode_window_workspace_bytes", stream, ms, true, cap);
+}
+
+int fa_decode_fp8_softcap_supported(const fa_decode_fp8_args *a, const fa_window *w, const fa_softcap *cap) {
+    return decode_plan(a, true, w, true, cap).status == FA_OK;
+}
+int fa_decode_fp8_softcap_num_splits(const fa_decode_fp8_args *a, const fa_window *w, const fa_softcap *cap) {
+    return plan_splits(decode_plan(a, true, w, true, cap));
+}
+int fa_decode_fp8_softcap_launch(const fa_decode_fp8_args *a, const fa_window *w, const fa_softcap *cap, void *stream, float *ms) {
+    return decode_launch(a, true, w, "fa_decode_fp8_window_workspace_bytes", stream, ms, true, cap);
 }
 
 // ---- the KV-cache append in front of a decode --------------------------------------------------------------------------------

@@ -48,6 +48,16 @@
 //  * a lane whose key lies below lo_min FETCHES key lo_min (as one at or beyond len fetches len - 1) and is masked;
 //  * the mask is lo <= key < hi per row, both derived from the row's position.  The partial format, the combine kernel and the
 //    merge are unchanged.
+//
+// What logit soft-capping changes (DecodeSoftcapArgs / DecodeFp8SoftcapArgs: the windowed forms -- a window of (-1, -1) runs through
+// them -- and the cap's A = softcap sqrt(128) and 1 / A; `if constexpr (CAP)` marks the sites):
+//  * in compute_unit every S accumulator goes through A tanh(S / A) = A - 2 A / (exp2(S cap_k) + 1), cap_k = 2 log2(e) / A, one
+//    v_exp_f32 and one v_rcp_f32 per element, right behind the S^T MFMAs and in front of the `seen` select, a row tile at a time
+//    (no second S-sized array lives): a masked key stays -inf (tanh(-inf) = -1 would bring it back to life).  exp2 overflowing
+//    gives A, underflowing -A: no NaN at either end;
+//  * fp8: a tanh between S and the exponent forbids folding k_descale into c, so it goes into cap_k = k_descale 2 log2(e) / A, one
+//    scalar per workgroup; the capped S is in the 16-bit form's units, scale and c are the 16-bit form's constants, and
+//    lse = m / sqrt(128) + log(l).  The combine kernel, the partial format, the merge, the fetch contract and lo_min are unchanged.
 #pragma once
 #include <type_traits>
 
@@ -86,6 +96,16 @@ struct DecodeFp8WindowArgs {
     int32_t left, right;
 };
 
+// ... and logit soft-capping on the windowed forms: A = softcap * sqrt(128) and 1 / A (the host rounds each once)
+struct DecodeSoftcapArgs {
+    DecodeWindowArgs w;
+    float cap_a, cap_inv_a;
+};
+struct DecodeFp8SoftcapArgs {
+    DecodeFp8WindowArgs w;
+    float cap_a, cap_inv_a;
+};
+
 namespace decode {
 constexpr int D = 128, UNIT = 32, TILE = 64, NWAVES = 4, THREADS = NWAVES * 64;
 constexpr int VROW = 288;              // bytes per key of the V image: 256 + 32, so the 8 keys a 32-lane half's transposed read
@@ -98,11 +118,16 @@ __host__ __device__ inline const DecodeArgs &common(const DecodeArgs &a) { retur
 __host__ __device__ inline const DecodeArgs &common(const DecodeFp8Args &a) { return a.d; }
 __host__ __device__ inline const DecodeArgs &common(const DecodeWindowArgs &a) { return a.d; }
 __host__ __device__ inline const DecodeArgs &common(const DecodeFp8WindowArgs &a) { return a.f.d; }
+__host__ __device__ inline const DecodeArgs &common(const DecodeSoftcapArgs &a) { return a.w.d; }
+__host__ __device__ inline const DecodeArgs &common(const DecodeFp8SoftcapArgs &a) { return a.w.f.d; }
 // the fp8 forms' descales
 __host__ __device__ inline const DecodeFp8Args &fp8_part(const DecodeFp8Args &a) { return a; }
 __host__ __device__ inline const DecodeFp8Args &fp8_part(const DecodeFp8WindowArgs &a) { return a.f; }
-template <class ARGS> constexpr bool is_fp8 = std::is_same_v<ARGS, DecodeFp8Args> || std::is_same_v<ARGS, DecodeFp8WindowArgs>;
-template <class ARGS> constexpr bool is_window = std::is_same_v<ARGS, DecodeWindowArgs> || std::is_same_v<ARGS, DecodeFp8WindowArgs>;
+__host__ __device__ inline const DecodeFp8Args &fp8_part(const DecodeFp8SoftcapArgs &a) { return a.w.f; }
+template <class ARGS> constexpr bool is_cap = std::is_same_v<ARGS, DecodeSoftcapArgs> || std::is_same_v<ARGS, DecodeFp8SoftcapArgs>;
+template <class ARGS>
+constexpr bool is_fp8 = std::is_same_v<ARGS, DecodeFp8Args> || std::is_same_v<ARGS, DecodeFp8WindowArgs> || std::is_same_v<ARGS, DecodeFp8SoftcapArgs>;
+template <class ARGS> constexpr bool is_window = std::is_same_v<ARGS, DecodeWindowArgs> || std::is_same_v<ARGS, DecodeFp8WindowArgs> || is_cap<ARGS>;
 
 // (eight e4m3fn values as eight values of Q's type: cvt_fp8x8, fa_fwd_kernel.hpp)
 }  // namespace decode
@@ -112,7 +137,7 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
     using namespace decode;
-    constexpr bool FP8 = is_fp8<ARGS>, WINDOW = is_window<ARGS>;
+    constexpr bool FP8 = is_fp8<ARGS>, WINDOW = is_window<ARGS>, CAP = is_cap<ARGS>;
     constexpr int KS = D / 32, DT16 = D / 16;
     constexpr int MERGE = NT * DT16 * 64 * 16;   // one wave's accumulators
     constexpr int MAIN = NWAVES * VBYTES > MERGE ? NWAVES * VBYTES : MERGE;
@@ -136,7 +161,14 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     [[maybe_unused]] int lo_min = 0;   // window: the lowest key a row of this workgroup sees (<= len - 1 when len > 0)
     int t0, t1;
     if constexpr (WINDOW) {
-        if (args.left >= 0) {
+        // (the capped forms' window is a member of a member, written out beside the windowed forms' line here and below: one more
+        // value or inlined call in front of it would renumber the blocks the windowed units' kept ISA names)
+        if constexpr (CAP) {
+            if (args.w.left >= 0) {
+                const int64_t lo = (int64_t)len - a.seqlen_q - args.w.left;
+                lo_min = lo > 0 ? (int)lo : 0;
+            }
+        } else if (args.left >= 0) {
             const int64_t lo = (int64_t)len - a.seqlen_q - args.left;
             lo_min = lo > 0 ? (int)lo : 0;
         }
@@ -164,8 +196,13 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     [[maybe_unused]] int w_left = 0, w_right = 0;
     if constexpr (WINDOW) {   // unbounded, or beyond what any length reaches (the host: len <= 2^30 - 128; p >= -seqlen_q >= -64): all one
         constexpr int FAR = (1 << 30) + 64;
-        w_left = args.left < 0 || args.left > FAR ? FAR : args.left;
-        w_right = args.right < 0 || args.right > FAR ? FAR : args.right;
+        if constexpr (CAP) {
+            w_left = args.w.left < 0 || args.w.left > FAR ? FAR : args.w.left;
+            w_right = args.w.right < 0 || args.w.right > FAR ? FAR : args.w.right;
+        } else {
+            w_left = args.left < 0 || args.left > FAR ? FAR : args.left;
+            w_right = args.right < 0 || args.right > FAR ? FAR : args.right;
+        }
     }
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -183,7 +220,14 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     }
 
     float scale, c;   // logits (fp8: raw logits) -> logits, and -> the exponent of exp2
-    if constexpr (FP8) {
+    // CAP: S -> A tanh(S / A) = cap_a + cap_m2a / (exp2(S cap_k) + 1); fp8: S is raw, so k_descale goes into cap_k, not into c
+    [[maybe_unused]] float cap_a = 0.0f, cap_m2a = 0.0f, cap_k = 0.0f;
+    if constexpr (CAP) {
+        cap_a = args.cap_a;
+        cap_m2a = -2.0f * args.cap_a;
+        cap_k = kd * (args.cap_inv_a * 2.8853900817779268f);   // 2 log2(e) / A (16-bit: kd = 1)
+    }
+    if constexpr (FP8 && !CAP) {
         scale = kd / __builtin_sqrtf((float)D);
         c = scale * 1.4426950408889634074f;
     } else {
@@ -307,7 +351,13 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
                 bool seen;
                 if constexpr (WINDOW) seen = from_lo + (unsigned)(16 * (j >> 2) + (j & 3)) < span;
                 else seen = key_g + 16 * (j >> 2) + (j & 3) < lim[nt];
-                s[j] = seen ? S[nt][j >> 2][j & 3] : ninf;
+                if constexpr (CAP) {
+                    const float e = __builtin_amdgcn_exp2f(S[nt][j >> 2][j & 3] * cap_k);
+                    const float capped = __builtin_fmaf(__builtin_amdgcn_rcpf(e + 1.0f), cap_m2a, cap_a);
+                    s[j] = seen ? capped : ninf;
+                } else {
+                    s[j] = seen ? S[nt][j >> 2][j & 3] : ninf;
+                }
                 mx = fmaxf(mx, s[j]);
             }
             const float m_new = fmaxf(m[nt], quad_max(mx));
@@ -373,9 +423,10 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     // the same operations.)
     int li_e = li, g_e = g, group_e = a.group;
     [[maybe_unused]] float kd_e = kd;
-    if constexpr (WINDOW) asm volatile("" : "+v"(li_e), "+v"(g_e), "+s"(kd_e), "+s"(group_e));
+    if constexpr (CAP) asm volatile("" : "+v"(li_e), "+v"(g_e), "+s"(group_e));   // (the cap's scale is a constant: no descale behind the loop)
+    else if constexpr (WINDOW) asm volatile("" : "+v"(li_e), "+v"(g_e), "+s"(kd_e), "+s"(group_e));
     const int lane_e = WINDOW ? (g_e << 4 | li_e) : lane;
-    const float scale_e = WINDOW && FP8 ? kd_e / __builtin_sqrtf((float)D) : scale;
+    const float scale_e = WINDOW && FP8 && !CAP ? kd_e / __builtin_sqrtf((float)D) : scale;
 
     // the four waves' states into wave 0: one reference per row for all of them, then plain sums in wave order
 #pragma unroll
@@ -479,8 +530,8 @@ __global__ void __launch_bounds__(64) fa_decode_combine_kernel(const DecodeArgs 
 
 // The enqueue of one decode in either form: the split kernel and, for num_splits > 1, the combine kernel (the partial format
 // is the same, so the fp8 form launches it on its DecodeArgs part) on stream s.  Instantiated by fa_decode.hip (DecodeArgs),
-// fa_decode_fp8.hip (DecodeFp8Args), fa_decode_window.hip (DecodeWindowArgs) and fa_decode_fp8_window.hip (DecodeFp8WindowArgs),
-// which hold the kernels.
+// fa_decode_fp8.hip (DecodeFp8Args), fa_decode_window.hip (DecodeWindowArgs), fa_decode_fp8_window.hip (DecodeFp8WindowArgs),
+// fa_decode_softcap.hip (DecodeSoftcapArgs) and fa_decode_fp8_softcap.hip (DecodeFp8SoftcapArgs), which hold the kernels.
 template <class ARGS, int DT, int NT, bool PAGED>
 static hipError_t decode_enqueue_t(const ARGS &args, hipStream_t s) {
     const DecodeArgs &a = decode::common(args);
@@ -512,5 +563,7 @@ hipError_t decode_enqueue(const DecodeArgs &a, int dtype, hipStream_t s);       
 hipError_t decode_fp8_enqueue(const DecodeFp8Args &a, int dtype, hipStream_t s);   // fa_decode_fp8.hip
 hipError_t decode_window_enqueue(const DecodeWindowArgs &a, int dtype, hipStream_t s);          // fa_decode_window.hip
 hipError_t decode_fp8_window_enqueue(const DecodeFp8WindowArgs &a, int dtype, hipStream_t s);   // fa_decode_fp8_window.hip
+hipError_t decode_softcap_enqueue(const DecodeSoftcapArgs &a, int dtype, hipStream_t s);          // fa_decode_softcap.hip
+hipError_t decode_fp8_softcap_enqueue(const DecodeFp8SoftcapArgs &a, int dtype, hipStream_t s);   // fa_decode_fp8_softcap.hip
 
 }  // namespace fa

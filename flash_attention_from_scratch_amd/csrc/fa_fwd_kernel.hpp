@@ -524,9 +524,23 @@ struct KernelArgsVarlenSoftcap {
     float cap_a, cap_inv_a;
 };
 typedef void (*kernel_fn_varlen_softcap)(const KernelArgsVarlenSoftcap);
+// ... and on both cache prefills (fa_fwd_launch_varlen_kvcache_softcap, fa_fwd_launch_varlen_kvcache_fp8_softcap):
+// fa_inst_varlen_kvcache_softcap.hip and fa_inst_varlen_kvcache_fp8_softcap.hip define FA_KERNEL_VARLEN_SOFTCAP beside the windowed
+// cache slice's macros and get fa_fwd_kernel_varlen_kvcache_softcap / fa_fwd_kernel_varlen_kvcache_fp8_softcap INSTEAD of the windowed
+// kernel.  16-bit cache: the same step.  fp8 cache: a tanh between S and the exponent forbids folding k_descale into c, so the
+// descale goes into the cap's constant instead, cap_k = k_descale 2 log2(e) / A (one scalar per workgroup): the capped S is in the
+// 16-bit form's units, c is the plain constant and the lse line is the 16-bit form's.
+template <class W> struct Softcapped {
+    W w;
+    float cap_a, cap_inv_a;
+};
+typedef Softcapped<KernelArgsVarlenKVCacheWindow> KernelArgsVarlenKVCacheSoftcap;
+typedef Softcapped<KernelArgsVarlenKVCacheFp8Window> KernelArgsVarlenKVCacheFp8Softcap;
+typedef void (*kernel_fn_varlen_kvcache_softcap)(const KernelArgsVarlenKVCacheSoftcap);
+typedef void (*kernel_fn_varlen_kvcache_fp8_softcap)(const KernelArgsVarlenKVCacheFp8Softcap);
 #ifdef FA_KERNEL_VARLEN_SOFTCAP
-#if !defined(FA_KERNEL_VARLEN_WINDOW) || defined(FA_KERNEL_VARLEN_KVCACHE)
-#error "the soft-capped form is built on the packed windowed form"
+#if !defined(FA_KERNEL_VARLEN_WINDOW)
+#error "the soft-capped forms are built on the windowed forms"
 #endif
 #define FA_CAP_S(S) cap_S(S)
 #else
@@ -541,12 +555,18 @@ typedef void (*kernel_fn_varlen_softcap)(const KernelArgsVarlenSoftcap);
 #endif
 #ifdef FA_KERNEL_VARLEN_KVCACHE_FP8
 #define FA_FP8_CACHE true
-#define FA_K_DESCALED(c0) (fa8.k_descale ? (c0) * fa8.k_descale[(int64_t)b * fa8.ds_bs + h / va.group] : (c0))
 #define FA_ST_SS32 kv_ss   // the K / V seq stride of the register-staged transport: the cache's (bytes) ...
+#ifdef FA_KERNEL_VARLEN_SOFTCAP
+// (soft-capped: k_descale sits in the cap's constant, so c and the lse line are the 16-bit form's)
+#define FA_K_DESCALED(c0) c0
+#define FA_LSE_M_TIMES_C(m, c) m * c
+#else
+#define FA_K_DESCALED(c0) (fa8.k_descale ? (c0) * fa8.k_descale[(int64_t)b * fa8.ds_bs + h / va.group] : (c0))
 // m c of the LSE line, rounded before log2 l is added.  With c a compile-time constant (every other form) hipcc moves the
 // product into finite_or_zero's select, which keeps it from contracting with the add; with c a run-time value (c0 k_descale)
 // it would form fma(m, c, log2 l) and lse would differ from the 16-bit cache's in the last bit.
 #define FA_LSE_M_TIMES_C(m, c) mul_rounded(m, c)
+#endif
 #else
 #define FA_FP8_CACHE false
 #define FA_K_DESCALED(c0) c0
@@ -596,7 +616,16 @@ __global__ void
 #ifdef FA_KERNEL_VARLEN
 // (one workgroup per SIMD set: with m live up to the LSE store the 256-register budget of two waves per SIMD spills)
 __launch_bounds__(NWAVES * 64, 1)
-#if defined(FA_KERNEL_VARLEN_KVCACHE_FP8) && defined(FA_KERNEL_VARLEN_WINDOW)
+#if defined(FA_KERNEL_VARLEN_KVCACHE_FP8) && defined(FA_KERNEL_VARLEN_SOFTCAP)
+fa_fwd_kernel_varlen_kvcache_fp8_softcap(const KernelArgsVarlenKVCacheFp8Softcap sa) {
+    const KernelArgsVarlenKVCacheFp8Window &wa = sa.w;
+    const KernelArgsVarlenKVCacheFp8 &fa8 = wa.a;
+    const KernelArgsVarlenKVCache &qa = fa8.c;
+#elif defined(FA_KERNEL_VARLEN_KVCACHE) && defined(FA_KERNEL_VARLEN_SOFTCAP)
+fa_fwd_kernel_varlen_kvcache_softcap(const KernelArgsVarlenKVCacheSoftcap sa) {
+    const KernelArgsVarlenKVCacheWindow &wa = sa.w;
+    const KernelArgsVarlenKVCache &qa = wa.a;
+#elif defined(FA_KERNEL_VARLEN_KVCACHE_FP8) && defined(FA_KERNEL_VARLEN_WINDOW)
 fa_fwd_kernel_varlen_kvcache_fp8_window(const KernelArgsVarlenKVCacheFp8Window wa) {
     const KernelArgsVarlenKVCacheFp8 &fa8 = wa.a;
     const KernelArgsVarlenKVCache &qa = fa8.c;
@@ -1126,7 +1155,13 @@ fa_fwd_kernel(const KernelArgs args) {
 #ifdef FA_KERNEL_VARLEN_SOFTCAP
     // FA_CAP_S: S -> A tanh(S / A) with tanh(x) = 1 - 2 / (exp2(2 x log2 e) + 1), one v_exp_f32 and one v_rcp_f32 per element.
     // exp2 overflowing to +inf gives 1 - 2 / inf = 1 and underflowing to 0 gives 1 - 2 = -1: no NaN at either end.
+#ifdef FA_KERNEL_VARLEN_KVCACHE_FP8
+    // (fp8 cache: S arrives in raw, undescaled units; k_descale times the constant brings the tanh's argument to the 16-bit form's)
+    const float cap_a = sa.cap_a, cap_m2a = -2.0f * sa.cap_a,
+                cap_k = (fa8.k_descale ? fa8.k_descale[(int64_t)b * fa8.ds_bs + h / va.group] : 1.0f) * (sa.cap_inv_a * 2.8853900817779268f);
+#else
     const float cap_a = sa.cap_a, cap_m2a = -2.0f * sa.cap_a, cap_k = sa.cap_inv_a * 2.8853900817779268f;   // 2 log2(e) / A
+#endif
     auto cap_S = [&](f32x16 (&S)[QT][NTW]) {
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt)

@@ -151,8 +151,25 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
                                                    advance_seqlens=advance_seqlens, window_size=window_size)
 
 
+def forward_kvcache_softcap(q, k_cache, v_cache, cache_seqlens, softcap, block_table=None, causal=False, return_lse=False,
+                            max_seqlen_k=None, num_splits=0, timed=False, k_descale=None, v_descale=None, window_size=(-1, -1), k=None,
+                            v=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, advance_seqlens=False):
+    """forward_kvcache with logit soft-capping (flash-attn's softcap, Gemma-2's attention): every other argument is
+    forward_kvcache's, with its meaning, checks and defaults -- both cache types, paged and contiguous, the window, the fused
+    append.  softcap, required, a Python float or int, finite and >= 0: the logit of a key the row sees becomes
+    softcap * tanh(s / softcap), s = q . k / sqrt(128) on the dequantized key, applied before any mask (a masked key stays -inf);
+    lse is the log-sum-exp of the capped logits.  0 is off: forward_kvcache with the same arguments, bit for bit.  With k / v the
+    append runs first, unchanged: the cap belongs to the attention only.  The split count and the workspace are the windowed
+    call's.  A bad window_size is reported first, then a bad softcap: both a ValueError before any tensor is looked at."""
+    return flash_attention_kernels.forward_kvcache_softcap(q, k_cache, v_cache, cache_seqlens, softcap, block_table=block_table,
+                                                           causal=causal, return_lse=return_lse, max_seqlen_k=max_seqlen_k,
+                                                           num_splits=num_splits, timed=timed, k_descale=k_descale, v_descale=v_descale,
+                                                           window_size=window_size, k=k, v=v, rotary_cos=rotary_cos, rotary_sin=rotary_sin,
+                                                           rotary_interleaved=rotary_interleaved, advance_seqlens=advance_seqlens)
+
+
 def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table=None, causal=False,
-                           max_seqlen_k=None, timed=False, k_descale=None, v_descale=None, *, window_size=(-1, -1)):
+                           max_seqlen_k=None, timed=False, k_descale=None, v_descale=None, *, window_size=(-1, -1), softcap=0.0):
     """Prefill against a K / V cache (flash-attn's flash_attn_varlen_func(..., block_table=)): chunked prefill
     behind a cached prefix, prompts behind a shared prefix, verification of more rows than forward_kvcache serves.  q
     (total_q, n_heads, 128) holds the query rows of all sequences packed, sequence i's at rows cu_seqlens_q[i] ..
@@ -177,10 +194,17 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
     with another bounded right is a ValueError, like values below -1).  (-1, -1) is the call above, unchanged.  Each block of 128
     query rows visits only the key tiles of its rows' windows; no cache row, page or block_table entry wholly below
     max(0, len_k - len_q - left) is read, so such rows and pages may be stale, freed or reused.  Both cache types, paged and
-    contiguous; bit for bit forward_varlen(cu_seqlens_k=, window_size=) on the same keys packed."""
+    contiguous; bit for bit forward_varlen(cu_seqlens_k=, window_size=) on the same keys packed.
+
+    Logit soft-capping (forward_varlen's softcap, so a model trained with a cap prefills and decodes by one rule):
+    softcap, keyword only, a Python float or int, finite and >= 0.  The logit of a key the row sees becomes
+    softcap * tanh(s / softcap), s = q . k / sqrt(128) on the dequantized key, applied before any mask; lse is the log-sum-exp of the
+    capped logits.  0 is the call above, unchanged.  With or without a window, both cache types; with a 16-bit cache bit for bit
+    forward_varlen(cu_seqlens_k=, window_size=, softcap=) on the same keys packed.  A bad window_size is reported first, then a bad
+    softcap, both a ValueError before any tensor is looked at."""
     return flash_attention_kernels.forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens,
                                                           block_table=block_table, causal=causal, max_seqlen_k=max_seqlen_k, timed=timed,
-                                                          k_descale=k_descale, v_descale=v_descale, window_size=window_size)
+                                                          k_descale=k_descale, v_descale=v_descale, window_size=window_size, softcap=softcap)
 
 
 def append_kvcache(k_cache, v_cache, k, v, cache_seqlens, block_table=None, q=None, rotary_cos=None, rotary_sin=None,

@@ -522,7 +522,8 @@ def _window(window_size, causal):
 
 
 def _softcap(softcap):
-    """softcap as forward_varlen, attention_varlen and backward_varlen_softcap take it -> None for 0 (no cap: the entry points
+    """softcap as forward_varlen, attention_varlen, backward_varlen_softcap, forward_varlen_kvcache and forward_kvcache_softcap take
+    it -> None for 0 (no cap: the entry points
     without one), else the float.  A Python float or int (no bool, no tensor), finite and >= 0; anything else is a ValueError before
     the library is asked."""
     if isinstance(softcap, bool) or not isinstance(softcap, (int, float)):
@@ -778,8 +779,30 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
     window_size=(left, right), Python ints, -1 = unbounded: query row i, at position p = len - seqlen_q + i, sees the keys
     max(0, p - left) .. min(len - 1, p + right); causal means right = 0.  (-1, -1) takes the entry points above unchanged, anything
     else fa_decode_window_launch / fa_decode_fp8_window_launch, which fetch nothing below the lowest key a row sees.  With k / v
-    the window applies to the lengths after the append.  Bad values are a ValueError."""
+    the window applies to the lengths after the append.  Bad values are a ValueError.
+    (Logit soft-capping: forward_kvcache_softcap, the same call with a softcap.)"""
+    return _forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table, causal, return_lse, max_seqlen_k, num_splits, timed, k_descale,
+                            v_descale, _window(window_size, causal), k, v, rotary_cos, rotary_sin, rotary_interleaved, advance_seqlens, None)
+
+
+def forward_kvcache_softcap(q, k_cache, v_cache, cache_seqlens, softcap, block_table=None, causal=False, return_lse=False,
+                            max_seqlen_k=None, num_splits=0, timed=False, k_descale=None, v_descale=None, window_size=(-1, -1), k=None,
+                            v=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, advance_seqlens=False):
+    """forward_kvcache with logit soft-capping (fa_decode_softcap_launch, fa_decode_fp8_softcap_launch for an fp8 cache): every other
+    argument is forward_kvcache's, with its meaning, checks and defaults.  softcap, required, a Python float or int, finite and >= 0
+    (flash-attn's): the logit of a key the row sees becomes softcap * tanh(s / softcap), s = q . k / sqrt(128) on the dequantized
+    key; masked keys stay -inf, lse is the log-sum-exp of the capped logits.  0 is off: forward_kvcache with the same arguments, the
+    same entry points and bits.  Anything else goes through the capped entry points with the window, (-1, -1) included; the split
+    count and the workspace are the windowed entry's.  With k / v the append runs first, unchanged: the cap belongs to the attention
+    only.  A bad window_size is reported first, then a bad softcap: both a ValueError before any tensor is looked at."""
     window = _window(window_size, causal)
+    return _forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table, causal, return_lse, max_seqlen_k, num_splits, timed, k_descale,
+                            v_descale, window, k, v, rotary_cos, rotary_sin, rotary_interleaved, advance_seqlens, _softcap(softcap))
+
+
+def _forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table, causal, return_lse, max_seqlen_k, num_splits, timed, k_descale,
+                     v_descale, window, k, v, rotary_cos, rotary_sin, rotary_interleaved, advance_seqlens, cap):
+    """The one body of forward_kvcache (cap None) and forward_kvcache_softcap (cap a float, or None for 0); window: _window's."""
     if k is not None or v is not None or rotary_cos is not None or rotary_sin is not None or advance_seqlens:
         if k is None or v is None:
             raise RuntimeError("k and v come together; rotary_cos / rotary_sin and advance_seqlens need them (the append is what they act on)")
@@ -801,7 +824,14 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
     lse = torch.empty((batch, n_heads, seqlen_q), dtype=torch.float32, device=q.device) if return_lse else None
     args.o, args.lse = o.data_ptr(), (lse.data_ptr() if return_lse else None)
     lib = _capi.load()
-    if window is None:
+    if cap is not None:   # (the capped entry points always take a window: (-1, -1) is none)
+        w, sc = _capi.make_window(*(window or (-1, -1))), _capi.make_softcap(cap)
+        # (no workspace query of their own: the windowed entry's bytes for the same arguments are what the launch asks for)
+        sized, run = ((lib.fa_decode_fp8_window_workspace_bytes, lib.fa_decode_fp8_softcap_launch) if fp8 else
+                      (lib.fa_decode_window_workspace_bytes, lib.fa_decode_softcap_launch))
+        workspace_bytes = lambda a: sized(a, ctypes.byref(w))                                           # noqa: E731
+        launch = lambda a, stream, ms: run(a, ctypes.byref(w), ctypes.byref(sc), stream, ms)            # noqa: E731
+    elif window is None:
         workspace_bytes, launch = ((lib.fa_decode_fp8_workspace_bytes, lib.fa_decode_fp8_launch) if fp8 else
                                    (lib.fa_decode_workspace_bytes, lib.fa_decode_launch))
     else:
@@ -825,7 +855,7 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
 
 
 def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table=None, causal=False,
-                           max_seqlen_k=None, timed=False, k_descale=None, v_descale=None, *, window_size=(-1, -1)):
+                           max_seqlen_k=None, timed=False, k_descale=None, v_descale=None, *, window_size=(-1, -1), softcap=0.0):
     """Prefill against a K / V cache (fa_fwd_launch_varlen_kvcache): forward_varlen(cu_seqlens_k=) whose keys are read from the
     cache in place.  q (total_q, n_heads, 128) packed, cu_seqlens_q an int32 device tensor of n_seqs + 1 row offsets, max_seqlen_q
     a Python int; k_cache, v_cache (n_seqs, seqlen_cache, n_kv_heads, 128), or with block_table (n_seqs, max_pages_per_seq) int32 on
@@ -843,8 +873,14 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
     means right = 0.  (-1, -1) takes the entry points above unchanged, anything else fa_fwd_launch_varlen_kvcache_window /
     fa_fwd_launch_varlen_kvcache_fp8_window: a Q block visits only the key tiles of its rows' windows, and no cache row, page
     or block_table entry wholly below the sequence's lowest visible key max(0, len_k - len_q - left) is read.  Bad values are a
-    ValueError, before any tensor is looked at."""
+    ValueError, before any tensor is looked at.
+    softcap, keyword only, a Python float or int, finite and >= 0 (forward_varlen's): the logit of a key the row sees becomes
+    softcap * tanh(s / softcap), s = q . k / sqrt(128) on the dequantized key; masked keys stay -inf, lse is the log-sum-exp of the
+    capped logits.  0 is off: the call above, the same entry points and bits.  Anything else goes through
+    fa_fwd_launch_varlen_kvcache_softcap / fa_fwd_launch_varlen_kvcache_fp8_softcap with the window, (-1, -1) included.  A bad
+    window_size is reported first, then a bad softcap."""
     window = _window(window_size, causal)
+    cap = _softcap(softcap)
     tensors = [(q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cu_seqlens_q, "cu_seqlens_q"), (cache_seqlens, "cache_seqlens")]
     if block_table is not None:
         tensors.append((block_table, "block_table"))
@@ -903,16 +939,21 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
         ms = ctypes.c_float(0.0)
         opts = _capi.make_opts(causal=causal, ms=ms if timed else None)
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        # (a window goes in front of opts, and picks the entry point's _window form)
+        # (a window goes in front of opts, and picks the entry point's _window form; a cap behind it picks the _softcap form, which
+        # always takes a window: (-1, -1) is none)
+        form = "" if window is None else "_window"
         w = [ctypes.byref(_capi.make_window(*window))] if window is not None else []
+        if cap is not None:
+            form = "_softcap"
+            w = [ctypes.byref(_capi.make_window(*(window or (-1, -1)))), ctypes.byref(_capi.make_softcap(cap))]
         tail = w + [ctypes.byref(opts), ctypes.c_void_p(lse.data_ptr()), stream]
         if fp8:
             sc = _capi.make_kvcache_fp8_scales(k_descale=k_descale.data_ptr(), v_descale=v_descale.data_ptr(),
                                                descale_batch_stride=k_descale.stride(0))
-            launch = lib.fa_fwd_launch_varlen_kvcache_fp8_window if w else lib.fa_fwd_launch_varlen_kvcache_fp8
+            launch = getattr(lib, "fa_fwd_launch_varlen_kvcache_fp8" + form)
             _capi.check(launch(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(vq), ctypes.byref(kc), ctypes.byref(sc), *tail))
         else:
-            launch = lib.fa_fwd_launch_varlen_kvcache_window if w else lib.fa_fwd_launch_varlen_kvcache
+            launch = getattr(lib, "fa_fwd_launch_varlen_kvcache" + form)
             _capi.check(launch(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(vq), ctypes.byref(kc), *tail))
     return (o, lse, float(ms.value)) if timed else (o, lse)
 

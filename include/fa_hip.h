@@ -832,6 +832,40 @@ int fa_bwd_launch_varlen_qk_softcap(const fa_bwd_varlen_qk_args *args, const fa_
                                     void *stream, float *ms);
 
 /*
+ * Logit soft-capping on the inference path: the cache prefill and the decode, 16-bit and fp8 cache.  The same
+ * definition as above: the logit of a key a row sees is softcap * tanh(s / softcap), s = q . k / sqrt(128) on the DEQUANTIZED key,
+ * applied before any mask; lse is the log-sum-exp of the capped logits, a row that sees no key gives o = 0, lse = -inf.
+ *
+ * Every entry takes the arguments of its windowed sibling (fa_fwd_launch_varlen_kvcache_window, .._fp8_window, fa_decode_window_*,
+ * fa_decode_fp8_window_*), a window included -- (-1, -1) is legal there and means none -- and an fa_softcap behind it.  Kernels of
+ * their own (the windowed text plus the cap): the sibling's fetch contract, tile ranges, grids and partial format.  An fp8 cache's
+ * k_descale goes into the tanh's argument (a tanh between the raw product and the exponent forbids folding it into the exponent's
+ * constant); v_descale stays in the final 1 / l.  The decode's split count and workspace are the windowed entry's for the same
+ * arguments: the cap does not enter the rule.  The capped decodes therefore have no workspace query of their own:
+ * fa_decode_window_workspace_bytes(args, window) / fa_decode_fp8_window_workspace_bytes(args, window) size the launch.
+ * Deterministic, no atomics, graph-capturable.
+ *
+ * Refused before any HIP call, in this order: what the windowed sibling refuses, with its status and message; then a null
+ * fa_softcap (FA_ERR_NULL); then its struct_size, or a softcap that is NaN, infinite or <= 0 (FA_ERR_SHAPE).  This level has no
+ * "off": without a cap, call the windowed sibling.
+ */
+int fa_fwd_varlen_kvcache_softcap_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_kvcache_softcap(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                         const fa_kvcache_layout *cache, const fa_window *window, const fa_softcap *softcap,
+                                         const fa_fwd_opts *opts, float *lse, void *stream);
+int fa_fwd_varlen_kvcache_fp8_softcap_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_kvcache_fp8_softcap(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                             const fa_kvcache_layout *cache, const fa_kvcache_fp8_scales *scales, const fa_window *window,
+                                             const fa_softcap *softcap, const fa_fwd_opts *opts, float *lse, void *stream);
+int fa_decode_softcap_supported(const fa_decode_args *args, const fa_window *window, const fa_softcap *softcap);
+int fa_decode_softcap_num_splits(const fa_decode_args *args, const fa_window *window, const fa_softcap *softcap);
+int fa_decode_softcap_launch(const fa_decode_args *args, const fa_window *window, const fa_softcap *softcap, void *stream, float *ms);
+int fa_decode_fp8_softcap_supported(const fa_decode_fp8_args *args, const fa_window *window, const fa_softcap *softcap);
+int fa_decode_fp8_softcap_num_splits(const fa_decode_fp8_args *args, const fa_window *window, const fa_softcap *softcap);
+int fa_decode_fp8_softcap_launch(const fa_decode_fp8_args *args, const fa_window *window, const fa_softcap *softcap, void *stream,
+                                 float *ms);
+
+/*
  * The step in front of a decode: append seqlen_new new K / V rows per batch entry to the cache IN PLACE, at the positions the
  * device-side lengths name, optionally rotate the new keys and the query (rotary embedding), quantize for an fp8 cache, and
  * advance the lengths.  One kernel on `stream`; the host reads none of the device arrays, so the launch is asynchronous and
