@@ -585,4 +585,46 @@ __global__ void __launch_bounds__(bwd::THREADS, 1) fa_bwd_dq_varlen_kernel(const
         for (int gg = 0; gg < 4; ++gg) store4<DT>(dq + 32 * t + 8 * gg, dQ[t], gg, inv_sqrt_d);
 }
 
+// fa_bwd_varlen.hip: fa_bwd_delta_varlen_kernel as that unit builds it, over the (n_heads, total_tokens) rows of o and dout
+// (delta = sum_d dO O knows neither of a second range, nor of a window, nor of a cap)
+hipError_t bwd_varlen_delta_enqueue(const BwdVarlenArgs &a, int dtype, hipStream_t s);
+
+// One backward of a two-range form (ARGS: BwdVarlenQKArgs, BwdVarlenWindowArgs, BwdVarlenSoftcapArgs), three or four launches on
+// one stream; the unit that calls this builds that form's kernels.  Delta over total_q, dK / dV (one workgroup per sequence,
+// K / V head, split part and key block of max_seqlen_k), their fixed-order sum over total_k when split > 1, dQ (per Q block of
+// max_seqlen_q).  The grids depend on the host's arguments alone: neither cu_seqlens nor a window sizes one (a workgroup whose
+// window reaches no row or no key returns its zeros at once).
+template <class ARGS, int DT, bool CAUSAL>
+static hipError_t bwd_varlen_enqueue_any(const ARGS &a, hipStream_t s) {
+    BwdVarlenArgs d = {};   // what the delta kernel reads
+    d.o = a.o;
+    d.dout = a.dout;
+    d.delta = a.delta;
+    d.out_ss = a.out_ss;
+    d.out_hs = a.out_hs;
+    d.n_heads = a.n_heads;
+    d.total_tokens = a.total_tokens;
+    hipError_t rc = hipSuccess;
+    if (a.total_tokens > 0) {   // (no query rows: only the zeros of dK / dV are left to write)
+        rc = bwd_varlen_delta_enqueue(d, DT, s);
+        if (rc != hipSuccess) return rc;
+    }
+    void *params[] = {(void *)&a};
+    const int64_t n_kv = a.n_heads / a.group;
+    const dim3 block(bwd::THREADS);
+    if (a.total_k > 0) {   // (no key rows: nothing to write, and the dQ kernel stores zeros)
+        rc = hipLaunchKernel((const void *)&fa_bwd_dkdv_varlen_kernel<ARGS, DT, CAUSAL>,
+                             dim3((unsigned)((int64_t)a.n_seqs * n_kv * a.split * a.n_blocks_k)), block, params, 0, s);
+        if (rc != hipSuccess) return rc;
+        if (a.split > 1) {
+            const int64_t n = n_kv * a.total_k * 2 * (bwd::D / 8);
+            rc = hipLaunchKernel((const void *)&fa_bwd_dkdv_reduce_varlen_kernel<ARGS, DT>, dim3((unsigned)((n + 255) / 256)), dim3(256), params, 0, s);
+            if (rc != hipSuccess) return rc;
+        }
+    }
+    if (a.total_tokens == 0) return hipSuccess;
+    return hipLaunchKernel((const void *)&fa_bwd_dq_varlen_kernel<ARGS, DT, CAUSAL>, dim3((unsigned)((int64_t)a.n_seqs * a.n_heads * a.n_blocks)),
+                           block, params, 0, s);
+}
+
 }  // namespace fa

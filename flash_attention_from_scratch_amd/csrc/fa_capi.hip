@@ -42,37 +42,27 @@ kernel_fn_gqa gqa_kernel_dt5(bool masked, bool spec);
 // fa_bwd.hip: delta, dK / dV and dQ of one backward, enqueued on `s`
 hipError_t bwd_enqueue(const BwdArgs &a, int dtype, bool causal, hipStream_t s);
 hipError_t bwd_gqa_enqueue(const BwdGqaArgs &g, int dtype, bool causal, hipStream_t s);
-// fa_inst_varlen.hip: the packed variable-length forward (equal or separate Q and K / V lengths)
-kernel_fn_varlen varlen_kernel_dt15(bool first_block_skip);
-kernel_fn_varlen varlen_kernel_dt5(bool first_block_skip);
-int varlen_lds_bytes_dt15();
-// fa_inst_varlen_kvcache.hip: the same forward with its keys taken from a KV cache (the varlen form's LDS)
-kernel_fn_varlen_kvcache varlen_kvcache_kernel_dt15(bool first_block_skip);
-kernel_fn_varlen_kvcache varlen_kvcache_kernel_dt5(bool first_block_skip);
-// fa_inst_varlen_kvcache_fp8.hip: ... from an fp8 (e4m3fn) KV cache (the same LDS)
-kernel_fn_varlen_kvcache_fp8 varlen_kvcache_fp8_kernel_dt15(bool first_block_skip);
-kernel_fn_varlen_kvcache_fp8 varlen_kvcache_fp8_kernel_dt5(bool first_block_skip);
-// fa_inst_varlen_window.hip, fa_inst_varlen_kvcache_window.hip, fa_inst_varlen_kvcache_fp8_window.hip: the three under a sliding window
-kernel_fn_varlen_window varlen_window_kernel_dt15(bool first_block_skip);
-kernel_fn_varlen_window varlen_window_kernel_dt5(bool first_block_skip);
-kernel_fn_varlen_kvcache_window varlen_kvcache_window_kernel_dt15(bool first_block_skip);
-kernel_fn_varlen_kvcache_window varlen_kvcache_window_kernel_dt5(bool first_block_skip);
-kernel_fn_varlen_kvcache_fp8_window varlen_kvcache_fp8_window_kernel_dt15(bool first_block_skip);
-kernel_fn_varlen_kvcache_fp8_window varlen_kvcache_fp8_window_kernel_dt5(bool first_block_skip);
+// fa_inst_varlen.hip: the packed variable-length forward, one slice per form and dtype.  The forms, X(key side, extra, suffix):
+// key side 0 packed keys (equal or separate Q and K / V lengths) | 1 a KV cache | 2 an fp8 (e4m3fn) KV cache; extra 0 nothing |
+// 1 a sliding window | 2 a sliding window and logit soft-capping.  A new form is one entry here (and one in csrc/Makefile's
+// VARLEN_FORMS, and its arm in fa_fwd_kernel.hpp).
+#define FA_VARLEN_FORMS(X)                                                       \
+    X(0, 0, )             X(0, 1, _window)             X(0, 2, _softcap)         \
+    X(1, 0, _kvcache)     X(1, 1, _kvcache_window)     X(1, 2, _kvcache_softcap) \
+    X(2, 0, _kvcache_fp8) X(2, 1, _kvcache_fp8_window) X(2, 2, _kvcache_fp8_softcap)
+#define FA_X(KEYS, EXTRA, SFX)                                              \
+    kernel_fn_varlen##SFX varlen##SFX##_kernel_dt15(bool first_block_skip); \
+    kernel_fn_varlen##SFX varlen##SFX##_kernel_dt5(bool first_block_skip);
+FA_VARLEN_FORMS(FA_X)
+#undef FA_X
+int varlen_lds_bytes_dt15();   // (every form's LDS)
 // fa_bwd_varlen.hip / fa_bwd_varlen_qk.hip: the packed backward, and its form with separate Q and K / V lengths
 hipError_t bwd_varlen_enqueue(const BwdVarlenArgs &a, int dtype, bool causal, hipStream_t s);
 hipError_t bwd_varlen_qk_enqueue(const BwdVarlenQKArgs &a, int dtype, bool causal, hipStream_t s);
 // fa_bwd_varlen_window.hip: ... under a sliding window (causal arrives as right = 0)
 hipError_t bwd_varlen_window_enqueue(const BwdVarlenWindowArgs &a, int dtype, hipStream_t s);
-// fa_inst_varlen_softcap.hip, fa_bwd_varlen_softcap.hip: the packed windowed forward and backward with logit soft-capping
-kernel_fn_varlen_softcap varlen_softcap_kernel_dt15(bool first_block_skip);
-kernel_fn_varlen_softcap varlen_softcap_kernel_dt5(bool first_block_skip);
+// fa_bwd_varlen_softcap.hip: ... with logit soft-capping on top
 hipError_t bwd_varlen_softcap_enqueue(const BwdVarlenSoftcapArgs &a, int dtype, hipStream_t s);
-// fa_inst_varlen_kvcache_softcap.hip, fa_inst_varlen_kvcache_fp8_softcap.hip: both windowed cache prefills with logit soft-capping
-kernel_fn_varlen_kvcache_softcap varlen_kvcache_softcap_kernel_dt15(bool first_block_skip);
-kernel_fn_varlen_kvcache_softcap varlen_kvcache_softcap_kernel_dt5(bool first_block_skip);
-kernel_fn_varlen_kvcache_fp8_softcap varlen_kvcache_fp8_softcap_kernel_dt15(bool first_block_skip);
-kernel_fn_varlen_kvcache_fp8_softcap varlen_kvcache_fp8_softcap_kernel_dt5(bool first_block_skip);
 }  // namespace fa
 
 namespace {
@@ -1233,19 +1223,37 @@ void softcap_constants(const fa_softcap *c, float *a, float *inv_a) {
     *inv_a = (float)(1.0 / A);
 }
 
-// the forward of `entry` (a public entry point; `total`: its name for the query side's total)
-// `kc` non-null: the key side is a KV cache (fa_fwd_launch_varlen_kvcache), and vk is not used
-// `fp8_side`: ... an fp8 one (fa_fwd_launch_varlen_kvcache_fp8): k, v are bytes, kv's strides count bytes, `sc` holds the descales
-// `windowed`: the entry's sliding-window form, with its fa_window `w` (null is refused, behind everything the entry itself refuses)
-// `capped`: ... of a windowed form (packed or either cache) with logit soft-capping, its fa_softcap `cap` refused behind the window's rules
-int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
-                      const fa_varlen_layout *vk, const fa_fwd_opts *opts, float *lse, void *stream, const fa_kvcache_layout *kc = nullptr,
-                      bool cache_side = false, const fa_kvcache_fp8_scales *sc = nullptr, bool fp8_side = false, bool windowed = false,
-                      const fa_window *w = nullptr, bool capped = false, const fa_softcap *cap = nullptr) {
-    if (cache_side) vk = vq;   // (one valid layout for the checks both launches share)
-    if (!args || !kv || !vq || !vk || (cache_side && !kc) || (fp8_side && !sc)) return fail(FA_ERR_NULL, "null pointer argument");
+// the kernel of a form of the varlen forward (FA_VARLEN_FORMS), by key side, extra and dtype
+const void *varlen_kernel(int keys, int extra, bool bf16, bool first_block_skip) {
+#define FA_X(KEYS, EXTRA, SFX)          \
+    if (keys == KEYS && extra == EXTRA) \
+        return bf16 ? (const void *)fa::varlen##SFX##_kernel_dt15(first_block_skip) : (const void *)fa::varlen##SFX##_kernel_dt5(first_block_skip);
+    FA_VARLEN_FORMS(FA_X)
+#undef FA_X
+    return nullptr;
+}
+
+// What a public entry point asks of fwd_launch_varlen beyond the arguments all of them share: its name and its name for the query
+// side's total (for the messages), and its form.  The form comes from the entry point, never from a pointer being null.
+enum { KEYS_PACKED = 0, KEYS_CACHE = 1, KEYS_FP8_CACHE = 2 };   // fa_inst_varlen.hip's key side ...
+enum { EXTRA_NONE = 0, EXTRA_WINDOW = 1, EXTRA_SOFTCAP = 2 };   // ... and extra
+struct VarlenCall {
+    const char *entry, *total;
+    int keys, extra;
+    const fa_varlen_layout *vk;        // KEYS_PACKED: the key side's ranges
+    const fa_kvcache_layout *kc;       // a cache: its layout (vk is not used)
+    const fa_kvcache_fp8_scales *sc;   // KEYS_FP8_CACHE: k, v are bytes, kv's strides count bytes, `sc` holds the descales
+    const fa_window *w;                // EXTRA_WINDOW and up (null is refused, behind everything the entry itself refuses)
+    const fa_softcap *cap;             // EXTRA_SOFTCAP (refused behind the window's rules)
+};
+int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
+                      const fa_fwd_opts *opts, float *lse, void *stream) {
+    const bool cache_side = call.keys != KEYS_PACKED, fp8_side = call.keys == KEYS_FP8_CACHE;
+    const bool windowed = call.extra != EXTRA_NONE, capped = call.extra == EXTRA_SOFTCAP;
+    const fa_varlen_layout *vk = cache_side ? vq : call.vk;   // (one valid layout for the checks both launches share)
+    if (!args || !kv || !vq || !vk || (cache_side && !call.kc) || (fp8_side && !call.sc)) return fail(FA_ERR_NULL, "null pointer argument");
     if (!args->q || !args->k || !args->v || !args->o) return fail(FA_ERR_NULL, "null pointer argument");
-    if (!lse) return fail(FA_ERR_NULL, "lse is null: %s needs a (n_heads, %s) fp32 buffer", entry, total);
+    if (!lse) return fail(FA_ERR_NULL, "lse is null: %s needs a (n_heads, %s) fp32 buffer", call.entry, call.total);
     if (args->cfg.dtype != FA_FP16 && args->cfg.dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
     if (kv->struct_size < sizeof(fa_kv_layout))
         return fail(FA_ERR_SHAPE, "fa_kv_layout.struct_size (%u) is smaller than this library's (%zu)", kv->struct_size, sizeof(fa_kv_layout));
@@ -1275,15 +1283,15 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
     if (((uintptr_t)args->q | (uintptr_t)args->k | (uintptr_t)args->v | (uintptr_t)args->o) & 15)
         return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
     if ((uintptr_t)lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
-    if (cache_side && (rc = kvcache_validate(cache, kc, fp8_side ? sc : nullptr)) != FA_OK) return rc;
+    if (cache_side && (rc = kvcache_validate(cache, call.kc, fp8_side ? call.sc : nullptr)) != FA_OK) return rc;
     if (windowed) {   // (the key bound: the cache's capacity, or the packed key side's max_seqlen; then the query side's)
-        if ((rc = window_validate(w, o.causal, cache_side ? cache.capacity() : 0)) != FA_OK) return rc;
+        if ((rc = window_validate(call.w, o.causal, cache_side ? cache.capacity() : 0)) != FA_OK) return rc;
         if (!cache_side && vk->max_seqlen > kWindowMaxLen)
             return fail(FA_ERR_SHAPE, "max_seqlen_k too large for a window: at most 2^30 - 128 keys per sequence");
         if (vq->max_seqlen > kWindowMaxLen)
             return fail(FA_ERR_SHAPE, "max_seqlen_q too large for a window: at most 2^30 - 128 query rows per sequence");
     }
-    if (capped && (rc = softcap_validate(cap)) != FA_OK) return rc;
+    if (capped && (rc = softcap_validate(call.cap)) != FA_OK) return rc;
     if (vq->total_tokens == 0) {   // (no query rows: nothing to write)
         if (o.ms) *o.ms = 0.0f;
         return FA_OK;
@@ -1292,10 +1300,13 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
     if (!dev) return rc;
     const char *why;
     const fa::KernelEntry *e = varlen_entry(&args->cfg, &why);
-    fa::KernelArgsVarlenKVCacheFp8Window wf8;   // (the widest form: the cache forms' arguments are its members)
-    fa::KernelArgsVarlenKVCacheFp8 &fa8 = wf8.a;
-    fa::KernelArgsVarlenKVCache &ca = fa8.c;
-    fa::KernelArgsVarlenQK qa;
+    // the widest arguments of each key side: every narrower form's are their first member, and the member's address is what its kernel takes
+    fa::KernelArgsVarlenSoftcap pa;
+    fa::KernelArgsVarlenKVCacheSoftcap c16;
+    fa::KernelArgsVarlenKVCacheFp8Softcap c8;
+    fa::KernelArgsVarlenKVCacheFp8 &fa8 = c8.w.a;
+    fa::KernelArgsVarlenKVCache &ca = fp8_side ? fa8.c : c16.w.a;
+    fa::KernelArgsVarlenQK &qa = pa.w.a;
     fa::KernelArgsVarlen &va = cache_side ? ca.v : qa.v;
     va.base.q = args->q;
     va.base.k = args->k;
@@ -1317,72 +1328,37 @@ int fwd_launch_varlen(const char *entry, const char *total, const fa_fwd_args *a
     va.group = (int32_t)(args->n_heads / kv->n_kv_heads);
     va.total_tokens = (int32_t)vq->total_tokens;
     va.max_seqlen = (int32_t)vq->max_seqlen;
-    qa.cu_seqlens_k = vk->cu_seqlens;
-    qa.total_k = (int32_t)vk->total_tokens;
-    qa.max_seqlen_k = (int32_t)vk->max_seqlen;
-    const bool fbs = e->softmax_mode == FA_SOFTMAX_FIRST_BLOCK_SKIP;
-    const void *fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kernel_dt15(fbs) : (const void *)fa::varlen_kernel_dt5(fbs);
-    void *kernel_args = &qa;
-    if (cache_side) {
-        const int64_t cap = cache.capacity();
+    if (!cache_side) {
+        qa.cu_seqlens_k = vk->cu_seqlens;
+        qa.total_k = (int32_t)vk->total_tokens;
+        qa.max_seqlen_k = (int32_t)vk->max_seqlen;
+    } else {
+        const int64_t cap_k = cache.capacity();
         ca.cache_seqlens = cache.cache_seqlens;
         ca.block_table = cache.block_table;
         ca.page_stride = kv->kv_batch_stride;
         ca.bt_stride = cache.paged() ? (int32_t)cache.block_table_stride : 0;
         ca.num_pages = (int32_t)cache.slots();
-        ca.tiles_per_page = (int32_t)(cache.paged() ? cache.page_size / 64 : (cap + 63) / 64);   // (contiguous: one "page" per entry)
-        ca.max_len = (int32_t)(cache.max_seqlen_k > 0 ? cache.max_seqlen_k : cap);
-        fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kvcache_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_kernel_dt5(fbs);
-        kernel_args = &ca;
+        ca.tiles_per_page = (int32_t)(cache.paged() ? cache.page_size / 64 : (cap_k + 63) / 64);   // (contiguous: one "page" per entry)
+        ca.max_len = (int32_t)(cache.max_seqlen_k > 0 ? cache.max_seqlen_k : cap_k);
     }
     if (fp8_side) {
         fa8.k_descale = cache.k_descale;
         fa8.v_descale = cache.v_descale;
         fa8.ds_bs = cache.descale_bs;
-        fn = args->cfg.dtype == FA_BF16 ? (const void *)fa::varlen_kvcache_fp8_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_fp8_kernel_dt5(fbs);
-        kernel_args = &fa8;
     }
-    // the sliding-window forms: the same arguments and (left, right), causal as right = 0 (the kernel's one rule for both)
-    fa::KernelArgsVarlenWindow wqa;
-    fa::KernelArgsVarlenKVCacheWindow wca;
-    fa::KernelArgsVarlenSoftcap sqa;
-    fa::KernelArgsVarlenKVCacheSoftcap sca;
-    fa::KernelArgsVarlenKVCacheFp8Softcap sf8;
-    if (windowed) {
-        const bool bf16 = args->cfg.dtype == FA_BF16;
-        wf8.left = w->left;
-        wf8.right = window_right(w, o.causal);
-        if (fp8_side) {
-            fn = bf16 ? (const void *)fa::varlen_kvcache_fp8_window_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_fp8_window_kernel_dt5(fbs);
-            kernel_args = &wf8;
-            if (capped) {
-                sf8.w = wf8;
-                softcap_constants(cap, &sf8.cap_a, &sf8.cap_inv_a);
-                fn = bf16 ? (const void *)fa::varlen_kvcache_fp8_softcap_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_fp8_softcap_kernel_dt5(fbs);
-                kernel_args = &sf8;
-            }
-        } else if (cache_side) {
-            wca = {ca, wf8.left, wf8.right};
-            fn = bf16 ? (const void *)fa::varlen_kvcache_window_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_window_kernel_dt5(fbs);
-            kernel_args = &wca;
-            if (capped) {
-                sca.w = wca;
-                softcap_constants(cap, &sca.cap_a, &sca.cap_inv_a);
-                fn = bf16 ? (const void *)fa::varlen_kvcache_softcap_kernel_dt15(fbs) : (const void *)fa::varlen_kvcache_softcap_kernel_dt5(fbs);
-                kernel_args = &sca;
-            }
-        } else {
-            wqa = {qa, wf8.left, wf8.right};
-            fn = bf16 ? (const void *)fa::varlen_window_kernel_dt15(fbs) : (const void *)fa::varlen_window_kernel_dt5(fbs);
-            kernel_args = &wqa;
-            if (capped) {
-                sqa.w = wqa;
-                softcap_constants(cap, &sqa.cap_a, &sqa.cap_inv_a);
-                fn = bf16 ? (const void *)fa::varlen_softcap_kernel_dt15(fbs) : (const void *)fa::varlen_softcap_kernel_dt5(fbs);
-                kernel_args = &sqa;
-            }
-        }
-    }
+    // the window and the cap into the key side's arguments, and the member the form's kernel takes (all three at offset 0: the
+    // static_asserts of fa_fwd_kernel.hpp)
+    auto form_args = [&](auto &s) -> void * {
+        if (!windowed) return &s.w.a;
+        s.w.left = call.w->left;   // (causal as right = 0: the kernel's one rule for both)
+        s.w.right = window_right(call.w, o.causal);
+        if (!capped) return &s.w;
+        softcap_constants(call.cap, &s.cap_a, &s.cap_inv_a);
+        return &s;
+    };
+    void *kernel_args = fp8_side ? form_args(c8) : cache_side ? form_args(c16) : form_args(pa);
+    const void *fn = varlen_kernel(call.keys, call.extra, args->cfg.dtype == FA_BF16, e->softmax_mode == FA_SOFTMAX_FIRST_BLOCK_SKIP);
     const dim3 grid((unsigned)(va.base.n_bh * va.base.n_q_blocks)), block((unsigned)e->threads);
     const hipStream_t s = (hipStream_t)stream;
     return enqueue_timed([&] {
@@ -1536,67 +1512,67 @@ int fa_fwd_varlen_qk_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts
 
 int fa_fwd_launch_varlen(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vl, const fa_fwd_opts *opts, float *lse,
                          void *stream) {
-    return fwd_launch_varlen("fa_fwd_launch_varlen", "total_tokens", args, kv, vl, vl, opts, lse, stream);
+    return fwd_launch_varlen({"fa_fwd_launch_varlen", "total_tokens", KEYS_PACKED, EXTRA_NONE, vl}, args, kv, vl, opts, lse, stream);
 }
 int fa_fwd_launch_varlen_qk(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_varlen_layout *vk,
                             const fa_fwd_opts *opts, float *lse, void *stream) {
-    return fwd_launch_varlen("fa_fwd_launch_varlen_qk", "total_q", args, kv, vq, vk, opts, lse, stream);
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_qk", "total_q", KEYS_PACKED, EXTRA_NONE, vk}, args, kv, vq, opts, lse, stream);
 }
 
 int fa_fwd_varlen_kvcache_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
 
 int fa_fwd_launch_varlen_kvcache(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_kvcache_layout *kc,
                                  const fa_fwd_opts *opts, float *lse, void *stream) {
-    return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true);
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache", "total_q", KEYS_CACHE, EXTRA_NONE, nullptr, kc}, args, kv, vq, opts, lse, stream);
 }
 
 int fa_fwd_varlen_kvcache_fp8_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
 
 int fa_fwd_launch_varlen_kvcache_fp8(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_kvcache_layout *kc,
                                      const fa_kvcache_fp8_scales *sc, const fa_fwd_opts *opts, float *lse, void *stream) {
-    return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache_fp8", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true, sc, true);
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_fp8", "total_q", KEYS_FP8_CACHE, EXTRA_NONE, nullptr, kc, sc}, args, kv, vq, opts, lse, stream);
 }
 
 // the sliding-window forms of the three: the same body with an fa_window (served: what the sibling serves)
 int fa_fwd_varlen_qk_window_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
 int fa_fwd_launch_varlen_qk_window(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_varlen_layout *vk,
                                    const fa_window *w, const fa_fwd_opts *opts, float *lse, void *stream) {
-    return fwd_launch_varlen("fa_fwd_launch_varlen_qk_window", "total_q", args, kv, vq, vk, opts, lse, stream, nullptr, false, nullptr, false, true, w);
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_qk_window", "total_q", KEYS_PACKED, EXTRA_WINDOW, vk, nullptr, nullptr, w}, args, kv, vq, opts, lse, stream);
 }
 // ... with logit soft-capping: the windowed packed body with an fa_softcap behind the window (served: what the sibling serves)
 int fa_fwd_varlen_qk_softcap_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
 int fa_fwd_launch_varlen_qk_softcap(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_varlen_layout *vk,
                                     const fa_window *w, const fa_softcap *cap, const fa_fwd_opts *opts, float *lse, void *stream) {
-    return fwd_launch_varlen("fa_fwd_launch_varlen_qk_softcap", "total_q", args, kv, vq, vk, opts, lse, stream, nullptr, false, nullptr, false, true, w,
-                             true, cap);
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_qk_softcap", "total_q", KEYS_PACKED, EXTRA_SOFTCAP, vk, nullptr, nullptr, w, cap}, args, kv, vq, opts,
+                             lse, stream);
 }
 int fa_fwd_varlen_kvcache_window_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
 int fa_fwd_launch_varlen_kvcache_window(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
                                         const fa_kvcache_layout *kc, const fa_window *w, const fa_fwd_opts *opts, float *lse, void *stream) {
-    return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache_window", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true, nullptr, false,
-                             true, w);
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_window", "total_q", KEYS_CACHE, EXTRA_WINDOW, nullptr, kc, nullptr, w}, args, kv, vq, opts,
+                             lse, stream);
 }
 int fa_fwd_varlen_kvcache_fp8_window_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
 int fa_fwd_launch_varlen_kvcache_fp8_window(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
                                             const fa_kvcache_layout *kc, const fa_kvcache_fp8_scales *sc, const fa_window *w,
                                             const fa_fwd_opts *opts, float *lse, void *stream) {
-    return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache_fp8_window", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true, sc, true,
-                             true, w);
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_fp8_window", "total_q", KEYS_FP8_CACHE, EXTRA_WINDOW, nullptr, kc, sc, w}, args, kv, vq, opts,
+                             lse, stream);
 }
 // ... and both windowed cache prefills with logit soft-capping: an fa_softcap behind the window (served: what the sibling serves)
 int fa_fwd_varlen_kvcache_softcap_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
 int fa_fwd_launch_varlen_kvcache_softcap(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
                                          const fa_kvcache_layout *kc, const fa_window *w, const fa_softcap *cap, const fa_fwd_opts *opts,
                                          float *lse, void *stream) {
-    return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache_softcap", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true, nullptr, false,
-                             true, w, true, cap);
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_softcap", "total_q", KEYS_CACHE, EXTRA_SOFTCAP, nullptr, kc, nullptr, w, cap}, args, kv, vq,
+                             opts, lse, stream);
 }
 int fa_fwd_varlen_kvcache_fp8_softcap_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
 int fa_fwd_launch_varlen_kvcache_fp8_softcap(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
                                              const fa_kvcache_layout *kc, const fa_kvcache_fp8_scales *sc, const fa_window *w,
                                              const fa_softcap *cap, const fa_fwd_opts *opts, float *lse, void *stream) {
-    return fwd_launch_varlen("fa_fwd_launch_varlen_kvcache_fp8_softcap", "total_q", args, kv, vq, nullptr, opts, lse, stream, kc, true, sc, true,
-                             true, w, true, cap);
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_fp8_softcap", "total_q", KEYS_FP8_CACHE, EXTRA_SOFTCAP, nullptr, kc, sc, w, cap}, args, kv, vq,
+                             opts, lse, stream);
 }
 
 int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *a) {

@@ -61,6 +61,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <type_traits>
 
@@ -434,7 +435,8 @@ struct FwdTraits {
 // VARLEN (packed variable-length sequences, the training path: fa_fwd_launch_varlen, fa_fwd_launch_varlen_qk):
 // fa_fwd_kernel_varlen is the body of fa_fwd_kernel whose workgroup finds its sequence's rows in cu_seqlens on the device,
 // addresses K / V with a head count and strides of their own (grouped-query attention) and also writes the row log-sum-exp.
-// Only fa_inst_varlen.hip defines FA_KERNEL_VARLEN, and gets that kernel INSTEAD of fa_fwd_kernel (MASK forms only): the
+// Only fa_inst_varlen.hip names a form (FA_VARLEN_KEYS / FA_VARLEN_EXTRA below, from which FA_KERNEL_VARLEN and its siblings
+// follow), and gets that form's kernel INSTEAD of fa_fwd_kernel (MASK forms only): the
 // product's kernels keep their names and, compiled from the same text, their code.  FA_KV_SS32 is the K / V seq stride in
 // the body.
 // Sequence i owns query rows cu_seqlens[i] .. of q / o / lse (the range KernelArgsVarlen describes) and key rows
@@ -458,8 +460,8 @@ struct KernelArgsVarlenQK {
 };
 typedef void (*kernel_fn_varlen)(const KernelArgsVarlenQK);
 // VARLEN against a KV cache (prefill behind a cached prefix: fa_fwd_launch_varlen_kvcache): fa_fwd_kernel_varlen_kvcache is
-// fa_fwd_kernel_varlen whose sequence b takes its key rows from a cache instead of a packed range.  Only
-// fa_inst_varlen_kvcache.hip defines FA_KERNEL_VARLEN_KVCACHE (beside FA_KERNEL_VARLEN) and gets that kernel INSTEAD of
+// fa_fwd_kernel_varlen whose sequence b takes its key rows from a cache instead of a packed range.  Key side 1 defines
+// FA_KERNEL_VARLEN_KVCACHE (beside FA_KERNEL_VARLEN) and gives that kernel INSTEAD of
 // fa_fwd_kernel_varlen.  len_k = cache_seqlens[b], clamped to [0, max_len]; tile t (keys 64 t ..) lies at
 //   page_stride * entry + (t % tiles_per_page) * 64 * kv_seq_stride + kv_head * kv_head_stride      (elements from k / v)
 // with entry = clamp(block_table[b][t / tiles_per_page], 0, num_pages - 1), or = b for a contiguous cache (block_table null:
@@ -478,8 +480,8 @@ struct KernelArgsVarlenKVCache {
 };
 typedef void (*kernel_fn_varlen_kvcache)(const KernelArgsVarlenKVCache);
 // ... against an fp8 (e4m3fn) cache (fa_fwd_launch_varlen_kvcache_fp8): fa_fwd_kernel_varlen_kvcache_fp8 is
-// fa_fwd_kernel_varlen_kvcache with one more way to FETCH a tile.  Only fa_inst_varlen_kvcache_fp8.hip defines
-// FA_KERNEL_VARLEN_KVCACHE_FP8 (beside the other two) and gets that kernel INSTEAD; `if constexpr (FP8)` (or an #ifdef arm where
+// fa_fwd_kernel_varlen_kvcache with one more way to FETCH a tile.  Key side 2 defines
+// FA_KERNEL_VARLEN_KVCACHE_FP8 (beside the other two) and gives that kernel INSTEAD; `if constexpr (FP8)` (or an #ifdef arm where
 // a name exists in one form only) marks every site where the two differ.  k and v hold one byte per element, so the cache's
 // strides count bytes.  The DMA cannot convert, so the tiles take the register-staged transport (DMA == false) with the
 // conversion between the load and the LDS write: the LDS images are byte for byte what the DMA builds from the dequantized
@@ -494,8 +496,8 @@ struct KernelArgsVarlenKVCacheFp8 {
 typedef void (*kernel_fn_varlen_kvcache_fp8)(const KernelArgsVarlenKVCacheFp8);
 // A sliding window on any of the three (fa_fwd_launch_varlen_qk_window, fa_fwd_launch_varlen_kvcache_window,
 // fa_fwd_launch_varlen_kvcache_fp8_window): the form's arguments and (left, right), -1 = unbounded, causal arriving as right = 0
-// (args.causal then only orders the Q blocks).  fa_inst_varlen*_window.hip define FA_KERNEL_VARLEN_WINDOW beside their sibling's
-// macros and get fa_fwd_kernel_varlen*_window INSTEAD; `if constexpr (WIN)` or an #ifdef arm marks every site that differs
+// (args.causal then only orders the Q blocks).  Extra 1 defines FA_KERNEL_VARLEN_WINDOW beside the key side's
+// macros and gives fa_fwd_kernel_varlen*_window INSTEAD; `if constexpr (WIN)` or an #ifdef arm marks every site that differs
 // (DESIGN.md 10.13).  Query row r of sequence b sits at position p = r + (len_k - len_q) and sees the keys
 // lo_r = max(0, p - left) .. hi_r = min(len_k - 1, p + right); a row with hi_r < lo_r (p + right < 0) gives o = 0, lse = -inf.
 // Both bounds grow with r, so a workgroup owning rows r0 .. r1 visits the tiles hi_r1 / 64 down to lo_r0 / 64 and nothing else:
@@ -514,8 +516,8 @@ typedef void (*kernel_fn_varlen_window)(const KernelArgsVarlenWindow);
 typedef void (*kernel_fn_varlen_kvcache_window)(const KernelArgsVarlenKVCacheWindow);
 typedef void (*kernel_fn_varlen_kvcache_fp8_window)(const KernelArgsVarlenKVCacheFp8Window);
 // Logit soft-capping on the packed forward (fa_fwd_launch_varlen_qk_softcap): the logit of a key a row sees is
-// softcap tanh(s / softcap), s = q . k / sqrt(d).  fa_inst_varlen_softcap.hip defines FA_KERNEL_VARLEN_SOFTCAP beside the windowed
-// slice's two macros and gets fa_fwd_kernel_varlen_softcap INSTEAD of fa_fwd_kernel_varlen_window: the windowed text (a window of
+// softcap tanh(s / softcap), s = q . k / sqrt(d).  Extra 2 defines FA_KERNEL_VARLEN_SOFTCAP beside the windowed
+// slice's two macros and gives fa_fwd_kernel_varlen_softcap INSTEAD of fa_fwd_kernel_varlen_window: the windowed text (a window of
 // (-1, -1) runs through it) with one more step, FA_CAP_S, on every S tile right behind qk() and in front of the masks -- a masked
 // key stays -inf (tanh(-inf) = -1 would bring it back to life).  The step replaces the raw S = q . k by A tanh(S / A),
 // A = softcap sqrt(d), so c, the running max, alpha and the lse line behind it stand as they are.  The host passes A and 1 / A.
@@ -525,8 +527,8 @@ struct KernelArgsVarlenSoftcap {
 };
 typedef void (*kernel_fn_varlen_softcap)(const KernelArgsVarlenSoftcap);
 // ... and on both cache prefills (fa_fwd_launch_varlen_kvcache_softcap, fa_fwd_launch_varlen_kvcache_fp8_softcap):
-// fa_inst_varlen_kvcache_softcap.hip and fa_inst_varlen_kvcache_fp8_softcap.hip define FA_KERNEL_VARLEN_SOFTCAP beside the windowed
-// cache slice's macros and get fa_fwd_kernel_varlen_kvcache_softcap / fa_fwd_kernel_varlen_kvcache_fp8_softcap INSTEAD of the windowed
+// extra 2 on key side 1 or 2 defines FA_KERNEL_VARLEN_SOFTCAP beside the windowed
+// cache slice's macros and gives fa_fwd_kernel_varlen_kvcache_softcap / fa_fwd_kernel_varlen_kvcache_fp8_softcap INSTEAD of the windowed
 // kernel.  16-bit cache: the same step.  fp8 cache: a tanh between S and the exponent forbids folding k_descale into c, so the
 // descale goes into the cap's constant instead, cap_k = k_descale 2 log2(e) / A (one scalar per workgroup): the capped S is in the
 // 16-bit form's units, c is the plain constant and the lse line is the 16-bit form's.
@@ -538,10 +540,65 @@ typedef Softcapped<KernelArgsVarlenKVCacheWindow> KernelArgsVarlenKVCacheSoftcap
 typedef Softcapped<KernelArgsVarlenKVCacheFp8Window> KernelArgsVarlenKVCacheFp8Softcap;
 typedef void (*kernel_fn_varlen_kvcache_softcap)(const KernelArgsVarlenKVCacheSoftcap);
 typedef void (*kernel_fn_varlen_kvcache_fp8_softcap)(const KernelArgsVarlenKVCacheFp8Softcap);
-#ifdef FA_KERNEL_VARLEN_SOFTCAP
-#if !defined(FA_KERNEL_VARLEN_WINDOW)
-#error "the soft-capped forms are built on the windowed forms"
+// Every wrapper's first member sits at offset 0, so the widest struct of a key side starts with the arguments of each narrower form:
+// the host fills that one struct and passes the address of the member the chosen kernel takes (fa_capi.hip, fwd_launch_varlen).
+// (KernelArgsVarlenSoftcap repeats Softcapped<KernelArgsVarlenWindow> field for field; it stays a struct of its own because its
+// name is part of fa_fwd_kernel_varlen_softcap's mangled name.)
+static_assert(std::is_standard_layout<KernelArgsVarlenSoftcap>::value && std::is_standard_layout<KernelArgsVarlenKVCacheSoftcap>::value &&
+                  std::is_standard_layout<KernelArgsVarlenKVCacheFp8Softcap>::value,
+              "the varlen forms' arguments are standard layout");
+static_assert(offsetof(KernelArgsVarlenSoftcap, w) == 0 && offsetof(KernelArgsVarlenWindow, a) == 0, "packed: softcap > window > QK");
+static_assert(offsetof(KernelArgsVarlenKVCacheSoftcap, w) == 0 && offsetof(KernelArgsVarlenKVCacheWindow, a) == 0,
+              "cache: softcap > window > cache");
+static_assert(offsetof(KernelArgsVarlenKVCacheFp8Softcap, w) == 0 && offsetof(KernelArgsVarlenKVCacheFp8Window, a) == 0 &&
+                  offsetof(KernelArgsVarlenKVCacheFp8, c) == 0,
+              "fp8 cache: softcap > window > fp8 > cache");
+
+// The form a translation unit builds is named once, by two numbers on its command line (fa_inst_varlen.hip, csrc/Makefile):
+//   FA_VARLEN_KEYS   0 packed keys (cu_seqlens_k) | 1 a KV cache | 2 an fp8 KV cache
+//   FA_VARLEN_EXTRA  0 nothing | 1 a sliding window | 2 a sliding window and logit soft-capping
+// The FA_KERNEL_VARLEN_* macros of the body's arms, the kernel's name (FA_VARLEN_NAME(fa_fwd_kernel_varlen, )) and its argument
+// follow from them here: a new key side or extra is one arm below, one in front of the kernel's body, and its arms in the body.
+#ifdef FA_VARLEN_KEYS
+#define FA_KERNEL_VARLEN
+#if FA_VARLEN_KEYS == 0
+#define FA_VARLEN_KEYS_SFX
+#define FA_VARLEN_KEY_ARGS KernelArgsVarlenQK
+#define FA_VARLEN_KEY_PARAM qa
+#define FA_VARLEN_CAP_ARGS KernelArgsVarlenSoftcap
+#elif FA_VARLEN_KEYS == 1
+#define FA_KERNEL_VARLEN_KVCACHE
+#define FA_VARLEN_KEYS_SFX _kvcache
+#define FA_VARLEN_KEY_ARGS KernelArgsVarlenKVCache
+#define FA_VARLEN_KEY_PARAM qa
+#define FA_VARLEN_CAP_ARGS KernelArgsVarlenKVCacheSoftcap
+#elif FA_VARLEN_KEYS == 2
+#define FA_KERNEL_VARLEN_KVCACHE
+#define FA_KERNEL_VARLEN_KVCACHE_FP8
+#define FA_VARLEN_KEYS_SFX _kvcache_fp8
+#define FA_VARLEN_KEY_ARGS KernelArgsVarlenKVCacheFp8
+#define FA_VARLEN_KEY_PARAM fa8   // (qa is its cache member)
+#define FA_VARLEN_CAP_ARGS KernelArgsVarlenKVCacheFp8Softcap
+#else
+#error "FA_VARLEN_KEYS: 0 = packed, 1 = KV cache, 2 = fp8 KV cache"
 #endif
+#if FA_VARLEN_EXTRA == 0
+#define FA_VARLEN_EXTRA_SFX
+#elif FA_VARLEN_EXTRA == 1
+#define FA_KERNEL_VARLEN_WINDOW
+#define FA_VARLEN_EXTRA_SFX _window
+#elif FA_VARLEN_EXTRA == 2
+#define FA_KERNEL_VARLEN_WINDOW
+#define FA_KERNEL_VARLEN_SOFTCAP
+#define FA_VARLEN_EXTRA_SFX _softcap
+#else
+#error "FA_VARLEN_EXTRA: 0 = none, 1 = sliding window, 2 = sliding window and soft-capping"
+#endif
+#define FA_CAT4_(a, b, c, d) a##b##c##d
+#define FA_CAT4(a, b, c, d) FA_CAT4_(a, b, c, d)
+#define FA_VARLEN_NAME(pre, post) FA_CAT4(pre, FA_VARLEN_KEYS_SFX, FA_VARLEN_EXTRA_SFX, post)   // e.g. pre_kvcache_fp8_softcap post
+#endif
+#ifdef FA_KERNEL_VARLEN_SOFTCAP   // (built on the windowed forms: extra 2 defines both)
 #define FA_CAP_S(S) cap_S(S)
 #else
 #define FA_CAP_S(S)
@@ -616,36 +673,19 @@ __global__ void
 #ifdef FA_KERNEL_VARLEN
 // (one workgroup per SIMD set: with m live up to the LSE store the 256-register budget of two waves per SIMD spills)
 __launch_bounds__(NWAVES * 64, 1)
-#if defined(FA_KERNEL_VARLEN_KVCACHE_FP8) && defined(FA_KERNEL_VARLEN_SOFTCAP)
-fa_fwd_kernel_varlen_kvcache_fp8_softcap(const KernelArgsVarlenKVCacheFp8Softcap sa) {
-    const KernelArgsVarlenKVCacheFp8Window &wa = sa.w;
-    const KernelArgsVarlenKVCacheFp8 &fa8 = wa.a;
-    const KernelArgsVarlenKVCache &qa = fa8.c;
-#elif defined(FA_KERNEL_VARLEN_KVCACHE) && defined(FA_KERNEL_VARLEN_SOFTCAP)
-fa_fwd_kernel_varlen_kvcache_softcap(const KernelArgsVarlenKVCacheSoftcap sa) {
-    const KernelArgsVarlenKVCacheWindow &wa = sa.w;
-    const KernelArgsVarlenKVCache &qa = wa.a;
-#elif defined(FA_KERNEL_VARLEN_KVCACHE_FP8) && defined(FA_KERNEL_VARLEN_WINDOW)
-fa_fwd_kernel_varlen_kvcache_fp8_window(const KernelArgsVarlenKVCacheFp8Window wa) {
-    const KernelArgsVarlenKVCacheFp8 &fa8 = wa.a;
-    const KernelArgsVarlenKVCache &qa = fa8.c;
-#elif defined(FA_KERNEL_VARLEN_KVCACHE_FP8)
-fa_fwd_kernel_varlen_kvcache_fp8(const KernelArgsVarlenKVCacheFp8 fa8) {
-    const KernelArgsVarlenKVCache &qa = fa8.c;
-#elif defined(FA_KERNEL_VARLEN_KVCACHE) && defined(FA_KERNEL_VARLEN_WINDOW)
-fa_fwd_kernel_varlen_kvcache_window(const KernelArgsVarlenKVCacheWindow wa) {
-    const KernelArgsVarlenKVCache &qa = wa.a;
-#elif defined(FA_KERNEL_VARLEN_KVCACHE)
-fa_fwd_kernel_varlen_kvcache(const KernelArgsVarlenKVCache qa) {
-#elif defined(FA_KERNEL_VARLEN_SOFTCAP)
-fa_fwd_kernel_varlen_softcap(const KernelArgsVarlenSoftcap sa) {
-    const KernelArgsVarlenWindow &wa = sa.w;
-    const KernelArgsVarlenQK &qa = wa.a;
-#elif defined(FA_KERNEL_VARLEN_WINDOW)
-fa_fwd_kernel_varlen_window(const KernelArgsVarlenWindow wa) {
-    const KernelArgsVarlenQK &qa = wa.a;
+// (the argument by the extra, sa > wa > the key side's, which is qa itself or, against an fp8 cache, fa8 > qa)
+#if FA_VARLEN_EXTRA == 2
+FA_VARLEN_NAME(fa_fwd_kernel_varlen, )(const FA_VARLEN_CAP_ARGS sa) {
+    const Windowed<FA_VARLEN_KEY_ARGS> &wa = sa.w;
+    const FA_VARLEN_KEY_ARGS &FA_VARLEN_KEY_PARAM = wa.a;
+#elif FA_VARLEN_EXTRA == 1
+FA_VARLEN_NAME(fa_fwd_kernel_varlen, )(const Windowed<FA_VARLEN_KEY_ARGS> wa) {
+    const FA_VARLEN_KEY_ARGS &FA_VARLEN_KEY_PARAM = wa.a;
 #else
-fa_fwd_kernel_varlen(const KernelArgsVarlenQK qa) {
+FA_VARLEN_NAME(fa_fwd_kernel_varlen, )(const FA_VARLEN_KEY_ARGS FA_VARLEN_KEY_PARAM) {
+#endif
+#if FA_VARLEN_KEYS == 2
+    const KernelArgsVarlenKVCache &qa = fa8.c;
 #endif
     // (the fp8 cache's form: the same kernel on the register-staged transport, which can convert)
     static_assert(MASK && DMA != FA_FP8_CACHE && KSPLIT == 1 && ABL == 0 && QT == 1,

@@ -218,7 +218,7 @@ def test_kvcache_slices_are_kept_with_no_scratch_and_no_vector_spill():
     """The figures the compiler writes beside each kernel of the kept ISA (the kernel-resource-usage remarks, as comments and as
     metadata): no scratch, no vector-register spill; scalars spilled to lanes are allowed and recorded in DESIGN.md 10.9."""
     for dt in (15, 5):
-        text = _isa(f"varlen_kvcache_dt{dt}", "fa_inst_varlen_kvcache")
+        text = _isa(f"varlen_kvcache_dt{dt}", "fa_inst_varlen")
         # the two forms (with and without the first-block skip) of the new kernel, and neither kernel it is built from
         assert len(re.findall(r"^_ZN2fa28fa_fwd_kernel_varlen_kvcacheI\w+:", text, flags=re.M)) == 2
         assert re.search(r"^_ZN2fa20fa_fwd_kernel_varlenI", text, flags=re.M) is None

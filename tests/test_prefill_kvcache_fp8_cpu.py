@@ -176,7 +176,7 @@ def test_fp8_slices_are_kept_with_no_scratch_and_no_vector_spill():
     """The figures the compiler writes beside each kernel of the kept ISA (the kernel-resource-usage remarks, as comments and as
     metadata): no scratch, no vector-register spill.  The register figures are printed; DESIGN.md 10.10 records them."""
     for dt in (15, 5):
-        path = os.path.join(BUILD, f"varlen_kvcache_fp8_dt{dt}", "fa_inst_varlen_kvcache_fp8-hip-amdgcn-amd-amdhsa-gfx950.s")
+        path = os.path.join(BUILD, f"varlen_kvcache_fp8_dt{dt}", "fa_inst_varlen-hip-amdgcn-amd-amdhsa-gfx950.s")
         assert os.path.exists(path), "the build keeps the ISA of every slice under csrc/build (make -C flash_attention_from_scratch_amd/csrc)"
         text = open(path).read()
         # the two forms (with and without the first-block skip) of the new kernel, and none of the kernels it is built from
@@ -193,7 +193,7 @@ def test_fp8_slices_are_kept_with_no_scratch_and_no_vector_spill():
         assert len(sgpr_spills) == 2
     # the 16-bit cache's slice keeps its two kernels
     for dt in (15, 5):
-        text = open(os.path.join(BUILD, f"varlen_kvcache_dt{dt}", "fa_inst_varlen_kvcache-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
+        text = open(os.path.join(BUILD, f"varlen_kvcache_dt{dt}", "fa_inst_varlen-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
         assert len(re.findall(r"^_ZN2fa28fa_fwd_kernel_varlen_kvcacheI\w+:", text, flags=re.M)) == 2
         assert "kvcache_fp8" not in text
 

@@ -175,9 +175,9 @@ def test_bad_window_sizes_are_value_errors_before_any_tensor_is_looked_at():
         fak.forward_varlen_kvcache(None, None, None, None, None, None, window_size=(16, 0))
 
 
-SLICES = [("varlen_window", "fa_inst_varlen_window", "27fa_fwd_kernel_varlen_window"),
-          ("varlen_kvcache_window", "fa_inst_varlen_kvcache_window", "35fa_fwd_kernel_varlen_kvcache_window"),
-          ("varlen_kvcache_fp8_window", "fa_inst_varlen_kvcache_fp8_window", "39fa_fwd_kernel_varlen_kvcache_fp8_window")]
+SLICES = [("varlen_window", "fa_inst_varlen", "27fa_fwd_kernel_varlen_window"),
+          ("varlen_kvcache_window", "fa_inst_varlen", "35fa_fwd_kernel_varlen_kvcache_window"),
+          ("varlen_kvcache_fp8_window", "fa_inst_varlen", "39fa_fwd_kernel_varlen_kvcache_fp8_window")]
 
 
 @pytest.mark.parametrize("folder,unit,kernel", SLICES, ids=[s[0] for s in SLICES])

@@ -277,7 +277,7 @@ def test_the_backward_is_sized_by_the_two_range_workspace_query():
 
 @pytest.mark.parametrize("dt", [15, 5])
 def test_the_forward_slice_is_kept_with_two_kernels_mfma_no_scratch_no_vector_spill(dt):
-    path = os.path.join(BUILD, f"varlen_softcap_dt{dt}", "fa_inst_varlen_softcap-hip-amdgcn-amd-amdhsa-gfx950.s")
+    path = os.path.join(BUILD, f"varlen_softcap_dt{dt}", "fa_inst_varlen-hip-amdgcn-amd-amdhsa-gfx950.s")
     assert os.path.exists(path), "the build keeps the ISA of every slice under csrc/build (make -C flash_attention_from_scratch_amd/csrc)"
     text = open(path).read()
     names = set(re.findall(r"^\s+\.name:\s+(_Z\w+)$", text, re.M))

@@ -285,8 +285,8 @@ def test_the_split_count_and_the_workspace_are_the_windowed_entrys():
 
 # ---- 5: the kept ISA --------------------------------------------------------------------------------------------------------------
 
-PREFILL_SLICES = [("varlen_kvcache_softcap", "fa_inst_varlen_kvcache_softcap", "36fa_fwd_kernel_varlen_kvcache_softcap", "23KernelArgsVarlenKVCacheE", 1),
-                  ("varlen_kvcache_fp8_softcap", "fa_inst_varlen_kvcache_fp8_softcap", "40fa_fwd_kernel_varlen_kvcache_fp8_softcap",
+PREFILL_SLICES = [("varlen_kvcache_softcap", "fa_inst_varlen", "36fa_fwd_kernel_varlen_kvcache_softcap", "23KernelArgsVarlenKVCacheE", 1),
+                  ("varlen_kvcache_fp8_softcap", "fa_inst_varlen", "40fa_fwd_kernel_varlen_kvcache_fp8_softcap",
                    "26KernelArgsVarlenKVCacheFp8E", 0)]
 
 
