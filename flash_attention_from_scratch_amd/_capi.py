@@ -45,6 +45,8 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_varlen_kvcache_fp8_window_supported", "fa_fwd_launch_varlen_kvcache_fp8_window",
     "fa_bwd_launch_varlen_qk_window",
     "fa_fwd_varlen_qk_softcap_supported", "fa_fwd_launch_varlen_qk_softcap", "fa_bwd_launch_varlen_qk_softcap",
+    "fa_fwd_varlen_qk_sinks_supported", "fa_fwd_launch_varlen_qk_sinks", "fa_bwd_varlen_qk_sinks_workspace_bytes",
+    "fa_bwd_launch_varlen_qk_sinks",
     "fa_fwd_varlen_kvcache_softcap_supported", "fa_fwd_launch_varlen_kvcache_softcap",
     "fa_fwd_varlen_kvcache_fp8_softcap_supported", "fa_fwd_launch_varlen_kvcache_fp8_softcap",
     "fa_decode_softcap_supported", "fa_decode_softcap_num_splits", "fa_decode_softcap_launch",
@@ -206,6 +208,14 @@ class FaSoftcap(ctypes.Structure):   # fa_softcap (logit soft-capping: softcap *
 
 def make_softcap(softcap):
     return FaSoftcap(struct_size=ctypes.sizeof(FaSoftcap), softcap=softcap)
+
+
+class FaSinks(ctypes.Structure):   # fa_sinks (learned attention sinks: one fp32 logit per query head in the softmax's denominator)
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_heads", ctypes.c_int32), ("sinks", ctypes.c_void_p)]
+
+
+def make_sinks(sinks_ptr, n_heads):
+    return FaSinks(struct_size=ctypes.sizeof(FaSinks), n_heads=n_heads, sinks=sinks_ptr)
 
 
 class FaKvcacheAppendArgs(ctypes.Structure):   # fa_kvcache_append_args (the append / rotary / quantize / advance step in front of a decode)
@@ -453,6 +463,18 @@ def load():
     argtypes = list(lib.fa_bwd_launch_varlen_qk_window.argtypes)
     lib.fa_bwd_launch_varlen_qk_softcap.restype = ctypes.c_int
     lib.fa_bwd_launch_varlen_qk_softcap.argtypes = argtypes[:2] + [ctypes.POINTER(FaSoftcap)] + argtypes[2:]
+    # the forms with attention sinks: the windowed sibling's arguments with an fa_sinks behind the fa_window, in the backward
+    # dsinks (n_heads fp32 on the device) behind that; the backward has a workspace query of its own (the two-range one's value)
+    lib.fa_fwd_varlen_qk_sinks_supported.restype = ctypes.c_int
+    lib.fa_fwd_varlen_qk_sinks_supported.argtypes = [cfg_p, ctypes.POINTER(FaFwdOpts)]
+    argtypes = list(lib.fa_fwd_launch_varlen_qk_window.argtypes)
+    lib.fa_fwd_launch_varlen_qk_sinks.restype = ctypes.c_int
+    lib.fa_fwd_launch_varlen_qk_sinks.argtypes = argtypes[:-3] + [ctypes.POINTER(FaSinks)] + argtypes[-3:]
+    lib.fa_bwd_varlen_qk_sinks_workspace_bytes.restype = ctypes.c_int64
+    lib.fa_bwd_varlen_qk_sinks_workspace_bytes.argtypes = [ctypes.POINTER(FaBwdVarlenQKArgs)]
+    argtypes = list(lib.fa_bwd_launch_varlen_qk_window.argtypes)
+    lib.fa_bwd_launch_varlen_qk_sinks.restype = ctypes.c_int
+    lib.fa_bwd_launch_varlen_qk_sinks.argtypes = argtypes[:2] + [ctypes.POINTER(FaSinks), ctypes.c_void_p] + argtypes[2:]
     # ... and of both cache prefills and both decodes: again the windowed sibling's arguments with an fa_softcap behind the fa_window
     for name in ("varlen_kvcache", "varlen_kvcache_fp8"):
         fn = getattr(lib, f"fa_fwd_{name}_softcap_supported")

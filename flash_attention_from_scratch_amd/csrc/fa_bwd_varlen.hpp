@@ -57,6 +57,25 @@
 // the S accumulator at -lse sqrt(d) so that exp2(c S) is P at once; a tanh in between forbids that, so here S starts at 0,
 // t = tanh(S / A) with A = softcap sqrt(d), p = exp2(c A t - lse log2(e)) (a dead row's -inf gives p = 0, never inf - inf), and
 // dS = p (dP - delta) (1 - t^2).  t lives in S's registers until p replaces it; the masks behind are the window form's.
+//
+// What attention sinks add (fa_bwd_launch_varlen_qk_sinks, BwdVarlenSinksArgs, fa_bwd_varlen_sinks.hip): no form of
+// these kernels at all.  Head h's sink is one more logit z = sinks[h] in the softmax's denominator with a zero value vector.  With
+// the forward's lse (which includes the sink) P = exp(S - lse) sums to less than 1 per row, delta = rowsum(dO o O) is unchanged
+// (the sink's value is 0) and dS = P o (dP - delta) stands: dQ, dK, dV are what the WINDOW form computes from that lse, so the
+// sink backward runs fa_bwd_varlen_window.hip's kernels as they are (no window: left = right = 2^30) and adds one reduction,
+// dsinks[h] = - sum_rows exp(z - lse) delta (fa_bwd_dsinks_varlen_kernel, in that unit).
+// Why the window form and not the unwindowed ones: a row that sees no key now has a FINITE lse (= z), so it is not `dead` in
+// load() / lse_q above -- its S starts at -z sqrt(d) like any live row's and exp2 gives some p > 0, possibly +inf.  The unwindowed
+// forms would let that p through (their only guard for such a row is S = -inf from lse == -inf).  The window form masks by a
+// SELECT on p behind `outside`, and `outside` is true on every tile a dead row appears in:
+//  * a row r is dead iff len_k = 0 (no dK / dV workgroup gets past its first test, dQ sweeps no tile) or r + shift + right < 0;
+//  * dK / dV: a swept tile `it` that holds r has it * 64 <= r, so it * 64 + shift + right < 0 <= kb * 128 + 127: the last term of
+//    `outside`; dQ: a block qb that holds r has qb * 128 <= r, so qb * 128 + shift + right < 0 <= kt * 64 + 63: the last term
+//    of `outside` there;
+//  * the select's `key > query + shift + right` holds for every key >= 0, so p = 0 exactly (a select, so even p = +inf goes), dS = 0 *
+//    (dP - delta) with both finite: dq = 0 for that row and nothing of it in dK / dV.  delta of such a row is 0 (o = 0), so it adds
+//    exactly 0 to dsinks as well.
+// A head with z = -inf has the lse of the call without sinks, -inf on its dead rows: the `dead` path as ever.
 #pragma once
 #include <type_traits>
 
@@ -110,6 +129,14 @@ struct BwdVarlenWindowArgs : BwdVarlenQKArgs {
 // A = softcap sqrt(d), 1 / A, which the host computes in double and rounds once
 struct BwdVarlenSoftcapArgs : BwdVarlenWindowArgs {
     float cap_a, cap_inv_a;
+};
+
+// ... with attention sinks (fa_bwd_launch_varlen_qk_sinks): the window form's arguments, as its kernels take them, and what the
+// sinks' own gradient reads and writes
+struct BwdVarlenSinksArgs {
+    BwdVarlenWindowArgs w;
+    const float *sinks;   // (n_heads) fp32
+    float *dsinks;        // (n_heads) fp32, written
 };
 
 namespace bwd {

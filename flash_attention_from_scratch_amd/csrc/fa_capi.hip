@@ -44,10 +44,10 @@ hipError_t bwd_enqueue(const BwdArgs &a, int dtype, bool causal, hipStream_t s);
 hipError_t bwd_gqa_enqueue(const BwdGqaArgs &g, int dtype, bool causal, hipStream_t s);
 // fa_inst_varlen.hip: the packed variable-length forward, one slice per form and dtype.  The forms, X(key side, extra, suffix):
 // key side 0 packed keys (equal or separate Q and K / V lengths) | 1 a KV cache | 2 an fp8 (e4m3fn) KV cache; extra 0 nothing |
-// 1 a sliding window | 2 a sliding window and logit soft-capping.  A new form is one entry here (and one in csrc/Makefile's
+// 1 a sliding window | 2 a sliding window and logit soft-capping | 3 a sliding window and attention sinks (packed keys only).  A new form is one entry here (and one in csrc/Makefile's
 // VARLEN_FORMS, and its arm in fa_fwd_kernel.hpp).
 #define FA_VARLEN_FORMS(X)                                                       \
-    X(0, 0, )             X(0, 1, _window)             X(0, 2, _softcap)         \
+    X(0, 0, )             X(0, 1, _window)             X(0, 2, _softcap)         X(0, 3, _sinks) \
     X(1, 0, _kvcache)     X(1, 1, _kvcache_window)     X(1, 2, _kvcache_softcap) \
     X(2, 0, _kvcache_fp8) X(2, 1, _kvcache_fp8_window) X(2, 2, _kvcache_fp8_softcap)
 #define FA_X(KEYS, EXTRA, SFX)                                              \
@@ -63,6 +63,8 @@ hipError_t bwd_varlen_qk_enqueue(const BwdVarlenQKArgs &a, int dtype, bool causa
 hipError_t bwd_varlen_window_enqueue(const BwdVarlenWindowArgs &a, int dtype, hipStream_t s);
 // fa_bwd_varlen_softcap.hip: ... with logit soft-capping on top
 hipError_t bwd_varlen_softcap_enqueue(const BwdVarlenSoftcapArgs &a, int dtype, hipStream_t s);
+// fa_bwd_varlen_sinks.hip: the window form's backward from an lse that includes the sinks, then the sinks' own gradient
+hipError_t bwd_varlen_sinks_enqueue(const BwdVarlenSinksArgs &a, int dtype, hipStream_t s);
 }  // namespace fa
 
 namespace {
@@ -339,6 +341,17 @@ void do_init_body(int dev, DeviceState *st) {
             st->status = FA_ERR_LAUNCH;
             snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, varlen soft-capped form) on device %d: %s", fa::varlen_lds_bytes_dt15(),
                      dev, hipGetErrorString(rc));
+            return;
+        }
+    }
+    // ... and the form with attention sinks (fa_fwd_launch_varlen_qk_sinks)
+    for (int i = 0; i < 4; ++i) {
+        const void *fn = (i & 2) ? (const void *)fa::varlen_sinks_kernel_dt5((i & 1) != 0) : (const void *)fa::varlen_sinks_kernel_dt15((i & 1) != 0);
+        const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, fa::varlen_lds_bytes_dt15());
+        if (rc != hipSuccess) {
+            st->status = FA_ERR_LAUNCH;
+            snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(%d B LDS, varlen sinks form) on device %d: %s", fa::varlen_lds_bytes_dt15(), dev,
+                     hipGetErrorString(rc));
             return;
         }
     }
@@ -1223,6 +1236,20 @@ void softcap_constants(const fa_softcap *c, float *a, float *inv_a) {
     *inv_a = (float)(1.0 / A);
 }
 
+// ---- fa_sinks: the rules of the entry points with attention sinks (called behind the windowed sibling's own rules) ----------
+// (`dsinks`: the backward's output, refused beside the sinks; `want_dsinks` false: the forward, which has none)
+int sinks_validate(const fa_sinks *sk, int64_t n_heads, bool want_dsinks, const float *dsinks) {
+    if (!sk) return fail(FA_ERR_NULL, "fa_sinks is null: one fp32 logit per query head is needed (without sinks, call the windowed entry point: this level has no \"off\")");
+    if (!sk->sinks) return fail(FA_ERR_NULL, "fa_sinks.sinks is null: a device pointer to n_heads fp32 logits is needed");
+    if (want_dsinks && !dsinks) return fail(FA_ERR_NULL, "dsinks is null: the backward writes the sinks' gradient, n_heads fp32, there");
+    if (sk->struct_size < sizeof(fa_sinks))
+        return fail(FA_ERR_SHAPE, "fa_sinks.struct_size (%u) is smaller than this library's (%zu)", sk->struct_size, sizeof(fa_sinks));
+    if (sk->n_heads != n_heads)
+        return fail(FA_ERR_SHAPE, "fa_sinks.n_heads (%d) does not match the call's n_heads (%lld): sinks are per query head", sk->n_heads,
+                    (long long)n_heads);
+    return FA_OK;
+}
+
 // the kernel of a form of the varlen forward (FA_VARLEN_FORMS), by key side, extra and dtype
 const void *varlen_kernel(int keys, int extra, bool bf16, bool first_block_skip) {
 #define FA_X(KEYS, EXTRA, SFX)          \
@@ -1236,7 +1263,7 @@ const void *varlen_kernel(int keys, int extra, bool bf16, bool first_block_skip)
 // What a public entry point asks of fwd_launch_varlen beyond the arguments all of them share: its name and its name for the query
 // side's total (for the messages), and its form.  The form comes from the entry point, never from a pointer being null.
 enum { KEYS_PACKED = 0, KEYS_CACHE = 1, KEYS_FP8_CACHE = 2 };   // fa_inst_varlen.hip's key side ...
-enum { EXTRA_NONE = 0, EXTRA_WINDOW = 1, EXTRA_SOFTCAP = 2 };   // ... and extra
+enum { EXTRA_NONE = 0, EXTRA_WINDOW = 1, EXTRA_SOFTCAP = 2, EXTRA_SINKS = 3 };   // ... and extra
 struct VarlenCall {
     const char *entry, *total;
     int keys, extra;
@@ -1245,11 +1272,13 @@ struct VarlenCall {
     const fa_kvcache_fp8_scales *sc;   // KEYS_FP8_CACHE: k, v are bytes, kv's strides count bytes, `sc` holds the descales
     const fa_window *w;                // EXTRA_WINDOW and up (null is refused, behind everything the entry itself refuses)
     const fa_softcap *cap;             // EXTRA_SOFTCAP (refused behind the window's rules)
+    const fa_sinks *sinks;             // EXTRA_SINKS, KEYS_PACKED only (refused behind the window's rules)
 };
 int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
                       const fa_fwd_opts *opts, float *lse, void *stream) {
     const bool cache_side = call.keys != KEYS_PACKED, fp8_side = call.keys == KEYS_FP8_CACHE;
     const bool windowed = call.extra != EXTRA_NONE, capped = call.extra == EXTRA_SOFTCAP;
+    const bool sunk = call.extra == EXTRA_SINKS;   // (packed keys only: its one entry point)
     const fa_varlen_layout *vk = cache_side ? vq : call.vk;   // (one valid layout for the checks both launches share)
     if (!args || !kv || !vq || !vk || (cache_side && !call.kc) || (fp8_side && !call.sc)) return fail(FA_ERR_NULL, "null pointer argument");
     if (!args->q || !args->k || !args->v || !args->o) return fail(FA_ERR_NULL, "null pointer argument");
@@ -1292,6 +1321,7 @@ int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_
             return fail(FA_ERR_SHAPE, "max_seqlen_q too large for a window: at most 2^30 - 128 query rows per sequence");
     }
     if (capped && (rc = softcap_validate(call.cap)) != FA_OK) return rc;
+    if (sunk && (rc = sinks_validate(call.sinks, args->n_heads, false, nullptr)) != FA_OK) return rc;
     if (vq->total_tokens == 0) {   // (no query rows: nothing to write)
         if (o.ms) *o.ms = 0.0f;
         return FA_OK;
@@ -1358,6 +1388,12 @@ int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_
         return &s;
     };
     void *kernel_args = fp8_side ? form_args(c8) : cache_side ? form_args(c16) : form_args(pa);
+    fa::KernelArgsVarlenSinks ps;   // (the sinks form: the packed side's windowed arguments, filled above, and the pointer)
+    if (sunk) {
+        ps.w = pa.w;
+        ps.sinks = call.sinks->sinks;
+        kernel_args = &ps;
+    }
     const void *fn = varlen_kernel(call.keys, call.extra, args->cfg.dtype == FA_BF16, e->softmax_mode == FA_SOFTMAX_FIRST_BLOCK_SKIP);
     const dim3 grid((unsigned)(va.base.n_bh * va.base.n_q_blocks)), block((unsigned)e->threads);
     const hipStream_t s = (hipStream_t)stream;
@@ -1559,6 +1595,13 @@ int fa_fwd_launch_varlen_kvcache_fp8_window(const fa_fwd_args *args, const fa_kv
     return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_fp8_window", "total_q", KEYS_FP8_CACHE, EXTRA_WINDOW, nullptr, kc, sc, w}, args, kv, vq, opts,
                              lse, stream);
 }
+// ... with attention sinks: the windowed packed body with an fa_sinks behind the window (served: what the sibling serves)
+int fa_fwd_varlen_qk_sinks_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
+int fa_fwd_launch_varlen_qk_sinks(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_varlen_layout *vk,
+                                  const fa_window *w, const fa_sinks *sinks, const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_qk_sinks", "total_q", KEYS_PACKED, EXTRA_SINKS, vk, nullptr, nullptr, w, nullptr, sinks}, args, kv, vq,
+                             opts, lse, stream);
+}
 // ... and both windowed cache prefills with logit soft-capping: an fa_softcap behind the window (served: what the sibling serves)
 int fa_fwd_varlen_kvcache_softcap_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
 int fa_fwd_launch_varlen_kvcache_softcap(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
@@ -1654,6 +1697,36 @@ int fa_bwd_launch_varlen_qk_window(const fa_bwd_varlen_qk_args *a, const fa_wind
 // ... with logit soft-capping: the sibling's checks and the window's, then the cap's
 int fa_bwd_launch_varlen_qk_softcap(const fa_bwd_varlen_qk_args *a, const fa_window *w, const fa_softcap *cap, void *stream, float *ms) {
     return bwd_launch_varlen_window(a, w, true, cap, stream, ms);
+}
+// ... with attention sinks: the sibling's checks and the window's, then the sinks'.  The kernels are the window form's (the
+// forward's lse holds the sink; fa_bwd_varlen.hpp), and one more reduces lse and the workspace's delta to dsinks.  No partials: the
+// workspace is the sibling's.  (No query rows but key rows: the window form writes the zeros of dK / dV and dsinks is written, as zeros.)
+int64_t fa_bwd_varlen_qk_sinks_workspace_bytes(const fa_bwd_varlen_qk_args *a) { return bwd_varlen_workspace_bytes(a, true); }
+int fa_bwd_launch_varlen_qk_sinks(const fa_bwd_varlen_qk_args *a, const fa_window *w, const fa_sinks *sinks, float *dsinks, void *stream, float *ms) {
+    int rc = bwd_varlen_checks(a, true, "total_q", "fa_bwd_varlen_qk_workspace_bytes");
+    if (rc != FA_OK) return rc;
+    if ((rc = window_validate(w, a->causal, 0)) != FA_OK) return rc;
+    if (a->varlen_k.max_seqlen > kWindowMaxLen)
+        return fail(FA_ERR_SHAPE, "max_seqlen_k too large for a window: at most 2^30 - 128 keys per sequence");
+    if (a->varlen.max_seqlen > kWindowMaxLen)
+        return fail(FA_ERR_SHAPE, "max_seqlen_q too large for a window: at most 2^30 - 128 query rows per sequence");
+    if ((rc = sinks_validate(sinks, a->n_heads, true, dsinks)) != FA_OK) return rc;
+    if (a->varlen.total_tokens == 0 && a->varlen_k.total_tokens == 0) {   // (like the sibling: no device, nothing written)
+        if (ms) *ms = 0.0f;
+        return FA_OK;
+    }
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    fa::BwdVarlenSinksArgs sa;
+    bwd_varlen_fill(sa.w, a);
+    constexpr int32_t kFar = 1 << 30;   // (as in bwd_launch_varlen_window)
+    const int32_t right = window_right(w, a->causal);
+    sa.w.left = w->left < 0 || w->left > kFar ? kFar : w->left;
+    sa.w.right = right < 0 || right > kFar ? kFar : right;
+    sa.sinks = sinks->sinks;
+    sa.dsinks = dsinks;
+    const hipStream_t s = (hipStream_t)stream;
+    return enqueue_timed([&] { return fa::bwd_varlen_sinks_enqueue(sa, a->dtype, s); }, s, ms);
 }
 
 // ---- KV-cache decode ------------------------------------------------------------------------------------------------------

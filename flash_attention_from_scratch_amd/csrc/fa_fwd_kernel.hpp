@@ -540,6 +540,22 @@ typedef Softcapped<KernelArgsVarlenKVCacheWindow> KernelArgsVarlenKVCacheSoftcap
 typedef Softcapped<KernelArgsVarlenKVCacheFp8Window> KernelArgsVarlenKVCacheFp8Softcap;
 typedef void (*kernel_fn_varlen_kvcache_softcap)(const KernelArgsVarlenKVCacheSoftcap);
 typedef void (*kernel_fn_varlen_kvcache_fp8_softcap)(const KernelArgsVarlenKVCacheFp8Softcap);
+// A learned attention sink on the packed forward (fa_fwd_launch_varlen_qk_sinks): query head h carries one more
+// logit z = sinks[h] that joins the softmax's denominator and has no value vector,
+//   lse = ln(exp(z) + sum_j exp(s_j)),   o = sum_j exp(s_j - lse) v_j;   z = -inf: no sink for that head.
+// Extra 3 defines FA_KERNEL_VARLEN_SINKS beside the windowed slice's two macros and gives fa_fwd_kernel_varlen_sinks INSTEAD of
+// fa_fwd_kernel_varlen_window: the windowed text (a window of (-1, -1) runs through it) whose loop is untouched.  Two sites differ:
+// the n_kv == 0 exit writes lse = z, and the end of an item folds the sink into l (sink_end below: the lse line and the
+// epilogue's 1 / l).  A row that saw no key (l = 0) gives o = 0 and lse = z exactly.  sinks[h] is a workgroup-uniform load made
+// at the end, not held across the loop.  Built for packed keys only.
+template <class W> struct Sunk {
+    W w;
+    const float *sinks;   // (n_heads) fp32 (DEVICE)
+};
+typedef Sunk<KernelArgsVarlenWindow> KernelArgsVarlenSinks;
+typedef void (*kernel_fn_varlen_sinks)(const KernelArgsVarlenSinks);
+static_assert(std::is_standard_layout<KernelArgsVarlenSinks>::value && offsetof(KernelArgsVarlenSinks, w) == 0,
+              "packed: sinks > window > QK");
 // Every wrapper's first member sits at offset 0, so the widest struct of a key side starts with the arguments of each narrower form:
 // the host fills that one struct and passes the address of the member the chosen kernel takes (fa_capi.hip, fwd_launch_varlen).
 // (KernelArgsVarlenSoftcap repeats Softcapped<KernelArgsVarlenWindow> field for field; it stays a struct of its own because its
@@ -556,7 +572,8 @@ static_assert(offsetof(KernelArgsVarlenKVCacheFp8Softcap, w) == 0 && offsetof(Ke
 
 // The form a translation unit builds is named once, by two numbers on its command line (fa_inst_varlen.hip, csrc/Makefile):
 //   FA_VARLEN_KEYS   0 packed keys (cu_seqlens_k) | 1 a KV cache | 2 an fp8 KV cache
-//   FA_VARLEN_EXTRA  0 nothing | 1 a sliding window | 2 a sliding window and logit soft-capping
+//   FA_VARLEN_EXTRA  0 nothing | 1 a sliding window | 2 a sliding window and logit soft-capping |
+//                    3 a sliding window and attention sinks (packed keys only)
 // The FA_KERNEL_VARLEN_* macros of the body's arms, the kernel's name (FA_VARLEN_NAME(fa_fwd_kernel_varlen, )) and its argument
 // follow from them here: a new key side or extra is one arm below, one in front of the kernel's body, and its arms in the body.
 #ifdef FA_VARLEN_KEYS
@@ -591,8 +608,15 @@ static_assert(offsetof(KernelArgsVarlenKVCacheFp8Softcap, w) == 0 && offsetof(Ke
 #define FA_KERNEL_VARLEN_WINDOW
 #define FA_KERNEL_VARLEN_SOFTCAP
 #define FA_VARLEN_EXTRA_SFX _softcap
+#elif FA_VARLEN_EXTRA == 3
+#if FA_VARLEN_KEYS != 0
+#error "FA_VARLEN_EXTRA 3 (attention sinks) is built for packed keys only (FA_VARLEN_KEYS 0)"
+#endif
+#define FA_KERNEL_VARLEN_WINDOW
+#define FA_KERNEL_VARLEN_SINKS
+#define FA_VARLEN_EXTRA_SFX _sinks
 #else
-#error "FA_VARLEN_EXTRA: 0 = none, 1 = sliding window, 2 = sliding window and soft-capping"
+#error "FA_VARLEN_EXTRA: 0 = none, 1 = sliding window, 2 = sliding window and soft-capping, 3 = sliding window and sinks"
 #endif
 #define FA_CAT4_(a, b, c, d) a##b##c##d
 #define FA_CAT4(a, b, c, d) FA_CAT4_(a, b, c, d)
@@ -676,6 +700,10 @@ __launch_bounds__(NWAVES * 64, 1)
 // (the argument by the extra, sa > wa > the key side's, which is qa itself or, against an fp8 cache, fa8 > qa)
 #if FA_VARLEN_EXTRA == 2
 FA_VARLEN_NAME(fa_fwd_kernel_varlen, )(const FA_VARLEN_CAP_ARGS sa) {
+    const Windowed<FA_VARLEN_KEY_ARGS> &wa = sa.w;
+    const FA_VARLEN_KEY_ARGS &FA_VARLEN_KEY_PARAM = wa.a;
+#elif FA_VARLEN_EXTRA == 3
+FA_VARLEN_NAME(fa_fwd_kernel_varlen, )(const Sunk<Windowed<FA_VARLEN_KEY_ARGS>> sa) {
     const Windowed<FA_VARLEN_KEY_ARGS> &wa = sa.w;
     const FA_VARLEN_KEY_ARGS &FA_VARLEN_KEY_PARAM = wa.a;
 #elif FA_VARLEN_EXTRA == 1
@@ -861,7 +889,12 @@ fa_fwd_kernel(const KernelArgs args) {
             const int64_t row = z_row0 + RPP * i + z_rsub;
             if (row < q_len) *(s16x8 *)(Og + row * ss + z_chunk * 8) = s16x8{};
         }
+#ifdef FA_KERNEL_VARLEN_SINKS
+        // (the sink is the softmax's only member: lse = z)
+        if (lane < TR::kRowsPerWave && z_row0 + lane < q_len) z_lse[z_row0 + lane] = sa.sinks[h];
+#else
         if (lane < TR::kRowsPerWave && z_row0 + lane < q_len) z_lse[z_row0 + lane] = -__builtin_inff();
+#endif
         return;
     }
 #endif
@@ -1632,6 +1665,31 @@ fa_fwd_kernel(const KernelArgs args) {
     int64_t l_row0 = va.cu_seqlens[b];
     l_row0 = l_row0 < 0 ? 0 : (l_row0 > va.total_tokens ? va.total_tokens : l_row0);
     float *lse_rows = va.lse + ((int64_t)h * va.total_tokens + l_row0);
+#ifdef FA_KERNEL_VARLEN_SINKS
+    // The sink joins the denominator here, in log2 units against a common maximum so that neither term overflows:
+    //   M = max(m c, z log2 e),  l' = l exp2(m c - M) + exp2(z log2 e - M),  o = O exp2(m c - M) / l',  lse = (log2 l' + M) ln 2.
+    // z far above every logit: the first factor underflows to 0, l' = 1, lse = z, o = 0; far below: its term underflows and
+    // nothing changes.  A row with l = 0 (m = -inf: it saw no key) gives o = 0 and lse = z exactly -- with z = -inf that is
+    // -inf, and no exp2(-inf - -inf) is formed: where l > 0, m and with it M are finite.  z = -inf on a live row: M = m c, the
+    // factor is exp2(0) = 1, the sink's term 0: the windowed kernel's values.
+    const float sink_z = sa.sinks[h];   // (workgroup-uniform, read here and not held across the loop)
+    auto sink_end = [&](float l_row, float m_row, float &scale, float &lse_row) {
+        const float mc = m_row * c, zc = sink_z * 1.4426950408889634074f;
+        const float M = fmaxf(mc, zc);
+        const float a = __builtin_amdgcn_exp2f(mc - M);
+        const float l_all = l_row * a + __builtin_amdgcn_exp2f(zc - M);
+        const bool dead = l_row == 0.0f;
+        scale = dead ? 0.0f : a / l_all;
+        lse_row = dead ? sink_z : (__builtin_amdgcn_logf(l_all) + M) * 0.693147180559945309f;
+    };
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+        const int row = wave_row0 + qt * 32 + r31;
+        float scale, lse_row;
+        sink_end(pair_sum(l[qt]), m[qt], scale, lse_row);
+        if (hi == 0 && row < FA_Q_LEN_END) lse_rows[row] = lse_row;
+    }
+#else
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
         const float l_row = pair_sum(l[qt]);
@@ -1639,6 +1697,7 @@ fa_fwd_kernel(const KernelArgs args) {
         if (hi == 0 && row < FA_Q_LEN_END)   // (a row without keys: l = 0, m = -inf -> ln 0 + 0 = -inf)
             lse_rows[row] = (__builtin_amdgcn_logf(l_row) + FA_LSE_M_TIMES_C(finite_or_zero(m[qt]), c)) * 0.693147180559945309f;
     }
+#endif
 #endif
     if ((ABL & 32) && args.seq_len < 0) {  // never true: keeps the landing registers allocated
 #pragma unroll
@@ -1689,7 +1748,10 @@ fa_fwd_kernel(const KernelArgs args) {
         char *stage_o = smem + wave_r * (TR::kRowsPerWave * ROWB);
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
-#ifdef FA_KERNEL_VARLEN
+#ifdef FA_KERNEL_VARLEN_SINKS
+            float inv, lse_unused;   // (a row that saw no key: o = 0)
+            sink_end(pair_sum(l[qt]), m[qt], inv, lse_unused);
+#elif defined(FA_KERNEL_VARLEN)
             const float l_all = pair_sum(l[qt]);
 #ifdef FA_KERNEL_VARLEN_KVCACHE_FP8
             // ... with v_descale folded in (read here, not held across the loop)

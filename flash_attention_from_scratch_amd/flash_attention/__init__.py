@@ -258,6 +258,27 @@ def backward_varlen_softcap(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, softc
                                                            max_seqlen_k=max_seqlen_k)
 
 
+def forward_varlen_sinks(q, k, v, cu_seqlens, max_seqlen, sinks, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None, *,
+                         window_size=(-1, -1)):
+    """forward_varlen with learned attention sinks (gpt-oss's `sinks`, flash-attn's learnable_sink): sinks is a
+    contiguous fp32 (n_heads,) tensor on q's device, one logit z per QUERY head that joins the softmax's denominator and has no
+    value vector -- lse = log(exp(z) + sum_j exp(s_j)), o = sum_j exp(s_j - lse) v_j over the keys the row sees.  Every other
+    argument is forward_varlen's (no softcap).  A row that sees no key gives o = 0 and lse = z; z = -inf means no sink for that
+    head.  -> (o, lse[, ms]).  A bad window_size is a ValueError, a bad sinks a RuntimeError.  Without sinks, call forward_varlen."""
+    return flash_attention_kernels.forward_varlen_sinks(q, k, v, cu_seqlens, max_seqlen, sinks, causal=causal, timed=timed,
+                                                        cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k, window_size=window_size)
+
+
+def backward_varlen_sinks(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, sinks, window_size=(-1, -1), causal=False, timed=False,
+                          cu_seqlens_k=None, max_seqlen_k=None):
+    """The backward of forward_varlen_sinks: dQ, dK, dV and dsinks from that forward's o and lse under the same sinks and window
+     -> (dq, dk, dv, dsinks[, ms]), dsinks fp32 of shape (n_heads,).  dQ, dK, dV are backward_varlen_window's
+    kernels on the lse that holds the sink; dsinks[h] = - sum_rows exp(sinks[h] - lse[h, row]) delta[h, row].  A row that sees no
+    key gets dq = 0; a key no row sees gets dk = dv = 0, written; sinks[h] = -inf gives dsinks[h] = 0.  Deterministic."""
+    return flash_attention_kernels.backward_varlen_sinks(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, sinks, window_size,
+                                                         causal=causal, timed=timed, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
+
+
 def _varlen_needs_copy(t):
     return t.stride(2) != 1 or t.stride(0) % 8 != 0 or t.stride(1) % 8 != 0 or t.data_ptr() % 16 != 0
 
@@ -312,3 +333,47 @@ def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, cu_seqlens_k
     if (cu_seqlens_k is None) != (max_seqlen_k is None):
         raise ValueError("cu_seqlens_k and max_seqlen_k go together: give both (separate Q and K / V lengths) or neither")
     return _AttentionVarlen.apply(q, k, v, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k, tuple(window_size), softcap)
+
+
+class _AttentionVarlenSinks(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, sinks, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k, window_size=(-1, -1)):
+        if _varlen_needs_copy(q):
+            q = q.contiguous()
+        if _varlen_needs_copy(k) or _varlen_needs_copy(v) or v.stride() != k.stride():
+            k, v = k.contiguous(), v.contiguous()
+        o, lse = forward_varlen_sinks(q, k, v, cu_seqlens, max_seqlen, sinks, causal=causal, cu_seqlens_k=cu_seqlens_k,
+                                      max_seqlen_k=max_seqlen_k, window_size=window_size)
+        ctx.qk = cu_seqlens_k is not None
+        if ctx.qk:
+            ctx.save_for_backward(q, k, v, o, lse, sinks, cu_seqlens, cu_seqlens_k)
+        else:
+            ctx.save_for_backward(q, k, v, o, lse, sinks, cu_seqlens)
+        ctx.max_seqlen, ctx.max_seqlen_k, ctx.causal, ctx.window_size = max_seqlen, max_seqlen_k, causal, tuple(window_size)
+        return o
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, o, lse, sinks, cu_seqlens = ctx.saved_tensors[:7]
+        cu_seqlens_k = ctx.saved_tensors[7] if ctx.qk else None
+        dq, dk, dv, dsinks = backward_varlen_sinks(q, k, v, o, lse, dout.contiguous(), cu_seqlens, ctx.max_seqlen, sinks, ctx.window_size,
+                                                   causal=ctx.causal, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=ctx.max_seqlen_k)
+        return dq, dk, dv, dsinks, None, None, None, None, None, None
+
+
+def attention_varlen_sinks(q, k, v, cu_seqlens, max_seqlen, sinks, causal=False, cu_seqlens_k=None, max_seqlen_k=None, *,
+                           window_size=(-1, -1)):
+    """attention_varlen with learned attention sinks, with gradients for q, k, v AND sinks (gpt-oss's attention): the
+    forward and backward of forward_varlen_sinks / backward_varlen_sinks under one window.  sinks: (n_heads,) on q's device, fp32 or
+    q's dtype -- a 16-bit parameter is converted to fp32 here, outside the autograd function, so its gradient comes back in its own
+    dtype.  Every other argument is attention_varlen's (no softcap).  A bad window_size is a ValueError before any tensor is looked
+    at, a bad sinks a RuntimeError.  Without sinks, call attention_varlen."""
+    flash_attention_kernels._window(window_size, causal)
+    if (cu_seqlens_k is None) != (max_seqlen_k is None):
+        raise ValueError("cu_seqlens_k and max_seqlen_k go together: give both (separate Q and K / V lengths) or neither")
+    if isinstance(sinks, torch.Tensor) and isinstance(q, torch.Tensor) and sinks.dtype == q.dtype and sinks.dtype != torch.float32:
+        sinks = sinks.float()
+    if isinstance(sinks, torch.Tensor) and sinks.dim() == 1 and not sinks.is_contiguous():
+        sinks = sinks.contiguous()
+    flash_attention_kernels._check_sinks(sinks, q)
+    return _AttentionVarlenSinks.apply(q, k, v, sinks, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k, tuple(window_size))

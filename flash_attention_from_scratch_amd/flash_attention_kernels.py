@@ -373,6 +373,42 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
     (attention_varlen(softcap=) pairs the two)."""
     window = _window(window_size, causal)
     cap = _softcap(softcap)
+    return _forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, cap)
+
+
+def forward_varlen_sinks(q, k, v, cu_seqlens, max_seqlen, sinks, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None, *,
+                         window_size=(-1, -1)):
+    """forward_varlen with learned attention sinks (gpt-oss's `sinks`, flash-attn's learnable_sink; fa_fwd_launch_varlen_qk_sinks):
+    every other argument is forward_varlen's, with its meaning and checks (one range given: on both sides; (-1, -1) included).
+    sinks, required: a contiguous fp32 tensor of shape (n_heads,) on q's device, one logit z per QUERY head that joins the
+    softmax's denominator and has no value vector: lse = log(exp(z) + sum_j exp(s_j)), o = sum_j exp(s_j - lse) v_j.  A row that
+    sees no key gives o = 0 and lse = z; z = -inf means no sink for that head (forward_varlen's values; a dead row's lse = -inf).
+    The host never reads sinks.  No softcap here, and no "off": without sinks, call forward_varlen.  -> (o, lse[, ms]).  A bad
+    window_size is a ValueError before any tensor is looked at; a bad sinks a RuntimeError before the library is loaded.  The
+    gradients are backward_varlen_sinks's (attention_varlen_sinks pairs the two)."""
+    window = _window(window_size, causal)
+    _check_sinks(sinks, q)
+    return _forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, None, sinks)
+
+
+def _check_sinks(sinks, q, name="sinks"):
+    """sinks as forward_varlen_sinks and backward_varlen_sinks take it: a contiguous fp32 tensor of shape (n_heads,) on q's device
+    (checked in front of _check_varlen, so against q only where q is a packed tensor at all)"""
+    if not isinstance(sinks, torch.Tensor):
+        raise RuntimeError(f"{name} must be a tensor: fp32, contiguous, of shape (n_heads,), on q's device (got {type(sinks).__name__})")
+    if sinks.dtype != torch.float32:
+        raise RuntimeError(f"{name} must be fp32 (got {sinks.dtype}; attention_varlen_sinks converts for you)")
+    if sinks.dim() != 1 or not sinks.is_contiguous():
+        raise RuntimeError(f"{name} must be a contiguous tensor of shape (n_heads,) (got shape {tuple(sinks.shape)}, strides {sinks.stride()})")
+    if isinstance(q, torch.Tensor) and q.dim() == 3:
+        if sinks.shape[0] != q.shape[1]:
+            raise RuntimeError(f"{name} must have shape (n_heads,) = ({q.shape[1]},): one logit per query head (got {tuple(sinks.shape)})")
+        if sinks.device != q.device:
+            raise RuntimeError(f"{name} must be on q's device ({q.device}, got {sinks.device})")
+
+
+def _forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, cap, sinks=None):
+    """forward_varlen (window: _window's, cap: _softcap's) and forward_varlen_sinks (sinks a checked tensor, cap None)"""
     qk = _qk_sides(cu_seqlens_k, max_seqlen_k)
     _check_varlen(q, k, v, cu_seqlens, max_seqlen, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
     total, n_heads, d_head = q.shape
@@ -390,6 +426,12 @@ def forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, timed=False, c
     opts = _capi.make_opts(causal=causal, ms=ms if timed else None)
     with torch.cuda.device(q.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        if sinks is not None:
+            w, sk = _capi.make_window(*(window or (-1, -1))), _capi.make_sinks(sinks.data_ptr(), n_heads)
+            _capi.check(lib.fa_fwd_launch_varlen_qk_sinks(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(sides[0]), ctypes.byref(sides[-1]),
+                                                          ctypes.byref(w), ctypes.byref(sk), ctypes.byref(opts),
+                                                          ctypes.c_void_p(lse.data_ptr()), stream))
+            return (o, lse, float(ms.value)) if timed else (o, lse)
         if cap is not None:
             w, sc = _capi.make_window(*(window or (-1, -1))), _capi.make_softcap(cap)
             _capi.check(lib.fa_fwd_launch_varlen_qk_softcap(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(sides[0]), ctypes.byref(sides[-1]),
@@ -443,9 +485,24 @@ def backward_varlen_softcap(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, softc
     return _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, cap)
 
 
-def _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, cap=None):
-    """backward_varlen (window None), backward_varlen_window (window (left, right): the two-range arguments, given or not) and
-    backward_varlen_softcap (cap a float: the two-range arguments and a window, (-1, -1) where none is given)"""
+def backward_varlen_sinks(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, sinks, window_size=(-1, -1), causal=False, timed=False,
+                          cu_seqlens_k=None, max_seqlen_k=None):
+    """The backward of forward_varlen_sinks: dQ, dK, dV and dsinks from ITS o and lse under the same sinks and window_size
+    (fa_bwd_launch_varlen_qk_sinks; one range given: on both sides).  dQ, dK, dV are backward_varlen_window's kernels on that lse,
+    bit for bit ((-1, -1): its call with left = right = 2^30); dsinks[h] = - sum_rows exp(sinks[h] - lse[h, row]) delta[h, row], fp32
+    of shape (n_heads,), summed in a fixed order.  -> (dq, dk, dv, dsinks[, ms]).  A row that sees no key gets dq = 0 and adds
+    exactly 0 to dsinks; a key no row sees gets dk = dv = 0, written; a head with sinks[h] = -inf gets dsinks[h] = 0.  A bad
+    window_size is a ValueError before any tensor is looked at, a bad sinks a RuntimeError before the library is loaded."""
+    window = _window(window_size, causal)
+    _check_sinks(sinks, q)
+    return _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, None, sinks)
+
+
+def _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, cap=None,
+                     sinks=None):
+    """backward_varlen (window None), backward_varlen_window (window (left, right): the two-range arguments, given or not),
+    backward_varlen_softcap (cap a float: the two-range arguments and a window, (-1, -1) where none is given) and
+    backward_varlen_sinks (sinks a checked tensor: as with a cap, and dsinks behind dv in the result)"""
     qk = _qk_sides(cu_seqlens_k, max_seqlen_k)
     _check_varlen(q, k, v, cu_seqlens, max_seqlen, others=((o, "o"), (dout, "dout"), (lse, "lse")),
                   cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
@@ -471,10 +528,18 @@ def _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, time
         kv_seq_stride=k.stride(0), kv_head_stride=k.stride(1), dkv_seq_stride=dk.stride(0), dkv_head_stride=dk.stride(1),
         dtype=15 if q.dtype == torch.bfloat16 else 5, causal=1 if causal else 0, varlen=sides[0],
     )
-    if qk or window is not None or cap is not None:
+    dsinks = None
+    if qk or window is not None or cap is not None or sinks is not None:
         args = _capi.FaBwdVarlenQKArgs(struct_size=ctypes.sizeof(_capi.FaBwdVarlenQKArgs), varlen_k=sides[-1], **fields)
         workspace_bytes, launch = lib.fa_bwd_varlen_qk_workspace_bytes, lib.fa_bwd_launch_varlen_qk
-        if cap is not None:
+        if sinks is not None:
+            # (no rows on either side: the launch returns at once and writes nothing -- the sum over no rows is 0)
+            dsinks = (torch.empty if total or total_k else torch.zeros)((n_heads,), dtype=torch.float32, device=q.device)
+            w, sk = _capi.make_window(*(window or (-1, -1))), _capi.make_sinks(sinks.data_ptr(), n_heads)
+            workspace_bytes = lib.fa_bwd_varlen_qk_sinks_workspace_bytes
+            launch = lambda a, stream, ms: lib.fa_bwd_launch_varlen_qk_sinks(   # noqa: E731
+                a, ctypes.byref(w), ctypes.byref(sk), ctypes.c_void_p(dsinks.data_ptr()), stream, ms)
+        elif cap is not None:
             w, sc = _capi.make_window(*(window or (-1, -1))), _capi.make_softcap(cap)
             launch = lambda a, stream, ms: lib.fa_bwd_launch_varlen_qk_softcap(a, ctypes.byref(w), ctypes.byref(sc), stream, ms)   # noqa: E731
         elif window is not None:
@@ -491,7 +556,8 @@ def _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, time
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
         ms = ctypes.c_float(0.0)
         _capi.check(launch(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
-    return (dq, dk, dv, float(ms.value)) if timed else (dq, dk, dv)
+    grads = (dq, dk, dv) if sinks is None else (dq, dk, dv, dsinks)
+    return grads + (float(ms.value),) if timed else grads
 
 
 # ---- KV-cache decode (fa_decode_launch) ------------------------------------------------------------------------------------

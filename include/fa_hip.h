@@ -832,6 +832,44 @@ int fa_bwd_launch_varlen_qk_softcap(const fa_bwd_varlen_qk_args *args, const fa_
                                     void *stream, float *ms);
 
 /*
+ * Learned attention sinks on the packed training path (gpt-oss's `sinks`, flash-attn's learnable_sink / s_aux).
+ * Query head h carries one more logit z = sinks[h] that joins the softmax's denominator and has no value vector (per QUERY head,
+ * under grouped-query attention too).  With s_j = q . k_j / sqrt(128) over the keys a row sees (lengths, bottom-right causal rule
+ * and window exactly as in fa_fwd_launch_varlen_qk_window):
+ *     lse = log(exp(z) + sum_j exp(s_j))   (natural units),      o = sum_j exp(s_j - lse) v_j.
+ * A row that sees no key gives o = 0 and lse = z (not -inf: the sink is the softmax's only member), dq = 0, and adds exactly 0 to
+ * dsinks; a key no row sees gets dk = dv = 0, written.  z = -inf means "no sink for this head": o and lse are those of the call
+ * without sinks (a dead row's lse = -inf), dsinks[h] = 0, no NaN anywhere.  z = +inf and NaN are unspecified; the host never reads
+ * sinks.  The sink cannot overflow: it is folded in against max(row max, z), so z far above every logit gives lse = z, o -> 0, and
+ * z far below changes nothing.  Not combined with soft-capping: these calls take no fa_softcap.
+ *
+ * The backward: dQ, dK, dV are what fa_bwd_launch_varlen_qk_window computes from this lse (its kernels, unchanged: P = exp(S - lse)
+ * then sums to less than 1 per row, delta is unchanged), and
+ *     dsinks[h] = - sum over the rows of head h of exp(z - lse[h][row]) * delta[h][row]
+ * is written to `dsinks`, n_heads fp32 on the device (fp32 sums in a fixed order, no atomics: the same inputs give the same bits).
+ * Both launches take the arguments of their windowed sibling, a window included: (-1, -1) is legal there and means none.
+ * fa_bwd_varlen_qk_sinks_workspace_bytes(args) sizes the backward's workspace (the sibling's value).  Graph-capturable.  This level
+ * has no "off": without sinks, call the windowed entry points (or their unwindowed siblings).
+ *
+ * Refused before any HIP call, in this order: what the windowed sibling refuses, with its status and message; then a null fa_sinks
+ * or fa_sinks.sinks, and in the backward a null dsinks (FA_ERR_NULL); then a struct_size below sizeof(fa_sinks), or n_heads that is
+ * not the call's (FA_ERR_SHAPE).  total_q = total_k = 0 returns FA_OK without a device, like the sibling, and writes nothing: the
+ * sum over no rows, dsinks = 0, is then the caller's to write.
+ */
+typedef struct fa_sinks {
+    uint32_t struct_size;      /* sizeof(fa_sinks) */
+    int32_t n_heads;           /* the call's n_heads: one logit per query head */
+    const float *sinks;        /* (n_heads) fp32, DEVICE */
+} fa_sinks;
+int fa_fwd_varlen_qk_sinks_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_qk_sinks(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                  const fa_varlen_layout *varlen_k, const fa_window *window, const fa_sinks *sinks,
+                                  const fa_fwd_opts *opts, float *lse, void *stream);
+int64_t fa_bwd_varlen_qk_sinks_workspace_bytes(const fa_bwd_varlen_qk_args *args);
+int fa_bwd_launch_varlen_qk_sinks(const fa_bwd_varlen_qk_args *args, const fa_window *window, const fa_sinks *sinks, float *dsinks,
+                                  void *stream, float *ms);
+
+/*
  * Logit soft-capping on the inference path: the cache prefill and the decode, 16-bit and fp8 cache.  The same
  * definition as above: the logit of a key a row sees is softcap * tanh(s / softcap), s = q . k / sqrt(128) on the DEQUANTIZED key,
  * applied before any mask; lse is the log-sum-exp of the capped logits, a row that sees no key gives o = 0, lse = -inf.
