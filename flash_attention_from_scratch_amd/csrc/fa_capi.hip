@@ -44,12 +44,12 @@ hipError_t bwd_enqueue(const BwdArgs &a, int dtype, bool causal, hipStream_t s);
 hipError_t bwd_gqa_enqueue(const BwdGqaArgs &g, int dtype, bool causal, hipStream_t s);
 // fa_inst_varlen.hip: the packed variable-length forward, one slice per form and dtype.  The forms, X(key side, extra, suffix):
 // key side 0 packed keys (equal or separate Q and K / V lengths) | 1 a KV cache | 2 an fp8 (e4m3fn) KV cache; extra 0 nothing |
-// 1 a sliding window | 2 a sliding window and logit soft-capping | 3 a sliding window and attention sinks (packed keys only).  A new form is one entry here (and one in csrc/Makefile's
+// 1 a sliding window | 2 a sliding window and logit soft-capping | 3 a sliding window and attention sinks.  A new form is one entry here (and one in csrc/Makefile's
 // VARLEN_FORMS, and its arm in fa_fwd_kernel.hpp).
 #define FA_VARLEN_FORMS(X)                                                       \
     X(0, 0, )             X(0, 1, _window)             X(0, 2, _softcap)         X(0, 3, _sinks) \
-    X(1, 0, _kvcache)     X(1, 1, _kvcache_window)     X(1, 2, _kvcache_softcap) \
-    X(2, 0, _kvcache_fp8) X(2, 1, _kvcache_fp8_window) X(2, 2, _kvcache_fp8_softcap)
+    X(1, 0, _kvcache)     X(1, 1, _kvcache_window)     X(1, 2, _kvcache_softcap)     X(1, 3, _kvcache_sinks) \
+    X(2, 0, _kvcache_fp8) X(2, 1, _kvcache_fp8_window) X(2, 2, _kvcache_fp8_softcap) X(2, 3, _kvcache_fp8_sinks)
 #define FA_X(KEYS, EXTRA, SFX)                                              \
     kernel_fn_varlen##SFX varlen##SFX##_kernel_dt15(bool first_block_skip); \
     kernel_fn_varlen##SFX varlen##SFX##_kernel_dt5(bool first_block_skip);
@@ -1272,13 +1272,13 @@ struct VarlenCall {
     const fa_kvcache_fp8_scales *sc;   // KEYS_FP8_CACHE: k, v are bytes, kv's strides count bytes, `sc` holds the descales
     const fa_window *w;                // EXTRA_WINDOW and up (null is refused, behind everything the entry itself refuses)
     const fa_softcap *cap;             // EXTRA_SOFTCAP (refused behind the window's rules)
-    const fa_sinks *sinks;             // EXTRA_SINKS, KEYS_PACKED only (refused behind the window's rules)
+    const fa_sinks *sinks;             // EXTRA_SINKS (refused behind the window's rules)
 };
 int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
                       const fa_fwd_opts *opts, float *lse, void *stream) {
     const bool cache_side = call.keys != KEYS_PACKED, fp8_side = call.keys == KEYS_FP8_CACHE;
     const bool windowed = call.extra != EXTRA_NONE, capped = call.extra == EXTRA_SOFTCAP;
-    const bool sunk = call.extra == EXTRA_SINKS;   // (packed keys only: its one entry point)
+    const bool sunk = call.extra == EXTRA_SINKS;
     const fa_varlen_layout *vk = cache_side ? vq : call.vk;   // (one valid layout for the checks both launches share)
     if (!args || !kv || !vq || !vk || (cache_side && !call.kc) || (fp8_side && !call.sc)) return fail(FA_ERR_NULL, "null pointer argument");
     if (!args->q || !args->k || !args->v || !args->o) return fail(FA_ERR_NULL, "null pointer argument");
@@ -1388,12 +1388,16 @@ int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_
         return &s;
     };
     void *kernel_args = fp8_side ? form_args(c8) : cache_side ? form_args(c16) : form_args(pa);
-    fa::KernelArgsVarlenSinks ps;   // (the sinks form: the packed side's windowed arguments, filled above, and the pointer)
-    if (sunk) {
-        ps.w = pa.w;
-        ps.sinks = call.sinks->sinks;
-        kernel_args = &ps;
-    }
+    // (the sinks form: the key side's windowed arguments, filled above, and the pointer)
+    fa::KernelArgsVarlenSinks ps;
+    fa::KernelArgsVarlenKVCacheSinks ps16;
+    fa::KernelArgsVarlenKVCacheFp8Sinks ps8;
+    auto sunk_args = [&](auto &dst, const auto &windowed_args) -> void * {
+        dst.w = windowed_args;
+        dst.sinks = call.sinks->sinks;
+        return &dst;
+    };
+    if (sunk) kernel_args = fp8_side ? sunk_args(ps8, c8.w) : cache_side ? sunk_args(ps16, c16.w) : sunk_args(ps, pa.w);
     const void *fn = varlen_kernel(call.keys, call.extra, args->cfg.dtype == FA_BF16, e->softmax_mode == FA_SOFTMAX_FIRST_BLOCK_SKIP);
     const dim3 grid((unsigned)(va.base.n_bh * va.base.n_q_blocks)), block((unsigned)e->threads);
     const hipStream_t s = (hipStream_t)stream;
@@ -1602,6 +1606,20 @@ int fa_fwd_launch_varlen_qk_sinks(const fa_fwd_args *args, const fa_kv_layout *k
     return fwd_launch_varlen({"fa_fwd_launch_varlen_qk_sinks", "total_q", KEYS_PACKED, EXTRA_SINKS, vk, nullptr, nullptr, w, nullptr, sinks}, args, kv, vq,
                              opts, lse, stream);
 }
+// ... and both windowed cache prefills with attention sinks: an fa_sinks behind the window (served: what the sibling serves)
+int fa_fwd_varlen_kvcache_sinks_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
+int fa_fwd_launch_varlen_kvcache_sinks(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_kvcache_layout *kc,
+                                       const fa_window *w, const fa_sinks *sinks, const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_sinks", "total_q", KEYS_CACHE, EXTRA_SINKS, nullptr, kc, nullptr, w, nullptr, sinks}, args,
+                             kv, vq, opts, lse, stream);
+}
+int fa_fwd_varlen_kvcache_fp8_sinks_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
+int fa_fwd_launch_varlen_kvcache_fp8_sinks(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
+                                           const fa_kvcache_layout *kc, const fa_kvcache_fp8_scales *sc, const fa_window *w,
+                                           const fa_sinks *sinks, const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_fp8_sinks", "total_q", KEYS_FP8_CACHE, EXTRA_SINKS, nullptr, kc, sc, w, nullptr, sinks},
+                             args, kv, vq, opts, lse, stream);
+}
 // ... and both windowed cache prefills with logit soft-capping: an fa_softcap behind the window (served: what the sibling serves)
 int fa_fwd_varlen_kvcache_softcap_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_supported(cfg, opts); }
 int fa_fwd_launch_varlen_kvcache_softcap(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
@@ -1731,8 +1749,8 @@ int fa_bwd_launch_varlen_qk_sinks(const fa_bwd_varlen_qk_args *a, const fa_windo
 
 // ---- KV-cache decode ------------------------------------------------------------------------------------------------------
 // fa_decode_args and fa_decode_fp8_args carry the same members under the same names (the fp8 struct adds its encoding and
-// descales), so one text over either struct serves the twenty-two entry points: a planner (validate, then the split count) for the
-// sixteen queries and one launch body for the six launches (the soft-capped forms: four queries, two launches).  What only one struct has sits in the two decode_struct_rules.
+// descales), so one text over either struct serves the twenty-eight entry points: a planner (validate, then the split count) for the
+// twenty queries and one launch body for the eight launches (the soft-capped and the sink forms: four queries, two launches each).  What only one struct has sits in the two decode_struct_rules.
 namespace {
 extern "C++" {   // (as for the cache's rules above; the two overloads need it as well)
 constexpr int64_t kDecodeMaxRows = 64, kDecodeWantWgs = 256, kDecodeKeysPerSplit = 256, kDecodeMaxSplits = 128, kDecodeMaxForced = 1024;
@@ -1810,12 +1828,16 @@ template <class A> int64_t decode_splits(const A *a, const CacheView &c, const f
 
 // The planner of every decode entry point: the arguments (either struct) and, for a window form, its fa_window (null is refused
 // there) -> status, split count and the cache as validated.  `capped`: a soft-capped form, its fa_softcap refused behind the
-// window's rules; the cap does not enter the split rule.
-template <class A> DecodePlan decode_plan(const A *a, bool windowed, const fa_window *w, bool capped = false, const fa_softcap *cap = nullptr) {
+// window's rules; the cap does not enter the split rule.  `sunk`: a form with attention sinks, its fa_sinks refused in the same
+// place; the sinks do not enter the split rule either.
+template <class A>
+DecodePlan decode_plan(const A *a, bool windowed, const fa_window *w, bool capped = false, const fa_softcap *cap = nullptr, bool sunk = false,
+                       const fa_sinks *sk = nullptr) {
     DecodePlan p;
     p.status = decode_validate(a, p.cache);
     if (p.status == FA_OK && windowed) p.status = window_validate(w, a->causal, p.cache.capacity());
     if (p.status == FA_OK && capped) p.status = softcap_validate(cap);
+    if (p.status == FA_OK && sunk) p.status = sinks_validate(sk, a->n_heads, false, nullptr);
     if (p.status == FA_OK) p.splits = decode_splits(a, p.cache, windowed ? w : nullptr);
     return p;
 }
@@ -1866,11 +1888,12 @@ template <class A> void decode_fill(fa::DecodeArgs &d, const A *a, const CacheVi
     d.causal = a->causal != 0;
 }
 
-// The launch of all six forms; `ws_query`: the entry point's workspace query (a capped form: its windowed sibling's), for its message.  `capped`: a soft-capped form (always
-// windowed), its fa_softcap refused behind everything the windowed sibling refuses.
+// The launch of all eight forms; `ws_query`: the entry point's workspace query (a capped or sink form: its windowed sibling's), for its
+// message.  `capped`: a soft-capped form (always windowed), its fa_softcap refused behind everything the windowed sibling refuses;
+// `sunk`: a form with attention sinks (always windowed), its fa_sinks refused there likewise.
 template <class A>
 int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_query, void *stream, float *ms, bool capped = false,
-                  const fa_softcap *cap = nullptr) {
+                  const fa_softcap *cap = nullptr, bool sunk = false, const fa_sinks *sk = nullptr) {
     if (!a) return fail(FA_ERR_NULL, "null pointer argument");
     if (!a->q || !a->k || !a->v || !a->o) return fail(FA_ERR_NULL, "null tensor pointer (q, k, v and o are all needed)");
     if (!a->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to batch int32 lengths is needed");
@@ -1878,6 +1901,7 @@ int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_
     if (p.status != FA_OK) return p.status;
     if (a->batch == 0) {   // (nothing to do -- behind the cap's own rules, as in the packed form)
         if (capped && softcap_validate(cap) != FA_OK) return softcap_validate(cap);
+        if (sunk && sinks_validate(sk, a->n_heads, false, nullptr) != FA_OK) return sinks_validate(sk, a->n_heads, false, nullptr);
         if (ms) *ms = 0.0f;
         return FA_OK;
     }
@@ -1892,6 +1916,7 @@ int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_
     if (p.splits > 1 && ((uintptr_t)a->workspace & 15)) return fail(FA_ERR_ALIGN, "workspace must be 16-byte aligned (it holds the splits' fp32 partials)");
     if (windowed && (rc = cache_descale_alignment(c)) != FA_OK) return rc;
     if (capped && (rc = softcap_validate(cap)) != FA_OK) return rc;
+    if (sunk && (rc = sinks_validate(sk, a->n_heads, false, nullptr)) != FA_OK) return rc;
     DeviceState *dev = current_device(&rc);
     if (!dev) return rc;
     fa::DecodeFp8WindowArgs k;   // (the widest form: the other three's arguments are its members)
@@ -1909,8 +1934,11 @@ int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_
         ks8.cap_a = ks.cap_a;
         ks8.cap_inv_a = ks.cap_inv_a;
     }
+    const fa::DecodeSinksArgs kz = {kw, sunk ? sk->sinks : nullptr};
+    const fa::DecodeFp8SinksArgs kz8 = {k, kz.sinks};
     const hipStream_t s = (hipStream_t)stream;
     return enqueue_timed([&] {
+        if (sunk) return c.fp8 ? fa::decode_fp8_sinks_enqueue(kz8, a->dtype, s) : fa::decode_sinks_enqueue(kz, a->dtype, s);
         if (capped) return c.fp8 ? fa::decode_fp8_softcap_enqueue(ks8, a->dtype, s) : fa::decode_softcap_enqueue(ks, a->dtype, s);
         if (c.fp8) return windowed ? fa::decode_fp8_window_enqueue(k, a->dtype, s) : fa::decode_fp8_enqueue(k.f, a->dtype, s);
         return windowed ? fa::decode_window_enqueue(kw, a->dtype, s) : fa::decode_enqueue(k.f.d, a->dtype, s);
@@ -1968,6 +1996,28 @@ int fa_decode_fp8_softcap_num_splits(const fa_decode_fp8_args *a, const fa_windo
 }
 int fa_decode_fp8_softcap_launch(const fa_decode_fp8_args *a, const fa_window *w, const fa_softcap *cap, void *stream, float *ms) {
     return decode_launch(a, true, w, "fa_decode_fp8_window_workspace_bytes", stream, ms, true, cap);
+}
+
+// ... with attention sinks: the windowed forms with an fa_sinks behind the window.  The split count and the workspace are the windowed
+// entry's for the same arguments: no workspace query of their own, as for the capped decodes.
+int fa_decode_sinks_supported(const fa_decode_args *a, const fa_window *w, const fa_sinks *sinks) {
+    return decode_plan(a, true, w, false, nullptr, true, sinks).status == FA_OK;
+}
+int fa_decode_sinks_num_splits(const fa_decode_args *a, const fa_window *w, const fa_sinks *sinks) {
+    return plan_splits(decode_plan(a, true, w, false, nullptr, true, sinks));
+}
+int fa_decode_sinks_launch(const fa_decode_args *a, const fa_window *w, const fa_sinks *sinks, void *stream, float *ms) {
+    return decode_launch(a, true, w, "fa_decode_window_workspace_bytes", stream, ms, false, nullptr, true, sinks);
+}
+
+int fa_decode_fp8_sinks_supported(const fa_decode_fp8_args *a, const fa_window *w, const fa_sinks *sinks) {
+    return decode_plan(a, true, w, false, nullptr, true, sinks).status == FA_OK;
+}
+int fa_decode_fp8_sinks_num_splits(const fa_decode_fp8_args *a, const fa_window *w, const fa_sinks *sinks) {
+    return plan_splits(decode_plan(a, true, w, false, nullptr, true, sinks));
+}
+int fa_decode_fp8_sinks_launch(const fa_decode_fp8_args *a, const fa_window *w, const fa_sinks *sinks, void *stream, float *ms) {
+    return decode_launch(a, true, w, "fa_decode_fp8_window_workspace_bytes", stream, ms, false, nullptr, true, sinks);
 }
 
 // ---- the KV-cache append in front of a decode --------------------------------------------------------------------------------

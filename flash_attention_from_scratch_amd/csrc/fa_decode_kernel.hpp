@@ -58,6 +58,18 @@
 //  * fp8: a tanh between S and the exponent forbids folding k_descale into c, so it goes into cap_k = k_descale 2 log2(e) / A, one
 //    scalar per workgroup; the capped S is in the 16-bit form's units, scale and c are the 16-bit form's constants, and
 //    lse = m / sqrt(128) + log(l).  The combine kernel, the partial format, the merge, the fetch contract and lo_min are unchanged.
+//
+// What attention sinks change (DecodeSinksArgs / DecodeFp8SinksArgs: the windowed forms -- a window of (-1, -1) runs through them --
+// and one fp32 logit z = sinks[query head] that joins the softmax's denominator without a value vector; `if constexpr (SINK)`
+// marks the sites).  The loop, the partial format, the merge of the waves, the fetch contract and lo_min are
+// unchanged; the sink enters exactly once per row, whatever the split count:
+//  * num_splits == 1: wave 0's lane folds it into its row behind the merge, in natural units with ms = m * scale_e (fp8: scale_e
+//    carries k_descale, so z meets the dequantized logit): M = max(ms, z), a = exp(ms - M), l' = l a + exp(z - M),
+//    inv = v_descale a / l', lse = M + log l'.  z is loaded there, per lane, from its row's head; nothing is held across the loop.
+//    A row with l = 0 is selected out (o = 0, lse = z); where l > 0, m and with it M are finite, so no inf - inf is formed;
+//  * num_splits > 1: the split kernel writes the sink-free partials it writes today and fa_decode_combine_sinks_kernel takes the
+//    sink as one more member in front of the fixed-order sums: mx' = max(max_s lse_s, z), sum = sum_s exp(lse_s - mx') + exp(z - mx'),
+//    lse = mx' + log sum, o = sum_s exp(lse_s - lse) o_s in split order; mx' = -inf (no key, no sink): o = 0, lse = -inf.
 #pragma once
 #include <type_traits>
 
@@ -106,6 +118,16 @@ struct DecodeFp8SoftcapArgs {
     float cap_a, cap_inv_a;
 };
 
+// ... and attention sinks on the windowed forms: one fp32 logit per QUERY head (DEVICE), never read by the host
+struct DecodeSinksArgs {
+    DecodeWindowArgs w;
+    const float *sinks;   // (n_heads)
+};
+struct DecodeFp8SinksArgs {
+    DecodeFp8WindowArgs w;
+    const float *sinks;
+};
+
 namespace decode {
 constexpr int D = 128, UNIT = 32, TILE = 64, NWAVES = 4, THREADS = NWAVES * 64;
 constexpr int VROW = 288;              // bytes per key of the V image: 256 + 32, so the 8 keys a 32-lane half's transposed read
@@ -120,14 +142,20 @@ __host__ __device__ inline const DecodeArgs &common(const DecodeWindowArgs &a) {
 __host__ __device__ inline const DecodeArgs &common(const DecodeFp8WindowArgs &a) { return a.f.d; }
 __host__ __device__ inline const DecodeArgs &common(const DecodeSoftcapArgs &a) { return a.w.d; }
 __host__ __device__ inline const DecodeArgs &common(const DecodeFp8SoftcapArgs &a) { return a.w.f.d; }
+__host__ __device__ inline const DecodeArgs &common(const DecodeSinksArgs &a) { return a.w.d; }
+__host__ __device__ inline const DecodeArgs &common(const DecodeFp8SinksArgs &a) { return a.w.f.d; }
 // the fp8 forms' descales
 __host__ __device__ inline const DecodeFp8Args &fp8_part(const DecodeFp8Args &a) { return a; }
 __host__ __device__ inline const DecodeFp8Args &fp8_part(const DecodeFp8WindowArgs &a) { return a.f; }
 __host__ __device__ inline const DecodeFp8Args &fp8_part(const DecodeFp8SoftcapArgs &a) { return a.w.f; }
+__host__ __device__ inline const DecodeFp8Args &fp8_part(const DecodeFp8SinksArgs &a) { return a.w.f; }
 template <class ARGS> constexpr bool is_cap = std::is_same_v<ARGS, DecodeSoftcapArgs> || std::is_same_v<ARGS, DecodeFp8SoftcapArgs>;
+template <class ARGS> constexpr bool is_sink = std::is_same_v<ARGS, DecodeSinksArgs> || std::is_same_v<ARGS, DecodeFp8SinksArgs>;
 template <class ARGS>
-constexpr bool is_fp8 = std::is_same_v<ARGS, DecodeFp8Args> || std::is_same_v<ARGS, DecodeFp8WindowArgs> || std::is_same_v<ARGS, DecodeFp8SoftcapArgs>;
-template <class ARGS> constexpr bool is_window = std::is_same_v<ARGS, DecodeWindowArgs> || std::is_same_v<ARGS, DecodeFp8WindowArgs> || is_cap<ARGS>;
+constexpr bool is_fp8 = std::is_same_v<ARGS, DecodeFp8Args> || std::is_same_v<ARGS, DecodeFp8WindowArgs> ||
+                        std::is_same_v<ARGS, DecodeFp8SoftcapArgs> || std::is_same_v<ARGS, DecodeFp8SinksArgs>;
+template <class ARGS>
+constexpr bool is_window = std::is_same_v<ARGS, DecodeWindowArgs> || std::is_same_v<ARGS, DecodeFp8WindowArgs> || is_cap<ARGS> || is_sink<ARGS>;
 
 // (eight e4m3fn values as eight values of Q's type: cvt_fp8x8, fa_fwd_kernel.hpp)
 }  // namespace decode
@@ -137,7 +165,8 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
     using namespace decode;
-    constexpr bool FP8 = is_fp8<ARGS>, WINDOW = is_window<ARGS>, CAP = is_cap<ARGS>;
+    constexpr bool FP8 = is_fp8<ARGS>, WINDOW = is_window<ARGS>, CAP = is_cap<ARGS>, SINK = is_sink<ARGS>;
+    constexpr bool WIN_IN_W = CAP || SINK;   // the window is the member w's, not the arguments' own
     constexpr int KS = D / 32, DT16 = D / 16;
     constexpr int MERGE = NT * DT16 * 64 * 16;   // one wave's accumulators
     constexpr int MAIN = NWAVES * VBYTES > MERGE ? NWAVES * VBYTES : MERGE;
@@ -161,9 +190,9 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     [[maybe_unused]] int lo_min = 0;   // window: the lowest key a row of this workgroup sees (<= len - 1 when len > 0)
     int t0, t1;
     if constexpr (WINDOW) {
-        // (the capped forms' window is a member of a member, written out beside the windowed forms' line here and below: one more
-        // value or inlined call in front of it would renumber the blocks the windowed units' kept ISA names)
-        if constexpr (CAP) {
+        // (the capped and the sink forms' window is a member of a member, written out beside the windowed forms' line here and below:
+        // one more value or inlined call in front of it would renumber the blocks the windowed units' kept ISA names)
+        if constexpr (WIN_IN_W) {
             if (args.w.left >= 0) {
                 const int64_t lo = (int64_t)len - a.seqlen_q - args.w.left;
                 lo_min = lo > 0 ? (int)lo : 0;
@@ -196,7 +225,7 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
     [[maybe_unused]] int w_left = 0, w_right = 0;
     if constexpr (WINDOW) {   // unbounded, or beyond what any length reaches (the host: len <= 2^30 - 128; p >= -seqlen_q >= -64): all one
         constexpr int FAR = (1 << 30) + 64;
-        if constexpr (CAP) {
+        if constexpr (WIN_IN_W) {
             w_left = args.w.left < 0 || args.w.left > FAR ? FAR : args.w.left;
             w_right = args.w.right < 0 || args.w.right > FAR ? FAR : args.w.right;
         } else {
@@ -478,9 +507,21 @@ __global__ void __launch_bounds__(decode::THREADS) fa_decode_split_kernel(const 
         const int r = nt * 16 + li_e;
         if (r >= a.rows) continue;
         const bool any = l[nt] > 0.0f;
-        const float inv = any ? vd / l[nt] : 0.0f;
-        const float lse = any ? m[nt] * scale_e + __logf(l[nt]) : ninf;
+        float inv = any ? vd / l[nt] : 0.0f;
+        float lse = any ? m[nt] * scale_e + __logf(l[nt]) : ninf;
         const int qi = r / group_e, qh = kvh * group_e + r % group_e;
+        if constexpr (SINK) {
+            // one split: the row's sink joins here, once (more splits: the partials stay sink-free and the combine kernel adds it).
+            // Natural units against a common maximum, so that neither term overflows; a row without keys takes 0 for its m = -inf
+            // and is selected out, so no inf - inf is formed (where l > 0, m is finite and so is M)
+            if (nsp == 1) {
+                const float z = args.sinks[qh], ms = any ? m[nt] * scale_e : 0.0f;
+                const float M = fmaxf(ms, z);
+                const float al = __expf(ms - M), l_all = __builtin_fmaf(l[nt], al, __expf(z - M));
+                inv = any ? vd * al / l_all : 0.0f;
+                lse = any ? M + __logf(l_all) : z;
+            }
+        }
         if (nsp == 1) {
             uint16_t *op = a.o + (int64_t)b * a.o_bs + (int64_t)qi * a.o_ss + (int64_t)qh * a.o_hs + 4 * g_e;
 #pragma unroll
@@ -528,10 +569,38 @@ __global__ void __launch_bounds__(64) fa_decode_combine_kernel(const DecodeArgs 
     if (a.lse && threadIdx.x == 0) a.lse[((int64_t)b * a.n_heads + qh) * a.seqlen_q + qi] = lse;
 }
 
+// ... with the row's sink as one more member, in front of the fixed-order sums (the sink forms' partials are sink-free)
+template <int DT>
+__global__ void __launch_bounds__(64) fa_decode_combine_sinks_kernel(const DecodeArgs a, const float *const sinks) {
+    using E = Elem<DT>;
+    const int64_t row = blockIdx.x, n_rows = (int64_t)a.batch * a.n_kv_heads * a.rows;
+    const int r = (int)(row % a.rows), kvh = (int)((row / a.rows) % a.n_kv_heads), b = (int)(row / ((int64_t)a.rows * a.n_kv_heads));
+    const int qi = r / a.group, qh = kvh * a.group + r % a.group;
+    const float ninf = -__builtin_inff(), z = sinks[qh];
+    float mx = z;
+    for (int s = 0; s < a.num_splits; ++s) mx = fmaxf(mx, a.part_lse[s * n_rows + row]);
+    float lse = ninf, o0 = 0.0f, o1 = 0.0f;
+    if (mx != ninf) {   // (no key and no sink: o = 0, lse = -inf)
+        float sum = __expf(z - mx);
+        for (int s = 0; s < a.num_splits; ++s) sum += __expf(a.part_lse[s * n_rows + row] - mx);
+        lse = mx + __logf(sum);
+        for (int s = 0; s < a.num_splits; ++s) {
+            const float w = __expf(a.part_lse[s * n_rows + row] - lse);
+            const float2 v = *(const float2 *)(a.part_o + (s * n_rows + row) * decode::D + 2 * threadIdx.x);
+            o0 = __builtin_fmaf(w, v.x, o0);
+            o1 = __builtin_fmaf(w, v.y, o1);
+        }
+    }
+    uint16_t *op = a.o + (int64_t)b * a.o_bs + (int64_t)qi * a.o_ss + (int64_t)qh * a.o_hs;
+    *(unsigned *)(op + 2 * threadIdx.x) = E::pack2(o0, o1);
+    if (a.lse && threadIdx.x == 0) a.lse[((int64_t)b * a.n_heads + qh) * a.seqlen_q + qi] = lse;
+}
+
 // The enqueue of one decode in either form: the split kernel and, for num_splits > 1, the combine kernel (the partial format
 // is the same, so the fp8 form launches it on its DecodeArgs part) on stream s.  Instantiated by fa_decode.hip (DecodeArgs),
 // fa_decode_fp8.hip (DecodeFp8Args), fa_decode_window.hip (DecodeWindowArgs), fa_decode_fp8_window.hip (DecodeFp8WindowArgs),
-// fa_decode_softcap.hip (DecodeSoftcapArgs) and fa_decode_fp8_softcap.hip (DecodeFp8SoftcapArgs), which hold the kernels.
+// fa_decode_softcap.hip (DecodeSoftcapArgs), fa_decode_fp8_softcap.hip (DecodeFp8SoftcapArgs), fa_decode_sinks.hip (DecodeSinksArgs)
+// and fa_decode_fp8_sinks.hip (DecodeFp8SinksArgs), which hold the kernels.  The sink forms combine with the sink's kernel.
 template <class ARGS, int DT, int NT, bool PAGED>
 static hipError_t decode_enqueue_t(const ARGS &args, hipStream_t s) {
     const DecodeArgs &a = decode::common(args);
@@ -539,6 +608,12 @@ static hipError_t decode_enqueue_t(const ARGS &args, hipStream_t s) {
     const hipError_t rc = hipLaunchKernel((const void *)&fa_decode_split_kernel<ARGS, DT, NT, PAGED>,
                                           dim3((unsigned)((int64_t)a.batch * a.n_kv_heads * a.num_splits)), dim3(decode::THREADS), params, 0, s);
     if (rc != hipSuccess || a.num_splits == 1) return rc;
+    if constexpr (decode::is_sink<ARGS>) {
+        const float *sinks = args.sinks;
+        void *sparams[] = {(void *)&a, (void *)&sinks};
+        return hipLaunchKernel((const void *)&fa_decode_combine_sinks_kernel<DT>, dim3((unsigned)((int64_t)a.batch * a.n_kv_heads * a.rows)),
+                               dim3(64), sparams, 0, s);
+    }
     return hipLaunchKernel((const void *)&fa_decode_combine_kernel<DT>, dim3((unsigned)((int64_t)a.batch * a.n_kv_heads * a.rows)), dim3(64),
                            cparams, 0, s);
 }
@@ -565,5 +640,7 @@ hipError_t decode_window_enqueue(const DecodeWindowArgs &a, int dtype, hipStream
 hipError_t decode_fp8_window_enqueue(const DecodeFp8WindowArgs &a, int dtype, hipStream_t s);   // fa_decode_fp8_window.hip
 hipError_t decode_softcap_enqueue(const DecodeSoftcapArgs &a, int dtype, hipStream_t s);          // fa_decode_softcap.hip
 hipError_t decode_fp8_softcap_enqueue(const DecodeFp8SoftcapArgs &a, int dtype, hipStream_t s);   // fa_decode_fp8_softcap.hip
+hipError_t decode_sinks_enqueue(const DecodeSinksArgs &a, int dtype, hipStream_t s);          // fa_decode_sinks.hip
+hipError_t decode_fp8_sinks_enqueue(const DecodeFp8SinksArgs &a, int dtype, hipStream_t s);   // fa_decode_fp8_sinks.hip
 
 }  // namespace fa

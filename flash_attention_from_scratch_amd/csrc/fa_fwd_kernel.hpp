@@ -547,15 +547,26 @@ typedef void (*kernel_fn_varlen_kvcache_fp8_softcap)(const KernelArgsVarlenKVCac
 // fa_fwd_kernel_varlen_window: the windowed text (a window of (-1, -1) runs through it) whose loop is untouched.  Two sites differ:
 // the n_kv == 0 exit writes lse = z, and the end of an item folds the sink into l (sink_end below: the lse line and the
 // epilogue's 1 / l).  A row that saw no key (l = 0) gives o = 0 and lse = z exactly.  sinks[h] is a workgroup-uniform load made
-// at the end, not held across the loop.  Built for packed keys only.
+// at the end, not held across the loop.
+// ... and on both cache prefills (fa_fwd_launch_varlen_kvcache_sinks, fa_fwd_launch_varlen_kvcache_fp8_sinks): extra 3
+// on key side 1 or 2 gives fa_fwd_kernel_varlen_kvcache_sinks / fa_fwd_kernel_varlen_kvcache_fp8_sinks INSTEAD of the windowed cache
+// kernel, the same two sites.  fp8 cache: m is a raw logit and c carries k_descale, so sink_end's m c is that form's own
+// product and z meets the dequantized logit; v_descale scales its 1 / l' as it scales the fp8 epilogue's 1 / l.
 template <class W> struct Sunk {
     W w;
     const float *sinks;   // (n_heads) fp32 (DEVICE)
 };
 typedef Sunk<KernelArgsVarlenWindow> KernelArgsVarlenSinks;
+typedef Sunk<KernelArgsVarlenKVCacheWindow> KernelArgsVarlenKVCacheSinks;
+typedef Sunk<KernelArgsVarlenKVCacheFp8Window> KernelArgsVarlenKVCacheFp8Sinks;
 typedef void (*kernel_fn_varlen_sinks)(const KernelArgsVarlenSinks);
+typedef void (*kernel_fn_varlen_kvcache_sinks)(const KernelArgsVarlenKVCacheSinks);
+typedef void (*kernel_fn_varlen_kvcache_fp8_sinks)(const KernelArgsVarlenKVCacheFp8Sinks);
 static_assert(std::is_standard_layout<KernelArgsVarlenSinks>::value && offsetof(KernelArgsVarlenSinks, w) == 0,
               "packed: sinks > window > QK");
+static_assert(std::is_standard_layout<KernelArgsVarlenKVCacheSinks>::value && offsetof(KernelArgsVarlenKVCacheSinks, w) == 0 &&
+                  std::is_standard_layout<KernelArgsVarlenKVCacheFp8Sinks>::value && offsetof(KernelArgsVarlenKVCacheFp8Sinks, w) == 0,
+              "cache: sinks > window > (fp8 >) cache");
 // Every wrapper's first member sits at offset 0, so the widest struct of a key side starts with the arguments of each narrower form:
 // the host fills that one struct and passes the address of the member the chosen kernel takes (fa_capi.hip, fwd_launch_varlen).
 // (KernelArgsVarlenSoftcap repeats Softcapped<KernelArgsVarlenWindow> field for field; it stays a struct of its own because its
@@ -573,7 +584,7 @@ static_assert(offsetof(KernelArgsVarlenKVCacheFp8Softcap, w) == 0 && offsetof(Ke
 // The form a translation unit builds is named once, by two numbers on its command line (fa_inst_varlen.hip, csrc/Makefile):
 //   FA_VARLEN_KEYS   0 packed keys (cu_seqlens_k) | 1 a KV cache | 2 an fp8 KV cache
 //   FA_VARLEN_EXTRA  0 nothing | 1 a sliding window | 2 a sliding window and logit soft-capping |
-//                    3 a sliding window and attention sinks (packed keys only)
+//                    3 a sliding window and attention sinks
 // The FA_KERNEL_VARLEN_* macros of the body's arms, the kernel's name (FA_VARLEN_NAME(fa_fwd_kernel_varlen, )) and its argument
 // follow from them here: a new key side or extra is one arm below, one in front of the kernel's body, and its arms in the body.
 #ifdef FA_VARLEN_KEYS
@@ -609,9 +620,6 @@ static_assert(offsetof(KernelArgsVarlenKVCacheFp8Softcap, w) == 0 && offsetof(Ke
 #define FA_KERNEL_VARLEN_SOFTCAP
 #define FA_VARLEN_EXTRA_SFX _softcap
 #elif FA_VARLEN_EXTRA == 3
-#if FA_VARLEN_KEYS != 0
-#error "FA_VARLEN_EXTRA 3 (attention sinks) is built for packed keys only (FA_VARLEN_KEYS 0)"
-#endif
 #define FA_KERNEL_VARLEN_WINDOW
 #define FA_KERNEL_VARLEN_SINKS
 #define FA_VARLEN_EXTRA_SFX _sinks
@@ -1674,6 +1682,10 @@ fa_fwd_kernel(const KernelArgs args) {
     // factor is exp2(0) = 1, the sink's term 0: the windowed kernel's values.
     const float sink_z = sa.sinks[h];   // (workgroup-uniform, read here and not held across the loop)
     auto sink_end = [&](float l_row, float m_row, float &scale, float &lse_row) {
+        // (m c: the form's own product -- against an fp8 cache m is a raw logit and c carries k_descale.  The plain product in every
+        // form, not the lse line's FA_LSE_M_TIMES_C: hipcc takes M from the rounded products and contracts each product again into
+        // its subtraction, fma(m, c, -M), with c a constant and with c a run-time value alike, so a power-of-two k_descale gives the
+        // 16-bit form's bits; a product rounded before the subtraction would differ from them in the last bit)
         const float mc = m_row * c, zc = sink_z * 1.4426950408889634074f;
         const float M = fmaxf(mc, zc);
         const float a = __builtin_amdgcn_exp2f(mc - M);
@@ -1751,6 +1763,10 @@ fa_fwd_kernel(const KernelArgs args) {
 #ifdef FA_KERNEL_VARLEN_SINKS
             float inv, lse_unused;   // (a row that saw no key: o = 0)
             sink_end(pair_sum(l[qt]), m[qt], inv, lse_unused);
+#ifdef FA_KERNEL_VARLEN_KVCACHE_FP8
+            // ... with v_descale folded in (read here, not held across the loop)
+            inv *= fa8.v_descale ? fa8.v_descale[(int64_t)b * fa8.ds_bs + h / va.group] : 1.0f;
+#endif
 #elif defined(FA_KERNEL_VARLEN)
             const float l_all = pair_sum(l[qt]);
 #ifdef FA_KERNEL_VARLEN_KVCACHE_FP8

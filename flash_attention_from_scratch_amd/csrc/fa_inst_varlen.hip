@@ -3,7 +3,7 @@
 //   keys   0 packed keys (fa_fwd_launch_varlen, fa_fwd_launch_varlen_qk) | 1 a KV cache, contiguous or paged (..._kvcache) |
 //          2 an fp8 (e4m3fn) KV cache (..._kvcache_fp8)
 //   extra  0 nothing | 1 a sliding window (..._window) | 2 a sliding window and logit soft-capping (..._softcap) |
-//          3 a sliding window and attention sinks (fa_fwd_launch_varlen_qk_sinks; packed keys only)
+//          3 a sliding window and attention sinks (..._sinks)
 // The two numbers make fa_fwd_kernel.hpp define that form's kernel, fa_fwd_kernel_varlen<_kvcache|_kvcache_fp8><_window|_softcap|_sinks>,
 // from the body of fa_fwd_kernel (which this unit then does not have): the masked 32-rows-per-wave kernel at the
 // (B_r 128, B_c 64, 4 warps) + buffer shape, with and without the first-block skip -- the twins of the two masked entries of

@@ -207,6 +207,34 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
                                                           k_descale=k_descale, v_descale=v_descale, window_size=window_size, softcap=softcap)
 
 
+def forward_kvcache_sinks(q, k_cache, v_cache, cache_seqlens, sinks, block_table=None, causal=False, return_lse=False,
+                          max_seqlen_k=None, num_splits=0, timed=False, k_descale=None, v_descale=None, window_size=(-1, -1), k=None,
+                          v=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, advance_seqlens=False):
+    """forward_kvcache with learned attention sinks (gpt-oss's `sinks`): the softmax forward_varlen_sinks trains
+    under, so that the trained model can be served.  Every other argument is forward_kvcache's, with its meaning, checks and
+    defaults -- both cache types, paged and contiguous, the window, the fused append, graph capture.  sinks, required: a contiguous
+    fp32 tensor of shape (n_heads,) on q's device, one logit z per QUERY head that joins the softmax's denominator and has no value
+    vector; the host never reads it.  A row that sees no key gives o = 0, lse = z; z = -inf means no sink for that head.  The sink
+    enters once whatever num_splits is.  No softcap, and no "off": without sinks, call forward_kvcache.  A bad window_size is a
+    ValueError, a bad sinks a RuntimeError."""
+    return flash_attention_kernels.forward_kvcache_sinks(q, k_cache, v_cache, cache_seqlens, sinks, block_table=block_table, causal=causal,
+                                                         return_lse=return_lse, max_seqlen_k=max_seqlen_k, num_splits=num_splits,
+                                                         timed=timed, k_descale=k_descale, v_descale=v_descale, window_size=window_size,
+                                                         k=k, v=v, rotary_cos=rotary_cos, rotary_sin=rotary_sin,
+                                                         rotary_interleaved=rotary_interleaved, advance_seqlens=advance_seqlens)
+
+
+def forward_varlen_kvcache_sinks(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, sinks, block_table=None, causal=False,
+                                 max_seqlen_k=None, timed=False, k_descale=None, v_descale=None, *, window_size=(-1, -1)):
+    """forward_varlen_kvcache with learned attention sinks: forward_kvcache_sinks's sinks on the cache prefill, every
+    other argument forward_varlen_kvcache's (no softcap).  -> (o, lse[, ms]); with a 16-bit cache bit for bit
+    forward_varlen_sinks(cu_seqlens_k=, window_size=) on the same keys packed.  A row that sees no key gives o = 0 and lse = z."""
+    return flash_attention_kernels.forward_varlen_kvcache_sinks(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, sinks,
+                                                                block_table=block_table, causal=causal, max_seqlen_k=max_seqlen_k,
+                                                                timed=timed, k_descale=k_descale, v_descale=v_descale,
+                                                                window_size=window_size)
+
+
 def append_kvcache(k_cache, v_cache, k, v, cache_seqlens, block_table=None, q=None, rotary_cos=None, rotary_sin=None,
                    rotary_interleaved=False, causal=False, k_descale=None, v_descale=None, seqlens_out=None):
     """The step in front of a decode, one HIP kernel: write the new rows k, v (batch, seqlen_new, n_kv_heads, 128)

@@ -391,18 +391,18 @@ def forward_varlen_sinks(q, k, v, cu_seqlens, max_seqlen, sinks, causal=False, t
     return _forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, None, sinks)
 
 
-def _check_sinks(sinks, q, name="sinks"):
-    """sinks as forward_varlen_sinks and backward_varlen_sinks take it: a contiguous fp32 tensor of shape (n_heads,) on q's device
-    (checked in front of _check_varlen, so against q only where q is a packed tensor at all)"""
+def _check_sinks(sinks, q, name="sinks", q_dim=3):
+    """sinks as the calls with sinks take it: a contiguous fp32 tensor of shape (n_heads,) on q's device (checked in front of the
+    sibling's own checks, so against q only where q is a tensor of the call's shape at all: q_dim 3 packed, 4 forward_kvcache_sinks's)"""
     if not isinstance(sinks, torch.Tensor):
         raise RuntimeError(f"{name} must be a tensor: fp32, contiguous, of shape (n_heads,), on q's device (got {type(sinks).__name__})")
     if sinks.dtype != torch.float32:
         raise RuntimeError(f"{name} must be fp32 (got {sinks.dtype}; attention_varlen_sinks converts for you)")
     if sinks.dim() != 1 or not sinks.is_contiguous():
         raise RuntimeError(f"{name} must be a contiguous tensor of shape (n_heads,) (got shape {tuple(sinks.shape)}, strides {sinks.stride()})")
-    if isinstance(q, torch.Tensor) and q.dim() == 3:
-        if sinks.shape[0] != q.shape[1]:
-            raise RuntimeError(f"{name} must have shape (n_heads,) = ({q.shape[1]},): one logit per query head (got {tuple(sinks.shape)})")
+    if isinstance(q, torch.Tensor) and q.dim() == q_dim:
+        if sinks.shape[0] != q.shape[q_dim - 2]:
+            raise RuntimeError(f"{name} must have shape (n_heads,) = ({q.shape[q_dim - 2]},): one logit per query head (got {tuple(sinks.shape)})")
         if sinks.device != q.device:
             raise RuntimeError(f"{name} must be on q's device ({q.device}, got {sinks.device})")
 
@@ -846,7 +846,7 @@ def forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table=None, causal
     max(0, p - left) .. min(len - 1, p + right); causal means right = 0.  (-1, -1) takes the entry points above unchanged, anything
     else fa_decode_window_launch / fa_decode_fp8_window_launch, which fetch nothing below the lowest key a row sees.  With k / v
     the window applies to the lengths after the append.  Bad values are a ValueError.
-    (Logit soft-capping: forward_kvcache_softcap, the same call with a softcap.)"""
+    (Logit soft-capping: forward_kvcache_softcap, the same call with a softcap.  Attention sinks: forward_kvcache_sinks.)"""
     return _forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table, causal, return_lse, max_seqlen_k, num_splits, timed, k_descale,
                             v_descale, _window(window_size, causal), k, v, rotary_cos, rotary_sin, rotary_interleaved, advance_seqlens, None)
 
@@ -866,9 +866,29 @@ def forward_kvcache_softcap(q, k_cache, v_cache, cache_seqlens, softcap, block_t
                             v_descale, window, k, v, rotary_cos, rotary_sin, rotary_interleaved, advance_seqlens, _softcap(softcap))
 
 
+def forward_kvcache_sinks(q, k_cache, v_cache, cache_seqlens, sinks, block_table=None, causal=False, return_lse=False,
+                          max_seqlen_k=None, num_splits=0, timed=False, k_descale=None, v_descale=None, window_size=(-1, -1), k=None,
+                          v=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, advance_seqlens=False):
+    """forward_kvcache with learned attention sinks (fa_decode_sinks_launch, fa_decode_fp8_sinks_launch for an fp8 cache), the softmax
+    forward_varlen_sinks trains under: every other argument is forward_kvcache's, with its meaning, checks and defaults.  sinks,
+    required: a contiguous fp32 tensor of shape (n_heads,) on q's device, one logit z per QUERY head (under grouped-query attention
+    too) that joins the softmax's denominator and has no value vector: lse = log(exp(z) + sum_j exp(s_j)), o = sum_j exp(s_j - lse)
+    v_j over the keys the row sees; with an fp8 cache z meets the dequantized logit and v_descale still scales o.  A row that sees no
+    key gives o = 0, lse = z; z = -inf means no sink for that head (forward_kvcache's o and lse).  The host never reads sinks, so a
+    captured graph sees them rewritten in place.  The sink enters a row once whatever num_splits is; the split count and the
+    workspace are the windowed entry's.  With k / v the append runs first, unchanged.  No softcap here, and no "off": without sinks,
+    call forward_kvcache.  A bad window_size is a ValueError before any tensor is looked at; a bad sinks a RuntimeError before the
+    library is loaded."""
+    window = _window(window_size, causal)
+    _check_sinks(sinks, q, q_dim=4)
+    return _forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table, causal, return_lse, max_seqlen_k, num_splits, timed, k_descale,
+                            v_descale, window, k, v, rotary_cos, rotary_sin, rotary_interleaved, advance_seqlens, None, sinks)
+
+
 def _forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table, causal, return_lse, max_seqlen_k, num_splits, timed, k_descale,
-                     v_descale, window, k, v, rotary_cos, rotary_sin, rotary_interleaved, advance_seqlens, cap):
-    """The one body of forward_kvcache (cap None) and forward_kvcache_softcap (cap a float, or None for 0); window: _window's."""
+                     v_descale, window, k, v, rotary_cos, rotary_sin, rotary_interleaved, advance_seqlens, cap, sinks=None):
+    """The one body of forward_kvcache (cap None), forward_kvcache_softcap (cap a float, or None for 0) and forward_kvcache_sinks
+    (sinks a checked tensor, cap None); window: _window's."""
     if k is not None or v is not None or rotary_cos is not None or rotary_sin is not None or advance_seqlens:
         if k is None or v is None:
             raise RuntimeError("k and v come together; rotary_cos / rotary_sin and advance_seqlens need them (the append is what they act on)")
@@ -890,11 +910,13 @@ def _forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table, causal, re
     lse = torch.empty((batch, n_heads, seqlen_q), dtype=torch.float32, device=q.device) if return_lse else None
     args.o, args.lse = o.data_ptr(), (lse.data_ptr() if return_lse else None)
     lib = _capi.load()
-    if cap is not None:   # (the capped entry points always take a window: (-1, -1) is none)
-        w, sc = _capi.make_window(*(window or (-1, -1))), _capi.make_softcap(cap)
+    if cap is not None or sinks is not None:   # (the capped and the sink entry points always take a window: (-1, -1) is none)
+        w = _capi.make_window(*(window or (-1, -1)))
+        sc = _capi.make_softcap(cap) if cap is not None else _capi.make_sinks(sinks.data_ptr(), n_heads)
         # (no workspace query of their own: the windowed entry's bytes for the same arguments are what the launch asks for)
-        sized, run = ((lib.fa_decode_fp8_window_workspace_bytes, lib.fa_decode_fp8_softcap_launch) if fp8 else
-                      (lib.fa_decode_window_workspace_bytes, lib.fa_decode_softcap_launch))
+        form = "softcap" if cap is not None else "sinks"
+        sized, run = ((lib.fa_decode_fp8_window_workspace_bytes, getattr(lib, f"fa_decode_fp8_{form}_launch")) if fp8 else
+                      (lib.fa_decode_window_workspace_bytes, getattr(lib, f"fa_decode_{form}_launch")))
         workspace_bytes = lambda a: sized(a, ctypes.byref(w))                                           # noqa: E731
         launch = lambda a, stream, ms: run(a, ctypes.byref(w), ctypes.byref(sc), stream, ms)            # noqa: E731
     elif window is None:
@@ -918,6 +940,21 @@ def _forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table, causal, re
     if timed:
         out = out + (float(ms.value),)
     return out[0] if len(out) == 1 else out
+
+
+def forward_varlen_kvcache_sinks(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, sinks, block_table=None, causal=False,
+                                 max_seqlen_k=None, timed=False, k_descale=None, v_descale=None, *, window_size=(-1, -1)):
+    """forward_varlen_kvcache with learned attention sinks (fa_fwd_launch_varlen_kvcache_sinks, .._fp8_sinks for an fp8 cache): every
+    other argument is forward_varlen_kvcache's, with its meaning, checks and defaults.  sinks, required: forward_kvcache_sinks's -- a
+    contiguous fp32 tensor of shape (n_heads,) on q's device, never read by the host; row r of head h gets lse = log(exp(sinks[h]) +
+    sum_j exp(s_j)) and o = sum_j exp(s_j - lse) v_j over the keys it sees (an fp8 cache: the dequantized logits, and v_descale still
+    scales o), a row that sees no key o = 0, lse = sinks[h]; -inf is "no sink".  On a 16-bit cache o and lse are
+    forward_varlen_sinks(cu_seqlens_k=)'s bits on the gathered keys.  No softcap here, and no "off".  -> (o, lse[, ms]).  A bad
+    window_size is a ValueError before any tensor is looked at; a bad sinks a RuntimeError before the library is loaded."""
+    window = _window(window_size, causal)
+    _check_sinks(sinks, q)
+    return _forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, max_seqlen_k, timed,
+                                   k_descale, v_descale, window, None, sinks)
 
 
 def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table=None, causal=False,
@@ -944,9 +981,17 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
     softcap * tanh(s / softcap), s = q . k / sqrt(128) on the dequantized key; masked keys stay -inf, lse is the log-sum-exp of the
     capped logits.  0 is off: the call above, the same entry points and bits.  Anything else goes through
     fa_fwd_launch_varlen_kvcache_softcap / fa_fwd_launch_varlen_kvcache_fp8_softcap with the window, (-1, -1) included.  A bad
-    window_size is reported first, then a bad softcap."""
+    window_size is reported first, then a bad softcap.
+    (Attention sinks: forward_varlen_kvcache_sinks.)"""
     window = _window(window_size, causal)
-    cap = _softcap(softcap)
+    return _forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, max_seqlen_k, timed,
+                                   k_descale, v_descale, window, _softcap(softcap), None)
+
+
+def _forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, max_seqlen_k, timed, k_descale,
+                            v_descale, window, cap, sinks):
+    """The one body of forward_varlen_kvcache (window: _window's, cap: _softcap's, sinks None) and forward_varlen_kvcache_sinks (sinks a
+    checked tensor, cap None)"""
     tensors = [(q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cu_seqlens_q, "cu_seqlens_q"), (cache_seqlens, "cache_seqlens")]
     if block_table is not None:
         tensors.append((block_table, "block_table"))
@@ -1005,13 +1050,16 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
         ms = ctypes.c_float(0.0)
         opts = _capi.make_opts(causal=causal, ms=ms if timed else None)
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        # (a window goes in front of opts, and picks the entry point's _window form; a cap behind it picks the _softcap form, which
-        # always takes a window: (-1, -1) is none)
+        # (a window goes in front of opts, and picks the entry point's _window form; a cap or the sinks behind it pick the _softcap or
+        # the _sinks form, which always take a window: (-1, -1) is none)
         form = "" if window is None else "_window"
         w = [ctypes.byref(_capi.make_window(*window))] if window is not None else []
         if cap is not None:
             form = "_softcap"
             w = [ctypes.byref(_capi.make_window(*(window or (-1, -1)))), ctypes.byref(_capi.make_softcap(cap))]
+        if sinks is not None:
+            form = "_sinks"
+            w = [ctypes.byref(_capi.make_window(*(window or (-1, -1)))), ctypes.byref(_capi.make_sinks(sinks.data_ptr(), n_heads))]
         tail = w + [ctypes.byref(opts), ctypes.c_void_p(lse.data_ptr()), stream]
         if fp8:
             sc = _capi.make_kvcache_fp8_scales(k_descale=k_descale.data_ptr(), v_descale=v_descale.data_ptr(),

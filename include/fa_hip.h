@@ -904,6 +904,43 @@ int fa_decode_fp8_softcap_launch(const fa_decode_fp8_args *args, const fa_window
                                  float *ms);
 
 /*
+ * Attention sinks on the inference path: the cache prefill and the decode, 16-bit and fp8 cache -- the softmax a
+ * model trained through fa_fwd_launch_varlen_qk_sinks must be served under.  The definition above, under the call's lengths,
+ * bottom-right causal rule and window exactly as in the windowed sibling: with z = sinks[h] (fp32, one per QUERY head under
+ * grouped-query attention too, on the device, never read by the host) and s_j the logits of the keys the row sees,
+ *     lse = log(exp(z) + sum_j exp(s_j)),     o = sum_j exp(s_j - lse) v_j.
+ * A row that sees no key gives o = 0, lse = z.  z = -inf: no sink for that head, o and lse are the windowed sibling's (a dead
+ * row's lse = -inf), no NaN.  z far above or below every logit overflows nothing; z = +inf and NaN are unspecified.  fp8 cache:
+ * z is compared with the DEQUANTIZED logit, and v_descale still scales o.  Not combined with soft-capping.
+ *
+ * Every entry takes the arguments of its windowed sibling (fa_fwd_launch_varlen_kvcache_window, .._fp8_window, fa_decode_window_*,
+ * fa_decode_fp8_window_*), a window included -- (-1, -1) is legal there and means none -- and an fa_sinks behind it.  Kernels of
+ * their own: the sibling's fetch contract, tile ranges, grids and partial format.  The sink enters a row exactly once whatever the
+ * split count: with one split in the split kernel's epilogue, else in a combine kernel of its own, the partials staying sink-free.
+ * The decode's split count and workspace are the windowed entry's for the same arguments, so there is no workspace query of their
+ * own: fa_decode_window_workspace_bytes(args, window) / fa_decode_fp8_window_workspace_bytes(args, window) size the launch.
+ * Deterministic for a given num_splits, no atomics, graph-capturable.
+ *
+ * Refused before any HIP call, in this order: what the windowed sibling refuses, with its status and message; then a null fa_sinks
+ * or fa_sinks.sinks (FA_ERR_NULL); then a struct_size below sizeof(fa_sinks), or n_heads that is not the call's (FA_ERR_SHAPE).
+ * This level has no "off": without sinks, call the windowed sibling.
+ */
+int fa_fwd_varlen_kvcache_sinks_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_kvcache_sinks(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                       const fa_kvcache_layout *cache, const fa_window *window, const fa_sinks *sinks,
+                                       const fa_fwd_opts *opts, float *lse, void *stream);
+int fa_fwd_varlen_kvcache_fp8_sinks_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_kvcache_fp8_sinks(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                           const fa_kvcache_layout *cache, const fa_kvcache_fp8_scales *scales, const fa_window *window,
+                                           const fa_sinks *sinks, const fa_fwd_opts *opts, float *lse, void *stream);
+int fa_decode_sinks_supported(const fa_decode_args *args, const fa_window *window, const fa_sinks *sinks);
+int fa_decode_sinks_num_splits(const fa_decode_args *args, const fa_window *window, const fa_sinks *sinks);
+int fa_decode_sinks_launch(const fa_decode_args *args, const fa_window *window, const fa_sinks *sinks, void *stream, float *ms);
+int fa_decode_fp8_sinks_supported(const fa_decode_fp8_args *args, const fa_window *window, const fa_sinks *sinks);
+int fa_decode_fp8_sinks_num_splits(const fa_decode_fp8_args *args, const fa_window *window, const fa_sinks *sinks);
+int fa_decode_fp8_sinks_launch(const fa_decode_fp8_args *args, const fa_window *window, const fa_sinks *sinks, void *stream, float *ms);
+
+/*
  * The step in front of a decode: append seqlen_new new K / V rows per batch entry to the cache IN PLACE, at the positions the
  * device-side lengths name, optionally rotate the new keys and the query (rotary embedding), quantize for an fp8 cache, and
  * advance the lengths.  One kernel on `stream`; the host reads none of the device arrays, so the launch is asynchronous and
