@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_varlen_kvcache_fp8_sinks_supported", "fa_fwd_launch_varlen_kvcache_fp8_sinks",
     "fa_decode_sinks_supported", "fa_decode_sinks_num_splits", "fa_decode_sinks_launch",
     "fa_decode_fp8_sinks_supported", "fa_decode_fp8_sinks_num_splits", "fa_decode_fp8_sinks_launch",
+    "fa_decode_d64_supported", "fa_decode_d64_num_splits", "fa_decode_d64_workspace_bytes", "fa_decode_d64_launch",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -491,6 +492,10 @@ def load():
             for suffix in ("supported", "num_splits", "launch"):   # (sized by the windowed sibling's workspace query)
                 fn, sibling = getattr(lib, f"{name}_{form}_{suffix}"), getattr(lib, f"{name}_window_{suffix}")
                 fn.restype, fn.argtypes = sibling.restype, sibling.argtypes[:2] + [ctypes.POINTER(extra)] + sibling.argtypes[2:]
+    # the d_head = 64 decode: the windowed entry's arguments with an fa_sinks (null = none) behind the fa_window, its own workspace query
+    for suffix in ("supported", "num_splits", "workspace_bytes", "launch"):
+        fn, sibling = getattr(lib, f"fa_decode_d64_{suffix}"), getattr(lib, f"fa_decode_window_{suffix}")
+        fn.restype, fn.argtypes = sibling.restype, sibling.argtypes[:2] + [ctypes.POINTER(FaSinks)] + sibling.argtypes[2:]
     lib.fa_kvcache_append_launch.restype = ctypes.c_int
     lib.fa_kvcache_append_launch.argtypes = [ctypes.POINTER(FaKvcacheAppendArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p

@@ -21,6 +21,7 @@
 #include "fa_bwd_gqa.hpp"
 #include "fa_bwd_varlen.hpp"
 #include "fa_decode_kernel.hpp"
+#include "fa_decode64_kernel.hpp"
 #include "fa_kvcache_append_kernel.hpp"
 #include "fa_registry.hpp"
 
@@ -1008,6 +1009,7 @@ struct CacheView {
     int64_t entries = 0, n_kv_heads = 0;       // entries: batch, or the prefill's n_seqs
     int64_t kv_bs = 0, kv_ss = 0, kv_hs = 0;   // elements (an fp8 cache: bytes)
     bool fp8 = false;
+    int64_t d_head = 128;                      // decode at 64 (fa_decode_d64_*) says so; what is sized by it reads it here
     const float *k_descale = nullptr, *v_descale = nullptr;
     int64_t descale_bs = 0;
     const char *words_4b = "";   // the path's name for the pointers cache_alignment checks
@@ -1751,6 +1753,7 @@ int fa_bwd_launch_varlen_qk_sinks(const fa_bwd_varlen_qk_args *a, const fa_windo
 // fa_decode_args and fa_decode_fp8_args carry the same members under the same names (the fp8 struct adds its encoding and
 // descales), so one text over either struct serves the twenty-eight entry points: a planner (validate, then the split count) for the
 // twenty queries and one launch body for the eight launches (the soft-capped and the sink forms: four queries, two launches each).  What only one struct has sits in the two decode_struct_rules.
+// The four d_head = 64 entry points (fa_decode_d64_*) run through the same planner and launch body with the head dimension as a parameter.
 namespace {
 extern "C++" {   // (as for the cache's rules above; the two overloads need it as well)
 constexpr int64_t kDecodeMaxRows = 64, kDecodeWantWgs = 256, kDecodeKeysPerSplit = 256, kDecodeMaxSplits = 128, kDecodeMaxForced = 1024;
@@ -1779,12 +1782,16 @@ struct DecodePlan {
 int plan_splits(const DecodePlan &p) { return p.status != FA_OK ? p.status : (int)p.splits; }
 
 // everything but the pointers' values: dtype, kernel, sizes, strides -- in the order of the statuses' numbers; fills `c`
-template <class A> int decode_validate(const A *a, CacheView &c) {
+template <class A> int decode_validate(const A *a, CacheView &c, int64_t d_head = 128) {
     if (!a) return fail(FA_ERR_NULL, "null pointer argument");
+    c.d_head = d_head;
     int rc = decode_struct_rules(a, c);
     if (rc != FA_OK) return rc;
     if (a->dtype != FA_FP16 && a->dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
-    if (a->d_head != 128) return fail(FA_ERR_SHAPE, "decode supports d_head = 128 only (got %lld)", (long long)a->d_head);
+    if (a->d_head != d_head)
+        return fail(FA_ERR_SHAPE, d_head == 128 ? "decode supports d_head = 128 only (got %lld)"
+                                                : "fa_decode_d64 serves d_head = 64 only (got %lld; 128: fa_decode_sinks_launch and its siblings)",
+                    (long long)a->d_head);
     if (a->batch < 0 || a->seqlen_q <= 0 || a->n_heads <= 0) return fail(FA_ERR_SHAPE, "batch must not be negative, seqlen_q and n_heads must be positive");
     if (a->batch > INT32_MAX / 2 || a->n_heads > INT32_MAX / 2) return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
     if (a->n_kv_heads < 1 || a->n_kv_heads > a->n_heads || a->n_heads % a->n_kv_heads != 0)
@@ -1829,12 +1836,12 @@ template <class A> int64_t decode_splits(const A *a, const CacheView &c, const f
 // The planner of every decode entry point: the arguments (either struct) and, for a window form, its fa_window (null is refused
 // there) -> status, split count and the cache as validated.  `capped`: a soft-capped form, its fa_softcap refused behind the
 // window's rules; the cap does not enter the split rule.  `sunk`: a form with attention sinks, its fa_sinks refused in the same
-// place; the sinks do not enter the split rule either.
+// place; the sinks do not enter the split rule either.  `d_head`: 128, or 64 for fa_decode_d64_* (windowed always, sunk where it has sinks).
 template <class A>
 DecodePlan decode_plan(const A *a, bool windowed, const fa_window *w, bool capped = false, const fa_softcap *cap = nullptr, bool sunk = false,
-                       const fa_sinks *sk = nullptr) {
+                       const fa_sinks *sk = nullptr, int64_t d_head = 128) {
     DecodePlan p;
-    p.status = decode_validate(a, p.cache);
+    p.status = decode_validate(a, p.cache, d_head);
     if (p.status == FA_OK && windowed) p.status = window_validate(w, a->causal, p.cache.capacity());
     if (p.status == FA_OK && capped) p.status = softcap_validate(cap);
     if (p.status == FA_OK && sunk) p.status = sinks_validate(sk, a->n_heads, false, nullptr);
@@ -1842,16 +1849,16 @@ DecodePlan decode_plan(const A *a, bool windowed, const fa_window *w, bool cappe
     return p;
 }
 
-template <class A> int64_t decode_part_o_bytes(const A *a, int64_t splits) {
-    return (int64_t)sizeof(float) * splits * a->batch * a->n_kv_heads * (a->seqlen_q * (a->n_heads / a->n_kv_heads)) * 128;
+template <class A> int64_t decode_part_o_bytes(const A *a, int64_t splits, int64_t d_head) {
+    return (int64_t)sizeof(float) * splits * a->batch * a->n_kv_heads * (a->seqlen_q * (a->n_heads / a->n_kv_heads)) * d_head;
 }
 
-// the workspace of a plan: the fp32 partial o (a multiple of 512 bytes), then the partial lse; none for one split
+// the workspace of a plan: the fp32 partial o (a multiple of 512 bytes; d_head 64: of 256), then the partial lse; none for one split
 template <class A> int64_t plan_workspace(const A *a, const DecodePlan &p) {
     if (p.status != FA_OK) return p.status;
     if (p.splits == 1) return 0;
-    const int64_t po = decode_part_o_bytes(a, p.splits);
-    return po + ((po / 128 + 15) & ~(int64_t)15);
+    const int64_t po = decode_part_o_bytes(a, p.splits, p.cache.d_head);
+    return po + ((po / p.cache.d_head + 15) & ~(int64_t)15);
 }
 
 // the kernels' arguments from validated ones
@@ -1864,7 +1871,7 @@ template <class A> void decode_fill(fa::DecodeArgs &d, const A *a, const CacheVi
     d.cache_seqlens = c.cache_seqlens;
     d.block_table = c.block_table;
     d.part_o = splits > 1 ? (float *)a->workspace : nullptr;
-    d.part_lse = splits > 1 ? (float *)((char *)a->workspace + decode_part_o_bytes(a, splits)) : nullptr;
+    d.part_lse = splits > 1 ? (float *)((char *)a->workspace + decode_part_o_bytes(a, splits, c.d_head)) : nullptr;
     d.q_bs = a->q_batch_stride;
     d.q_ss = a->q_seq_stride;
     d.q_hs = a->q_head_stride;
@@ -1890,14 +1897,17 @@ template <class A> void decode_fill(fa::DecodeArgs &d, const A *a, const CacheVi
 
 // The launch of all eight forms; `ws_query`: the entry point's workspace query (a capped or sink form: its windowed sibling's), for its
 // message.  `capped`: a soft-capped form (always windowed), its fa_softcap refused behind everything the windowed sibling refuses;
-// `sunk`: a form with attention sinks (always windowed), its fa_sinks refused there likewise.
+// `sunk`: a form with attention sinks (always windowed), its fa_sinks refused there likewise.  `d_head` 64: fa_decode_d64_launch -- the
+// sink form's checks in its order, the kernels of fa_decode64.hip (one form: `sunk` only says whether there is a pointer); `ws_args`:
+// the workspace query's parameter list for the message, where it is not the windowed or the plain one.
 template <class A>
 int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_query, void *stream, float *ms, bool capped = false,
-                  const fa_softcap *cap = nullptr, bool sunk = false, const fa_sinks *sk = nullptr) {
+                  const fa_softcap *cap = nullptr, bool sunk = false, const fa_sinks *sk = nullptr, int64_t d_head = 128,
+                  const char *ws_args = nullptr) {
     if (!a) return fail(FA_ERR_NULL, "null pointer argument");
     if (!a->q || !a->k || !a->v || !a->o) return fail(FA_ERR_NULL, "null tensor pointer (q, k, v and o are all needed)");
     if (!a->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to batch int32 lengths is needed");
-    const DecodePlan p = decode_plan(a, windowed, w);
+    const DecodePlan p = decode_plan(a, windowed, w, false, nullptr, false, nullptr, d_head);
     if (p.status != FA_OK) return p.status;
     if (a->batch == 0) {   // (nothing to do -- behind the cap's own rules, as in the packed form)
         if (capped && softcap_validate(cap) != FA_OK) return softcap_validate(cap);
@@ -1907,7 +1917,7 @@ int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_
     }
     const CacheView &c = p.cache;
     if (p.splits > 1 && !a->workspace)
-        return fail(FA_ERR_NULL, "workspace is null: allocate %s(%s) bytes of device memory", ws_query, windowed ? "args, window" : "args");
+        return fail(FA_ERR_NULL, "workspace is null: allocate %s(%s) bytes of device memory", ws_query, ws_args ? ws_args : windowed ? "args, window" : "args");
     if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) & 15) return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
     int rc = cache_alignment(c, (uintptr_t)a->lse);
     if (rc != FA_OK) return rc;
@@ -1936,8 +1946,10 @@ int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_
     }
     const fa::DecodeSinksArgs kz = {kw, sunk ? sk->sinks : nullptr};
     const fa::DecodeFp8SinksArgs kz8 = {k, kz.sinks};
+    const fa::Decode64Args k64 = {k.f.d, k.left, k.right, kz.sinks};
     const hipStream_t s = (hipStream_t)stream;
     return enqueue_timed([&] {
+        if (d_head == 64) return fa::decode64_enqueue(k64, a->dtype, s);
         if (sunk) return c.fp8 ? fa::decode_fp8_sinks_enqueue(kz8, a->dtype, s) : fa::decode_sinks_enqueue(kz, a->dtype, s);
         if (capped) return c.fp8 ? fa::decode_fp8_softcap_enqueue(ks8, a->dtype, s) : fa::decode_softcap_enqueue(ks, a->dtype, s);
         if (c.fp8) return windowed ? fa::decode_fp8_window_enqueue(k, a->dtype, s) : fa::decode_fp8_enqueue(k.f, a->dtype, s);
@@ -2018,6 +2030,22 @@ int fa_decode_fp8_sinks_num_splits(const fa_decode_fp8_args *a, const fa_window 
 }
 int fa_decode_fp8_sinks_launch(const fa_decode_fp8_args *a, const fa_window *w, const fa_sinks *sinks, void *stream, float *ms) {
     return decode_launch(a, true, w, "fa_decode_fp8_window_workspace_bytes", stream, ms, false, nullptr, true, sinks);
+}
+
+// ... at d_head = 64: fa_decode_args with d_head = 64, a window always ((-1, -1): none) and an fa_sinks that may be
+// null (no sinks).  A 16-bit cache only.  The sink forms' planner, split rule and launch body with the head dimension as a parameter;
+// a workspace query of its own, since the partials are 64 wide.
+int fa_decode_d64_supported(const fa_decode_args *a, const fa_window *w, const fa_sinks *sinks) {
+    return decode_plan(a, true, w, false, nullptr, sinks != nullptr, sinks, 64).status == FA_OK;
+}
+int fa_decode_d64_num_splits(const fa_decode_args *a, const fa_window *w, const fa_sinks *sinks) {
+    return plan_splits(decode_plan(a, true, w, false, nullptr, sinks != nullptr, sinks, 64));
+}
+int64_t fa_decode_d64_workspace_bytes(const fa_decode_args *a, const fa_window *w, const fa_sinks *sinks) {
+    return plan_workspace(a, decode_plan(a, true, w, false, nullptr, sinks != nullptr, sinks, 64));
+}
+int fa_decode_d64_launch(const fa_decode_args *a, const fa_window *w, const fa_sinks *sinks, void *stream, float *ms) {
+    return decode_launch(a, true, w, "fa_decode_d64_workspace_bytes", stream, ms, false, nullptr, sinks != nullptr, sinks, 64, "args, window, sinks");
 }
 
 // ---- the KV-cache append in front of a decode --------------------------------------------------------------------------------

@@ -224,6 +224,26 @@ def forward_kvcache_sinks(q, k_cache, v_cache, cache_seqlens, sinks, block_table
                                                          rotary_interleaved=rotary_interleaved, advance_seqlens=advance_seqlens)
 
 
+def forward_kvcache_d64(q, k_cache, v_cache, cache_seqlens, sinks=None, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
+                        num_splits=0, timed=False, window_size=(-1, -1)):
+    """KV-cache decode at d_head = 64 (gpt-oss's head dimension): q (batch, seqlen_q, n_heads, 64) against k_cache,
+    v_cache (batch, seqlen_cache, n_kv_heads, 64) or, with block_table, pages (num_pages, page_size, n_kv_heads, 64), 16-bit in q's
+    dtype, at the scale 1 / sqrt(64).  Every argument is forward_kvcache_sinks's of that name, with its meaning, checks and defaults;
+    sinks may be None (no sinks: the bits of a tensor of -inf).  -> what forward_kvcache returns.  Kernels of their own, 32 keys
+    per wave visit; split-KV with a fixed-order combine, graph-capturable, the host reads no device array.  Not served at 64,
+    and so without a parameter here: fp8 caches, soft-capping, the fused append and rotary; more than 64 packed rows are refused."""
+    return flash_attention_kernels.forward_kvcache_d64(q, k_cache, v_cache, cache_seqlens, sinks=sinks, block_table=block_table, causal=causal,
+                                                       return_lse=return_lse, max_seqlen_k=max_seqlen_k, num_splits=num_splits, timed=timed,
+                                                       window_size=window_size)
+
+
+def kvcache_d64_num_splits(q, k_cache, v_cache, cache_seqlens, sinks=None, block_table=None, causal=False, max_seqlen_k=None, num_splits=0,
+                           window_size=(-1, -1)):
+    """The split count forward_kvcache_d64 uses for these arguments: the same checks, nothing allocated, no launch."""
+    return flash_attention_kernels.kvcache_d64_num_splits(q, k_cache, v_cache, cache_seqlens, sinks=sinks, block_table=block_table, causal=causal,
+                                                          max_seqlen_k=max_seqlen_k, num_splits=num_splits, window_size=window_size)
+
+
 def forward_varlen_kvcache_sinks(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, sinks, block_table=None, causal=False,
                                  max_seqlen_k=None, timed=False, k_descale=None, v_descale=None, *, window_size=(-1, -1)):
     """forward_varlen_kvcache with learned attention sinks: forward_kvcache_sinks's sinks on the cache prefill, every

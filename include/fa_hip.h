@@ -941,6 +941,24 @@ int fa_decode_fp8_sinks_num_splits(const fa_decode_fp8_args *args, const fa_wind
 int fa_decode_fp8_sinks_launch(const fa_decode_fp8_args *args, const fa_window *window, const fa_sinks *sinks, void *stream, float *ms);
 
 /*
+ * KV-cache decode at d_head = 64: what fa_decode_sinks_* serve at 128, for a 16-bit cache in q's dtype.  args is an
+ * fa_decode_args with d_head = 64: q and o (batch, seqlen_q, n_heads, 64), the caches (batch, seqlen_cache, n_kv_heads, 64) or
+ * (num_pages, page_size, n_kv_heads, 64); the logits' scale is 1 / sqrt(64).  window is required, (-1, -1) means none; sinks may be
+ * null: no sinks (a tensor of -inf gives the same bits).  Kernels of their own (32 keys per wave visit); the fetch contract,
+ * the clamping of lengths and block_table entries, the row packing, the split rule and the meaning of every field are
+ * fa_decode_window_*'s.  The workspace holds (num_splits, batch, n_kv_heads, rows, 64) fp32 partials and their lse:
+ * fa_decode_d64_workspace_bytes sizes it.  Deterministic for a given num_splits, no atomics, the host reads no device array,
+ * graph-capturable.  Not served at 64: fp8 caches, soft-capping, the fused append, more than 64 packed rows.
+ *
+ * Refused before any HIP call, in the order of fa_decode_sinks_*: d_head != 64 (FA_ERR_SHAPE) where they refuse d_head != 128; more
+ * than 64 packed rows or page_size % 64 != 0 (FA_ERR_NO_KERNEL); then the window's rules; then, for a non-null fa_sinks, its rules.
+ */
+int fa_decode_d64_supported(const fa_decode_args *args, const fa_window *window, const fa_sinks *sinks);
+int fa_decode_d64_num_splits(const fa_decode_args *args, const fa_window *window, const fa_sinks *sinks);
+int64_t fa_decode_d64_workspace_bytes(const fa_decode_args *args, const fa_window *window, const fa_sinks *sinks);
+int fa_decode_d64_launch(const fa_decode_args *args, const fa_window *window, const fa_sinks *sinks, void *stream, float *ms);
+
+/*
  * The step in front of a decode: append seqlen_new new K / V rows per batch entry to the cache IN PLACE, at the positions the
  * device-side lengths name, optionally rotate the new keys and the query (rotary embedding), quantize for an fp8 cache, and
  * advance the lengths.  One kernel on `stream`; the host reads none of the device arrays, so the launch is asynchronous and
