@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = (
     "fa_decode_sinks_supported", "fa_decode_sinks_num_splits", "fa_decode_sinks_launch",
     "fa_decode_fp8_sinks_supported", "fa_decode_fp8_sinks_num_splits", "fa_decode_fp8_sinks_launch",
     "fa_decode_d64_supported", "fa_decode_d64_num_splits", "fa_decode_d64_workspace_bytes", "fa_decode_d64_launch",
+    "fa_fwd_varlen_qk_d64_supported", "fa_fwd_launch_varlen_qk_d64",
+    "fa_fwd_varlen_kvcache_d64_supported", "fa_fwd_launch_varlen_kvcache_d64",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -496,6 +498,10 @@ def load():
     for suffix in ("supported", "num_splits", "workspace_bytes", "launch"):
         fn, sibling = getattr(lib, f"fa_decode_d64_{suffix}"), getattr(lib, f"fa_decode_window_{suffix}")
         fn.restype, fn.argtypes = sibling.restype, sibling.argtypes[:2] + [ctypes.POINTER(FaSinks)] + sibling.argtypes[2:]
+    # the d_head = 64 prefills: the sinks forms' arguments (the fa_sinks may be null)
+    for name in ("varlen_qk", "varlen_kvcache"):
+        for fn, sibling in ((f"fa_fwd_{name}_d64_supported", f"fa_fwd_{name}_sinks_supported"), (f"fa_fwd_launch_{name}_d64", f"fa_fwd_launch_{name}_sinks")):
+            getattr(lib, fn).restype, getattr(lib, fn).argtypes = ctypes.c_int, list(getattr(lib, sibling).argtypes)
     lib.fa_kvcache_append_launch.restype = ctypes.c_int
     lib.fa_kvcache_append_launch.argtypes = [ctypes.POINTER(FaKvcacheAppendArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p

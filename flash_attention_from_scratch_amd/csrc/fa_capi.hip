@@ -22,6 +22,7 @@
 #include "fa_bwd_varlen.hpp"
 #include "fa_decode_kernel.hpp"
 #include "fa_decode64_kernel.hpp"
+#include "fa_prefill64_kernel.hpp"
 #include "fa_kvcache_append_kernel.hpp"
 #include "fa_registry.hpp"
 
@@ -1185,6 +1186,8 @@ const fa::KernelEntry *varlen_entry(const fa_fwd_config *cfg, const char **why) 
 }
 const char *kNoVarlen = "packed variable-length sequences are served by the (B_r 128, B_c 64, 4 warps) + buffer configuration at d_head "
                         "128 only, plain or causal, without speculative, prescaled_q and stats";
+const char *kNoVarlen64 = "packed variable-length sequences at d_head = 64 are served in fp16 and bf16, plain or causal, without speculative, "
+                          "prescaled_q and stats";
 
 // the cache side of fa_fwd_launch_varlen_kvcache and its fp8 form (`sc`): `c` already holds kv's strides and heads and vq's n_seqs,
 // all validated; each struct is read once its own struct_size has passed
@@ -1274,10 +1277,12 @@ struct VarlenCall {
     const fa_kvcache_fp8_scales *sc;   // KEYS_FP8_CACHE: k, v are bytes, kv's strides count bytes, `sc` holds the descales
     const fa_window *w;                // EXTRA_WINDOW and up (null is refused, behind everything the entry itself refuses)
     const fa_softcap *cap;             // EXTRA_SOFTCAP (refused behind the window's rules)
-    const fa_sinks *sinks;             // EXTRA_SINKS (refused behind the window's rules)
+    const fa_sinks *sinks;             // EXTRA_SINKS (refused behind the window's rules; d_head = 64: may be null, no sinks)
 };
+// (d_head: 128, the forms of fa_fwd_kernel.hpp, or 64, fa_prefill64_kernel.hpp's -- the same rules in the same order and words, the
+// head dimension a parameter as in decode_validate; behind them the d64 entries fill their own arguments and enqueue their own kernel)
 int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq,
-                      const fa_fwd_opts *opts, float *lse, void *stream) {
+                      const fa_fwd_opts *opts, float *lse, void *stream, int64_t d_head = 128) {
     const bool cache_side = call.keys != KEYS_PACKED, fp8_side = call.keys == KEYS_FP8_CACHE;
     const bool windowed = call.extra != EXTRA_NONE, capped = call.extra == EXTRA_SOFTCAP;
     const bool sunk = call.extra == EXTRA_SINKS;
@@ -1291,9 +1296,14 @@ int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_
     fa_fwd_opts o;
     int rc = read_opts(opts, &o);
     if (rc != FA_OK) return rc;
-    if (!fa_fwd_varlen_supported(&args->cfg, opts)) return fail(FA_ERR_NO_KERNEL, "%s", kNoVarlen);
-    if (args->d_head != 128)
-        return fail(FA_ERR_SHAPE, "Tensor d_head (%lld) does not match kernel configuration d_head (%d)", (long long)args->d_head, 128);
+    if (d_head == 64) {
+        if (!fa_fwd_varlen_qk_d64_supported(&args->cfg, opts)) return fail(FA_ERR_NO_KERNEL, "%s", kNoVarlen64);
+        if (args->d_head != 64) return fail(FA_ERR_SHAPE, "%s supports d_head = 64 only (got %lld)", call.entry, (long long)args->d_head);
+    } else {
+        if (!fa_fwd_varlen_supported(&args->cfg, opts)) return fail(FA_ERR_NO_KERNEL, "%s", kNoVarlen);
+        if (args->d_head != 128)
+            return fail(FA_ERR_SHAPE, "Tensor d_head (%lld) does not match kernel configuration d_head (%d)", (long long)args->d_head, 128);
+    }
     if (args->n_heads <= 0) return fail(FA_ERR_SHAPE, "n_heads must be positive");
     if ((rc = varlen_qk_validate(vq, vk)) != FA_OK) return rc;
     if (kv->n_kv_heads < 1 || kv->n_kv_heads > args->n_heads || args->n_heads % kv->n_kv_heads != 0)
@@ -1323,10 +1333,49 @@ int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_
             return fail(FA_ERR_SHAPE, "max_seqlen_q too large for a window: at most 2^30 - 128 query rows per sequence");
     }
     if (capped && (rc = softcap_validate(call.cap)) != FA_OK) return rc;
-    if (sunk && (rc = sinks_validate(call.sinks, args->n_heads, false, nullptr)) != FA_OK) return rc;
+    if (sunk && (d_head == 128 || call.sinks) && (rc = sinks_validate(call.sinks, args->n_heads, false, nullptr)) != FA_OK) return rc;
     if (vq->total_tokens == 0) {   // (no query rows: nothing to write)
         if (o.ms) *o.ms = 0.0f;
         return FA_OK;
+    }
+    if (d_head == 64) {   // fa_prefill64_kernel.hpp: one kernel per dtype and key side, no per-device setup (48 KiB of static LDS)
+        fa::Prefill64Args p = {};
+        p.q = (const uint16_t *)args->q;
+        p.k = (const uint16_t *)args->k;
+        p.v = (const uint16_t *)args->v;
+        p.o = (uint16_t *)args->o;
+        p.lse = lse;
+        p.cu_q = vq->cu_seqlens;
+        p.sinks = call.sinks ? call.sinks->sinks : nullptr;
+        p.q_ss = args->seq_stride;
+        p.q_hs = args->head_stride;
+        p.kv_ss = kv->kv_seq_stride;
+        p.kv_hs = kv->kv_head_stride;
+        p.n_heads = (int32_t)args->n_heads;
+        p.group = (int32_t)(args->n_heads / kv->n_kv_heads);
+        p.n_q_blocks = (int32_t)((vq->max_seqlen + fa::prefill64::R - 1) / fa::prefill64::R);
+        p.total_q = (int32_t)vq->total_tokens;
+        p.max_seqlen_q = (int32_t)vq->max_seqlen;
+        if (!cache_side) {
+            p.cu_k = vk->cu_seqlens;
+            p.total_k = (int32_t)vk->total_tokens;
+            p.max_seqlen_k = (int32_t)vk->max_seqlen;
+        } else {
+            const int64_t cap_k = cache.capacity();
+            p.cache_seqlens = cache.cache_seqlens;
+            p.block_table = cache.block_table;
+            p.page_stride = kv->kv_batch_stride;
+            p.bt_stride = cache.paged() ? (int32_t)cache.block_table_stride : 0;
+            p.num_pages = (int32_t)cache.slots();
+            p.tiles_per_page = (int32_t)(cache.paged() ? cache.page_size / 64 : (cap_k + 63) / 64);   // (contiguous: one "page" per entry)
+            p.max_len = (int32_t)(cache.max_seqlen_k > 0 ? cache.max_seqlen_k : cap_k);
+        }
+        p.left = call.w->left;   // (causal as right = 0: the kernel's one rule for both)
+        p.right = window_right(call.w, o.causal);
+        const hipStream_t s = (hipStream_t)stream;
+        const int dtype = args->cfg.dtype == FA_BF16 ? 15 : 5;
+        const int64_t n_seqs = vq->n_seqs;
+        return enqueue_timed([&] { return fa::prefill64_enqueue(p, dtype, cache_side, n_seqs, s); }, s, o.ms);
     }
     DeviceState *dev = current_device(&rc);
     if (!dev) return rc;
@@ -1636,6 +1685,27 @@ int fa_fwd_launch_varlen_kvcache_fp8_softcap(const fa_fwd_args *args, const fa_k
                                              const fa_softcap *cap, const fa_fwd_opts *opts, float *lse, void *stream) {
     return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_fp8_softcap", "total_q", KEYS_FP8_CACHE, EXTRA_SOFTCAP, nullptr, kc, sc, w, cap}, args, kv, vq,
                              opts, lse, stream);
+}
+
+// d_head = 64: the sinks forms' arguments with args->d_head = 64 and an fa_sinks that may be null (no sinks: the
+// bits of z = -inf); of cfg only the dtype is read.  One kernel family of its own, fa_prefill64_kernel.hpp
+int fa_fwd_varlen_qk_d64_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) {
+    if (!cfg) return 0;
+    fa_fwd_opts o;
+    if (read_opts(opts, &o) != FA_OK) return 0;
+    if (o.speculative || o.prescaled_q || o.stats) return 0;
+    return cfg->dtype == FA_BF16 || cfg->dtype == FA_FP16;
+}
+int fa_fwd_launch_varlen_qk_d64(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_varlen_layout *vk,
+                                const fa_window *w, const fa_sinks *sinks, const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_qk_d64", "total_q", KEYS_PACKED, EXTRA_SINKS, vk, nullptr, nullptr, w, nullptr, sinks}, args, kv, vq,
+                             opts, lse, stream, 64);
+}
+int fa_fwd_varlen_kvcache_d64_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_qk_d64_supported(cfg, opts); }
+int fa_fwd_launch_varlen_kvcache_d64(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_kvcache_layout *kc,
+                                     const fa_window *w, const fa_sinks *sinks, const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_d64", "total_q", KEYS_CACHE, EXTRA_SINKS, nullptr, kc, nullptr, w, nullptr, sinks}, args,
+                             kv, vq, opts, lse, stream, 64);
 }
 
 int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *a) {

@@ -244,6 +244,27 @@ def kvcache_d64_num_splits(q, k_cache, v_cache, cache_seqlens, sinks=None, block
                                                           max_seqlen_k=max_seqlen_k, num_splits=num_splits, window_size=window_size)
 
 
+def forward_varlen_d64(q, k, v, cu_seqlens, max_seqlen, sinks=None, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None, *,
+                       window_size=(-1, -1)):
+    """Packed prefill at d_head = 64 (gpt-oss's head dimension): q (total_q, n_heads, 64), k and v (total_k, n_kv_heads,
+    64), at the scale 1 / sqrt(64).  Every argument is forward_varlen_sinks's of that name, with its meaning, checks and defaults;
+    sinks may be None (no sinks: the bits of a tensor of -inf).  -> (o, lse[, ms]).  A kernel of its own: 64 rows per wave, 256 per
+    workgroup, two waves per SIMD.  Forward only; no soft-capping."""
+    return flash_attention_kernels.forward_varlen_d64(q, k, v, cu_seqlens, max_seqlen, sinks=sinks, causal=causal, timed=timed,
+                                                      cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k, window_size=window_size)
+
+
+def forward_varlen_kvcache_d64(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, sinks=None, block_table=None, causal=False,
+                               max_seqlen_k=None, timed=False, *, window_size=(-1, -1)):
+    """Prefill against the cache forward_kvcache_d64 decodes from: q (total_q, n_heads, 64) packed; k_cache, v_cache
+    (n_seqs, seqlen_cache, n_kv_heads, 64) or, with block_table, pages (num_pages, page_size, n_kv_heads, 64), 16-bit in q's dtype.
+    Every argument is forward_varlen_kvcache_sinks's of that name, with its meaning, checks and defaults; sinks may be None.
+    -> (o, lse[, ms]), bit for bit forward_varlen_d64(cu_seqlens_k=) on the same keys packed.  No fp8 cache, no soft-capping."""
+    return flash_attention_kernels.forward_varlen_kvcache_d64(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, sinks=sinks,
+                                                              block_table=block_table, causal=causal, max_seqlen_k=max_seqlen_k, timed=timed,
+                                                              window_size=window_size)
+
+
 def forward_varlen_kvcache_sinks(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, sinks, block_table=None, causal=False,
                                  max_seqlen_k=None, timed=False, k_descale=None, v_descale=None, *, window_size=(-1, -1)):
     """forward_varlen_kvcache with learned attention sinks: forward_kvcache_sinks's sinks on the cache prefill, every

@@ -391,6 +391,20 @@ def forward_varlen_sinks(q, k, v, cu_seqlens, max_seqlen, sinks, causal=False, t
     return _forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, None, sinks)
 
 
+def forward_varlen_d64(q, k, v, cu_seqlens, max_seqlen, sinks=None, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None, *,
+                       window_size=(-1, -1)):
+    """forward_varlen_sinks at d_head = 64 (fa_fwd_launch_varlen_qk_d64): q (total_q, n_heads, 64), k and v
+    (total_k, n_kv_heads, 64); the logits' scale is 1 / sqrt(64).  Every other argument is forward_varlen_sinks's, with its meaning,
+    checks and defaults (one range given: on both sides), but sinks may be None: no sinks, the bits of a tensor of -inf.  -> (o, lse[, ms]),
+    lse fp32 (n_heads, total_q).  A kernel of its own (256 rows per workgroup); forward only.  A bad window_size is a ValueError before
+    any tensor is looked at, a bad sinks or another d_head a RuntimeError before the library is loaded.  Not here, and so without a
+    parameter: soft-capping, a backward."""
+    window = _window(window_size, causal)
+    if sinks is not None:
+        _check_sinks(sinks, q)
+    return _forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, None, sinks, d_head=64)
+
+
 def _check_sinks(sinks, q, name="sinks", q_dim=3):
     """sinks as the calls with sinks take it: a contiguous fp32 tensor of shape (n_heads,) on q's device (checked in front of the
     sibling's own checks, so against q only where q is a tensor of the call's shape at all: q_dim 3 packed, 4 forward_kvcache_sinks's)"""
@@ -407,10 +421,14 @@ def _check_sinks(sinks, q, name="sinks", q_dim=3):
             raise RuntimeError(f"{name} must be on q's device ({q.device}, got {sinks.device})")
 
 
-def _forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, cap, sinks=None):
-    """forward_varlen (window: _window's, cap: _softcap's) and forward_varlen_sinks (sinks a checked tensor, cap None)"""
+def _forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, cap, sinks=None, d_head=128):
+    """forward_varlen (window: _window's, cap: _softcap's), forward_varlen_sinks (sinks a checked tensor, cap None) and, d_head=64,
+    forward_varlen_d64 (sinks a checked tensor or None)"""
     qk = _qk_sides(cu_seqlens_k, max_seqlen_k)
     _check_varlen(q, k, v, cu_seqlens, max_seqlen, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
+    d64 = d_head == 64   # (the entry, not the tensor: forward_varlen on a 64-wide q is still the library's refusal)
+    if d64 and q.shape[2] != 64:
+        raise RuntimeError(f"forward_varlen_d64 supports d_head = 64 only (got {q.shape[2]})")
     total, n_heads, d_head = q.shape
     lib = _capi.load()
     cfg = _capi.make_config(varlen_config(q.dtype))
@@ -426,6 +444,12 @@ def _forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k
     opts = _capi.make_opts(causal=causal, ms=ms if timed else None)
     with torch.cuda.device(q.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        if d64:
+            w, sk = _capi.make_window(*(window or (-1, -1))), (None if sinks is None else _capi.make_sinks(sinks.data_ptr(), n_heads))
+            _capi.check(lib.fa_fwd_launch_varlen_qk_d64(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(sides[0]), ctypes.byref(sides[-1]),
+                                                        ctypes.byref(w), None if sk is None else ctypes.byref(sk), ctypes.byref(opts),
+                                                        ctypes.c_void_p(lse.data_ptr()), stream))
+            return (o, lse, float(ms.value)) if timed else (o, lse)
         if sinks is not None:
             w, sk = _capi.make_window(*(window or (-1, -1))), _capi.make_sinks(sinks.data_ptr(), n_heads)
             _capi.check(lib.fa_fwd_launch_varlen_qk_sinks(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(sides[0]), ctypes.byref(sides[-1]),
@@ -1004,6 +1028,22 @@ def forward_varlen_kvcache_sinks(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q
                                    k_descale, v_descale, window, None, sinks)
 
 
+def forward_varlen_kvcache_d64(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, sinks=None, block_table=None, causal=False,
+                               max_seqlen_k=None, timed=False, *, window_size=(-1, -1)):
+    """forward_varlen_kvcache_sinks at d_head = 64 (fa_fwd_launch_varlen_kvcache_d64): q (total_q, n_heads, 64); k_cache,
+    v_cache (n_seqs, seqlen_cache, n_kv_heads, 64), or with block_table (num_pages, page_size, n_kv_heads, 64), page_size % 64 == 0, in
+    q's dtype; the logits' scale is 1 / sqrt(64).  Every other argument is forward_varlen_kvcache_sinks's, with its meaning, checks and
+    defaults, but sinks may be None: no sinks, the bits of a tensor of -inf.  -> (o, lse[, ms]); o and lse are forward_varlen_d64's bits
+    on the gathered keys; what forward_kvcache_d64 decodes against, this call fills and verifies.  The host reads no device array;
+    graph-capturable.  A bad window_size is a ValueError before any tensor is looked at, a bad sinks, an fp8 cache or another d_head a
+    RuntimeError before the library is loaded.  Not here, and so without a parameter: fp8 caches and descales, soft-capping."""
+    window = _window(window_size, causal)
+    if sinks is not None:
+        _check_sinks(sinks, q)
+    return _forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, max_seqlen_k, timed,
+                                   None, None, window, None, sinks, d_head=64)
+
+
 def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table=None, causal=False,
                            max_seqlen_k=None, timed=False, k_descale=None, v_descale=None, *, window_size=(-1, -1), softcap=0.0):
     """Prefill against a K / V cache (fa_fwd_launch_varlen_kvcache): forward_varlen(cu_seqlens_k=) whose keys are read from the
@@ -1036,18 +1076,20 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
 
 
 def _forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, max_seqlen_k, timed, k_descale,
-                            v_descale, window, cap, sinks):
-    """The one body of forward_varlen_kvcache (window: _window's, cap: _softcap's, sinks None) and forward_varlen_kvcache_sinks (sinks a
-    checked tensor, cap None)"""
+                            v_descale, window, cap, sinks, d_head=128):
+    """The one body of forward_varlen_kvcache (window: _window's, cap: _softcap's, sinks None), forward_varlen_kvcache_sinks (sinks a
+    checked tensor, cap None) and, d_head=64, forward_varlen_kvcache_d64 (sinks a checked tensor or None; no fp8 cache)"""
     tensors = [(q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cu_seqlens_q, "cu_seqlens_q"), (cache_seqlens, "cache_seqlens")]
     if block_table is not None:
         tensors.append((block_table, "block_table"))
     _need_tensors(tensors)
     cache = _CacheSide(k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, "n_seqs", "q's")
-    fp8 = cache.dtypes(like=None, fp8_needs_descales=(
+    fp8 = cache.dtypes(like=None, fp8_needs_descales=None if d_head == 64 else (
         "forward_varlen_kvcache: an fp8 cache is not served without both k_descale and v_descale (fp32 (n_seqs, "
         "n_kv_heads) tensors on q's device; pass ones for an unscaled cache -- None does not mean 1 here)"))
     if fp8:
+        if d_head == 64:   # (still the entry's parameter here)
+            raise RuntimeError("forward_varlen_kvcache_d64 serves a 16-bit cache in q's dtype: an fp8 cache at d_head = 64 has no kernel")
         tensors += [(k_descale, "k_descale"), (v_descale, "v_descale")]
         _need_tensors(tensors[-2:])
         if k_cache.dim() == 4 and cu_seqlens_q.dim() == 1 and cu_seqlens_q.numel() >= 2:   # (what they are is checked before where they are)
@@ -1064,6 +1106,9 @@ def _forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cac
     if q.dim() != 3 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[3] != q.shape[2]:
         raise RuntimeError("q must have shape (total_q, n_heads, d_head), k_cache and v_cache one shape (n_seqs or num_pages, "
                            "seqlen_cache or page_size, n_kv_heads, d_head)")
+    d64 = d_head == 64   # (the entry, not the tensor)
+    if d64 and q.shape[2] != 64:
+        raise RuntimeError(f"forward_varlen_kvcache_d64 supports d_head = 64 only (got {q.shape[2]})")
     total, n_heads, d_head = q.shape
     n_kv = k_cache.shape[2]
     if n_kv < 1 or n_heads % n_kv != 0:
@@ -1107,6 +1152,10 @@ def _forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cac
         if sinks is not None:
             form = "_sinks"
             w = [ctypes.byref(_capi.make_window(*(window or (-1, -1)))), ctypes.byref(_capi.make_sinks(sinks.data_ptr(), n_heads))]
+        if d64:   # (the sinks form's arguments; the fa_sinks may be null)
+            form = "_d64"
+            w = [ctypes.byref(_capi.make_window(*(window or (-1, -1)))),
+                 None if sinks is None else ctypes.byref(_capi.make_sinks(sinks.data_ptr(), n_heads))]
         tail = w + [ctypes.byref(opts), ctypes.c_void_p(lse.data_ptr()), stream]
         if fp8:
             sc = _capi.make_kvcache_fp8_scales(k_descale=k_descale.data_ptr(), v_descale=v_descale.data_ptr(),

@@ -959,6 +959,28 @@ int64_t fa_decode_d64_workspace_bytes(const fa_decode_args *args, const fa_windo
 int fa_decode_d64_launch(const fa_decode_args *args, const fa_window *window, const fa_sinks *sinks, void *stream, float *ms);
 
 /*
+ * Prefill at d_head = 64 (ABI 6, additive): fa_fwd_launch_varlen_qk_sinks and fa_fwd_launch_varlen_kvcache_sinks
+ * with args->d_head = 64 -- q (total_q, n_heads, 64) packed, k / v (total_k, n_kv_heads, 64) packed or a 16-bit cache
+ * (n_seqs, seqlen_cache, n_kv_heads, 64) / (num_pages, page_size, n_kv_heads, 64) in q's dtype, page_size % 64 == 0 -- the logits'
+ * scale 1 / sqrt(64).  Every struct keeps its meaning, every rule its place, status and words; args->d_head != 64 is FA_ERR_SHAPE
+ * where the siblings refuse != 128.  Of args->cfg only dtype is read.  `window` is required ((-1, -1): none); `sinks` MAY BE NULL
+ * (no sinks: the bits of a tensor of -inf), a non-null one is checked behind the window as in the siblings.  speculative,
+ * prescaled_q and stats are refused; total_q = 0 returns FA_OK without a launch.  A kernel family of its own: 256 rows per
+ * workgroup, grid n_seqs * n_heads * ceil(max_seqlen_q / 256).  The lengths' clamping, the window's rule, the row without keys
+ * (o = 0, lse = z or -inf) and the fetch contract are the siblings'.  No workspace, no split, no atomics: the same bits for the
+ * same inputs, and the cache form's bits are the packed form's on the gathered keys.  The host reads no device array;
+ * graph-capturable; opts->ms is timed by the launch's own events.  Not here: fp8 caches, soft-capping, a backward.
+ */
+int fa_fwd_varlen_qk_d64_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_qk_d64(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                const fa_varlen_layout *varlen_k, const fa_window *window, const fa_sinks *sinks /* may be null */,
+                                const fa_fwd_opts *opts, float *lse, void *stream);
+int fa_fwd_varlen_kvcache_d64_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_kvcache_d64(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                     const fa_kvcache_layout *cache, const fa_window *window, const fa_sinks *sinks /* may be null */,
+                                     const fa_fwd_opts *opts, float *lse, void *stream);
+
+/*
  * The step in front of a decode: append seqlen_new new K / V rows per batch entry to the cache IN PLACE, at the positions the
  * device-side lengths name, optionally rotate the new keys and the query (rotary embedding), quantize for an fp8 cache, and
  * advance the lengths.  One kernel on `stream`; the host reads none of the device arrays, so the launch is asynchronous and
