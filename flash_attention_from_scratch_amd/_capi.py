@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "fa_decode_d64_supported", "fa_decode_d64_num_splits", "fa_decode_d64_workspace_bytes", "fa_decode_d64_launch",
     "fa_fwd_varlen_qk_d64_supported", "fa_fwd_launch_varlen_qk_d64",
     "fa_fwd_varlen_kvcache_d64_supported", "fa_fwd_launch_varlen_kvcache_d64",
+    "fa_bwd_varlen_qk_d64_workspace_bytes", "fa_bwd_launch_varlen_qk_d64",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -502,6 +503,10 @@ def load():
     for name in ("varlen_qk", "varlen_kvcache"):
         for fn, sibling in ((f"fa_fwd_{name}_d64_supported", f"fa_fwd_{name}_sinks_supported"), (f"fa_fwd_launch_{name}_d64", f"fa_fwd_launch_{name}_sinks")):
             getattr(lib, fn).restype, getattr(lib, fn).argtypes = ctypes.c_int, list(getattr(lib, sibling).argtypes)
+    # the d_head = 64 packed backward: the sinks form's arguments (the fa_sinks may be null, dsinks with it)
+    for fn, sibling in (("fa_bwd_varlen_qk_d64_workspace_bytes", "fa_bwd_varlen_qk_sinks_workspace_bytes"),
+                        ("fa_bwd_launch_varlen_qk_d64", "fa_bwd_launch_varlen_qk_sinks")):
+        getattr(lib, fn).restype, getattr(lib, fn).argtypes = getattr(lib, sibling).restype, list(getattr(lib, sibling).argtypes)
     lib.fa_kvcache_append_launch.restype = ctypes.c_int
     lib.fa_kvcache_append_launch.argtypes = [ctypes.POINTER(FaKvcacheAppendArgs), ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     lib.fa_last_error.restype = ctypes.c_char_p

@@ -20,6 +20,7 @@
 #include "../../include/fa_hip.h"
 #include "fa_bwd_gqa.hpp"
 #include "fa_bwd_varlen.hpp"
+#include "fa_bwd64_kernel.hpp"
 #include "fa_decode_kernel.hpp"
 #include "fa_decode64_kernel.hpp"
 #include "fa_prefill64_kernel.hpp"
@@ -1499,13 +1500,18 @@ int64_t bwd_varlen_delta_bytes(const fa_bwd_varlen_qk_args *a) {   // (n_heads, 
 }
 
 // own_key_side: the caller gave varlen_k (fa_*_varlen_qk), whose rows the reduce kernel's grid runs over
-int bwd_varlen_validate(const fa_bwd_varlen_qk_args *a, bool own_key_side) {
+// d_head: 128, the forms of fa_bwd_varlen.hpp, or 64, fa_bwd64_kernel.hpp's (fa_bwd_launch_varlen_qk_d64) -- the same rules in the
+// same order and words but for the head dimension's own
+int bwd_varlen_validate(const fa_bwd_varlen_qk_args *a, bool own_key_side, int64_t d_head = 128) {
     if (!a) return fail(FA_ERR_NULL, "null pointer argument");
     if (a->struct_size < sizeof(fa_bwd_varlen_qk_args))
         return fail(FA_ERR_SHAPE, "fa_bwd_varlen_qk_args.struct_size (%u) is smaller than this library's (%zu)", a->struct_size,
                     sizeof(fa_bwd_varlen_qk_args));
     if (a->dtype != FA_FP16 && a->dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
-    if (a->d_head != 128) return fail(FA_ERR_SHAPE, "the backward supports d_head = 128 only (got %lld)", (long long)a->d_head);
+    if (a->d_head != d_head)
+        return fail(FA_ERR_SHAPE, d_head == 128 ? "the backward supports d_head = 128 only (got %lld)"
+                                                : "fa_bwd_launch_varlen_qk_d64 supports d_head = 64 only (got %lld; 128: fa_bwd_launch_varlen_qk_sinks and its siblings)",
+                    (long long)a->d_head);
     if (a->n_heads <= 0) return fail(FA_ERR_SHAPE, "n_heads must be positive");
     int rc = varlen_qk_validate(&a->varlen, &a->varlen_k);
     if (rc != FA_OK) return rc;
@@ -1523,17 +1529,17 @@ int bwd_varlen_validate(const fa_bwd_varlen_qk_args *a, bool own_key_side) {
     return varlen_grid_check(&a->varlen_k, a->n_heads);   // (n_kv_heads * split <= n_heads)
 }
 
-int64_t bwd_varlen_workspace_bytes(const fa_bwd_varlen_qk_args *a, bool own_key_side) {
-    const int rc = bwd_varlen_validate(a, own_key_side);
+int64_t bwd_varlen_workspace_bytes(const fa_bwd_varlen_qk_args *a, bool own_key_side, int64_t d_head = 128) {
+    const int rc = bwd_varlen_validate(a, own_key_side, d_head);
     if (rc != FA_OK) return rc;
     const int64_t split = bwd_varlen_split(a);
-    return bwd_varlen_delta_bytes(a) + (split > 1 ? (int64_t)sizeof(float) * a->n_kv_heads * split * a->varlen_k.total_tokens * 2 * 128 : 0);
+    return bwd_varlen_delta_bytes(a) + (split > 1 ? (int64_t)sizeof(float) * a->n_kv_heads * split * a->varlen_k.total_tokens * 2 * d_head : 0);
 }
 
 // what a backward entry point refuses before it looks at the device; in its messages `total` is its name for the query side's
 // total, `workspace_fn` its workspace function
-int bwd_varlen_checks(const fa_bwd_varlen_qk_args *a, bool own_key_side, const char *total, const char *workspace_fn) {
-    int rc = bwd_varlen_validate(a, own_key_side);
+int bwd_varlen_checks(const fa_bwd_varlen_qk_args *a, bool own_key_side, const char *total, const char *workspace_fn, int64_t d_head = 128) {
+    int rc = bwd_varlen_validate(a, own_key_side, d_head);
     if (rc != FA_OK) return rc;
     if (!a->q || !a->k || !a->v || !a->o || !a->dout || !a->dq || !a->dk || !a->dv)
         return fail(FA_ERR_NULL, "null tensor pointer (q, k, v, o, dout, dq, dk and dv are all needed)");
@@ -1817,6 +1823,46 @@ int fa_bwd_launch_varlen_qk_sinks(const fa_bwd_varlen_qk_args *a, const fa_windo
     sa.dsinks = dsinks;
     const hipStream_t s = (hipStream_t)stream;
     return enqueue_timed([&] { return fa::bwd_varlen_sinks_enqueue(sa, a->dtype, s); }, s, ms);
+}
+
+// ... at d_head = 64: fa_bwd64_kernel.hpp's kernels, a family of their own.  The window form's checks with the head
+// dimension 64, then a non-null fa_sinks' rules and its dsinks; null sinks: no sinks, dsinks is not looked at.  The split is the
+// siblings' rule on the same 128-key blocks; a partial row is 2 x 64 floats.
+int64_t fa_bwd_varlen_qk_d64_workspace_bytes(const fa_bwd_varlen_qk_args *a) { return bwd_varlen_workspace_bytes(a, true, 64); }
+int fa_bwd_launch_varlen_qk_d64(const fa_bwd_varlen_qk_args *a, const fa_window *w, const fa_sinks *sinks, float *dsinks, void *stream, float *ms) {
+    int rc = bwd_varlen_checks(a, true, "total_q", "fa_bwd_varlen_qk_d64_workspace_bytes", 64);
+    if (rc != FA_OK) return rc;
+    if ((rc = window_validate(w, a->causal, 0)) != FA_OK) return rc;
+    if (a->varlen_k.max_seqlen > kWindowMaxLen)
+        return fail(FA_ERR_SHAPE, "max_seqlen_k too large for a window: at most 2^30 - 128 keys per sequence");
+    if (a->varlen.max_seqlen > kWindowMaxLen)
+        return fail(FA_ERR_SHAPE, "max_seqlen_q too large for a window: at most 2^30 - 128 query rows per sequence");
+    if (sinks && (rc = sinks_validate(sinks, a->n_heads, false, nullptr)) != FA_OK) return rc;
+    if (sinks && !dsinks) return fail(FA_ERR_NULL, "dsinks is null: the backward writes the sinks' gradient, n_heads fp32, there");
+    if (a->varlen.total_tokens == 0 && a->varlen_k.total_tokens == 0) {   // (like the siblings: no device, nothing written)
+        if (ms) *ms = 0.0f;
+        return FA_OK;
+    }
+    DeviceState *dev = current_device(&rc);
+    if (!dev) return rc;
+    fa::BwdVarlenQKArgs f;   // (the siblings' fill: pointers, strides, the split and the 128-row blocks of either side)
+    bwd_varlen_fill(f, a);
+    fa::Bwd64Args k = {};
+    k.q = f.q, k.k = f.k, k.v = f.v, k.o = f.o, k.dout = f.dout, k.lse = f.lse, k.delta = f.delta;
+    k.dq = f.dq, k.dk = f.dk, k.dv = f.dv, k.cu_q = f.cu_seqlens, k.cu_k = f.cu_seqlens_k, k.part = f.part;
+    k.sinks = sinks ? sinks->sinks : nullptr;
+    k.dsinks = sinks ? dsinks : nullptr;
+    k.q_ss = f.q_ss, k.q_hs = f.q_hs, k.out_ss = f.out_ss, k.out_hs = f.out_hs;
+    k.kv_ss = f.kv_ss, k.kv_hs = f.kv_hs, k.dkv_ss = f.dkv_ss, k.dkv_hs = f.dkv_hs;
+    k.n_seqs = f.n_seqs, k.n_heads = f.n_heads;
+    k.total_q = f.total_tokens, k.max_seqlen_q = f.max_seqlen, k.total_k = f.total_k, k.max_seqlen_k = f.max_seqlen_k;
+    k.group = f.group, k.split = f.split, k.n_blocks_q = f.n_blocks, k.n_blocks_k = f.n_blocks_k;
+    constexpr int32_t kFar = 1 << 30;   // (as in bwd_launch_varlen_window)
+    const int32_t right = window_right(w, a->causal);
+    k.left = w->left < 0 || w->left > kFar ? kFar : w->left;
+    k.right = right < 0 || right > kFar ? kFar : right;
+    const hipStream_t s = (hipStream_t)stream;
+    return enqueue_timed([&] { return fa::bwd64_enqueue(k, a->dtype, s); }, s, ms);
 }
 
 // ---- KV-cache decode ------------------------------------------------------------------------------------------------------

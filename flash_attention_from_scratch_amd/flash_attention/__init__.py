@@ -249,7 +249,7 @@ def forward_varlen_d64(q, k, v, cu_seqlens, max_seqlen, sinks=None, causal=False
     """Packed prefill at d_head = 64 (gpt-oss's head dimension): q (total_q, n_heads, 64), k and v (total_k, n_kv_heads,
     64), at the scale 1 / sqrt(64).  Every argument is forward_varlen_sinks's of that name, with its meaning, checks and defaults;
     sinks may be None (no sinks: the bits of a tensor of -inf).  -> (o, lse[, ms]).  A kernel of its own: 64 rows per wave, 256 per
-    workgroup, two waves per SIMD.  Forward only; no soft-capping."""
+    workgroup, two waves per SIMD.  The gradients are backward_varlen_d64's, and attention_varlen_d64 pairs the two.  No soft-capping."""
     return flash_attention_kernels.forward_varlen_d64(q, k, v, cu_seqlens, max_seqlen, sinks=sinks, causal=causal, timed=timed,
                                                       cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k, window_size=window_size)
 
@@ -446,3 +446,58 @@ def attention_varlen_sinks(q, k, v, cu_seqlens, max_seqlen, sinks, causal=False,
         sinks = sinks.contiguous()
     flash_attention_kernels._check_sinks(sinks, q)
     return _AttentionVarlenSinks.apply(q, k, v, sinks, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k, tuple(window_size))
+
+
+def backward_varlen_d64(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, sinks=None, window_size=(-1, -1), causal=False, timed=False,
+                        cu_seqlens_k=None, max_seqlen_k=None):
+    """The backward of forward_varlen_d64: dQ, dK, dV and, with sinks, dsinks from that forward's o and lse under the
+    same sinks and window, at the scale 1 / sqrt(64) -> (dq, dk, dv, dsinks[, ms]); dsinks is fp32 of shape (n_heads,), or None when
+    sinks is None.  Every argument is backward_varlen_sinks's of that name; MHA, GQA and MQA (dk, dv have n_kv_heads heads).  A row
+    that sees no key gets dq = 0; a key no row sees gets dk = dv = 0, written; sinks[h] = -inf gives dsinks[h] = 0.  Kernels of their
+    own: 32 keys / rows per wave, two waves per SIMD.  Deterministic.  A bad window_size is a ValueError, a bad sinks or another
+    d_head a RuntimeError.  No soft-capping."""
+    return flash_attention_kernels.backward_varlen_d64(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, sinks, window_size, causal=causal,
+                                                       timed=timed, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
+
+
+class _AttentionVarlenD64(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, sinks, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k, window_size=(-1, -1)):
+        if _varlen_needs_copy(q):
+            q = q.contiguous()
+        if _varlen_needs_copy(k) or _varlen_needs_copy(v) or v.stride() != k.stride():
+            k, v = k.contiguous(), v.contiguous()
+        o, lse = forward_varlen_d64(q, k, v, cu_seqlens, max_seqlen, sinks, causal=causal, cu_seqlens_k=cu_seqlens_k,
+                                    max_seqlen_k=max_seqlen_k, window_size=window_size)
+        ctx.qk, ctx.sunk = cu_seqlens_k is not None, sinks is not None
+        ctx.save_for_backward(q, k, v, o, lse, cu_seqlens, *((sinks,) if ctx.sunk else ()), *((cu_seqlens_k,) if ctx.qk else ()))
+        ctx.max_seqlen, ctx.max_seqlen_k, ctx.causal, ctx.window_size = max_seqlen, max_seqlen_k, causal, tuple(window_size)
+        return o
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, o, lse, cu_seqlens = ctx.saved_tensors[:6]
+        sinks = ctx.saved_tensors[6] if ctx.sunk else None
+        cu_seqlens_k = ctx.saved_tensors[-1] if ctx.qk else None
+        dq, dk, dv, dsinks = backward_varlen_d64(q, k, v, o, lse, dout.contiguous(), cu_seqlens, ctx.max_seqlen, sinks, ctx.window_size,
+                                                 causal=ctx.causal, cu_seqlens_k=cu_seqlens_k, max_seqlen_k=ctx.max_seqlen_k)
+        return dq, dk, dv, dsinks, None, None, None, None, None, None
+
+
+def attention_varlen_d64(q, k, v, cu_seqlens, max_seqlen, sinks=None, causal=False, cu_seqlens_k=None, max_seqlen_k=None, *,
+                         window_size=(-1, -1)):
+    """attention_varlen_sinks at d_head = 64, with gradients for q, k, v and (where given) sinks (gpt-oss's attention at
+    its own head dimension): forward_varlen_d64 and backward_varlen_d64 under one window, at the scale 1 / sqrt(64).  sinks: None (no
+    sinks, no gradient for them), or (n_heads,) on q's device, fp32 or q's dtype -- a 16-bit parameter is converted to fp32 here,
+    outside the autograd function, so its gradient comes back in its own dtype.  Every other argument is attention_varlen_sinks's.
+    A bad window_size is a ValueError before any tensor is looked at, a bad sinks or another d_head a RuntimeError."""
+    flash_attention_kernels._window(window_size, causal)
+    if (cu_seqlens_k is None) != (max_seqlen_k is None):
+        raise ValueError("cu_seqlens_k and max_seqlen_k go together: give both (separate Q and K / V lengths) or neither")
+    if sinks is not None:
+        if isinstance(sinks, torch.Tensor) and isinstance(q, torch.Tensor) and sinks.dtype == q.dtype and sinks.dtype != torch.float32:
+            sinks = sinks.float()
+        if isinstance(sinks, torch.Tensor) and sinks.dim() == 1 and not sinks.is_contiguous():
+            sinks = sinks.contiguous()
+        flash_attention_kernels._check_sinks(sinks, q)
+    return _AttentionVarlenD64.apply(q, k, v, sinks, cu_seqlens, max_seqlen, causal, cu_seqlens_k, max_seqlen_k, tuple(window_size))

@@ -396,9 +396,9 @@ def forward_varlen_d64(q, k, v, cu_seqlens, max_seqlen, sinks=None, causal=False
     """forward_varlen_sinks at d_head = 64 (fa_fwd_launch_varlen_qk_d64): q (total_q, n_heads, 64), k and v
     (total_k, n_kv_heads, 64); the logits' scale is 1 / sqrt(64).  Every other argument is forward_varlen_sinks's, with its meaning,
     checks and defaults (one range given: on both sides), but sinks may be None: no sinks, the bits of a tensor of -inf.  -> (o, lse[, ms]),
-    lse fp32 (n_heads, total_q).  A kernel of its own (256 rows per workgroup); forward only.  A bad window_size is a ValueError before
-    any tensor is looked at, a bad sinks or another d_head a RuntimeError before the library is loaded.  Not here, and so without a
-    parameter: soft-capping, a backward."""
+    lse fp32 (n_heads, total_q).  A kernel of its own (256 rows per workgroup).  A bad window_size is a ValueError before
+    any tensor is looked at, a bad sinks or another d_head a RuntimeError before the library is loaded.  The gradients are
+    backward_varlen_d64's (attention_varlen_d64 pairs the two).  Not here, and so without a parameter: soft-capping."""
     window = _window(window_size, causal)
     if sinks is not None:
         _check_sinks(sinks, q)
@@ -522,14 +522,36 @@ def backward_varlen_sinks(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, sinks, 
     return _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, None, sinks)
 
 
+def backward_varlen_d64(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, sinks=None, window_size=(-1, -1), causal=False, timed=False,
+                        cu_seqlens_k=None, max_seqlen_k=None):
+    """The backward of forward_varlen_d64 (fa_bwd_launch_varlen_qk_d64): dQ, dK, dV and, with sinks, dsinks from ITS o
+    and lse under the same sinks and window_size, at the scale 1 / sqrt(64).  q, o, dout (total_q, n_heads, 64), k and v
+    (total_k, n_kv_heads, 64); every other argument is backward_varlen_sinks's, with its meaning, checks and defaults (one range
+    given: on both sides), but sinks may be None: no sinks, the dq, dk, dv of a tensor of -inf.  -> (dq, dk, dv, dsinks[, ms]); dk and
+    dv have n_kv_heads heads, dsinks is fp32 (n_heads,), summed in a fixed order, or None when sinks is None.  A row that sees no
+    key gets dq = 0 and adds exactly 0 to dsinks; a key no row sees gets dk = dv = 0, written; sinks[h] = -inf gives dsinks[h] = 0.
+    Kernels of their own (128 keys / rows per workgroup, two workgroups per CU); deterministic, graph-capturable, the host reads no
+    device array.  A bad window_size is a ValueError before any tensor is looked at, a bad sinks or another d_head a RuntimeError
+    before the library is loaded.  Not here: soft-capping."""
+    window = _window(window_size, causal)
+    if sinks is not None:
+        _check_sinks(sinks, q)
+    return _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, None, sinks,
+                            d_head=64)
+
+
 def _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, cap=None,
-                     sinks=None):
+                     sinks=None, d_head=128):
     """backward_varlen (window None), backward_varlen_window (window (left, right): the two-range arguments, given or not),
-    backward_varlen_softcap (cap a float: the two-range arguments and a window, (-1, -1) where none is given) and
-    backward_varlen_sinks (sinks a checked tensor: as with a cap, and dsinks behind dv in the result)"""
+    backward_varlen_softcap (cap a float: the two-range arguments and a window, (-1, -1) where none is given),
+    backward_varlen_sinks (sinks a checked tensor: as with a cap, and dsinks behind dv in the result) and, d_head=64,
+    backward_varlen_d64 (sinks a checked tensor or None: dsinks, or None, behind dv)"""
     qk = _qk_sides(cu_seqlens_k, max_seqlen_k)
     _check_varlen(q, k, v, cu_seqlens, max_seqlen, others=((o, "o"), (dout, "dout"), (lse, "lse")),
                   cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k)
+    d64 = d_head == 64   # (the entry, not the tensor: backward_varlen_sinks on a 64-wide q is still the library's refusal)
+    if d64 and q.shape[2] != 64:
+        raise RuntimeError(f"backward_varlen_d64 supports d_head = 64 only (got {q.shape[2]})")
     total, n_heads, d_head = q.shape
     total_k, n_kv = k.shape[0], k.shape[1]
     total_name = "total_q" if qk else "total_tokens"
@@ -553,10 +575,18 @@ def _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, time
         dtype=15 if q.dtype == torch.bfloat16 else 5, causal=1 if causal else 0, varlen=sides[0],
     )
     dsinks = None
-    if qk or window is not None or cap is not None or sinks is not None:
+    if d64 or qk or window is not None or cap is not None or sinks is not None:
         args = _capi.FaBwdVarlenQKArgs(struct_size=ctypes.sizeof(_capi.FaBwdVarlenQKArgs), varlen_k=sides[-1], **fields)
         workspace_bytes, launch = lib.fa_bwd_varlen_qk_workspace_bytes, lib.fa_bwd_launch_varlen_qk
-        if sinks is not None:
+        if d64:
+            if sinks is not None:   # (no rows on either side: as below)
+                dsinks = (torch.empty if total or total_k else torch.zeros)((n_heads,), dtype=torch.float32, device=q.device)
+            w, sk = _capi.make_window(*(window or (-1, -1))), (None if sinks is None else _capi.make_sinks(sinks.data_ptr(), n_heads))
+            workspace_bytes = lib.fa_bwd_varlen_qk_d64_workspace_bytes
+            launch = lambda a, stream, ms: lib.fa_bwd_launch_varlen_qk_d64(   # noqa: E731
+                a, ctypes.byref(w), None if sk is None else ctypes.byref(sk), None if dsinks is None else ctypes.c_void_p(dsinks.data_ptr()),
+                stream, ms)
+        elif sinks is not None:
             # (no rows on either side: the launch returns at once and writes nothing -- the sum over no rows is 0)
             dsinks = (torch.empty if total or total_k else torch.zeros)((n_heads,), dtype=torch.float32, device=q.device)
             w, sk = _capi.make_window(*(window or (-1, -1))), _capi.make_sinks(sinks.data_ptr(), n_heads)
@@ -580,7 +610,7 @@ def _backward_varlen(q, k, v, o, lse, dout, cu_seqlens, max_seqlen, causal, time
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
         ms = ctypes.c_float(0.0)
         _capi.check(launch(ctypes.byref(args), stream, ctypes.byref(ms) if timed else None))
-    grads = (dq, dk, dv) if sinks is None else (dq, dk, dv, dsinks)
+    grads = (dq, dk, dv, dsinks) if d64 or sinks is not None else (dq, dk, dv)
     return grads + (float(ms.value),) if timed else grads
 
 

@@ -969,7 +969,8 @@ int fa_decode_d64_launch(const fa_decode_args *args, const fa_window *window, co
  * workgroup, grid n_seqs * n_heads * ceil(max_seqlen_q / 256).  The lengths' clamping, the window's rule, the row without keys
  * (o = 0, lse = z or -inf) and the fetch contract are the siblings'.  No workspace, no split, no atomics: the same bits for the
  * same inputs, and the cache form's bits are the packed form's on the gathered keys.  The host reads no device array;
- * graph-capturable; opts->ms is timed by the launch's own events.  Not here: fp8 caches, soft-capping, a backward.
+ * graph-capturable; opts->ms is timed by the launch's own events.  Not here: fp8 caches, soft-capping.  The
+ * backward of the packed form: fa_bwd_launch_varlen_qk_d64, below.
  */
 int fa_fwd_varlen_qk_d64_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
 int fa_fwd_launch_varlen_qk_d64(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
@@ -979,6 +980,29 @@ int fa_fwd_varlen_kvcache_d64_supported(const fa_fwd_config *cfg, const fa_fwd_o
 int fa_fwd_launch_varlen_kvcache_d64(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
                                      const fa_kvcache_layout *cache, const fa_window *window, const fa_sinks *sinks /* may be null */,
                                      const fa_fwd_opts *opts, float *lse, void *stream);
+
+/*
+ * The packed backward at d_head = 64 (ABI 6, additive): fa_bwd_launch_varlen_qk_sinks with args->d_head = 64 -- dq, dk,
+ * dv (and, with sinks, dsinks) from fa_fwd_launch_varlen_qk_d64's o and lse under the same window and sinks, at the scale
+ * 1 / sqrt(64).  fa_bwd_varlen_qk_args keeps its meaning: q, o, dout, dq (total_q, n_heads, 64), k, v, dk, dv (total_k, n_kv_heads, 64),
+ * lse fp32 (n_heads, total_q).  `window` is required ((-1, -1): none; causal means right = 0); `sinks` MAY BE NULL (no sinks: dq, dk,
+ * dv are those of a tensor of -inf, and dsinks is not looked at); with sinks, dsinks (n_heads fp32, DEVICE) is required and written:
+ *     dsinks[h] = - sum over the rows of head h of exp(z - lse[h][row]) * delta[h][row],   fp32, summed in a fixed order.
+ * The lengths' clamping, the bottom-right causal rule, the window's rule, the dead row (dq = 0, written; nothing of it in dK / dV or
+ * dsinks, whether its lse is -inf or z) and the unseen key (dk = dv = 0, written) are the d128 siblings'.  A kernel family of its
+ * own (fa_bwd64_kernel.hpp): 128 keys / rows per workgroup, two workgroups per CU; the dK / dV split is the siblings' rule, a
+ * function of the shape alone, and fa_bwd_varlen_qk_d64_workspace_bytes(args) sizes delta and the split's fp32 partials
+ * (n_kv_heads * split * total_k * 2 * 64 floats).  No float atomics and no waiting between workgroups: the same inputs give the
+ * same bits.  The host reads no device array; graph-capturable; `ms` is timed by the launch's own events.
+ *
+ * Refused before any HIP call, in this order: what fa_bwd_launch_varlen_qk_window refuses, with its status and words, but with
+ * args->d_head != 64 (FA_ERR_SHAPE) where that one refuses != 128; then, for a non-null fa_sinks, its rules (a null fa_sinks.sinks:
+ * FA_ERR_NULL; struct_size, n_heads: FA_ERR_SHAPE); then a null dsinks with sinks (FA_ERR_NULL).  total_q = total_k = 0 returns
+ * FA_OK without a device and writes nothing.  Not here: soft-capping, a dense (non-varlen) backward at 64.
+ */
+int64_t fa_bwd_varlen_qk_d64_workspace_bytes(const fa_bwd_varlen_qk_args *args);
+int fa_bwd_launch_varlen_qk_d64(const fa_bwd_varlen_qk_args *args, const fa_window *window, const fa_sinks *sinks /* may be null */,
+                                float *dsinks /* null iff sinks is null */, void *stream, float *ms);
 
 /*
  * The step in front of a decode: append seqlen_new new K / V rows per batch entry to the cache IN PLACE, at the positions the
