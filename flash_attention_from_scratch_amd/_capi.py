@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_varlen_qk_d64_supported", "fa_fwd_launch_varlen_qk_d64",
     "fa_fwd_varlen_kvcache_d64_supported", "fa_fwd_launch_varlen_kvcache_d64",
     "fa_bwd_varlen_qk_d64_workspace_bytes", "fa_bwd_launch_varlen_qk_d64",
+    "fa_decode_fp8_d64_supported", "fa_decode_fp8_d64_num_splits", "fa_decode_fp8_d64_workspace_bytes", "fa_decode_fp8_d64_launch",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -498,6 +499,9 @@ def load():
     # the d_head = 64 decode: the windowed entry's arguments with an fa_sinks (null = none) behind the fa_window, its own workspace query
     for suffix in ("supported", "num_splits", "workspace_bytes", "launch"):
         fn, sibling = getattr(lib, f"fa_decode_d64_{suffix}"), getattr(lib, f"fa_decode_window_{suffix}")
+        fn.restype, fn.argtypes = sibling.restype, sibling.argtypes[:2] + [ctypes.POINTER(FaSinks)] + sibling.argtypes[2:]
+        # ... and against an fp8 cache: the same over fa_decode_fp8_args
+        fn, sibling = getattr(lib, f"fa_decode_fp8_d64_{suffix}"), getattr(lib, f"fa_decode_fp8_window_{suffix}")
         fn.restype, fn.argtypes = sibling.restype, sibling.argtypes[:2] + [ctypes.POINTER(FaSinks)] + sibling.argtypes[2:]
     # the d_head = 64 prefills: the sinks forms' arguments (the fa_sinks may be null)
     for name in ("varlen_qk", "varlen_kvcache"):

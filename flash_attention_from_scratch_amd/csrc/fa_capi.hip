@@ -1869,7 +1869,8 @@ int fa_bwd_launch_varlen_qk_d64(const fa_bwd_varlen_qk_args *a, const fa_window 
 // fa_decode_args and fa_decode_fp8_args carry the same members under the same names (the fp8 struct adds its encoding and
 // descales), so one text over either struct serves the twenty-eight entry points: a planner (validate, then the split count) for the
 // twenty queries and one launch body for the eight launches (the soft-capped and the sink forms: four queries, two launches each).  What only one struct has sits in the two decode_struct_rules.
-// The four d_head = 64 entry points (fa_decode_d64_*) run through the same planner and launch body with the head dimension as a parameter.
+// The eight d_head = 64 entry points (fa_decode_d64_*, fa_decode_fp8_d64_*) run through the same planner and launch body with the head
+// dimension as a parameter.
 namespace {
 extern "C++" {   // (as for the cache's rules above; the two overloads need it as well)
 constexpr int64_t kDecodeMaxRows = 64, kDecodeWantWgs = 256, kDecodeKeysPerSplit = 256, kDecodeMaxSplits = 128, kDecodeMaxForced = 1024;
@@ -1883,7 +1884,8 @@ int decode_struct_rules(const fa_decode_fp8_args *a, CacheView &c) {
     if (a->struct_size < sizeof(fa_decode_fp8_args))
         return fail(FA_ERR_SHAPE, "fa_decode_fp8_args.struct_size (%u) is smaller than this library's (%zu)", a->struct_size,
                     sizeof(fa_decode_fp8_args));
-    if (a->kv_dtype != FA_KV_FP8_E4M3FN)
+    // (d_head = 64, fa_decode_fp8_d64_*: the fp8 side's rules come behind everything the 16-bit entry refuses -- decode_fp8_d64_rules)
+    if (c.d_head != 64 && a->kv_dtype != FA_KV_FP8_E4M3FN)
         return fail(FA_ERR_DTYPE, "kv_dtype (%d) is not served: the fp8 cache is e4m3fn (FA_KV_FP8_E4M3FN)", a->kv_dtype);
     c.fp8 = true;
     cache_descales(c, *a);
@@ -1928,7 +1930,18 @@ template <class A> int decode_validate(const A *a, CacheView &c, int64_t d_head 
     if ((rc = cache_strides(c, 8)) != FA_OK) return rc;
     if (a->batch * a->n_kv_heads * kDecodeMaxForced > INT32_MAX || a->batch * a->n_heads * a->seqlen_q > INT32_MAX)
         return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
+    if (d_head == 64) return FA_OK;                           // (the fp8 side's rules: decode_fp8_d64_rules, behind the window's and the sinks')
     if ((rc = cache_descale_stride(c)) != FA_OK) return rc;   // (the fp8 side's two: nothing to refuse in a 16-bit cache)
+    return cache_fp8_strides(c);
+}
+
+// What fa_decode_fp8_d64_* refuse of the fp8 side, behind every refusal of fa_decode_d64_* in that entry's order: the encoding, the
+// descales' stride, the strides in bytes -- fa_decode_fp8_sinks_*'s words.  A 16-bit struct has nothing to refuse here.
+int decode_fp8_d64_rules(const fa_decode_args *, const CacheView &) { return FA_OK; }
+int decode_fp8_d64_rules(const fa_decode_fp8_args *a, const CacheView &c) {
+    if (a->kv_dtype != FA_KV_FP8_E4M3FN)
+        return fail(FA_ERR_DTYPE, "kv_dtype (%d) is not served: the fp8 cache is e4m3fn (FA_KV_FP8_E4M3FN)", a->kv_dtype);
+    if (const int rc = cache_descale_stride(c)) return rc;
     return cache_fp8_strides(c);
 }
 
@@ -1955,12 +1968,13 @@ template <class A> int64_t decode_splits(const A *a, const CacheView &c, const f
 // place; the sinks do not enter the split rule either.  `d_head`: 128, or 64 for fa_decode_d64_* (windowed always, sunk where it has sinks).
 template <class A>
 DecodePlan decode_plan(const A *a, bool windowed, const fa_window *w, bool capped = false, const fa_softcap *cap = nullptr, bool sunk = false,
-                       const fa_sinks *sk = nullptr, int64_t d_head = 128) {
+                       const fa_sinks *sk = nullptr, int64_t d_head = 128, bool fp8_d64_rules = true) {
     DecodePlan p;
     p.status = decode_validate(a, p.cache, d_head);
     if (p.status == FA_OK && windowed) p.status = window_validate(w, a->causal, p.cache.capacity());
     if (p.status == FA_OK && capped) p.status = softcap_validate(cap);
     if (p.status == FA_OK && sunk) p.status = sinks_validate(sk, a->n_heads, false, nullptr);
+    if (p.status == FA_OK && d_head == 64 && fp8_d64_rules) p.status = decode_fp8_d64_rules(a, p.cache);   // (the launch asks them last)
     if (p.status == FA_OK) p.splits = decode_splits(a, p.cache, windowed ? w : nullptr);
     return p;
 }
@@ -2023,11 +2037,12 @@ int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_
     if (!a) return fail(FA_ERR_NULL, "null pointer argument");
     if (!a->q || !a->k || !a->v || !a->o) return fail(FA_ERR_NULL, "null tensor pointer (q, k, v and o are all needed)");
     if (!a->cache_seqlens) return fail(FA_ERR_NULL, "cache_seqlens is null: a DEVICE pointer to batch int32 lengths is needed");
-    const DecodePlan p = decode_plan(a, windowed, w, false, nullptr, false, nullptr, d_head);
+    const DecodePlan p = decode_plan(a, windowed, w, false, nullptr, false, nullptr, d_head, false);
     if (p.status != FA_OK) return p.status;
     if (a->batch == 0) {   // (nothing to do -- behind the cap's own rules, as in the packed form)
         if (capped && softcap_validate(cap) != FA_OK) return softcap_validate(cap);
         if (sunk && sinks_validate(sk, a->n_heads, false, nullptr) != FA_OK) return sinks_validate(sk, a->n_heads, false, nullptr);
+        if (d_head == 64 && decode_fp8_d64_rules(a, p.cache) != FA_OK) return decode_fp8_d64_rules(a, p.cache);
         if (ms) *ms = 0.0f;
         return FA_OK;
     }
@@ -2043,6 +2058,7 @@ int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_
     if (windowed && (rc = cache_descale_alignment(c)) != FA_OK) return rc;
     if (capped && (rc = softcap_validate(cap)) != FA_OK) return rc;
     if (sunk && (rc = sinks_validate(sk, a->n_heads, false, nullptr)) != FA_OK) return rc;
+    if (d_head == 64 && (rc = decode_fp8_d64_rules(a, p.cache)) != FA_OK) return rc;   // (fa_decode_fp8_d64_launch: the fp8 side, behind the 16-bit entry's refusals)
     DeviceState *dev = current_device(&rc);
     if (!dev) return rc;
     fa::DecodeFp8WindowArgs k;   // (the widest form: the other three's arguments are its members)
@@ -2063,9 +2079,10 @@ int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_
     const fa::DecodeSinksArgs kz = {kw, sunk ? sk->sinks : nullptr};
     const fa::DecodeFp8SinksArgs kz8 = {k, kz.sinks};
     const fa::Decode64Args k64 = {k.f.d, k.left, k.right, kz.sinks};
+    const fa::Decode64Fp8Args k64f = {k64, k.f.k_descale, k.f.v_descale, k.f.ds_bs};
     const hipStream_t s = (hipStream_t)stream;
     return enqueue_timed([&] {
-        if (d_head == 64) return fa::decode64_enqueue(k64, a->dtype, s);
+        if (d_head == 64) return c.fp8 ? fa::decode64_fp8_enqueue(k64f, a->dtype, s) : fa::decode64_enqueue(k64, a->dtype, s);
         if (sunk) return c.fp8 ? fa::decode_fp8_sinks_enqueue(kz8, a->dtype, s) : fa::decode_sinks_enqueue(kz, a->dtype, s);
         if (capped) return c.fp8 ? fa::decode_fp8_softcap_enqueue(ks8, a->dtype, s) : fa::decode_softcap_enqueue(ks, a->dtype, s);
         if (c.fp8) return windowed ? fa::decode_fp8_window_enqueue(k, a->dtype, s) : fa::decode_fp8_enqueue(k.f, a->dtype, s);
@@ -2162,6 +2179,23 @@ int64_t fa_decode_d64_workspace_bytes(const fa_decode_args *a, const fa_window *
 }
 int fa_decode_d64_launch(const fa_decode_args *a, const fa_window *w, const fa_sinks *sinks, void *stream, float *ms) {
     return decode_launch(a, true, w, "fa_decode_d64_workspace_bytes", stream, ms, false, nullptr, sinks != nullptr, sinks, 64, "args, window, sinks");
+}
+
+// ... against an fp8 (e4m3fn) cache: fa_decode_fp8_args with d_head = 64, otherwise fa_decode_d64_*'s parameters, planner,
+// split rule, workspace and launch body; the kernels of fa_decode64_fp8.hip.  Refused before any HIP call: what fa_decode_d64_* refuse,
+// in their order and words, then the fp8 side as fa_decode_fp8_sinks_* word it (kv_dtype, the descales' stride and alignment, strides in
+// bytes).
+int fa_decode_fp8_d64_supported(const fa_decode_fp8_args *a, const fa_window *w, const fa_sinks *sinks) {
+    return decode_plan(a, true, w, false, nullptr, sinks != nullptr, sinks, 64).status == FA_OK;
+}
+int fa_decode_fp8_d64_num_splits(const fa_decode_fp8_args *a, const fa_window *w, const fa_sinks *sinks) {
+    return plan_splits(decode_plan(a, true, w, false, nullptr, sinks != nullptr, sinks, 64));
+}
+int64_t fa_decode_fp8_d64_workspace_bytes(const fa_decode_fp8_args *a, const fa_window *w, const fa_sinks *sinks) {
+    return plan_workspace(a, decode_plan(a, true, w, false, nullptr, sinks != nullptr, sinks, 64));
+}
+int fa_decode_fp8_d64_launch(const fa_decode_fp8_args *a, const fa_window *w, const fa_sinks *sinks, void *stream, float *ms) {
+    return decode_launch(a, true, w, "fa_decode_fp8_d64_workspace_bytes", stream, ms, false, nullptr, sinks != nullptr, sinks, 64, "args, window, sinks");
 }
 
 // ---- the KV-cache append in front of a decode --------------------------------------------------------------------------------

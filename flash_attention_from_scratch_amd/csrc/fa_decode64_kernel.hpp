@@ -44,6 +44,44 @@
 //    rows, 64) fp32 and lse are sink-free, and fa_decode64_combine_kernel, 64 threads with one d each, takes z as the first member
 //    of its fixed-order sums.  No atomics: the same bits for the same inputs and the same num_splits.
 //  * scale = 1 / sqrt(64); c = scale * log2(e), rounded once from the double product.
+//
+// What an fp8 cache changes (OCP e4m3fn, Decode64Fp8Args: the arguments above and one fp32 descale per (batch entry, K / V head) and
+// tensor; `if constexpr (FP8)` marks every site).  A key is 64 bytes, not 128, and everything above that was argued
+// from 128 is argued again here.  Q, O, the grid, the four waves, NT, the transposed products, the split of the key tiles, the units'
+// round-robin, the merge, the sink-free partials, fa_decode64_combine_kernel, the window and the fetch contract are as above, word
+// for word (strides and offsets of the cache count bytes).
+//  * K: ONE 16-byte load per lane and 16-key tile serves both k-steps.  Lane (li, g) loads key 16 kt + li, d 16 g .. 16 g + 15: the
+//    four lanes of a key ask for its whole 64-byte row, so a wave load covers sixteen whole rows (the 16-bit form's covers sixteen
+//    half rows, and needs its second load for the other halves).  Bytes 8 s .. 8 s + 7 of the load are the lane's A operand of k-step
+//    s: element e of k-step s in lane group g multiplies d = 16 g + 8 s + e.  Q^T is loaded once in the same permutation of d (a dot
+//    product does not mind the order of its terms).  K stays fp8 in the prefetch registers -- 4 VGPRs per key tile against 8 -- and
+//    is converted with cvt_fp8x8 (v_cvt_scalef32_pk_{bf16,f16}_fp8, scale 1: every finite e4m3fn value is exact in both) right before
+//    its two MFMAs.
+//  * V: whole 64-byte rows, four lanes per key, sixteen keys per load: lane (q = (lane >> 2) & 3, c = lane & 3) of lane group g
+//    and load i takes key 16 i + vk8, d 16 c .. + 15, vk8 = 8 (g >> 1) + 2 (g & 1) + (q & 1) + 4 (q >> 1).  It converts its 16
+//    values and writes them to row 16 i + vk8 of the wave's 16-bit image as two 16-byte writes, columns 32 c and 32 c + 16 (bytes).
+//    The image, its pitch VROW = 160 and the transposed reads are the 16-bit form's: nothing of the read argument changes.
+//    Writes: sixteen lanes (one lane group g, what a 16-byte write serves per pass) now cover FOUR rows, and one write of a lane
+//    covers only half of the lane's 32 bytes.  In 16-byte slots modulo the banks' 256 bytes, row k starts at 10 k mod 16 -- always
+//    even -- and a lane's two halves are slots 10 k + 2 c + {0, 1}.  Written "low halves first", a pass would put its sixteen lanes
+//    on the eight even slots: a two-way conflict under ANY map of lanes to keys, which is why the 16-bit form's pairing alone does
+//    not carry over.  So the lanes of odd q write their HIGH half first (h = q & 1: the first write goes to slot 10 k + 2 c + h, the
+//    second to 10 k + 2 c + 1 - h; the halves are picked on the fp8 words, four v_cndmask per load, before the conversion).  A pass
+//    then wants two rows on the even slots and two on the odd ones, each pair covering all eight: rows k and k' cover disjoint
+//    halves of the even (odd) slots iff 10 (k - k') = 8 mod 16, i.e. k - k' = 4 mod 8 -- the 16-bit form's pairs (k, k + 4) again.
+//    vk8 deals a pass the rows {k, k + 4} with h = 0 and {k + 1, k + 5} with h = 1, k = 8 (g >> 1) + 2 (g & 1): group 0 writes
+//    rows 0 4 (slots 0 2 4 6, 8 10 12 14) and 1 5 (11 13 15 1, 3 5 7 9) -- every bank once, in both writes.
+//  * Prefetch: a 32-key unit is 2 K and 2 V loads of 16 bytes per lane (16-bit: 4 and 4) and 16 VGPRs (32).  With the 16-bit form's
+//    one unit ahead a wave would keep half the bytes in flight, so the distance is a parameter of this text beside UNIT: DIST = 1 or
+//    2 units ahead, DIST + 1 register sets taken in turn.  At NT = 4 and UNIT = 32: Q^T 32, O^T 64, S^T 32 and three sets of 16.
+//    (32, 1), (32, 2) and (64, 1) are instantiated and measured side by side ((64, 2) would keep twice the others'
+//    most in flight and, at NT = 4, needs scratch: not built); FA_DECODE64_UNIT and FA_DECODE64_AHEAD name one outright.  Where the
+//    cache streams the three are within the A/A spread of each other; under a short window (32, 1) is the fastest: it is shipped.
+//  * Descales: one scalar each per workgroup, read once; a null pointer means 1; no address depends on either.  k_descale folds
+//    into c = k_descale * (log2(e) / 8) (a float product; with k_descale = 1 the 16-bit form's c): S^T and m stay in raw logit
+//    units, and lse = m * k_descale / 8 + log l (a positive descale keeps the maximum the maximum).  v_descale folds into the final
+//    1 / l.  The sink meets the dequantized logit: ms = m * k_descale / 8 in the epilogue; the partials' lse carry it too, so the
+//    combine kernel is unchanged.  A row without keys: o = 0, lse = z.
 #pragma once
 #include "fa_decode_kernel.hpp"
 
@@ -55,31 +93,54 @@ struct Decode64Args {
     const float *sinks;     // (n_heads) fp32, DEVICE, or null
 };
 
+// the 16-bit form's arguments (k, v: the fp8 bytes; kv_*: strides in bytes) and the descales
+struct Decode64Fp8Args {
+    Decode64Args w;
+    const float *k_descale, *v_descale;   // (batch, n_kv_heads), row stride ds_bs; null = 1
+    int64_t ds_bs;
+};
+
 namespace decode64 {
 constexpr int D = 64, TILE = 64, NWAVES = 4, THREADS = NWAVES * 64;
 constexpr int VROW = 160;              // bytes per key of the V image (the argument is at the head of this file)
 constexpr int UNIT_SHIPPED = 32;       // keys per wave visit: 32 or 64, measured side by side
+constexpr int FP8_UNIT_SHIPPED = 32, FP8_DIST_SHIPPED = 1;   // the fp8 form's unit and prefetch distance, measured side by side
+__host__ __device__ inline const Decode64Args &common(const Decode64Args &a) { return a; }
+__host__ __device__ inline const Decode64Args &common(const Decode64Fp8Args &a) { return a.w; }
+template <class ARGS> constexpr bool is_fp8 = std::is_same_v<ARGS, Decode64Fp8Args>;
 }  // namespace decode64
 
-template <int DT, int NT, bool PAGED, int UNIT>
-__global__ void __launch_bounds__(decode64::THREADS) fa_decode64_split_kernel(const Decode64Args args) {
+// One text for both caches: ARGS names the form, DIST the units a wave's loads run ahead of its work (16-bit: 1).  (The two are the
+// kernel's own parameters, defaulted -- behind a shared body called from two kernels the 16-bit kernels' instructions come out in
+// another order; so they keep theirs, and only their mangled names grow by the two defaults.)
+template <int DT, int NT, bool PAGED, int UNIT, class ARGS = Decode64Args, int DIST = 1>
+__global__ void __launch_bounds__(decode64::THREADS) fa_decode64_split_kernel(const ARGS full) {
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
     using namespace decode64;
+    constexpr bool FP8 = is_fp8<ARGS>;
     static_assert(UNIT == 64 || UNIT == 32, "a unit is a whole 64-key tile or half of one");
-    constexpr int KS = D / 32, DT16 = D / 16, KT = UNIT / 16, VL = UNIT / 8, UPT = TILE / UNIT;   // (VL: V loads, UPT: units per tile)
+    static_assert(DIST == 1 || (FP8 && DIST == 2), "one unit ahead; an fp8 cache: one or two");
+    const Decode64Args &args = common(full);
+    constexpr int KS = D / 32, DT16 = D / 16, KT = UNIT / 16, VL = FP8 ? UNIT / 16 : UNIT / 8, UPT = TILE / UNIT;   // (VL: V loads, UPT: units per tile)
     constexpr int VBYTES = UNIT * VROW;   // one wave's image
     constexpr int MERGE = NT * DT16 * 64 * 16;   // one wave's accumulators
     constexpr int MAIN = NWAVES * VBYTES > MERGE ? NWAVES * VBYTES : MERGE;
     __shared__ __attribute__((aligned(16))) char smem[MAIN + (NWAVES + 1) * NT * 16 * 4];
     const DecodeArgs &a = args.d;
-    struct KRegs { vec8 r[KT][KS]; };   // one 64-key unit in the prefetch registers: 16 bytes per lane and load
-    struct VRegs { s16x8 r[VL]; };
+    struct KRegs16 { vec8 r[KT][KS]; };   // one 64-key unit in the prefetch registers: 16 bytes per lane and load
+    struct KRegs8 { u32x4 r[KT]; };       // (fp8: one load per key tile, both k-steps)
+    using KRegs = std::conditional_t<FP8, KRegs8, KRegs16>;
+    struct VRegs { std::conditional_t<FP8, u32x4, s16x8> r[VL]; };
+    [[maybe_unused]] const uint8_t *const k8 = (const uint8_t *)a.k, *const v8 = (const uint8_t *)a.v;   // fp8: the cache's bytes
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int li = lane & 15, g = lane >> 4;
-    const int vc = lane & 7, vk = (lane >> 4) + 4 * ((lane >> 3) & 1);   // V's load shape: key 8 i + vk, d 8 vc ..
+    // V's load shape: key 8 i + vk, d 8 vc .. (fp8: key 16 i + vk, d 16 vc .., and vh: the lane writes its high half first)
+    const int vc = FP8 ? lane & 3 : lane & 7;
+    const int vk = FP8 ? 8 * (g >> 1) + 2 * (g & 1) + ((lane >> 2) & 1) + 4 * ((lane >> 3) & 1) : (lane >> 4) + 4 * ((lane >> 3) & 1);
+    [[maybe_unused]] const bool vh = (lane >> 2) & 1;
     const int nsp = a.num_splits;
     const int split = blockIdx.x % nsp, kvh = (blockIdx.x / nsp) % a.n_kv_heads, b = blockIdx.x / (nsp * a.n_kv_heads);
 
@@ -97,7 +158,13 @@ __global__ void __launch_bounds__(decode64::THREADS) fa_decode64_split_kernel(co
     const int n_units = (len + UNIT - 1) / UNIT;
     const int u_begin = UPT * t0 > lo_min / UNIT ? UPT * t0 : lo_min / UNIT, u_end = UPT * t1 < n_units ? UPT * t1 : n_units;
 
-    // Q^T, resident; pos: the row's position p = len - seqlen_q + query position, from which each unit derives the row's bounds
+    [[maybe_unused]] float kd = 1.0f, vd = 1.0f;
+    if constexpr (FP8) {
+        kd = full.k_descale ? full.k_descale[(int64_t)b * full.ds_bs + kvh] : 1.0f;
+        vd = full.v_descale ? full.v_descale[(int64_t)b * full.ds_bs + kvh] : 1.0f;
+    }
+
+    // Q^T, resident (fp8: in K's permutation of d); pos: the row's position p = len - seqlen_q + query position, from which each unit derives the row's bounds
     // p - w_left and min(len, p + w_right + 1) -- neither needs its clamp at 0, keys are not negative
     vec8 Qr[NT][KS];
     int pos[NT];
@@ -109,14 +176,20 @@ __global__ void __launch_bounds__(decode64::THREADS) fa_decode64_split_kernel(co
         const int r = nt * 16 + li;
         const bool valid = r < a.rows;
         const int rr = valid ? r : 0, qi = rr / a.group, qh = kvh * a.group + rr % a.group;
-        const uint16_t *qp = a.q + (int64_t)b * a.q_bs + (int64_t)qi * a.q_ss + (int64_t)qh * a.q_hs + g * 8;
+        const uint16_t *qp = a.q + (int64_t)b * a.q_bs + (int64_t)qi * a.q_ss + (int64_t)qh * a.q_hs + g * (FP8 ? 16 : 8);
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) Qr[nt][ks] = *(const vec8 *)(qp + ks * 32);
+        for (int ks = 0; ks < KS; ++ks) Qr[nt][ks] = *(const vec8 *)(qp + ks * (FP8 ? 8 : 32));
         pos[nt] = !valid ? -(1 << 30) - 66 : len - a.seqlen_q + qi;   // (a padded row: p + w_right + 1 < 0)
     }
 
-    const float scale = 1.0f / __builtin_sqrtf((float)D);
-    const float c = (float)((double)scale * 1.4426950408889634074);
+    float scale, c;   // logits (fp8: raw logits) -> logits, and -> the exponent of exp2
+    if constexpr (FP8) {
+        scale = kd * 0.125f;
+        c = kd * 0.18033688011112042592f;   // log2(e) / 8
+    } else {
+        scale = 1.0f / __builtin_sqrtf((float)D);
+        c = (float)((double)scale * 1.4426950408889634074);
+    }
     const float ninf = -__builtin_inff();
 
     f32x4 O[NT][DT16];
@@ -155,22 +228,38 @@ __global__ void __launch_bounds__(decode64::THREADS) fa_decode64_split_kernel(co
             ko = ko < first ? first : ko;
             return ko < last ? ko : last;
         };
+        if constexpr (FP8) {
 #pragma unroll
-        for (int kt = 0; kt < KT; ++kt) {
-            const uint16_t *kp = a.k + base + (int64_t)(row0 + clamp_key(kt * 16 + li)) * a.kv_ss + g * 8;
+            for (int kt = 0; kt < KT; ++kt) Kr.r[kt] = *(const u32x4 *)(k8 + base + (int64_t)(row0 + clamp_key(kt * 16 + li)) * a.kv_ss + g * 16);
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) Kr.r[kt][ks] = *(const vec8 *)(kp + ks * 32);
+            for (int i = 0; i < VL; ++i) Vr.r[i] = *(const u32x4 *)(v8 + base + (int64_t)(row0 + clamp_key(i * 16 + vk)) * a.kv_ss + vc * 16);
+        } else {
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt) {
+                const uint16_t *kp = a.k + base + (int64_t)(row0 + clamp_key(kt * 16 + li)) * a.kv_ss + g * 8;
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) Kr.r[kt][ks] = *(const vec8 *)(kp + ks * 32);
+            }
+#pragma unroll
+            for (int i = 0; i < VL; ++i) Vr.r[i] = *(const s16x8 *)(a.v + base + (int64_t)(row0 + clamp_key(i * 8 + vk)) * a.kv_ss + vc * 8);
         }
-#pragma unroll
-        for (int i = 0; i < VL; ++i) Vr.r[i] = *(const s16x8 *)(a.v + base + (int64_t)(row0 + clamp_key(i * 8 + vk)) * a.kv_ss + vc * 8);
     };
 
     char *vs = smem + wave * VBYTES;
-    char *vwr = vs + vk * VROW + vc * 16;
+    char *vwr = vs + vk * VROW + vc * (FP8 ? 32 : 16);   // (fp8: the lane's 32 bytes; its first write goes to + 16 vh, its second to + 16 (1 - vh))
     const char *vrd = vs + (4 * g + (li >> 2)) * VROW + (li & 3) * 8;   // lane 4 q + p of a group: row q, columns 4 p ..
     auto compute_unit = [&](int u, const KRegs &Kr, const VRegs &Vr) {
+        if constexpr (FP8) {
 #pragma unroll
-        for (int i = 0; i < VL; ++i) *(s16x8 *)(vwr + i * 8 * VROW) = Vr.r[i];
+            for (int i = 0; i < VL; ++i) {
+                const u32x4 w = Vr.r[i];
+                *(vec8 *)(vwr + i * 16 * VROW + (vh ? 16 : 0)) = cvt_fp8x8<DT>(vh ? w[2] : w[0], vh ? w[3] : w[1]);
+                *(vec8 *)(vwr + i * 16 * VROW + (vh ? 0 : 16)) = cvt_fp8x8<DT>(vh ? w[0] : w[2], vh ? w[1] : w[3]);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < VL; ++i) *(s16x8 *)(vwr + i * 8 * VROW) = Vr.r[i];
+        }
         f32x4 S[NT][KT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
@@ -179,9 +268,13 @@ __global__ void __launch_bounds__(decode64::THREADS) fa_decode64_split_kernel(co
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
+            for (int ks = 0; ks < KS; ++ks) {
+                vec8 ka;
+                if constexpr (FP8) ka = cvt_fp8x8<DT>(Kr.r[kt][2 * ks], Kr.r[kt][2 * ks + 1]);
+                else ka = Kr.r[kt][ks];
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) S[nt][kt] = E::mfma16(Kr.r[kt][ks], Qr[nt][ks], S[nt][kt]);
+                for (int nt = 0; nt < NT; ++nt) S[nt][kt] = E::mfma16(ka, Qr[nt][ks], S[nt][kt]);
+            }
         vec8 Pb[NT][UNIT / 32];
         const int key_g = u * UNIT + 4 * g;
 #pragma unroll
@@ -233,7 +326,28 @@ __global__ void __launch_bounds__(decode64::THREADS) fa_decode64_split_kernel(co
 
     // Two register sets, A and B, taken in turn (the loop is unrolled by two, so no set is ever copied into the other): a unit's
     // loads are issued before the previous unit's work and waited for with the next unit's loads still in flight.
-    {
+    // fp8: DIST + 1 sets taken in turn the same way; set s holds the unit of step s, and its loads were issued DIST steps before.
+    if constexpr (FP8) {
+        KRegs Kr[DIST + 1];
+        VRegs Vr[DIST + 1];
+        int u = u_begin + wave;
+        // (the calls are inlined by attribute: left to its cost model, the inliner keeps the 64-row, 64-key form's compute_unit a
+        // call, with its closure and the register sets in scratch; on the lambdas themselves the attribute would reach the 16-bit kernels)
+        if (u < u_end) static_for<0, DIST>([&](auto d) __attribute__((always_inline)) {
+            [[clang::always_inline]] load_unit(u + decltype(d)::value * NWAVES, u, Kr[decltype(d)::value], Vr[decltype(d)::value]);
+        });
+        while (u < u_end) {
+            static_for<0, DIST + 1>([&](auto step) __attribute__((always_inline)) {
+                constexpr int s = decltype(step)::value, into = (s + DIST) % (DIST + 1);
+                if (u < u_end) {   // (false once: so are the steps behind it, u stays)
+                    [[clang::always_inline]] load_unit(u + DIST * NWAVES, u, Kr[into], Vr[into]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    [[clang::always_inline]] compute_unit(u, Kr[s], Vr[s]);
+                    u += NWAVES;
+                }
+            });
+        }
+    } else {
         KRegs Ka, Kb;
         VRegs Va, Vb;
         int u = u_begin + wave;
@@ -309,7 +423,8 @@ __global__ void __launch_bounds__(decode64::THREADS) fa_decode64_split_kernel(co
             const float z = args.sinks ? args.sinks[qh] : ninf, ms = any ? m[nt] * scale : 0.0f;
             const float M = fmaxf(ms, z);
             const float al = __expf(ms - M), l_all = __builtin_fmaf(l[nt], al, __expf(z - M));
-            const float inv = any ? al / l_all : 0.0f;
+            float inv = any ? al / l_all : 0.0f;
+            if constexpr (FP8) inv = any ? vd * al / l_all : 0.0f;
             const float lse = any ? M + __logf(l_all) : z;
             uint16_t *op = a.o + (int64_t)b * a.o_bs + (int64_t)qi * a.o_ss + (int64_t)qh * a.o_hs + 4 * g;
 #pragma unroll
@@ -321,7 +436,7 @@ __global__ void __launch_bounds__(decode64::THREADS) fa_decode64_split_kernel(co
             }
             if (a.lse && g == 0) a.lse[((int64_t)b * a.n_heads + qh) * a.seqlen_q + qi] = lse;
         } else {   // a sink-free partial: o normalised, lse = -inf for a row that saw no key in this split
-            const float inv = any ? 1.0f / l[nt] : 0.0f;
+            const float inv = any ? (FP8 ? vd : 1.0f) / l[nt] : 0.0f;
             const int64_t row = (((int64_t)split * a.batch + b) * a.n_kv_heads + kvh) * a.rows + r;
             float *pp = a.part_o + row * D + 4 * g;
 #pragma unroll
@@ -357,6 +472,7 @@ __global__ void __launch_bounds__(64) fa_decode64_combine_kernel(const Decode64A
     if (a.lse && threadIdx.x == 0) a.lse[((int64_t)b * a.n_heads + qh) * a.seqlen_q + qi] = lse;
 }
 
-hipError_t decode64_enqueue(const Decode64Args &a, int dtype, hipStream_t s);   // fa_decode64.hip
+hipError_t decode64_enqueue(const Decode64Args &a, int dtype, hipStream_t s);          // fa_decode64.hip
+hipError_t decode64_fp8_enqueue(const Decode64Fp8Args &a, int dtype, hipStream_t s);   // fa_decode64_fp8.hip
 
 }  // namespace fa

@@ -225,23 +225,27 @@ def forward_kvcache_sinks(q, k_cache, v_cache, cache_seqlens, sinks, block_table
 
 
 def forward_kvcache_d64(q, k_cache, v_cache, cache_seqlens, sinks=None, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
-                        num_splits=0, timed=False, window_size=(-1, -1)):
+                        num_splits=0, timed=False, window_size=(-1, -1), k_descale=None, v_descale=None):
     """KV-cache decode at d_head = 64 (gpt-oss's head dimension): q (batch, seqlen_q, n_heads, 64) against k_cache,
     v_cache (batch, seqlen_cache, n_kv_heads, 64) or, with block_table, pages (num_pages, page_size, n_kv_heads, 64), 16-bit in q's
     dtype, at the scale 1 / sqrt(64).  Every argument is forward_kvcache_sinks's of that name, with its meaning, checks and defaults;
     sinks may be None (no sinks: the bits of a tensor of -inf).  -> what forward_kvcache returns.  Kernels of their own, 32 keys
-    per wave visit; split-KV with a fixed-order combine, graph-capturable, the host reads no device array.  Not served at 64,
-    and so without a parameter here: fp8 caches, soft-capping, the fused append and rotary; more than 64 packed rows are refused."""
+    per wave visit; split-KV with a fixed-order combine, graph-capturable, the host reads no device array.
+    A torch.float8_e4m3fn cache (quantize_kvcache_fp8 makes one) is served with BOTH k_descale and v_descale, fp32
+    (batch, n_kv_heads) on the device: a key stands for float(k8) * k_descale[b, h], the sinks meet the dequantized logit, v_descale
+    scales o.  Without both it is a RuntimeError (pass ones for an unscaled cache); descales on a 16-bit cache are refused.  Not served
+    at 64, and so without a parameter here: soft-capping, the fused append and rotary; more than 64 packed rows are refused."""
     return flash_attention_kernels.forward_kvcache_d64(q, k_cache, v_cache, cache_seqlens, sinks=sinks, block_table=block_table, causal=causal,
                                                        return_lse=return_lse, max_seqlen_k=max_seqlen_k, num_splits=num_splits, timed=timed,
-                                                       window_size=window_size)
+                                                       window_size=window_size, k_descale=k_descale, v_descale=v_descale)
 
 
 def kvcache_d64_num_splits(q, k_cache, v_cache, cache_seqlens, sinks=None, block_table=None, causal=False, max_seqlen_k=None, num_splits=0,
-                           window_size=(-1, -1)):
+                           window_size=(-1, -1), k_descale=None, v_descale=None):
     """The split count forward_kvcache_d64 uses for these arguments: the same checks, nothing allocated, no launch."""
     return flash_attention_kernels.kvcache_d64_num_splits(q, k_cache, v_cache, cache_seqlens, sinks=sinks, block_table=block_table, causal=causal,
-                                                          max_seqlen_k=max_seqlen_k, num_splits=num_splits, window_size=window_size)
+                                                          max_seqlen_k=max_seqlen_k, num_splits=num_splits, window_size=window_size,
+                                                          k_descale=k_descale, v_descale=v_descale)
 
 
 def forward_varlen_d64(q, k, v, cu_seqlens, max_seqlen, sinks=None, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None, *,

@@ -996,49 +996,59 @@ def _forward_kvcache(q, k_cache, v_cache, cache_seqlens, block_table, causal, re
     return out[0] if len(out) == 1 else out
 
 
-def _decode_d64_args(q, k_cache, v_cache, cache_seqlens, sinks, block_table, causal, max_seqlen_k, num_splits, window_size):
-    """forward_kvcache_d64's checks, in forward_kvcache_sinks's order -> (q as the launch takes it, fa_decode_args still without o, lse
-    and workspace, the fa_window, the fa_sinks or None)."""
+def _decode_d64_args(q, k_cache, v_cache, cache_seqlens, sinks, block_table, causal, max_seqlen_k, num_splits, window_size, k_descale, v_descale):
+    """forward_kvcache_d64's checks, in forward_kvcache_sinks's order -> (q as the launch takes it, fa_decode_args or fa_decode_fp8_args
+    still without o, lse and workspace, the fa_window, the fa_sinks or None, the entry points' prefix)."""
     window = _window(window_size, causal)
     if sinks is not None:
         _check_sinks(sinks, q, q_dim=4)
-    q, args, fp8 = _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_seqlen_k, num_splits, None, None)
-    if fp8:
-        raise RuntimeError("forward_kvcache_d64 serves a 16-bit cache in q's dtype: an fp8 cache at d_head = 64 has no kernel")
-    return q, args, _capi.make_window(*(window or (-1, -1))), (None if sinks is None else _capi.make_sinks(sinks.data_ptr(), q.shape[2]))
+    # what the cache is and which descales belong to it, before where anything is (forward_varlen_kvcache's rule for fp8)
+    _need_tensors(((k_cache, "k_cache"), (v_cache, "v_cache")))
+    _CacheSide(k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, "batch", "q's").dtypes(like=None, fp8_needs_descales=(
+        "forward_kvcache_d64: an fp8 cache is not served without both k_descale and v_descale (fp32 (batch, n_kv_heads) tensors on "
+        "q's device; pass ones for an unscaled cache -- None does not mean 1 here)"))
+    q, args, fp8 = _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_seqlen_k, num_splits, k_descale, v_descale)
+    return (q, args, _capi.make_window(*(window or (-1, -1))), (None if sinks is None else _capi.make_sinks(sinks.data_ptr(), q.shape[2])),
+            "fa_decode_fp8_d64_" if fp8 else "fa_decode_d64_")
 
 
 def kvcache_d64_num_splits(q, k_cache, v_cache, cache_seqlens, sinks=None, block_table=None, causal=False, max_seqlen_k=None, num_splits=0,
-                           window_size=(-1, -1)):
-    """The split count forward_kvcache_d64 uses for these arguments (fa_decode_d64_num_splits): the same checks, nothing allocated, no
-    launch."""
-    _, args, w, sk = _decode_d64_args(q, k_cache, v_cache, cache_seqlens, sinks, block_table, causal, max_seqlen_k, num_splits, window_size)
-    return _capi.check(_capi.load().fa_decode_d64_num_splits(ctypes.byref(args), ctypes.byref(w), None if sk is None else ctypes.byref(sk)))
+                           window_size=(-1, -1), k_descale=None, v_descale=None):
+    """The split count forward_kvcache_d64 uses for these arguments (fa_decode_d64_num_splits, an fp8 cache: fa_decode_fp8_d64_num_splits,
+    the same rule): the same checks, nothing allocated, no launch."""
+    _, args, w, sk, entry = _decode_d64_args(q, k_cache, v_cache, cache_seqlens, sinks, block_table, causal, max_seqlen_k, num_splits,
+                                             window_size, k_descale, v_descale)
+    return _capi.check(getattr(_capi.load(), entry + "num_splits")(ctypes.byref(args), ctypes.byref(w), None if sk is None else ctypes.byref(sk)))
 
 
 def forward_kvcache_d64(q, k_cache, v_cache, cache_seqlens, sinks=None, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
-                        num_splits=0, timed=False, window_size=(-1, -1)):
+                        num_splits=0, timed=False, window_size=(-1, -1), k_descale=None, v_descale=None):
     """Decode attention against a K / V cache at d_head = 64 (fa_decode_d64_launch; DESIGN.md 10.16): q (batch, seqlen_q, n_heads, 64);
     k_cache, v_cache (batch, seqlen_cache, n_kv_heads, 64), or with block_table (num_pages, page_size, n_kv_heads, 64), in q's dtype;
     the logits' scale is 1 / sqrt(64).  cache_seqlens, block_table, causal, return_lse, max_seqlen_k, num_splits, timed and window_size
     are forward_kvcache's, with their meaning, checks and defaults; sinks is forward_kvcache_sinks's, or None for no sinks (the bits of
     a tensor of -inf).  -> what forward_kvcache returns.  The host reads no device array; graph-capturable.  A bad window_size is a
-    ValueError before any tensor is looked at, a bad sinks a RuntimeError before the library is loaded.  Not here, and so without a
-    parameter: fp8 caches and descales, soft-capping, the fused append (k=, v=) and rotary."""
-    q, args, w, sk = _decode_d64_args(q, k_cache, v_cache, cache_seqlens, sinks, block_table, causal, max_seqlen_k, num_splits, window_size)
+    ValueError before any tensor is looked at, a bad sinks a RuntimeError before the library is loaded.
+    A torch.float8_e4m3fn cache takes fa_decode_fp8_d64_launch and needs BOTH k_descale and v_descale, forward_kvcache's
+    (fp32 (batch, n_kv_heads) on the device, never read by the host: a captured graph sees them rewritten in place): key j of entry b
+    and K / V head h stands for float(k8[j]) * k_descale[b, h], the sinks meet the dequantized logit and v_descale scales o.  Without
+    both it is a RuntimeError before the library is loaded (pass ones for an unscaled cache); descales on a 16-bit cache are refused.
+    Not here, and so without a parameter: soft-capping, the fused append (k=, v=) and rotary."""
+    q, args, w, sk, entry = _decode_d64_args(q, k_cache, v_cache, cache_seqlens, sinks, block_table, causal, max_seqlen_k, num_splits,
+                                             window_size, k_descale, v_descale)
     batch, seqlen_q, n_heads, d_head = q.shape
     o = torch.empty((batch, seqlen_q, n_heads, d_head), dtype=q.dtype, device=q.device)
     lse = torch.empty((batch, n_heads, seqlen_q), dtype=torch.float32, device=q.device) if return_lse else None
     args.o, args.lse = o.data_ptr(), (lse.data_ptr() if return_lse else None)
     lib, more = _capi.load(), (ctypes.byref(w), None if sk is None else ctypes.byref(sk))
-    nbytes = lib.fa_decode_d64_workspace_bytes(ctypes.byref(args), *more)
+    nbytes = getattr(lib, entry + "workspace_bytes")(ctypes.byref(args), *more)
     _capi.check(nbytes if nbytes < 0 else 0)
     with torch.cuda.device(q.device):
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes > 0 else None   # (on the current stream's allocator)
         args.workspace = workspace.data_ptr() if workspace is not None else None
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
         ms = ctypes.c_float(0.0)
-        _capi.check(lib.fa_decode_d64_launch(ctypes.byref(args), *more, stream, ctypes.byref(ms) if timed else None))
+        _capi.check(getattr(lib, entry + "launch")(ctypes.byref(args), *more, stream, ctypes.byref(ms) if timed else None))
     out = ((o, lse) if return_lse else (o,)) + ((float(ms.value),) if timed else ())
     return out[0] if len(out) == 1 else out
 

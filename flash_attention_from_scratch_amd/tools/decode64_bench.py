@@ -97,27 +97,81 @@ def run(batch, left, dtype, reps):
     return line
 
 
+FP8_FORMS = (("32", "1"), ("32", "2"), ("64", "1"))   # (FA_DECODE64_UNIT, FA_DECODE64_AHEAD): the fp8 kernel's instantiated forms
+FP8_ARMS = ("d64", "fp8", "d64_2", "fp8_2") + tuple(f"fp8_u{u}a{d}" for u, d in FP8_FORMS)
+
+
+def run_fp8(batch, left, dtype, reps):
+    """--kv-dtype fp8: the fp8 call ("fp8": the shipped form; "fp8_u<unit>a<ahead>": each form named outright)
+    against the 16-bit d64 call ("d64") on the cache it was quantized from, A/A beside both, same process, alternating, medians of
+    the launch's own ms.  Bytes: K and V of the keys a row sees, one byte an element for fp8, two for 16-bit."""
+    import torch
+
+    import flash_attention
+    from flash_attention_from_scratch_amd.tools.decode_bench import _median
+
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    base = min(batch, 8)
+    rand = lambda *shape: torch.randn(shape, generator=gen, device="cuda").to(dtype)   # noqa: E731
+    k16, v16, q = rand(base, CACHE, HKV, 64), rand(base, CACHE, HKV, 64), rand(batch, 1, H, 64)
+    k8, v8, kd, vd = flash_attention.quantize_kvcache_fp8(k16, v16)
+    k8, v8 = k8.view(torch.uint8), v8.view(torch.uint8)   # (repeated as bytes)
+    k16, v16, k8, v8, kd, vd = (t.repeat(batch // base, *([1] * (t.dim() - 1))).contiguous() for t in (k16, v16, k8, v8, kd, vd))
+    k8, v8 = k8.view(torch.float8_e4m3fn), v8.view(torch.float8_e4m3fn)
+    lens = torch.full((batch,), CACHE, dtype=torch.int32, device="cuda")
+    sinks = torch.linspace(4.0, 7.0, H, device="cuda")
+    call = dict(causal=True, window_size=(-1, -1) if left < 0 else (left, 0), timed=True)
+    seen = CACHE if left < 0 else left + 1
+
+    def fp8(form=None):
+        os.environ.update(dict(zip(("FA_DECODE64_UNIT", "FA_DECODE64_AHEAD"), form)) if form else {})
+        try:
+            return flash_attention.forward_kvcache_d64(q, k8, v8, lens, sinks, k_descale=kd, v_descale=vd, **call)[-1]
+        finally:
+            for name in ("FA_DECODE64_UNIT", "FA_DECODE64_AHEAD") if form else ():
+                del os.environ[name]
+
+    forward = {"d64": lambda: flash_attention.forward_kvcache_d64(q, k16, v16, lens, sinks, **call)[-1], "fp8": fp8}
+    forward.update({"d64_2": forward["d64"], "fp8_2": fp8}, **{f"fp8_u{u}a{d}": (lambda form=(u, d): fp8(form)) for u, d in FP8_FORMS})
+    times = {name: [] for name in FP8_ARMS}
+    for i in range(reps + 2):   # (two warm-up rounds)
+        for name in FP8_ARMS:
+            t = forward[name]()
+            if i > 1:
+                times[name].append(t)
+    line = {"kv_dtype": "fp8_e4m3fn", "batch": batch, "seqlen_q": 1, "len_k": CACHE, "window_left": left, "n_heads": H, "n_kv_heads": HKV,
+            "dtype": str(dtype).replace("torch.", ""), "reps": reps}
+    line.update({f"{name}_ms": _median(ts) for name, ts in times.items()})
+    if left < 0:
+        line.update({f"{name}_gbps": 2 * (2 if name.startswith("d64") else 1) * batch * HKV * seen * 64 / (line[f"{name}_ms"] * 1e6) for name in FP8_ARMS})
+    line.update({f"{name}_over_d64": line[f"{name}_ms"] / line["d64_ms"] for name in FP8_ARMS[1:]})
+    line["fp8_over_fp8_2"] = line["fp8_ms"] / line["fp8_2_ms"]
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16")
+    ap.add_argument("--kv-dtype", choices=("16", "fp8"), default="16", help="fp8: the fp8 cache's forms against the 16-bit d64 call")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
 
+    fp8 = a.kv_dtype == "fp8"
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "inference", f"decode64_bench_{a.dtype}.jsonl")
+        a.out = os.path.join(ROOT, "profiles", "inference", f"decode64_{'fp8_' if fp8 else ''}bench_{a.dtype}.jsonl")
     assert torch.cuda.is_available(), "decode64_bench.py needs the GPU"
     dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float16
     lines = []
     for case in CASES:
-        lines.append(run(*case, dtype, a.reps))
+        lines.append((run_fp8 if fp8 else run)(*case, dtype, a.reps))
         print(json.dumps(lines[-1]), flush=True)
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     with open(a.out, "w") as f:
         f.writelines(json.dumps(ln) + "\n" for ln in lines)
-    sys.exit(0 if all(ln["gate_d64_beats_padded"] for ln in lines) else 1)
+    sys.exit(0 if fp8 or all(ln["gate_d64_beats_padded"] for ln in lines) else 1)
 
 
 if __name__ == "__main__":

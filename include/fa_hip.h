@@ -948,7 +948,7 @@ int fa_decode_fp8_sinks_launch(const fa_decode_fp8_args *args, const fa_window *
  * the clamping of lengths and block_table entries, the row packing, the split rule and the meaning of every field are
  * fa_decode_window_*'s.  The workspace holds (num_splits, batch, n_kv_heads, rows, 64) fp32 partials and their lse:
  * fa_decode_d64_workspace_bytes sizes it.  Deterministic for a given num_splits, no atomics, the host reads no device array,
- * graph-capturable.  Not served at 64: fp8 caches, soft-capping, the fused append, more than 64 packed rows.
+ * graph-capturable.  Not served at 64: soft-capping, the fused append, more than 64 packed rows.
  *
  * Refused before any HIP call, in the order of fa_decode_sinks_*: d_head != 64 (FA_ERR_SHAPE) where they refuse d_head != 128; more
  * than 64 packed rows or page_size % 64 != 0 (FA_ERR_NO_KERNEL); then the window's rules; then, for a non-null fa_sinks, its rules.
@@ -957,6 +957,22 @@ int fa_decode_d64_supported(const fa_decode_args *args, const fa_window *window,
 int fa_decode_d64_num_splits(const fa_decode_args *args, const fa_window *window, const fa_sinks *sinks);
 int64_t fa_decode_d64_workspace_bytes(const fa_decode_args *args, const fa_window *window, const fa_sinks *sinks);
 int fa_decode_d64_launch(const fa_decode_args *args, const fa_window *window, const fa_sinks *sinks, void *stream, float *ms);
+
+/*
+ * ... against an fp8 (e4m3fn) cache (ABI 6, additive): fa_decode_d64_* over an fa_decode_fp8_args with d_head = 64 --
+ * the caches hold e4m3fn bytes (strides in bytes), key j of entry b and K / V head h standing for float(k8[j]) * k_descale[b, h];
+ * k_descale / v_descale are fp32 (batch, n_kv_heads) on the DEVICE, never read by the host, null = 1.  q, o, the window, the sinks
+ * (which meet the dequantized logit; v_descale still scales o), the fetch contract, the split rule and the workspace bytes are
+ * fa_decode_d64_*'s for the same shapes.  Kernels of their own (fa_decode64_fp8.hip).
+ *
+ * Refused before any HIP call: first what fa_decode_d64_* refuse, in their order and words; then the fp8 side in
+ * fa_decode_fp8_sinks_*'s words -- kv_dtype (FA_ERR_DTYPE), descale_batch_stride, strides that are no multiple of 16 bytes, and in the
+ * launch the descales' alignment.
+ */
+int fa_decode_fp8_d64_supported(const fa_decode_fp8_args *args, const fa_window *window, const fa_sinks *sinks);
+int fa_decode_fp8_d64_num_splits(const fa_decode_fp8_args *args, const fa_window *window, const fa_sinks *sinks);
+int64_t fa_decode_fp8_d64_workspace_bytes(const fa_decode_fp8_args *args, const fa_window *window, const fa_sinks *sinks);
+int fa_decode_fp8_d64_launch(const fa_decode_fp8_args *args, const fa_window *window, const fa_sinks *sinks, void *stream, float *ms);
 
 /*
  * Prefill at d_head = 64 (ABI 6, additive): fa_fwd_launch_varlen_qk_sinks and fa_fwd_launch_varlen_kvcache_sinks
