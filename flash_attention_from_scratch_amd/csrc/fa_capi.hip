@@ -1224,6 +1224,19 @@ int kvcache_validate(CacheView &c, const fa_kvcache_layout *kc, const fa_kvcache
     if ((rc = cache_descale_stride(c)) != FA_OK) return rc;
     return cache_descale_alignment(c);
 }
+// What fa_fwd_launch_varlen_kvcache_fp8_d64 refuses of the fp8 side, behind every refusal of fa_fwd_launch_varlen_kvcache_d64 in that
+// entry's order: kvcache_validate's fp8 rules in their words, with the byte strides' rule (which the d128 entry asks first) among them
+int prefill64_fp8_rules(CacheView &c, const fa_kvcache_fp8_scales *sc) {
+    if (sc->struct_size < sizeof(fa_kvcache_fp8_scales))
+        return fail(FA_ERR_SHAPE, "fa_kvcache_fp8_scales.struct_size (%u) is smaller than this library's (%zu)", sc->struct_size,
+                    sizeof(fa_kvcache_fp8_scales));
+    if (sc->kv_dtype != FA_KV_FP8_E4M3FN)
+        return fail(FA_ERR_DTYPE, "kv_dtype (%d) is not served: the fp8 cache is e4m3fn (FA_KV_FP8_E4M3FN)", sc->kv_dtype);
+    cache_descales(c, *sc);
+    if (const int rc = cache_descale_stride(c)) return rc;
+    if (const int rc = cache_fp8_strides(c)) return rc;
+    return cache_descale_alignment(c);
+}
 
 // ---- fa_softcap: the rules of the soft-capped entry points (called behind the windowed sibling's own rules) -----------------
 int softcap_validate(const fa_softcap *c) {
@@ -1287,6 +1300,9 @@ int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_
     const bool cache_side = call.keys != KEYS_PACKED, fp8_side = call.keys == KEYS_FP8_CACHE;
     const bool windowed = call.extra != EXTRA_NONE, capped = call.extra == EXTRA_SOFTCAP;
     const bool sunk = call.extra == EXTRA_SINKS;
+    // (d_head = 64 against an fp8 cache: everything the 16-bit d64 entry refuses comes first, in its words -- the byte strides pass its
+    // rules as elements -- and the fp8 side's own rules behind the sinks', prefill64_fp8_rules)
+    const bool fp8_rules_here = fp8_side && d_head == 128;
     const fa_varlen_layout *vk = cache_side ? vq : call.vk;   // (one valid layout for the checks both launches share)
     if (!args || !kv || !vq || !vk || (cache_side && !call.kc) || (fp8_side && !call.sc)) return fail(FA_ERR_NULL, "null pointer argument");
     if (!args->q || !args->k || !args->v || !args->o) return fail(FA_ERR_NULL, "null pointer argument");
@@ -1319,13 +1335,13 @@ int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_
     cache.kv_ss = kv->kv_seq_stride;
     cache.kv_hs = kv->kv_head_stride;
     cache.fp8 = fp8_side;
-    if ((rc = cache_fp8_strides(cache)) != FA_OK) return rc;
-    if ((rc = check_strides_varlen(fp8_side ? "kv (fp8 cache: bytes for elements)" : "kv", kv->n_kv_heads, kv->kv_seq_stride, kv->kv_head_stride)) != FA_OK) return rc;
+    if (fp8_rules_here && (rc = cache_fp8_strides(cache)) != FA_OK) return rc;
+    if ((rc = check_strides_varlen(fp8_rules_here ? "kv (fp8 cache: bytes for elements)" : "kv", kv->n_kv_heads, kv->kv_seq_stride, kv->kv_head_stride)) != FA_OK) return rc;
     if ((rc = varlen_grid_check(vq, args->n_heads)) != FA_OK) return rc;
     if (((uintptr_t)args->q | (uintptr_t)args->k | (uintptr_t)args->v | (uintptr_t)args->o) & 15)
         return fail(FA_ERR_ALIGN, "q, k, v, o must be 16-byte aligned");
     if ((uintptr_t)lse & 3) return fail(FA_ERR_ALIGN, "lse must be 4-byte aligned");
-    if (cache_side && (rc = kvcache_validate(cache, call.kc, fp8_side ? call.sc : nullptr)) != FA_OK) return rc;
+    if (cache_side && (rc = kvcache_validate(cache, call.kc, fp8_rules_here ? call.sc : nullptr)) != FA_OK) return rc;
     if (windowed) {   // (the key bound: the cache's capacity, or the packed key side's max_seqlen; then the query side's)
         if ((rc = window_validate(call.w, o.causal, cache_side ? cache.capacity() : 0)) != FA_OK) return rc;
         if (!cache_side && vk->max_seqlen > kWindowMaxLen)
@@ -1335,6 +1351,7 @@ int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_
     }
     if (capped && (rc = softcap_validate(call.cap)) != FA_OK) return rc;
     if (sunk && (d_head == 128 || call.sinks) && (rc = sinks_validate(call.sinks, args->n_heads, false, nullptr)) != FA_OK) return rc;
+    if (fp8_side && !fp8_rules_here && (rc = prefill64_fp8_rules(cache, call.sc)) != FA_OK) return rc;
     if (vq->total_tokens == 0) {   // (no query rows: nothing to write)
         if (o.ms) *o.ms = 0.0f;
         return FA_OK;
@@ -1371,12 +1388,17 @@ int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_
             p.tiles_per_page = (int32_t)(cache.paged() ? cache.page_size / 64 : (cap_k + 63) / 64);   // (contiguous: one "page" per entry)
             p.max_len = (int32_t)(cache.max_seqlen_k > 0 ? cache.max_seqlen_k : cap_k);
         }
+        if (fp8_side) {   // (k, v are bytes and every kv stride counts bytes: the kernel's FP8 form reads them so)
+            p.k_descale = cache.k_descale;
+            p.v_descale = cache.v_descale;
+            p.ds_bs = cache.descale_bs;
+        }
         p.left = call.w->left;   // (causal as right = 0: the kernel's one rule for both)
         p.right = window_right(call.w, o.causal);
         const hipStream_t s = (hipStream_t)stream;
         const int dtype = args->cfg.dtype == FA_BF16 ? 15 : 5;
         const int64_t n_seqs = vq->n_seqs;
-        return enqueue_timed([&] { return fa::prefill64_enqueue(p, dtype, cache_side, n_seqs, s); }, s, o.ms);
+        return enqueue_timed([&] { return fp8_side ? fa::prefill64_fp8_enqueue(p, dtype, n_seqs, s) : fa::prefill64_enqueue(p, dtype, cache_side, n_seqs, s); }, s, o.ms);
     }
     DeviceState *dev = current_device(&rc);
     if (!dev) return rc;
@@ -1712,6 +1734,14 @@ int fa_fwd_launch_varlen_kvcache_d64(const fa_fwd_args *args, const fa_kv_layout
                                      const fa_window *w, const fa_sinks *sinks, const fa_fwd_opts *opts, float *lse, void *stream) {
     return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_d64", "total_q", KEYS_CACHE, EXTRA_SINKS, nullptr, kc, nullptr, w, nullptr, sinks}, args,
                              kv, vq, opts, lse, stream, 64);
+}
+// ... against an fp8 (e4m3fn) cache: the 16-bit entry's rules first, then the fp8 side's (prefill64_fp8_rules)
+int fa_fwd_varlen_kvcache_fp8_d64_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_qk_d64_supported(cfg, opts); }
+int fa_fwd_launch_varlen_kvcache_fp8_d64(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_kvcache_layout *kc,
+                                         const fa_kvcache_fp8_scales *sc, const fa_window *w, const fa_sinks *sinks, const fa_fwd_opts *opts,
+                                         float *lse, void *stream) {
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_fp8_d64", "total_q", KEYS_FP8_CACHE, EXTRA_SINKS, nullptr, kc, sc, w, nullptr, sinks},
+                             args, kv, vq, opts, lse, stream, 64);
 }
 
 int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *a) {

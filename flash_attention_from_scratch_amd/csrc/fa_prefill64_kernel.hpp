@@ -48,6 +48,12 @@
 //    instructions, so a null pointer and a tensor of -inf give the same bits.  A row without keys: o = 0, lse = z.
 //  * The packed and the cache form differ only in how a tile's base address is found: the same bits on the same keys.  Fixed walk
 //    order, no atomics, no workspace.
+//  * FP8: the cache holds e4m3fn bytes, its strides count bytes.  The DMA cannot convert, so the raw tile (4 KiB of K,
+//    4 KiB of V) lands in a ring of three 8-KiB raw stages behind two 16-bit stages (56 KiB, still two workgroups per CU), and at the
+//    tile seam, when S and P are dead, each lane converts the 32 bytes it fetched itself into the two images above, byte for byte
+//    (convert_tile): the visit, the masks and the epilogue are the 16-bit form's text and arithmetic, so with power-of-two descales
+//    the bits are the 16-bit form's on the dequantized cache.  k_descale multiplies c and the epilogue's scale (S and m stay raw
+//    logits), v_descale the final 1 / l; the sink meets the dequantized logit.
 #pragma once
 #include "fa_fwd_kernel.hpp"
 
@@ -70,21 +76,30 @@ struct Prefill64Args {
     int32_t total_k, max_seqlen_k;   // packed keys
     int32_t bt_stride, num_pages, tiles_per_page, max_len;   // cache (contiguous: tiles_per_page covers the whole entry)
     int32_t left, right;           // -1 = unbounded (causal: right = 0)
+    const float *k_descale, *v_descale;   // fp8 cache: (n_seqs, n_kv_heads) fp32, row stride ds_bs; null = 1
+    int64_t ds_bs;
 };
 
 namespace prefill64 {
 constexpr int D = 64, TILE = 64, NWAVES = 4, THREADS = NWAVES * 64, RW = 64, R = NWAVES * RW, STAGES = 3;
 constexpr int TILE_BYTES = TILE * D * 2, STAGE_BYTES = 2 * TILE_BYTES;   // K then V
 constexpr int PIECES = 2 * TILE_BYTES / 1024 / NWAVES;                   // DMA pieces per wave and tile: 2 of K, 2 of V
+// the fp8 cache's transport (FP8, below): two converted stages in front of a ring of three raw ones, 56 KiB
+constexpr int RAW_TILE_BYTES = TILE * D, RAW_STAGE_BYTES = 2 * RAW_TILE_BYTES, RAW_PIECES = 2;   // per wave and tile: 1 KiB of K, 1 of V
+constexpr int CONV_STAGES = 2, RAW_BASE = CONV_STAGES * STAGE_BYTES, FP8_LDS_BYTES = RAW_BASE + STAGES * RAW_STAGE_BYTES;
+template <bool FP8> struct KvElem { typedef uint16_t type; };
+template <> struct KvElem<true> { typedef uint8_t type; };   // (an fp8 cache's strides count bytes)
 }  // namespace prefill64
 
-template <int DT, bool CACHE>
+template <int DT, bool CACHE, bool FP8 = false>
 __global__ void __launch_bounds__(prefill64::THREADS, 2) fa_prefill64_kernel(const Prefill64Args a) {
+    static_assert(CACHE || !FP8, "fp8 keys live in a cache");
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
     using namespace prefill64;
+    using KV = typename KvElem<FP8>::type;
     constexpr int KS = D / 16, DT32 = D / 32, QT = RW / 32, NT = TILE / 32;
-    __shared__ __attribute__((aligned(1024))) char smem[STAGES * STAGE_BYTES];
+    __shared__ __attribute__((aligned(1024))) char smem[FP8 ? FP8_LDS_BYTES : STAGES * STAGE_BYTES];
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -131,8 +146,13 @@ __global__ void __launch_bounds__(prefill64::THREADS, 2) fa_prefill64_kernel(con
     const int wt_lo = wave_live ? lo_of(w0) / TILE : 1, wt_hi = wave_live ? hi_of(w1) / TILE : 0;
     const int plain_lo = w0 < len_q ? lo_of(w1) : 0, plain_hi = w0 < len_q ? hi_of(w0) : -1;   // a tile inside [plain_lo, plain_hi] needs no mask
 
-    const float scale = 1.0f / __builtin_sqrtf((float)D);
-    const float c = (float)((double)scale * 1.4426950408889634074);
+    // (fp8 cache: k_descale times both constants, one scalar per workgroup -- S and the running maximum stay raw logits, and the
+    // exponents, the rescale and the epilogue's m scale come out in dequantized units; a power of two changes no rounding)
+    float kd = 1.0f;
+    if constexpr (FP8) kd = a.k_descale ? a.k_descale[(int64_t)b * a.ds_bs + h / a.group] : 1.0f;
+    const float scale0 = 1.0f / __builtin_sqrtf((float)D);
+    const float scale = FP8 ? scale0 * kd : scale0;
+    const float c = FP8 ? (float)((double)scale0 * 1.4426950408889634074) * kd : (float)((double)scale0 * 1.4426950408889634074);
     const float ninf = -__builtin_inff();
 
     f32x16 O[QT][DT32];
@@ -154,9 +174,9 @@ __global__ void __launch_bounds__(prefill64::THREADS, 2) fa_prefill64_kernel(con
     }
 
     const int kvh = h / a.group;
-    const uint16_t *Kg = a.k + (int64_t)kvh * a.kv_hs, *Vg = a.v + (int64_t)kvh * a.kv_hs;
+    const KV *Kg = (const KV *)a.k + (int64_t)kvh * a.kv_hs, *Vg = (const KV *)a.v + (int64_t)kvh * a.kv_hs;
     const unsigned smem_base = __builtin_amdgcn_readfirstlane(lds_addr(smem));
-    const unsigned row_bytes = (unsigned)(a.kv_ss * 2);
+    const unsigned row_bytes = (unsigned)(a.kv_ss * sizeof(KV));
 
     // the walk over the key tiles, ascending: tile t's base offset (elements from k / v).  Cache: page and tile-in-page by counters,
     // the page's table entry requested when the walk enters the page before it (a scalar load through the constant address space:
@@ -188,9 +208,21 @@ __global__ void __launch_bounds__(prefill64::THREADS, 2) fa_prefill64_kernel(con
         // the tile's rows that may be fetched: [first, last], both inside the tile (the floor tile holds wg_lo, the top tile wg_hi)
         const int key0 = t * TILE;
         const int first = wg_lo > key0 ? wg_lo - key0 : 0, last = len_k - 1 - key0 < TILE - 1 ? len_k - 1 - key0 : TILE - 1;
+        if constexpr (FP8) {
+            // raw bytes: the wave's piece is keys 16 wave .. + 15 of K and of V, lane: key 16 wave + lane / 4, bytes 16 (lane & 3) .. + 15
+            // of its 64 -- the same clamp, and the lane that fetched a chunk is the one that converts it (convert_tile)
+            const unsigned dst = smem_base + RAW_BASE + stage * RAW_STAGE_BYTES + wave * 1024;
+            int ln = lane;
+            asm volatile("" : "+v"(ln));   // (formed per tile, as in convert_tile)
+            int r = 16 * wave + (ln >> 2);
+            r = r < first ? first : (r > last ? last : r);
+            const unsigned off = (unsigned)r * row_bytes + (unsigned)((ln & 3) << 4);
+            glds16_sv(Kg + base, off, dst);
+            glds16_sv(Vg + base, off, dst + RAW_TILE_BYTES);
+        }
         const unsigned dst = smem_base + stage * STAGE_BYTES;
 #pragma unroll
-        for (int j = 0; j < PIECES / 2; ++j) {
+        for (int j = 0; j < (FP8 ? 0 : PIECES / 2); ++j) {
             const int i = wave + NWAVES * j;   // piece i: keys 8 i .. 8 i + 7 of K and of V
             int kr = 8 * i + (lane >> 3), vr = 8 * i + ((lane & 31) >> 2);
             const int swz = (kr >> 1) & 7;
@@ -208,6 +240,29 @@ __global__ void __launch_bounds__(prefill64::THREADS, 2) fa_prefill64_kernel(con
                 if (paged && walk_page < page_hi) walk_next = bt_row[walk_page + 1];
             }
         }
+    };
+
+    // fp8: raw stage `raw` -> converted stage `conv`, the images the DMA builds for a 16-bit cache, byte for byte.  A lane converts the
+    // 16 + 16 bytes it fetched itself (so the raw ring needs no barrier: its own vmcnt wait is all), lane-linear ds_read_b128s.  K:
+    // chunks 2 q and 2 q + 1 of key 16 wave + lane / 4 go to slots (2 q + e) ^ swizzle of its 128-byte row -- sixteen lanes are four
+    // consecutive keys x four q: the two even keys share a 128-byte half of the 256 and differ in the swizzle's bit 0, so with e
+    // fixed one takes the even slots and the other the odd ones; the odd keys likewise in the other half: every bank once.  V: the 32
+    // contiguous bytes at [key / 8][q / 2][key % 8][16 (q & 1) ..]; q and q + 2 lie 512 bytes apart, the same banks, so the lanes of
+    // q >= 2 write their two halves in the other order.
+    auto convert_tile = [&](int raw, int conv) {
+        int ln = lane;
+        asm volatile("" : "+v"(ln));   // (the lane's offsets are formed here, per tile: held across the visit they cost registers the budget lacks)
+        const char *rp = smem + RAW_BASE + raw * RAW_STAGE_BYTES + wave * 1024 + ln * 16;
+        char *kt = smem + conv * STAGE_BYTES, *vt = kt + TILE_BYTES;
+        const u32x4 k8 = *(const u32x4 *)rp, v8 = *(const u32x4 *)(rp + RAW_TILE_BYTES);
+        const int key = 16 * wave + (ln >> 2), q4 = ln & 3, swz = (key >> 1) & 7;
+        *(vec8 *)(kt + key * 128 + (((2 * q4) ^ swz) << 4)) = cvt_fp8x8<DT>(k8[0], k8[1]);
+        *(vec8 *)(kt + key * 128 + (((2 * q4 + 1) ^ swz) << 4)) = cvt_fp8x8<DT>(k8[2], k8[3]);
+        char *vp = vt + (key >> 3) * 1024 + (q4 >> 1) * 512 + (key & 7) * 64 + (q4 & 1) * 32;
+        const bool flip = q4 >> 1;
+        const vec8 v_lo = cvt_fp8x8<DT>(v8[0], v8[1]), v_hi = cvt_fp8x8<DT>(v8[2], v8[3]);
+        *(vec8 *)(vp + (flip ? 16 : 0)) = flip ? v_hi : v_lo;
+        *(vec8 *)(vp + (flip ? 0 : 16)) = flip ? v_lo : v_hi;
     };
 
     // per-lane LDS read offsets: K's A operand (row r31 of a 32-key tile, chunk (2 ks + hi) ^ swizzle) and V^T's transposed reads
@@ -302,6 +357,8 @@ __global__ void __launch_bounds__(prefill64::THREADS, 2) fa_prefill64_kernel(con
     if (n_tiles > 0) {
         issue_tile();
         if (n_tiles > 1) issue_tile();
+        if constexpr (FP8)
+            if (n_tiles > 2) issue_tile();   // (the raw ring runs three tiles ahead)
         // Q^T, resident: row r (one past len_q reads row len_q - 1), d 16 ks + 8 hi .. + 7.  The empty asm is the registers' first use:
         // the loads' wait stands here, in front of the loop, not in it
 #pragma unroll
@@ -315,8 +372,34 @@ __global__ void __launch_bounds__(prefill64::THREADS, 2) fa_prefill64_kernel(con
         for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(Qr[qt][ks]));
+        if constexpr (FP8) {
+            // One barrier per tile, with a prologue that converts tile 0.  Iteration `it`: the wave's own raw pieces of tile it + 1 have
+            // landed (at most tile it + 2's two in flight); the barrier publishes converted tile `it` and tells that every wave is done
+            // with tile it - 1, whose converted stage tile it + 1 takes; raw tile it + 3 is requested into the raw stage of tile `it`,
+            // which this wave alone read, an iteration ago; then convert it + 1, visit `it`.
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            convert_tile(0, 0);
+            int raw = 1;   // tile it + 1's raw stage
+            for (int it = 0; it < n_tiles; ++it) {
+                if (it + 2 < n_tiles)
+                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RAW_PIECES) : "memory");
+                else
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                wg_barrier();
+                if (issued < n_tiles) issue_tile();
+                if (it + 1 < n_tiles) convert_tile(raw, (it + 1) & 1);
+                raw = raw + 1 == STAGES ? 0 : raw + 1;
+                const int t = t_lo + it;
+                if (t >= wt_lo && t <= wt_hi) {   // (wave-uniform)
+                    if (t * TILE >= plain_lo && t * TILE + TILE - 1 <= plain_hi)
+                        visit(t, it & 1, BoolTag<false>{});
+                    else
+                        visit(t, it & 1, BoolTag<true>{});
+                }
+            }
+        }
         int stage = 0;
-        for (int it = 0; it < n_tiles; ++it) {
+        for (int it = 0; it < (FP8 ? 0 : n_tiles); ++it) {
             // tile `it` has landed: this wave's pieces by the counted wait, the other waves' by the barrier, which also tells that
             // every wave is done with tile it - 1 -- whose stage the request for tile it + 2 takes
             if (it + 1 < n_tiles)
@@ -349,7 +432,8 @@ __global__ void __launch_bounds__(prefill64::THREADS, 2) fa_prefill64_kernel(con
         const float ms = any ? m[qt] * scale : 0.0f;
         const float M = fmaxf(ms, z);
         const float al = __expf(ms - M), l_all = __builtin_fmaf(l_row, al, __expf(z - M));
-        const float inv = any ? al / l_all : 0.0f;
+        float inv = any ? al / l_all : 0.0f;
+        if constexpr (FP8) inv *= a.v_descale ? a.v_descale[(int64_t)b * a.ds_bs + kvh] : 1.0f;   // (read here, not held across the loop)
         const float lse = any ? M + __logf(l_all) : z;
         uint16_t *op = a.o + (q_row0 + r) * a.q_ss + (int64_t)h * a.q_hs + 4 * hi;
 #pragma unroll
@@ -366,5 +450,6 @@ __global__ void __launch_bounds__(prefill64::THREADS, 2) fa_prefill64_kernel(con
 }
 
 hipError_t prefill64_enqueue(const Prefill64Args &a, int dtype, bool cache, int64_t n_seqs, hipStream_t s);   // fa_prefill64.hip
+hipError_t prefill64_fp8_enqueue(const Prefill64Args &a, int dtype, int64_t n_seqs, hipStream_t s);            // fa_prefill64_fp8.hip
 
 }  // namespace fa

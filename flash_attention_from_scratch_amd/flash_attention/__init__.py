@@ -259,14 +259,18 @@ def forward_varlen_d64(q, k, v, cu_seqlens, max_seqlen, sinks=None, causal=False
 
 
 def forward_varlen_kvcache_d64(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, sinks=None, block_table=None, causal=False,
-                               max_seqlen_k=None, timed=False, *, window_size=(-1, -1)):
+                               max_seqlen_k=None, timed=False, *, window_size=(-1, -1), k_descale=None, v_descale=None):
     """Prefill against the cache forward_kvcache_d64 decodes from: q (total_q, n_heads, 64) packed; k_cache, v_cache
     (n_seqs, seqlen_cache, n_kv_heads, 64) or, with block_table, pages (num_pages, page_size, n_kv_heads, 64), 16-bit in q's dtype.
     Every argument is forward_varlen_kvcache_sinks's of that name, with its meaning, checks and defaults; sinks may be None.
-    -> (o, lse[, ms]), bit for bit forward_varlen_d64(cu_seqlens_k=) on the same keys packed.  No fp8 cache, no soft-capping."""
+    -> (o, lse[, ms]), bit for bit forward_varlen_d64(cu_seqlens_k=) on the same keys packed.  No soft-capping.
+    A torch.float8_e4m3fn cache (quantize_kvcache_fp8 makes one) is read in place with BOTH k_descale and v_descale,
+    fp32 (n_seqs, n_kv_heads) on the device: a key stands for float(k8) * k_descale[b, h], the sinks meet the dequantized logit,
+    v_descale scales o; with power-of-two descales the bits are this call's on the dequantized 16-bit cache.  Without both it is a
+    RuntimeError (pass ones for an unscaled cache); descales on a 16-bit cache are refused."""
     return flash_attention_kernels.forward_varlen_kvcache_d64(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, sinks=sinks,
                                                               block_table=block_table, causal=causal, max_seqlen_k=max_seqlen_k, timed=timed,
-                                                              window_size=window_size)
+                                                              window_size=window_size, k_descale=k_descale, v_descale=v_descale)
 
 
 def forward_varlen_kvcache_sinks(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, sinks, block_table=None, causal=False,

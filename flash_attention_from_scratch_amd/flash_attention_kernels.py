@@ -1069,19 +1069,26 @@ def forward_varlen_kvcache_sinks(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q
 
 
 def forward_varlen_kvcache_d64(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, sinks=None, block_table=None, causal=False,
-                               max_seqlen_k=None, timed=False, *, window_size=(-1, -1)):
+                               max_seqlen_k=None, timed=False, *, window_size=(-1, -1), k_descale=None, v_descale=None):
     """forward_varlen_kvcache_sinks at d_head = 64 (fa_fwd_launch_varlen_kvcache_d64): q (total_q, n_heads, 64); k_cache,
     v_cache (n_seqs, seqlen_cache, n_kv_heads, 64), or with block_table (num_pages, page_size, n_kv_heads, 64), page_size % 64 == 0, in
     q's dtype; the logits' scale is 1 / sqrt(64).  Every other argument is forward_varlen_kvcache_sinks's, with its meaning, checks and
     defaults, but sinks may be None: no sinks, the bits of a tensor of -inf.  -> (o, lse[, ms]); o and lse are forward_varlen_d64's bits
     on the gathered keys; what forward_kvcache_d64 decodes against, this call fills and verifies.  The host reads no device array;
-    graph-capturable.  A bad window_size is a ValueError before any tensor is looked at, a bad sinks, an fp8 cache or another d_head a
-    RuntimeError before the library is loaded.  Not here, and so without a parameter: fp8 caches and descales, soft-capping."""
+    graph-capturable.  A bad window_size is a ValueError before any tensor is looked at, a bad sinks or another d_head a RuntimeError
+    before the library is loaded.
+    A torch.float8_e4m3fn cache takes fa_fwd_launch_varlen_kvcache_fp8_d64 and needs BOTH k_descale and v_descale,
+    forward_varlen_kvcache's (fp32 (n_seqs, n_kv_heads) on q's device, indexed by the sequence for a paged cache too, never read by the
+    host: a captured graph sees them rewritten in place): key j of sequence b and K / V head h stands for float(k8[j]) * k_descale[b, h],
+    the sinks meet the dequantized logit and v_descale scales o.  With unit or power-of-two descales o and lse are this call's bits on
+    the dequantized 16-bit cache.  Without both it is a RuntimeError before the library is loaded (pass ones for an unscaled cache); an
+    e5m2 cache, mixed cache dtypes and descales on a 16-bit cache are refused in forward_varlen_kvcache's words.
+    Not here, and so without a parameter: soft-capping."""
     window = _window(window_size, causal)
     if sinks is not None:
         _check_sinks(sinks, q)
     return _forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, max_seqlen_k, timed,
-                                   None, None, window, None, sinks, d_head=64)
+                                   k_descale, v_descale, window, None, sinks, d_head=64)
 
 
 def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table=None, causal=False,
@@ -1118,18 +1125,16 @@ def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
 def _forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, max_seqlen_k, timed, k_descale,
                             v_descale, window, cap, sinks, d_head=128):
     """The one body of forward_varlen_kvcache (window: _window's, cap: _softcap's, sinks None), forward_varlen_kvcache_sinks (sinks a
-    checked tensor, cap None) and, d_head=64, forward_varlen_kvcache_d64 (sinks a checked tensor or None; no fp8 cache)"""
+    checked tensor, cap None) and, d_head=64, forward_varlen_kvcache_d64 (sinks a checked tensor or None)"""
     tensors = [(q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cu_seqlens_q, "cu_seqlens_q"), (cache_seqlens, "cache_seqlens")]
     if block_table is not None:
         tensors.append((block_table, "block_table"))
     _need_tensors(tensors)
     cache = _CacheSide(k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, "n_seqs", "q's")
-    fp8 = cache.dtypes(like=None, fp8_needs_descales=None if d_head == 64 else (
-        "forward_varlen_kvcache: an fp8 cache is not served without both k_descale and v_descale (fp32 (n_seqs, "
-        "n_kv_heads) tensors on q's device; pass ones for an unscaled cache -- None does not mean 1 here)"))
+    fp8 = cache.dtypes(like=None, fp8_needs_descales=(
+        f"forward_varlen_kvcache{'_d64' if d_head == 64 else ''}: an fp8 cache is not served without both k_descale and v_descale (fp32 "
+        "(n_seqs, n_kv_heads) tensors on q's device; pass ones for an unscaled cache -- None does not mean 1 here)"))
     if fp8:
-        if d_head == 64:   # (still the entry's parameter here)
-            raise RuntimeError("forward_varlen_kvcache_d64 serves a 16-bit cache in q's dtype: an fp8 cache at d_head = 64 has no kernel")
         tensors += [(k_descale, "k_descale"), (v_descale, "v_descale")]
         _need_tensors(tensors[-2:])
         if k_cache.dim() == 4 and cu_seqlens_q.dim() == 1 and cu_seqlens_q.numel() >= 2:   # (what they are is checked before where they are)
@@ -1192,7 +1197,7 @@ def _forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cac
         if sinks is not None:
             form = "_sinks"
             w = [ctypes.byref(_capi.make_window(*(window or (-1, -1)))), ctypes.byref(_capi.make_sinks(sinks.data_ptr(), n_heads))]
-        if d64:   # (the sinks form's arguments; the fa_sinks may be null)
+        if d64:   # (the sinks form's arguments; the fa_sinks may be null -- fp8: fa_fwd_launch_varlen_kvcache_fp8_d64)
             form = "_d64"
             w = [ctypes.byref(_capi.make_window(*(window or (-1, -1)))),
                  None if sinks is None else ctypes.byref(_capi.make_sinks(sinks.data_ptr(), n_heads))]

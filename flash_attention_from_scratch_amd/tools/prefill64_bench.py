@@ -11,7 +11,16 @@ windowed cases' visited-tile ratio (64-key tiles the d64 kernel's 256-row workgr
 line, the useful TFLOP/s of (a) on a non-causal batch 4 x 16 heads x 4096 (4 B H S^2 D operations).  Clocks are whatever the device
 runs at.  Written to profiles/inference/prefill64_bench_<dtype>.jsonl unless --out says otherwise.
 
-    python flash_attention_from_scratch_amd/tools/prefill64_bench.py [--reps N] [--out FILE]
+--kv-dtype fp8 times forward_varlen_kvcache_d64 against an e4m3fn cache instead, the same protocol: the chunk cases
+and 8 x 4096 rows against a contiguous cache of 4096 keys; written to profiles/inference/prefill64_fp8_bench_<dtype>.jsonl.
+  - "fp8":     the call on the fp8 cache and its descales;                                                                     (a)
+  - "dequant": what a caller could do without it: dequantize the whole cache to 16 bit (torch, timed by events around it), then the
+               16-bit call (timed by its own events);                                                                           (b)
+  - "bf16":    the 16-bit call on the cache the fp8 one was quantized from (half the bytes are the fp8 arm's to win);            (c)
+  - "fp8_2":   (a) a second time, the A/A spread.
+Reported per line, not gated (exit status 0): whether (a) / (b) < 1 by more than the A/A spread, and (a) / (c) beside it.
+
+    python flash_attention_from_scratch_amd/tools/prefill64_bench.py [--reps N] [--out FILE] [--kv-dtype fp8]
 """
 import argparse
 import json
@@ -87,6 +96,50 @@ def run(kind, left, dtype, reps):
     return line
 
 
+def run_fp8(kind, left, dtype, reps):
+    """one case against an fp8 cache: "chunk" as in run(), "contiguous": 8 x 4096 rows against a contiguous cache of 4096 keys"""
+    import torch
+
+    import flash_attention as fa
+
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    i32 = lambda x: torch.tensor(x, dtype=torch.int32, device="cuda")   # noqa: E731
+    sinks = torch.linspace(4.0, 7.0, H, device="cuda")
+    call = dict(causal=True, window_size=(-1, -1) if left < 0 else (left, 0), timed=True)
+    len_q, len_k = (4096, 4096) if kind == "contiguous" else (2048, 65536 + 2048)
+    q, cu, lens = torch.randn((BATCH * len_q, H, 64), generator=gen, device="cuda").to(dtype), i32(list(range(0, BATCH * len_q + 1, len_q))), i32([len_k] * BATCH)
+    k16, v16 = (torch.randn((BATCH, len_k, HKV, 64), generator=gen, device="cuda").to(dtype) for _ in range(2))
+    k8, v8, kd, vd = fa.quantize_kvcache_fp8(k16, v16)
+    more, owner = {}, torch.arange(BATCH, device="cuda")   # (owner: the sequence whose descale a cache entry or page takes)
+    if kind == "chunk":   # pages of 256 behind a shuffled table
+        n = len_k // PAGE
+        table = torch.randperm(BATCH * n, generator=torch.Generator().manual_seed(0)).cuda()
+        scatter = lambda t: torch.empty_like(t.view(BATCH * n, PAGE, HKV, 64)).index_copy_(0, table, t.view(BATCH * n, PAGE, HKV, 64))   # noqa: E731
+        k16, v16, k8, v8 = scatter(k16), scatter(v16), scatter(k8.view(torch.uint8)).view(k8.dtype), scatter(v8.view(torch.uint8)).view(v8.dtype)
+        owner = torch.empty(BATCH * n, dtype=torch.int64, device="cuda").index_copy_(0, table, torch.arange(BATCH, device="cuda").repeat_interleave(n))
+        more = dict(block_table=table.view(BATCH, n).to(torch.int32))
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def dequant():
+        start.record()
+        kk, vv = (t8.to(dtype) * d[owner][:, None, :, None].to(dtype) for t8, d in ((k8, kd), (v8, vd)))
+        stop.record()
+        ms = fa.forward_varlen_kvcache_d64(q, kk, vv, cu, len_q, lens, sinks, **more, **call)[-1]   # (synchronizes: timed)
+        return start.elapsed_time(stop) + ms
+
+    forward = {"fp8": lambda: fa.forward_varlen_kvcache_d64(q, k8, v8, cu, len_q, lens, sinks, k_descale=kd, v_descale=vd, **more, **call)[-1],
+               "dequant": dequant, "bf16": lambda: fa.forward_varlen_kvcache_d64(q, k16, v16, cu, len_q, lens, sinks, **more, **call)[-1]}
+    forward["fp8_2"] = forward["fp8"]
+    line = {"case": kind, "kv_dtype": "fp8_e4m3fn", "batch": BATCH, "len_q": len_q, "len_k": len_k, "window_left": left, "n_heads": H, "n_kv_heads": HKV,
+            "dtype": str(dtype).replace("torch.", ""), "reps": reps}
+    line.update(_alternate(forward, reps))
+    line["fp8_over_dequant"] = line["fp8_ms"] / line["dequant_ms"]
+    line["fp8_over_bf16"] = line["fp8_ms"] / line["bf16_ms"]
+    line["fp8_over_fp8_2"] = line["fp8_ms"] / line["fp8_2_ms"]
+    line["fp8_beats_dequant"] = line["fp8_over_dequant"] < 1.0 - abs(1.0 - line["fp8_over_fp8_2"])
+    return line
+
+
 def dense_rate(dtype, reps):
     """ungated: the useful TFLOP/s of (a) on a non-causal batch of 4 sequences x 16 heads x 4096"""
     import torch
@@ -107,15 +160,27 @@ def main():
     ap.add_argument("--reps", type=int, default=11)
     ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--kv-dtype", choices=("16bit", "fp8"), default="16bit")
     a = ap.parse_args()
     import torch
 
+    fp8 = a.kv_dtype == "fp8"
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "inference", f"prefill64_bench_{a.dtype}.jsonl")
+        a.out = os.path.join(ROOT, "profiles", "inference", f"prefill64_{'fp8_' if fp8 else ''}bench_{a.dtype}.jsonl")
     assert torch.cuda.is_available(), "prefill64_bench.py needs the GPU"
     assert a.reps >= 10, "medians of at least 10"
     dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float16
     lines = []
+    if fp8:
+        for case in (("chunk", -1), ("chunk", LEFT), ("contiguous", -1)):
+            lines.append(run_fp8(*case, dtype, a.reps))
+            print(json.dumps(lines[-1]), flush=True)
+            torch.cuda.empty_cache()
+        lines[-1].update(device=torch.cuda.get_device_name(0), torch=torch.__version__, hip=torch.version.hip)
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "w") as f:
+            f.writelines(json.dumps(ln) + "\n" for ln in lines)
+        sys.exit(0)
     for case in CASES:
         lines.append(run(*case, dtype, a.reps))
         print(json.dumps(lines[-1]), flush=True)

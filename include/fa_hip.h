@@ -985,8 +985,8 @@ int fa_decode_fp8_d64_launch(const fa_decode_fp8_args *args, const fa_window *wi
  * workgroup, grid n_seqs * n_heads * ceil(max_seqlen_q / 256).  The lengths' clamping, the window's rule, the row without keys
  * (o = 0, lse = z or -inf) and the fetch contract are the siblings'.  No workspace, no split, no atomics: the same bits for the
  * same inputs, and the cache form's bits are the packed form's on the gathered keys.  The host reads no device array;
- * graph-capturable; opts->ms is timed by the launch's own events.  Not here: fp8 caches, soft-capping.  The
- * backward of the packed form: fa_bwd_launch_varlen_qk_d64, below.
+ * graph-capturable; opts->ms is timed by the launch's own events.  Not here: soft-capping.  The backward of the packed form:
+ * fa_bwd_launch_varlen_qk_d64, below; an fp8 cache: fa_fwd_launch_varlen_kvcache_fp8_d64, below.
  */
 int fa_fwd_varlen_qk_d64_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
 int fa_fwd_launch_varlen_qk_d64(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
@@ -996,6 +996,26 @@ int fa_fwd_varlen_kvcache_d64_supported(const fa_fwd_config *cfg, const fa_fwd_o
 int fa_fwd_launch_varlen_kvcache_d64(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
                                      const fa_kvcache_layout *cache, const fa_window *window, const fa_sinks *sinks /* may be null */,
                                      const fa_fwd_opts *opts, float *lse, void *stream);
+
+/*
+ * ... against an fp8 (e4m3fn) cache (ABI 6, additive): fa_fwd_launch_varlen_kvcache_d64 with an fa_kvcache_fp8_scales
+ * behind the fa_kvcache_layout, its place in fa_fwd_launch_varlen_kvcache_fp8_sinks.  args->k, ->v hold e4m3fn bytes in the two cache
+ * shapes, so kv's strides count BYTES; key j of sequence b and K / V head h stands for float(k8[j]) * k_descale[b][h], likewise V
+ * (b is the sequence for a paged cache too); k_descale / v_descale are fp32 (n_seqs, n_kv_heads) on the DEVICE, never read by the
+ * host, null = 1.  The sinks meet the dequantized logit and v_descale scales o.  q, o, lse, the window, the sinks, the grid and the
+ * fetch contract are the 16-bit entry's, and so are o's and lse's bits on the dequantized cache when the descaled values are exact
+ * in q's type and the descales are powers of two.  Kernels of their own (fa_prefill64_fp8.hip): the raw bytes travel global -> LDS
+ * and are converted there, no fp8 MFMA operand, Q is not quantized.
+ *
+ * Refused before any HIP call: first what fa_fwd_launch_varlen_kvcache_d64 refuses, in its order and words; then the fp8 side in
+ * fa_fwd_launch_varlen_kvcache_fp8's words -- struct_size (FA_ERR_SHAPE), kv_dtype (FA_ERR_DTYPE), descale_batch_stride < n_kv_heads
+ * with a descale given (FA_ERR_SHAPE), kv strides that are no multiple of 16 bytes and descales not 4-byte aligned (FA_ERR_ALIGN).
+ * total_q = 0 returns FA_OK without a launch.
+ */
+int fa_fwd_varlen_kvcache_fp8_d64_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_kvcache_fp8_d64(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                         const fa_kvcache_layout *cache, const fa_kvcache_fp8_scales *scales, const fa_window *window,
+                                         const fa_sinks *sinks /* may be null */, const fa_fwd_opts *opts, float *lse, void *stream);
 
 /*
  * The packed backward at d_head = 64 (ABI 6, additive): fa_bwd_launch_varlen_qk_sinks with args->d_head = 64 -- dq, dk,
