@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "fa_bwd_varlen_qk_d64_workspace_bytes", "fa_bwd_launch_varlen_qk_d64",
     "fa_decode_fp8_d64_supported", "fa_decode_fp8_d64_num_splits", "fa_decode_fp8_d64_workspace_bytes", "fa_decode_fp8_d64_launch",
     "fa_fwd_varlen_kvcache_fp8_d64_supported", "fa_fwd_launch_varlen_kvcache_fp8_d64",
+    "fa_decode_d256_supported", "fa_decode_d256_num_splits", "fa_decode_d256_workspace_bytes", "fa_decode_d256_launch",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -504,6 +505,9 @@ def load():
         # ... and against an fp8 cache: the same over fa_decode_fp8_args
         fn, sibling = getattr(lib, f"fa_decode_fp8_d64_{suffix}"), getattr(lib, f"fa_decode_fp8_window_{suffix}")
         fn.restype, fn.argtypes = sibling.restype, sibling.argtypes[:2] + [ctypes.POINTER(FaSinks)] + sibling.argtypes[2:]
+        # the d_head = 256 decode: the windowed entry's arguments with an fa_softcap (null = no cap) behind the fa_window
+        fn, sibling = getattr(lib, f"fa_decode_d256_{suffix}"), getattr(lib, f"fa_decode_window_{suffix}")
+        fn.restype, fn.argtypes = sibling.restype, sibling.argtypes[:2] + [ctypes.POINTER(FaSoftcap)] + sibling.argtypes[2:]
     # the d_head = 64 prefills: the sinks forms' arguments (the fa_sinks may be null)
     for name in ("varlen_qk", "varlen_kvcache", "varlen_kvcache_fp8"):
         for fn, sibling in ((f"fa_fwd_{name}_d64_supported", f"fa_fwd_{name}_sinks_supported"), (f"fa_fwd_launch_{name}_d64", f"fa_fwd_launch_{name}_sinks")):

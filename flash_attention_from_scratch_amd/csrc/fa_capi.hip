@@ -23,6 +23,7 @@
 #include "fa_bwd64_kernel.hpp"
 #include "fa_decode_kernel.hpp"
 #include "fa_decode64_kernel.hpp"
+#include "fa_decode256_kernel.hpp"
 #include "fa_prefill64_kernel.hpp"
 #include "fa_kvcache_append_kernel.hpp"
 #include "fa_registry.hpp"
@@ -1248,9 +1249,9 @@ int softcap_validate(const fa_softcap *c) {
                     (double)c->softcap);
     return FA_OK;
 }
-// what the kernels take: A = softcap sqrt(d_head) and 1 / A, computed in double and rounded once (d_head = 128)
-void softcap_constants(const fa_softcap *c, float *a, float *inv_a) {
-    const double A = (double)c->softcap * std::sqrt(128.0);
+// what the kernels take: A = softcap sqrt(d_head) and 1 / A, computed in double and rounded once (d_head = 128, or fa_decode_d256_*'s 256)
+void softcap_constants(const fa_softcap *c, float *a, float *inv_a, double d_head = 128.0) {
+    const double A = (double)c->softcap * std::sqrt(d_head);
     *a = (float)A;
     *inv_a = (float)(1.0 / A);
 }
@@ -1938,7 +1939,8 @@ template <class A> int decode_validate(const A *a, CacheView &c, int64_t d_head 
     if (a->dtype != FA_FP16 && a->dtype != FA_BF16) return fail(FA_ERR_DTYPE, "Only fp16 and bf16 are supported");
     if (a->d_head != d_head)
         return fail(FA_ERR_SHAPE, d_head == 128 ? "decode supports d_head = 128 only (got %lld)"
-                                                : "fa_decode_d64 serves d_head = 64 only (got %lld; 128: fa_decode_sinks_launch and its siblings)",
+                                  : d_head == 64 ? "fa_decode_d64 serves d_head = 64 only (got %lld; 128: fa_decode_sinks_launch and its siblings)"
+                                                 : "fa_decode_d256 serves d_head = 256 only (got %lld; 128: fa_decode_softcap_launch and its siblings)",
                     (long long)a->d_head);
     if (a->batch < 0 || a->seqlen_q <= 0 || a->n_heads <= 0) return fail(FA_ERR_SHAPE, "batch must not be negative, seqlen_q and n_heads must be positive");
     if (a->batch > INT32_MAX / 2 || a->n_heads > INT32_MAX / 2) return fail(FA_ERR_SHAPE, "problem too large for a 1-D grid");
@@ -1946,6 +1948,9 @@ template <class A> int decode_validate(const A *a, CacheView &c, int64_t d_head 
         return fail(FA_ERR_SHAPE, "grouped-query attention needs n_kv_heads (%lld) to divide n_heads (%lld)", (long long)a->n_kv_heads,
                     (long long)a->n_heads);
     const int64_t group = a->n_heads / a->n_kv_heads;
+    if (d_head == 256 && (a->seqlen_q > fa::decode256::MAX_ROWS || a->seqlen_q * group > fa::decode256::MAX_ROWS))
+        return fail(FA_ERR_NO_KERNEL, "decode at d_head = 256 serves seqlen_q * (n_heads / n_kv_heads) <= 32 packed query rows (got %lld * %lld)",
+                    (long long)a->seqlen_q, (long long)group);
     if (a->seqlen_q > kDecodeMaxRows || a->seqlen_q * group > kDecodeMaxRows)
         return fail(FA_ERR_NO_KERNEL, "decode serves seqlen_q * (n_heads / n_kv_heads) <= 64 packed query rows (got %lld * %lld): use the "
                                       "forward entry points for longer queries", (long long)a->seqlen_q, (long long)group);
@@ -2110,8 +2115,11 @@ int decode_launch(const A *a, bool windowed, const fa_window *w, const char *ws_
     const fa::DecodeFp8SinksArgs kz8 = {k, kz.sinks};
     const fa::Decode64Args k64 = {k.f.d, k.left, k.right, kz.sinks};
     const fa::Decode64Fp8Args k64f = {k64, k.f.k_descale, k.f.v_descale, k.f.ds_bs};
+    fa::Decode256Args k256 = {k.f.d, k.left, k.right, 0.0f, 0.0f};
+    if (capped && d_head == 256) softcap_constants(cap, &k256.cap_a, &k256.cap_inv_a, 256.0);
     const hipStream_t s = (hipStream_t)stream;
     return enqueue_timed([&] {
+        if (d_head == 256) return fa::decode256_enqueue(k256, a->dtype, capped, s);
         if (d_head == 64) return c.fp8 ? fa::decode64_fp8_enqueue(k64f, a->dtype, s) : fa::decode64_enqueue(k64, a->dtype, s);
         if (sunk) return c.fp8 ? fa::decode_fp8_sinks_enqueue(kz8, a->dtype, s) : fa::decode_sinks_enqueue(kz, a->dtype, s);
         if (capped) return c.fp8 ? fa::decode_fp8_softcap_enqueue(ks8, a->dtype, s) : fa::decode_softcap_enqueue(ks, a->dtype, s);
@@ -2226,6 +2234,22 @@ int64_t fa_decode_fp8_d64_workspace_bytes(const fa_decode_fp8_args *a, const fa_
 }
 int fa_decode_fp8_d64_launch(const fa_decode_fp8_args *a, const fa_window *w, const fa_sinks *sinks, void *stream, float *ms) {
     return decode_launch(a, true, w, "fa_decode_fp8_d64_workspace_bytes", stream, ms, false, nullptr, sinks != nullptr, sinks, 64, "args, window, sinks");
+}
+
+// ... at d_head = 256: fa_decode_args with d_head = 256, a window always ((-1, -1): none) and an fa_softcap that may be
+// null (no cap).  A 16-bit cache only, at most 32 packed rows.  The capped forms' planner, split rule and launch body with the head
+// dimension as a parameter; a workspace query of its own, since the partials are 256 wide.
+int fa_decode_d256_supported(const fa_decode_args *a, const fa_window *w, const fa_softcap *cap) {
+    return decode_plan(a, true, w, cap != nullptr, cap, false, nullptr, 256).status == FA_OK;
+}
+int fa_decode_d256_num_splits(const fa_decode_args *a, const fa_window *w, const fa_softcap *cap) {
+    return plan_splits(decode_plan(a, true, w, cap != nullptr, cap, false, nullptr, 256));
+}
+int64_t fa_decode_d256_workspace_bytes(const fa_decode_args *a, const fa_window *w, const fa_softcap *cap) {
+    return plan_workspace(a, decode_plan(a, true, w, cap != nullptr, cap, false, nullptr, 256));
+}
+int fa_decode_d256_launch(const fa_decode_args *a, const fa_window *w, const fa_softcap *cap, void *stream, float *ms) {
+    return decode_launch(a, true, w, "fa_decode_d256_workspace_bytes", stream, ms, cap != nullptr, cap, false, nullptr, 256, "args, window, softcap");
 }
 
 // ---- the KV-cache append in front of a decode --------------------------------------------------------------------------------

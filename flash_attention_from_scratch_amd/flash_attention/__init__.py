@@ -248,6 +248,27 @@ def kvcache_d64_num_splits(q, k_cache, v_cache, cache_seqlens, sinks=None, block
                                                           k_descale=k_descale, v_descale=v_descale)
 
 
+def forward_kvcache_d256(q, k_cache, v_cache, cache_seqlens, softcap=0.0, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
+                         num_splits=0, timed=False, window_size=(-1, -1)):
+    """KV-cache decode at d_head = 256 (Gemma-2's and Gemma-3's head dimension): q (batch, seqlen_q, n_heads, 256)
+    against k_cache, v_cache (batch, seqlen_cache, n_kv_heads, 256) or, with block_table, pages (num_pages, page_size, n_kv_heads,
+    256), 16-bit in q's dtype, at the scale 1 / sqrt(256), at most 32 packed rows seqlen_q * (n_heads / n_kv_heads).  Every argument is
+    forward_kvcache_softcap's of that name, with its meaning, checks and errors; softcap = 0 means no cap.  -> what forward_kvcache
+    returns.  Kernels of their own, 16 keys per wave visit; split-KV with a fixed-order combine, graph-capturable, the host reads no
+    device array.  Not served at 256, and so without a parameter here: an fp8 cache, sinks, the fused append and rotary."""
+    return flash_attention_kernels.forward_kvcache_d256(q, k_cache, v_cache, cache_seqlens, softcap=softcap, block_table=block_table,
+                                                        causal=causal, return_lse=return_lse, max_seqlen_k=max_seqlen_k, num_splits=num_splits,
+                                                        timed=timed, window_size=window_size)
+
+
+def kvcache_d256_num_splits(q, k_cache, v_cache, cache_seqlens, softcap=0.0, block_table=None, causal=False, max_seqlen_k=None, num_splits=0,
+                            window_size=(-1, -1)):
+    """The split count forward_kvcache_d256 uses for these arguments: the same checks, nothing allocated, no launch."""
+    return flash_attention_kernels.kvcache_d256_num_splits(q, k_cache, v_cache, cache_seqlens, softcap=softcap, block_table=block_table,
+                                                           causal=causal, max_seqlen_k=max_seqlen_k, num_splits=num_splits,
+                                                           window_size=window_size)
+
+
 def forward_varlen_d64(q, k, v, cu_seqlens, max_seqlen, sinks=None, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None, *,
                        window_size=(-1, -1)):
     """Packed prefill at d_head = 64 (gpt-oss's head dimension): q (total_q, n_heads, 64), k and v (total_k, n_kv_heads,

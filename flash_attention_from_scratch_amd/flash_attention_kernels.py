@@ -1053,6 +1053,56 @@ def forward_kvcache_d64(q, k_cache, v_cache, cache_seqlens, sinks=None, block_ta
     return out[0] if len(out) == 1 else out
 
 
+def _decode_d256_args(q, k_cache, v_cache, cache_seqlens, softcap, block_table, causal, max_seqlen_k, num_splits, window_size):
+    """forward_kvcache_d256's checks, in forward_kvcache_softcap's order (a bad window, then a bad cap: both a ValueError before any
+    tensor is looked at) -> (q as the launch takes it, fa_decode_args still without o, lse and workspace, the fa_window, the fa_softcap
+    or None)."""
+    window = _window(window_size, causal)
+    cap = _softcap(softcap)
+    _need_tensors(((q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cache_seqlens, "cache_seqlens")))
+    if k_cache.dtype in _FLOAT8_DTYPES or v_cache.dtype in _FLOAT8_DTYPES:
+        raise RuntimeError("forward_kvcache_d256: an fp8 cache is not served at d_head = 256 (a 16-bit cache in q's dtype)")
+    q, args, _ = _decode_args(q, k_cache, v_cache, cache_seqlens, block_table, causal, max_seqlen_k, num_splits, None, None)
+    return q, args, _capi.make_window(*(window or (-1, -1))), (None if cap is None else _capi.make_softcap(cap))
+
+
+def kvcache_d256_num_splits(q, k_cache, v_cache, cache_seqlens, softcap=0.0, block_table=None, causal=False, max_seqlen_k=None, num_splits=0,
+                            window_size=(-1, -1)):
+    """The split count forward_kvcache_d256 uses for these arguments (fa_decode_d256_num_splits): the same checks, nothing allocated,
+    no launch."""
+    _, args, w, sc = _decode_d256_args(q, k_cache, v_cache, cache_seqlens, softcap, block_table, causal, max_seqlen_k, num_splits, window_size)
+    return _capi.check(_capi.load().fa_decode_d256_num_splits(ctypes.byref(args), ctypes.byref(w), None if sc is None else ctypes.byref(sc)))
+
+
+def forward_kvcache_d256(q, k_cache, v_cache, cache_seqlens, softcap=0.0, block_table=None, causal=False, return_lse=False, max_seqlen_k=None,
+                         num_splits=0, timed=False, window_size=(-1, -1)):
+    """Decode attention against a K / V cache at d_head = 256 (fa_decode_d256_launch), the Gemma-2 / Gemma-3 head
+    dimension: q (batch, seqlen_q, n_heads, 256); k_cache, v_cache (batch, seqlen_cache, n_kv_heads, 256), or with block_table
+    (num_pages, page_size, n_kv_heads, 256), in q's dtype; the logits' scale is 1 / sqrt(256); at most 32 packed rows
+    seqlen_q * (n_heads / n_kv_heads).  softcap, cache_seqlens, block_table, causal, return_lse, max_seqlen_k, num_splits, timed and
+    window_size are forward_kvcache_softcap's, with their meaning, checks and errors: the logit of a key the row sees becomes
+    softcap * tanh(q . k / 16 / softcap), masked keys stay -inf, lse is taken over the capped logits, 0 is off (the uncapped
+    kernels).  -> what forward_kvcache returns.  The host reads no device array; graph-capturable.  A bad window_size is reported
+    first, then a bad softcap: both a ValueError before the library is loaded.
+    Not here, and so without a parameter: an fp8 cache and its descales, sinks, the fused append (k=, v=) and rotary."""
+    q, args, w, sc = _decode_d256_args(q, k_cache, v_cache, cache_seqlens, softcap, block_table, causal, max_seqlen_k, num_splits, window_size)
+    batch, seqlen_q, n_heads, d_head = q.shape
+    o = torch.empty((batch, seqlen_q, n_heads, d_head), dtype=q.dtype, device=q.device)
+    lse = torch.empty((batch, n_heads, seqlen_q), dtype=torch.float32, device=q.device) if return_lse else None
+    args.o, args.lse = o.data_ptr(), (lse.data_ptr() if return_lse else None)
+    lib, more = _capi.load(), (ctypes.byref(w), None if sc is None else ctypes.byref(sc))
+    nbytes = lib.fa_decode_d256_workspace_bytes(ctypes.byref(args), *more)
+    _capi.check(nbytes if nbytes < 0 else 0)
+    with torch.cuda.device(q.device):
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes > 0 else None   # (on the current stream's allocator)
+        args.workspace = workspace.data_ptr() if workspace is not None else None
+        stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        ms = ctypes.c_float(0.0)
+        _capi.check(lib.fa_decode_d256_launch(ctypes.byref(args), *more, stream, ctypes.byref(ms) if timed else None))
+    out = ((o, lse) if return_lse else (o,)) + ((float(ms.value),) if timed else ())
+    return out[0] if len(out) == 1 else out
+
+
 def forward_varlen_kvcache_sinks(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, sinks, block_table=None, causal=False,
                                  max_seqlen_k=None, timed=False, k_descale=None, v_descale=None, *, window_size=(-1, -1)):
     """forward_varlen_kvcache with learned attention sinks (fa_fwd_launch_varlen_kvcache_sinks, .._fp8_sinks for an fp8 cache): every

@@ -975,6 +975,27 @@ int64_t fa_decode_fp8_d64_workspace_bytes(const fa_decode_fp8_args *args, const 
 int fa_decode_fp8_d64_launch(const fa_decode_fp8_args *args, const fa_window *window, const fa_sinks *sinks, void *stream, float *ms);
 
 /*
+ * KV-cache decode at d_head = 256 (ABI 6, additive): what fa_decode_softcap_* serve at 128, for a 16-bit cache in q's
+ * dtype -- the Gemma-2 / Gemma-3 head dimension.  args is an fa_decode_args with d_head = 256: q and o (batch, seqlen_q, n_heads, 256),
+ * the caches (batch, seqlen_cache, n_kv_heads, 256) or (num_pages, page_size, n_kv_heads, 256); the logits' scale is 1 / sqrt(256).
+ * window is required, (-1, -1) means none; softcap MAY BE NULL: no cap; a non-null one is fa_decode_softcap_*'s (the logit of a key the
+ * row sees becomes softcap * tanh(q . k / 16 / softcap), lse over the capped logits).  Kernels of their own (16 keys per wave
+ * visit), at most 32 packed rows seqlen_q * (n_heads / n_kv_heads); the fetch contract, the clamping of lengths and block_table
+ * entries, the row packing, the split rule and the meaning of every field are fa_decode_window_*'s.  The workspace holds
+ * (num_splits, batch, n_kv_heads, rows, 256) fp32 partials and their lse: fa_decode_d256_workspace_bytes sizes it.  Deterministic for
+ * a given num_splits, no atomics, the host reads no device array, graph-capturable.  Not served at 256: an fp8 cache, sinks, the fused
+ * append, more than 32 packed rows, a caller-given scale.
+ *
+ * Refused before any HIP call, in the order of fa_decode_softcap_*: d_head != 256 (FA_ERR_SHAPE) where they refuse d_head != 128; more
+ * than 32 packed rows or page_size % 64 != 0 (FA_ERR_NO_KERNEL); then the window's rules; then, for a non-null fa_softcap, its rules.
+ */
+int fa_decode_d256_supported(const fa_decode_args *args, const fa_window *window, const fa_softcap *softcap /* null: no cap */);
+int fa_decode_d256_num_splits(const fa_decode_args *args, const fa_window *window, const fa_softcap *softcap /* null: no cap */);
+int64_t fa_decode_d256_workspace_bytes(const fa_decode_args *args, const fa_window *window, const fa_softcap *softcap /* null: no cap */);
+int fa_decode_d256_launch(const fa_decode_args *args, const fa_window *window, const fa_softcap *softcap /* null: no cap */, void *stream,
+                          float *ms);
+
+/*
  * Prefill at d_head = 64 (ABI 6, additive): fa_fwd_launch_varlen_qk_sinks and fa_fwd_launch_varlen_kvcache_sinks
  * with args->d_head = 64 -- q (total_q, n_heads, 64) packed, k / v (total_k, n_kv_heads, 64) packed or a 16-bit cache
  * (n_seqs, seqlen_cache, n_kv_heads, 64) / (num_pages, page_size, n_kv_heads, 64) in q's dtype, page_size % 64 == 0 -- the logits'
