@@ -5,4 +5,5 @@ from flash_attention_from_scratch_amd.flash_attention import (  # noqa: F401
     forward_kvcache_softcap, forward_timed, forward_varlen, forward_varlen_kvcache, forward_varlen_kvcache_sinks, forward_varlen_sinks,
     forward_varlen_d64, forward_varlen_kvcache_d64, kvcache_d64_num_splits, quantize_kvcache_fp8,
     attention_varlen_d64, backward_varlen_d64, forward_kvcache_d256, kvcache_d256_num_splits,
+    forward_varlen_d256, forward_varlen_kvcache_d256,
 )

@@ -62,6 +62,8 @@ EXPORTED_SYMBOLS = (
     "fa_decode_fp8_d64_supported", "fa_decode_fp8_d64_num_splits", "fa_decode_fp8_d64_workspace_bytes", "fa_decode_fp8_d64_launch",
     "fa_fwd_varlen_kvcache_fp8_d64_supported", "fa_fwd_launch_varlen_kvcache_fp8_d64",
     "fa_decode_d256_supported", "fa_decode_d256_num_splits", "fa_decode_d256_workspace_bytes", "fa_decode_d256_launch",
+    "fa_fwd_varlen_qk_d256_supported", "fa_fwd_launch_varlen_qk_d256",
+    "fa_fwd_varlen_kvcache_d256_supported", "fa_fwd_launch_varlen_kvcache_d256",
 )
 FA_KV_FP8_E4M3FN = 1  # fa_kv_dtype
 FA_SPECULATIVE_OFF, FA_SPECULATIVE_ALWAYS, FA_SPECULATIVE_ADAPTIVE = 0, 1, 2  # fa_speculative_mode
@@ -511,6 +513,10 @@ def load():
     # the d_head = 64 prefills: the sinks forms' arguments (the fa_sinks may be null)
     for name in ("varlen_qk", "varlen_kvcache", "varlen_kvcache_fp8"):
         for fn, sibling in ((f"fa_fwd_{name}_d64_supported", f"fa_fwd_{name}_sinks_supported"), (f"fa_fwd_launch_{name}_d64", f"fa_fwd_launch_{name}_sinks")):
+            getattr(lib, fn).restype, getattr(lib, fn).argtypes = ctypes.c_int, list(getattr(lib, sibling).argtypes)
+    # the d_head = 256 prefills: the soft-capped forms' arguments (the fa_softcap may be null)
+    for name in ("varlen_qk", "varlen_kvcache"):
+        for fn, sibling in ((f"fa_fwd_{name}_d256_supported", f"fa_fwd_{name}_softcap_supported"), (f"fa_fwd_launch_{name}_d256", f"fa_fwd_launch_{name}_softcap")):
             getattr(lib, fn).restype, getattr(lib, fn).argtypes = ctypes.c_int, list(getattr(lib, sibling).argtypes)
     # the d_head = 64 packed backward: the sinks form's arguments (the fa_sinks may be null, dsinks with it)
     for fn, sibling in (("fa_bwd_varlen_qk_d64_workspace_bytes", "fa_bwd_varlen_qk_sinks_workspace_bytes"),

@@ -25,6 +25,7 @@
 #include "fa_decode64_kernel.hpp"
 #include "fa_decode256_kernel.hpp"
 #include "fa_prefill64_kernel.hpp"
+#include "fa_prefill256_kernel.hpp"
 #include "fa_kvcache_append_kernel.hpp"
 #include "fa_registry.hpp"
 
@@ -358,6 +359,12 @@ void do_init_body(int dev, DeviceState *st) {
                      hipGetErrorString(rc));
             return;
         }
+    }
+    // ... and the prefill at d_head = 256 (fa_fwd_launch_varlen_qk_d256, _kvcache_d256): 128 KiB or 96 KiB by tile form
+    if (const hipError_t rc = fa::prefill256_device_init(); rc != hipSuccess) {
+        st->status = FA_ERR_LAUNCH;
+        snprintf(st->err, sizeof(st->err), "hipFuncSetAttribute(d_head = 256 prefill) on device %d: %s", dev, hipGetErrorString(rc));
+        return;
     }
 }
 
@@ -1190,6 +1197,8 @@ const char *kNoVarlen = "packed variable-length sequences are served by the (B_r
                         "128 only, plain or causal, without speculative, prescaled_q and stats";
 const char *kNoVarlen64 = "packed variable-length sequences at d_head = 64 are served in fp16 and bf16, plain or causal, without speculative, "
                           "prescaled_q and stats";
+const char *kNoVarlen256 = "packed variable-length sequences at d_head = 256 are served in fp16 and bf16, plain or causal, without speculative, "
+                           "prescaled_q and stats";
 
 // the cache side of fa_fwd_launch_varlen_kvcache and its fp8 form (`sc`): `c` already holds kv's strides and heads and vq's n_seqs,
 // all validated; each struct is read once its own struct_size has passed
@@ -1317,6 +1326,9 @@ int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_
     if (d_head == 64) {
         if (!fa_fwd_varlen_qk_d64_supported(&args->cfg, opts)) return fail(FA_ERR_NO_KERNEL, "%s", kNoVarlen64);
         if (args->d_head != 64) return fail(FA_ERR_SHAPE, "%s supports d_head = 64 only (got %lld)", call.entry, (long long)args->d_head);
+    } else if (d_head == 256) {
+        if (!fa_fwd_varlen_qk_d256_supported(&args->cfg, opts)) return fail(FA_ERR_NO_KERNEL, "%s", kNoVarlen256);
+        if (args->d_head != 256) return fail(FA_ERR_SHAPE, "%s supports d_head = 256 only (got %lld)", call.entry, (long long)args->d_head);
     } else {
         if (!fa_fwd_varlen_supported(&args->cfg, opts)) return fail(FA_ERR_NO_KERNEL, "%s", kNoVarlen);
         if (args->d_head != 128)
@@ -1403,6 +1415,45 @@ int fwd_launch_varlen(const VarlenCall &call, const fa_fwd_args *args, const fa_
     }
     DeviceState *dev = current_device(&rc);
     if (!dev) return rc;
+    if (d_head == 256) {   // fa_prefill256_kernel.hpp: one kernel per dtype, key side, cap and tile form; their dynamic LDS was opted in to above
+        fa::Prefill256Args p = {};
+        p.q = (const uint16_t *)args->q;
+        p.k = (const uint16_t *)args->k;
+        p.v = (const uint16_t *)args->v;
+        p.o = (uint16_t *)args->o;
+        p.lse = lse;
+        p.cu_q = vq->cu_seqlens;
+        p.q_ss = args->seq_stride;
+        p.q_hs = args->head_stride;
+        p.kv_ss = kv->kv_seq_stride;
+        p.kv_hs = kv->kv_head_stride;
+        p.n_heads = (int32_t)args->n_heads;
+        p.group = (int32_t)(args->n_heads / kv->n_kv_heads);
+        p.n_q_blocks = (int32_t)((vq->max_seqlen + fa::prefill256::R - 1) / fa::prefill256::R);
+        p.total_q = (int32_t)vq->total_tokens;
+        p.max_seqlen_q = (int32_t)vq->max_seqlen;
+        if (!cache_side) {
+            p.cu_k = vk->cu_seqlens;
+            p.total_k = (int32_t)vk->total_tokens;
+            p.max_seqlen_k = (int32_t)vk->max_seqlen;
+        } else {
+            const int64_t cap_k = cache.capacity();
+            p.cache_seqlens = cache.cache_seqlens;
+            p.block_table = cache.block_table;
+            p.page_stride = kv->kv_batch_stride;
+            p.bt_stride = cache.paged() ? (int32_t)cache.block_table_stride : 0;
+            p.num_pages = (int32_t)cache.slots();
+            p.tiles_per_page = (int32_t)(cache.paged() ? cache.page_size / 64 : (cap_k + 63) / 64);   // (contiguous: one "page" per entry)
+            p.max_len = (int32_t)(cache.max_seqlen_k > 0 ? cache.max_seqlen_k : cap_k);
+        }
+        p.left = call.w->left;   // (causal as right = 0: the kernel's one rule for both)
+        p.right = window_right(call.w, o.causal);
+        if (capped) softcap_constants(call.cap, &p.cap_a, &p.cap_inv_a, 256.0);
+        const hipStream_t s = (hipStream_t)stream;
+        const int dtype = args->cfg.dtype == FA_BF16 ? 15 : 5;
+        const int64_t n_seqs = vq->n_seqs;
+        return enqueue_timed([&] { return fa::prefill256_enqueue(p, dtype, cache_side, capped, n_seqs, s); }, s, o.ms);
+    }
     const char *why;
     const fa::KernelEntry *e = varlen_entry(&args->cfg, &why);
     // the widest arguments of each key side: every narrower form's are their first member, and the member's address is what its kernel takes
@@ -1743,6 +1794,22 @@ int fa_fwd_launch_varlen_kvcache_fp8_d64(const fa_fwd_args *args, const fa_kv_la
                                          float *lse, void *stream) {
     return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_fp8_d64", "total_q", KEYS_FP8_CACHE, EXTRA_SINKS, nullptr, kc, sc, w, nullptr, sinks},
                              args, kv, vq, opts, lse, stream, 64);
+}
+
+// d_head = 256: the d64 entries' arguments with args->d_head = 256 and, where they take an fa_sinks, an fa_softcap
+// that may be null (no cap: the windowed form, the kernel built without the cap); of cfg only the dtype is read.  One kernel family
+// of its own, fa_prefill256_kernel.hpp
+int fa_fwd_varlen_qk_d256_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_qk_d64_supported(cfg, opts); }
+int fa_fwd_launch_varlen_qk_d256(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_varlen_layout *vk,
+                                 const fa_window *w, const fa_softcap *cap, const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_qk_d256", "total_q", KEYS_PACKED, cap ? EXTRA_SOFTCAP : EXTRA_WINDOW, vk, nullptr, nullptr, w, cap},
+                             args, kv, vq, opts, lse, stream, 256);
+}
+int fa_fwd_varlen_kvcache_d256_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts) { return fa_fwd_varlen_qk_d64_supported(cfg, opts); }
+int fa_fwd_launch_varlen_kvcache_d256(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *vq, const fa_kvcache_layout *kc,
+                                      const fa_window *w, const fa_softcap *cap, const fa_fwd_opts *opts, float *lse, void *stream) {
+    return fwd_launch_varlen({"fa_fwd_launch_varlen_kvcache_d256", "total_q", KEYS_CACHE, cap ? EXTRA_SOFTCAP : EXTRA_WINDOW, nullptr, kc, nullptr, w, cap},
+                             args, kv, vq, opts, lse, stream, 256);
 }
 
 int64_t fa_bwd_varlen_workspace_bytes(const fa_bwd_varlen_args *a) {

@@ -269,6 +269,28 @@ def kvcache_d256_num_splits(q, k_cache, v_cache, cache_seqlens, softcap=0.0, blo
                                                            window_size=window_size)
 
 
+def forward_varlen_d256(q, k, v, cu_seqlens, max_seqlen, softcap=0.0, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None, *,
+                        window_size=(-1, -1)):
+    """Packed prefill at d_head = 256 (Gemma-2's and Gemma-3's head dimension): q (total_q, n_heads, 256), k and v
+    (total_k, n_kv_heads, 256), at the scale 1 / sqrt(256).  Every argument is forward_varlen's of that name, with its meaning, checks
+    and defaults, and softcap is forward_kvcache_d256's (0 means no cap).  -> (o, lse[, ms]).  A kernel of its own: 32 rows per wave,
+    128 per workgroup, one wave per SIMD, 64-key tiles through 128 KiB of LDS.  Forward only; no sinks."""
+    return flash_attention_kernels.forward_varlen_d256(q, k, v, cu_seqlens, max_seqlen, softcap=softcap, causal=causal, timed=timed,
+                                                       cu_seqlens_k=cu_seqlens_k, max_seqlen_k=max_seqlen_k, window_size=window_size)
+
+
+def forward_varlen_kvcache_d256(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, softcap=0.0, block_table=None, causal=False,
+                                max_seqlen_k=None, timed=False, *, window_size=(-1, -1)):
+    """Prefill against the cache forward_kvcache_d256 decodes from: q (total_q, n_heads, 256) packed; k_cache, v_cache
+    (n_seqs, seqlen_cache, n_kv_heads, 256) or, with block_table, pages (num_pages, page_size, n_kv_heads, 256), 16-bit in q's dtype.
+    Every argument is forward_varlen_kvcache's of that name, with its meaning, checks and defaults, and softcap is
+    forward_kvcache_d256's (0 means no cap).  -> (o, lse[, ms]), bit for bit forward_varlen_d256(cu_seqlens_k=) on the same keys packed.
+    Not served at 256, and so without a parameter here: an fp8 cache, sinks, the fused append and rotary."""
+    return flash_attention_kernels.forward_varlen_kvcache_d256(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, softcap=softcap,
+                                                               block_table=block_table, causal=causal, max_seqlen_k=max_seqlen_k,
+                                                               timed=timed, window_size=window_size)
+
+
 def forward_varlen_d64(q, k, v, cu_seqlens, max_seqlen, sinks=None, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None, *,
                        window_size=(-1, -1)):
     """Packed prefill at d_head = 64 (gpt-oss's head dimension): q (total_q, n_heads, 64), k and v (total_k, n_kv_heads,

@@ -405,6 +405,21 @@ def forward_varlen_d64(q, k, v, cu_seqlens, max_seqlen, sinks=None, causal=False
     return _forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, None, sinks, d_head=64)
 
 
+def forward_varlen_d256(q, k, v, cu_seqlens, max_seqlen, softcap=0.0, causal=False, timed=False, cu_seqlens_k=None, max_seqlen_k=None, *,
+                        window_size=(-1, -1)):
+    """forward_varlen at d_head = 256 (fa_fwd_launch_varlen_qk_d256), the Gemma-2 / Gemma-3 head dimension: q
+    (total_q, n_heads, 256), k and v (total_k, n_kv_heads, 256); the logits' scale is 1 / sqrt(256).  Every other argument is
+    forward_varlen's, with its meaning, checks and defaults (one range given: on both sides), and softcap is forward_kvcache_d256's:
+    the logit of a key the row sees becomes softcap * tanh(q . k / 16 / softcap), masked keys stay -inf, lse is taken over the capped
+    logits, 0 is off (the kernel built without the cap).  -> (o, lse[, ms]), lse fp32 (n_heads, total_q); a row that sees no key gives
+    o = 0, lse = -inf.  A kernel of its own (128 rows per workgroup).  Forward only.  A bad window_size is reported first, then a bad
+    softcap: both a ValueError before the library is loaded; another d_head is a RuntimeError.
+    Not here, and so without a parameter: sinks, a backward."""
+    window = _window(window_size, causal)
+    cap = _softcap(softcap)
+    return _forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k, max_seqlen_k, window, cap, None, d_head=256)
+
+
 def _check_sinks(sinks, q, name="sinks", q_dim=3):
     """sinks as the calls with sinks take it: a contiguous fp32 tensor of shape (n_heads,) on q's device (checked in front of the
     sibling's own checks, so against q only where q is a tensor of the call's shape at all: q_dim 3 packed, 4 forward_kvcache_sinks's)"""
@@ -429,6 +444,9 @@ def _forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k
     d64 = d_head == 64   # (the entry, not the tensor: forward_varlen on a 64-wide q is still the library's refusal)
     if d64 and q.shape[2] != 64:
         raise RuntimeError(f"forward_varlen_d64 supports d_head = 64 only (got {q.shape[2]})")
+    d256 = d_head == 256
+    if d256 and q.shape[2] != 256:
+        raise RuntimeError(f"forward_varlen_d256 supports d_head = 256 only (got {q.shape[2]})")
     total, n_heads, d_head = q.shape
     lib = _capi.load()
     cfg = _capi.make_config(varlen_config(q.dtype))
@@ -449,6 +467,12 @@ def _forward_varlen(q, k, v, cu_seqlens, max_seqlen, causal, timed, cu_seqlens_k
             _capi.check(lib.fa_fwd_launch_varlen_qk_d64(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(sides[0]), ctypes.byref(sides[-1]),
                                                         ctypes.byref(w), None if sk is None else ctypes.byref(sk), ctypes.byref(opts),
                                                         ctypes.c_void_p(lse.data_ptr()), stream))
+            return (o, lse, float(ms.value)) if timed else (o, lse)
+        if d256:   # (the d64 entry's arguments with an fa_softcap, which may be null, for its fa_sinks)
+            w, sc = _capi.make_window(*(window or (-1, -1))), (None if cap is None else _capi.make_softcap(cap))
+            _capi.check(lib.fa_fwd_launch_varlen_qk_d256(ctypes.byref(args), ctypes.byref(kv), ctypes.byref(sides[0]), ctypes.byref(sides[-1]),
+                                                         ctypes.byref(w), None if sc is None else ctypes.byref(sc), ctypes.byref(opts),
+                                                         ctypes.c_void_p(lse.data_ptr()), stream))
             return (o, lse, float(ms.value)) if timed else (o, lse)
         if sinks is not None:
             w, sk = _capi.make_window(*(window or (-1, -1))), _capi.make_sinks(sinks.data_ptr(), n_heads)
@@ -1141,6 +1165,25 @@ def forward_varlen_kvcache_d64(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, 
                                    k_descale, v_descale, window, None, sinks, d_head=64)
 
 
+def forward_varlen_kvcache_d256(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, softcap=0.0, block_table=None, causal=False,
+                                max_seqlen_k=None, timed=False, *, window_size=(-1, -1)):
+    """forward_varlen_kvcache at d_head = 256 (fa_fwd_launch_varlen_kvcache_d256): q (total_q, n_heads, 256); k_cache,
+    v_cache what forward_kvcache_d256 decodes against -- (n_seqs, seqlen_cache, n_kv_heads, 256), or with block_table (num_pages,
+    page_size, n_kv_heads, 256), page_size % 64 == 0, 16-bit in q's dtype; the logits' scale is 1 / sqrt(256).  Every other argument is
+    forward_varlen_kvcache's, with its meaning, checks and defaults, and softcap is forward_kvcache_d256's (0 is off: the kernel built
+    without the cap).  -> (o, lse[, ms]); o and lse are forward_varlen_d256's bits on the gathered keys.  This call fills the cache's
+    attention, prefills a chunk behind a cached prefix and verifies any number of packed rows.  The host reads no device array;
+    graph-capturable.  A bad window_size is reported first, then a bad softcap: both a ValueError before the library is loaded; an fp8
+    cache or another d_head is a RuntimeError.
+    Not here, and so without a parameter: an fp8 cache and its descales, sinks, the fused append (k=, v=) and rotary."""
+    window = _window(window_size, causal)
+    cap = _softcap(softcap)
+    if any(isinstance(t, torch.Tensor) and t.dtype in _FLOAT8_DTYPES for t in (k_cache, v_cache)):
+        raise RuntimeError("forward_varlen_kvcache_d256: an fp8 cache is not served at d_head = 256 (a 16-bit cache in q's dtype)")
+    return _forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, max_seqlen_k, timed,
+                                   None, None, window, cap, None, d_head=256)
+
+
 def forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table=None, causal=False,
                            max_seqlen_k=None, timed=False, k_descale=None, v_descale=None, *, window_size=(-1, -1), softcap=0.0):
     """Prefill against a K / V cache (fa_fwd_launch_varlen_kvcache): forward_varlen(cu_seqlens_k=) whose keys are read from the
@@ -1204,6 +1247,9 @@ def _forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cac
     d64 = d_head == 64   # (the entry, not the tensor)
     if d64 and q.shape[2] != 64:
         raise RuntimeError(f"forward_varlen_kvcache_d64 supports d_head = 64 only (got {q.shape[2]})")
+    d256 = d_head == 256
+    if d256 and q.shape[2] != 256:
+        raise RuntimeError(f"forward_varlen_kvcache_d256 supports d_head = 256 only (got {q.shape[2]})")
     total, n_heads, d_head = q.shape
     n_kv = k_cache.shape[2]
     if n_kv < 1 or n_heads % n_kv != 0:
@@ -1251,6 +1297,9 @@ def _forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cac
             form = "_d64"
             w = [ctypes.byref(_capi.make_window(*(window or (-1, -1)))),
                  None if sinks is None else ctypes.byref(_capi.make_sinks(sinks.data_ptr(), n_heads))]
+        if d256:   # (likewise with an fa_softcap, which may be null)
+            form = "_d256"
+            w = [ctypes.byref(_capi.make_window(*(window or (-1, -1)))), None if cap is None else ctypes.byref(_capi.make_softcap(cap))]
         tail = w + [ctypes.byref(opts), ctypes.c_void_p(lse.data_ptr()), stream]
         if fp8:
             sc = _capi.make_kvcache_fp8_scales(k_descale=k_descale.data_ptr(), v_descale=v_descale.data_ptr(),

@@ -1062,6 +1062,30 @@ int fa_bwd_launch_varlen_qk_d64(const fa_bwd_varlen_qk_args *args, const fa_wind
                                 float *dsinks /* null iff sinks is null */, void *stream, float *ms);
 
 /*
+ * Prefill at d_head = 256 (ABI 6, additive): fa_fwd_launch_varlen_qk_d64 and fa_fwd_launch_varlen_kvcache_d64 with
+ * args->d_head = 256 and an fa_softcap where those take an fa_sinks -- q (total_q, n_heads, 256) packed, k / v (total_k, n_kv_heads,
+ * 256) packed or the 16-bit cache fa_decode_d256_* read, (n_seqs, seqlen_cache, n_kv_heads, 256) / (num_pages, page_size, n_kv_heads,
+ * 256) in q's dtype, page_size % 64 == 0 -- the logits' scale 1 / sqrt(256).  Every struct keeps its meaning, every rule its place,
+ * status and words; args->d_head != 256 is FA_ERR_SHAPE where the siblings refuse theirs.  Of args->cfg only dtype is read.  `window`
+ * is required ((-1, -1): none); `softcap` MAY BE NULL (no cap: the kernel built without it), a non-null one is checked behind the
+ * window's rules (fa_softcap's, as in fa_decode_d256_*) and caps the scaled logit in front of every mask; lse is over the capped
+ * logits.  speculative, prescaled_q and stats are refused; total_q = 0 returns FA_OK without a launch.  A kernel family of its own
+ * (fa_prefill256_kernel.hpp): 128 rows per workgroup, grid n_seqs * ceil(max_seqlen_q / 128) * n_heads, 128 KiB of dynamic LDS.  The
+ * lengths' clamping, the window's rule, the row without keys (o = 0, lse = -inf) and the fetch contract are the siblings'.  No
+ * workspace, no split, no atomics: the same bits for the same inputs, and the cache form's bits are the packed form's on the
+ * gathered keys.  The host reads no device array; graph-capturable; opts->ms is timed by the launch's own events.  Not here: an fp8
+ * cache, sinks, the fused append, a backward.
+ */
+int fa_fwd_varlen_qk_d256_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_qk_d256(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                 const fa_varlen_layout *varlen_k, const fa_window *window, const fa_softcap *softcap /* null: no cap */,
+                                 const fa_fwd_opts *opts, float *lse, void *stream);
+int fa_fwd_varlen_kvcache_d256_supported(const fa_fwd_config *cfg, const fa_fwd_opts *opts);
+int fa_fwd_launch_varlen_kvcache_d256(const fa_fwd_args *args, const fa_kv_layout *kv, const fa_varlen_layout *varlen_q,
+                                      const fa_kvcache_layout *cache, const fa_window *window, const fa_softcap *softcap /* null: no cap */,
+                                      const fa_fwd_opts *opts, float *lse, void *stream);
+
+/*
  * The step in front of a decode: append seqlen_new new K / V rows per batch entry to the cache IN PLACE, at the positions the
  * device-side lengths name, optionally rotate the new keys and the query (rotary embedding), quantize for an fp8 cache, and
  * advance the lengths.  One kernel on `stream`; the host reads none of the device arrays, so the launch is asynchronous and
